@@ -15,10 +15,17 @@ so `value` is the input-to-output rate a sampler sees (H2D + D2H inclusive, ever
 region; pipeline fill and drain are inside it too).  All draws are generated before the clock starts.  The rate of the same kernels
 over inputs that stay resident in HBM, and the rate with the full template block coming back, are extra keys.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line carrying `roofline` (the kernel with the largest time per launch inside the timed region -- on direct-P_l runs the
+A plain run sets up, warms up, times the K steps and prints the headline keys (`value`, `ms_per_step`, ...): nothing else runs, and no HIP
+events bracket kernels inside its timed loop.  `--dump-outputs DIR` writes what the timed loop handed its caller in its last step to
+DIR/plk.npy (float64 [B, Nl, Nk]; N > 1: the gathered block [N, B, Nl, Nk] rank 0 receives); the inputs depend on the arguments only.
+`--full` adds everything below: the kernel timers inside the timed loop, the check of every timed step against the synchronous path,
+the side keys (templates first, dependent sampler, resident inputs, batch 256, cfg 3 / cfg 5, drop-in), the rooflines and the CPU
+baseline (`--no-cpu-baseline`, `--no-extras` leave parts of it out).
+
+With --full, rank 0 prints ONE JSON line carrying `roofline` (the kernel with the largest time per launch inside the timed region -- on direct-P_l runs the
 resummation kernel resum_plk_kernel -- timed live with HIP events on its own stream; `frac` = EXECUTED FP64 flops / time / peak, the executed count
 derived from the compiled kernel's instruction counts -- eftpipe_amd/csrc/isa_counts.json, written by tools/isa_counts.py at build time -- and from
 the batch each bracketed launch carried; `frac_alone`: the same kernel with nothing beside it; `roofline_step`: all launches of a step) and
@@ -45,10 +52,21 @@ NPOW, NS_DEV, NKLOW = 257, 80, 7
 COALESCE = int(os.environ.get("EFTB_BENCH_COALESCE", "4"))  # steps the engine may launch together when they are still queued (Engine(coalesce=...): device state for COALESCE x batch)
 DEPTH = int(os.environ.get("EFTB_BENCH_DEPTH", "12"))  # steps queued on the GPU ahead of the one being fetched (1..6; direct-P_l steps are four pipeline stages deep: 618-650 k evaluations/s at 2, 660-668 k at 3, 663-695 k at 4; templates first, round 2: measured 276-279 k evaluations/s at 2, 279 k at 3 over 40 steps, and 273 k vs 266 k over 20: the drain is longer)
 DIRECT = os.environ.get("EFTB_BENCH_DIRECT", "1") != "0"   # `value` on direct-P_l runs (EFTB_O_PLK_DIRECT); 0: templates first
+NPOOL = 256   # distinct draw sets at most: a set costs ~10 ms of host time, so W + K steps beyond NPOOL cycle through the NPOOL sets
 
 
 STEP_TIMES = [] if os.environ.get("EFTB_BENCH_STEP_TIMES") else None
 HOST_PROFILE = [0.0, 0.0] if os.environ.get("EFTB_BENCH_HOST_PROFILE") else None  # diagnostics: seconds of the timed loop inside eng.step() / inside keeper.put()  # diagnostics: host time at which each timed step's P_l had been fetched
+
+
+def draw_set(i, nb, rank=0):
+    """Draw set i of a rank: nb seeded SYNTH-PLIN cosmologies (dict of kin, Pin, f, DA, H) and their bias rows."""
+    from eftpipe_amd import synth
+    from eftpipe_amd.parambasis import bias_row
+
+    d = synth.draw_batch(nb, z=Z, seed=12345 + 7919 * i + 104729 * rank)
+    d["bias"] = np.stack([bias_row(float(f), BS, None, ES, kmA=0.7, krA=0.25, ndA=4.5e-5) for f in d["f"]])
+    return d
 
 
 def cpu_baseline(picks, budget_s=20.0):
@@ -256,6 +274,8 @@ def main():
     ap.add_argument("--batch", type=int, default=128, help="cosmologies per GPU per step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra rates (resident loop, templates back, drop-in latency)")
+    ap.add_argument("--full", action="store_true", help="also run every check, side key, roofline and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the P_l of the last timed step to DIR/plk.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -266,7 +286,6 @@ def main():
     from eftpipe_amd import _lib as L
     from eftpipe_amd import dist, synth
     from eftpipe_amd.engine import Engine, comm_unique_id, mfma_f64_peak
-    from eftpipe_amd.parambasis import bias_row
     from eftpipe_amd.tables import EngineConfig
 
     cp = dist.ControlPlane()
@@ -322,27 +341,30 @@ def main():
         else:
             ok = 0.0
         exchange = "rccl" if cp.max(1.0 - ok) == 0.0 else "host-fallback"
+    if args.dump_outputs and exchange == "host-fallback":
+        raise SystemExit("bench.py: --dump-outputs needs the RCCL gather (the host-side fallback keeps no P_l)")
 
-    # ---- every draw set of the run, generated before the clock starts: W + K sets of B new cosmologies per rank
-    def draw_set(i, nb=None):
-        d = synth.draw_batch(nb or B, z=Z, seed=12345 + 7919 * i + 104729 * rank)
-        d["bias"] = np.stack([bias_row(float(f), BS, None, ES, kmA=0.7, krA=0.25, ndA=4.5e-5) for f in d["f"]])
-        return d
-
-    sets = [draw_set(i) for i in range(W + K)]
+    # ---- every draw set of the run, generated before the clock starts: W + K sets of B new cosmologies per rank (more than NPOOL: the steps cycle
+    # through the first NPOOL of them)
+    pool = [draw_set(i, B, rank) for i in range(min(W + K, NPOOL))]
+    sets = [pool[i % len(pool)] for i in range(W + K)]
     # the untimed extension of the warm-up (below) cycles through a ring of sixteen draw sets of its own (the W asked for + as many more as it takes)
     NRING = 16
-    ring_sets = (sets[:W] + [draw_set(W + K + j) for j in range(max(0, NRING - W))])[:NRING] if W > 0 else []
-    # ... and K more for the side key bare_warmup_*: the same K-step loop timed right behind the W warm-up steps asked for, before the extension
-    bare_sets = [draw_set(W + K + NRING + j) for j in range(K)] if W > 0 and os.environ.get("EFTB_BENCH_BARE", "1") != "0" else []
+    ring_sets = (sets[:W] + [draw_set(W + K + j, B, rank) for j in range(max(0, NRING - W))])[:NRING] if W > 0 else []
+    # ... and K more (--full) for the side key bare_warmup_*: the same K-step loop timed right behind the W warm-up steps asked for, before the extension
+    bare_sets = ([draw_set(W + K + NRING + j, B, rank) for j in range(min(K, NPOOL))] if args.full and W > 0 and os.environ.get("EFTB_BENCH_BARE", "1") != "0"
+                 else [])
     mask = eng.full_mask(reduce=True)
-    # every timed step's P_l of this rank.  N = 1: a page-locked array the sampler owns -- each step's copy-out writes its slice directly
+    # the timed steps' P_l of this rank.  N = 1: a page-locked array the sampler owns -- each step's copy-out writes its slice directly
     # (eng.step(out=...) = eftb_set_step_output: no second host copy; EFTB_BENCH_OWN_OUTPUT=0: the engine's own host block and a copy by a second
-    # host thread, the form up to round 4's first session -- 1.6 MB per step at 10-20 GB/s of one thread: 0.4 ms of a 20-step run)
-    OWN_OUT = exchange == "none" and os.environ.get("EFTB_BENCH_OWN_OUTPUT", "1") != "0" and K * B * NL * NK * 8 <= (2 << 30)
-    results = eng.pinned_empty((K, B, NL, NK)) if OWN_OUT else np.zeros((K, B, NL, NK))
+    # host thread, the form up to round 4's first session -- 1.6 MB per step at 10-20 GB/s of one thread: 0.4 ms of a 20-step run).
+    # Step i writes slot i % KEEP, which step i - KEEP (fetched DEPTH steps after its launch) no longer needs: a plain run keeps the last steps only,
+    # --full every timed step for the checks below, up to 2 GiB (beyond that the last KEEP)
+    KEEP = min(K, max(NRING, DEPTH + 1, (2 << 30) // (B * NL * NK * 8) if args.full else 0))
+    OWN_OUT = exchange == "none" and os.environ.get("EFTB_BENCH_OWN_OUTPUT", "1") != "0"
+    results = eng.pinned_empty((KEEP, B, NL, NK)) if OWN_OUT else np.zeros((KEEP, B, NL, NK))
     results.fill(0.0)                                                     # (touched: the sampler's output buffers exist before the clock starts, no first-touch page faults inside it)
-    warm_out = eng.pinned_empty((max(W, NRING), B, NL, NK)) if OWN_OUT else None   # where the untimed warm-up steps deliver
+    warm_out = eng.pinned_empty((max(NRING, DEPTH + 1), B, NL, NK)) if OWN_OUT else None   # where the untimed warm-up steps deliver
     # (multi-GPU: the root takes every step's gathered block [world, B, NL, NK] as a view of the engine's page-locked host copy -- 12.6 MB per
     # step at 8 ranks, more than one host thread can copy again in a step's time -- and keeps a copy of its own rank's slice for the check below)
 
@@ -368,7 +390,7 @@ def main():
         def run(self):
             while True:
                 view, idx = self.q.get()
-                np.copyto(results[idx], view)
+                np.copyto(results[idx % KEEP], view)
                 self.q.task_done()
 
         def put(self, view, idx):
@@ -397,7 +419,7 @@ def main():
                 if HOST_PROFILE is not None:
                     ta = time.perf_counter()
                 view = eng.step(mask, d["Pin"], d["f"], d["DA"], d["H"], bias=d["bias"], back=DEPTH if i >= DEPTH else -1, shape=(B, NL, NK),
-                                out=(results[i] if keep else warm_out[i % len(warm_out)]) if OWN_OUT else None)
+                                out=(results[i % KEEP] if keep else warm_out[i % len(warm_out)]) if OWN_OUT else None)
                 if HOST_PROFILE is not None:
                     tb = time.perf_counter()
                 if view is not None:
@@ -459,9 +481,10 @@ def main():
         bare_elapsed = cp.max(time.perf_counter() - tb0)
     # HIP events around every second launch of the dominant kernel inside the timed region, on the stream it runs on (every launch costs the loop
     # about 1.5 %: two more packets per step on the queue the resummation waits in) -- switched on before the warm-up extension, so that nothing
-    # but the resets below stands between its last step and the timed region
-    eng.time_kernels(1)  # the resummation kernel: the launch with the largest time of either kind of step (direct-P_l runs: the synthesis and the AP kernel are timed in an untimed repeat of the loop, below)
-    eng.time_dominant(0 if os.environ.get("EFTB_BENCH_NO_EVENTS") else int(os.environ.get("EFTB_BENCH_EVENT_EVERY", "2")))
+    # but the resets below stands between its last step and the timed region (--full only: a plain run brackets nothing)
+    if args.full:
+        eng.time_kernels(1)  # the resummation kernel: the launch with the largest time of either kind of step (direct-P_l runs: the synthesis and the AP kernel are timed in an untimed repeat of the loop, below)
+        eng.time_dominant(0 if os.environ.get("EFTB_BENCH_NO_EVENTS") else int(os.environ.get("EFTB_BENCH_EVENT_EVERY", "2")))
     import gc
 
     gc.collect()
@@ -475,21 +498,66 @@ def main():
     while W > 0 and cp.max(1.0 if (time.perf_counter() - tw) * 1e3 < warm_ms else 0.0) > 0.0:
         loop(0, WARM_CHUNK, keep=False, src=ring_sets)
         warm_steps += WARM_CHUNK
-    for kind in range(3):
-        eng.kernel_time(kind, reset=True)
-    eng.submit_stats(enable=True, reset=True)   # host clocks of the staged steps (two steady_clock reads per call: ~50 ns)
+    if args.full:
+        for kind in range(3):
+            eng.kernel_time(kind, reset=True)
+        eng.submit_stats(enable=True, reset=True)   # host clocks of the staged steps (two steady_clock reads per call: ~50 ns)
     cp.barrier()
     t0 = time.perf_counter()
     loop(W, K, keep=True)
     cp.barrier()
     elapsed = cp.max(time.perf_counter() - t0)
     gc.enable()
+    if STEP_TIMES:
+        print("[bench] fetch-complete times since t0 (ms):", " ".join(f"{(t - t0) * 1e3:.3f}" for t in STEP_TIMES), file=sys.stderr)
+
+    value = B * world * K / elapsed
+    valid = exchange in ("none", "rccl") and not shared_device
+    if args.dump_outputs and rank == 0:
+        # what the timed loop handed its caller in its last step (N > 1: the gathered block of every rank's P_l, as the root receives it)
+        last = eng.fetch_gathered(B, back=0, copy=False) if exchange == "rccl" else results[(K - 1) % KEEP]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "plk.npy"), np.array(last, dtype=np.float64))
+    if rank == 0:
+        out = {
+            "metric": "theory P_l(k) evaluations/sec (single tracer, Nk=512, l=0,2,4)",
+            "value": value, "unit": "evaluations/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic (SYNTH-PLIN v1; a new draw set of `batch_per_gpu` cosmologies every step, seeds 12345 + 7919 step + 104729 rank; "
+                                    f"beyond {NPOOL} warm-up + timed steps the steps cycle through the first {NPOOL} sets)",
+            "config": {"workload": "cfg2: single-tracer LRG z=0.7, Nl=3 (l=0,2,4), Nk=512, IR-resum + AP, P_l via west-coast bias contraction; "
+                                   "H2D+D2H inclusive: every step stages new inputs from host memory and its P_l is fetched to host memory inside the timed region; "
+                                   f"`value` pipelines INDEPENDENT batches at depth {DEPTH} (step i's P_l is taken after step i + {DEPTH} has been handed in; steps still queued when "
+                                   f"the library's submission thread reaches them leave as one launch of up to {COALESCE} steps -- Engine(coalesce={COALESCE}) --, each fetched by itself); the rate a "
+                                   "sampler sees whose next step depends on this step's P_l is the side key sync_step_evaluations_per_s (--full)"
+                                   + ("; every step's P_l is delivered into the sampler's own page-locked results array by the copy-out behind the step (eftb_set_step_output), "
+                                      "where --full compares it with the synchronous path afterwards" if OWN_OUT else "")
+                                   + ("; `value` is measured on direct-P_l runs (EFTB_O_PLK_DIRECT: the bias contraction is taken before the synthesis of the loop pieces, the "
+                                      "resummation and the AP stage, with which it commutes -- same P_l, no template block); the templates-first rate of the same loop (rounds 1-2) is "
+                                      "the side key templates_first_evaluations_per_s, and --full compares every timed step of the two" if DIRECT else ""),
+                       "batch_per_gpu": B,
+                       "parallelism": (f"batch-sharded x{world}, per-step gather of P_l to rank 0 via {exchange}, rank 0 receives every step's gathered block in page-locked host memory"
+                                       if world > 1 or force_comm else "single GPU")},
+            "valid": bool(valid),
+            "warmup_steps_run": warm_steps,
+            "warmup_note": f"{W} untimed pipelined steps as asked, then the same untimed loop run continuously (chunks of {WARM_CHUNK} steps over a ring of {NRING} further draw sets) until "
+                           f"{warm_ms:.0f} ms had passed ({warm_steps} steps in all): the timed region (a few ms) otherwise runs in the state of a GPU that has just left idle -- of three "
+                           "200-step passes back to back the first takes 10 % longer per step than the others; EFTB_BENCH_PREWARM_MS=0 switches the extension off",
+        }
+        if not valid:
+            out["invalid_reason"] = ("P_l was gathered over host sockets, not RCCL" if exchange == "host-fallback" else "ranks shared one GPU") + " -- a rehearsal of the launch path, not a measurement"
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        cp.barrier()
+        eng.close()
+        cp.close()
+        return
+
     host_stats = eng.submit_stats(enable=False, reset=True)
     if HOST_PROFILE is not None:
         print(f"[bench] main thread, per timed step: eng.step {HOST_PROFILE[0] / K * 1e6:.1f} us (of which waiting for results {host_stats['wait_us_per_step']:.1f}, filling the staging "
               f"block {host_stats['fill_us_per_step']:.1f}), keeper.put {HOST_PROFILE[1] / K * 1e6:.1f} us; wall {elapsed / K * 1e6:.1f} us", file=sys.stderr)
-    if STEP_TIMES:
-        print("[bench] fetch-complete times since t0 (ms):", " ".join(f"{(t - t0) * 1e3:.3f}" for t in STEP_TIMES), file=sys.stderr)
     ktimes = [eng.kernel_time(kind, reset=True, cosmologies=True) for kind in range(3)]  # (resummation, synthesis, AP kernel): (ms, launches, cosmologies carried) inside the timed region
     dom_ms, dom_n = ktimes[0][:2]
     if DIRECT and not os.environ.get("EFTB_BENCH_NO_EVENTS"):
@@ -501,20 +569,20 @@ def main():
     eng.time_dominant(False)
     eng.time_kernels(1)
 
-    # ---- the timed loop's own outputs, checked: finite, and EVERY timed step bit-identical to the synchronous one-call path on the same draws
+    # ---- the timed loop's own outputs, checked: finite, and EVERY kept timed step bit-identical to the synchronous one-call path on the same draws
     steps_checked = 0
     if exchange == "none" or (exchange == "rccl" and rank == 0):
         assert np.all(np.isfinite(results)), "non-finite P_l(k) in the timed loop"
-    for i in range(K):
+    for i in range(K - KEEP, K):
         d = sets[W + i]
         sync_plk = eng.eval_batch(d["Pin"], d["f"], d["DA"], d["H"], bias=d["bias"], templates=False)
         if exchange == "none" or (exchange == "rccl" and rank == 0):
-            assert np.array_equal(results[i], sync_plk), f"pipelined step {i} differs from the synchronous path"
+            assert np.array_equal(results[i % KEEP], sync_plk), f"pipelined step {i} differs from the synchronous path"
             steps_checked += 1
     if exchange == "rccl" and rank == 0:  # every rank's block of the last exchange (still in place: nothing was exchanged after it)
         last = eng.fetch_gathered(B, back=0, copy=False)
         assert last.shape == (world, B, NL, NK) and np.all(np.isfinite(last)), "non-finite P_l(k) in the gathered block"
-        assert np.array_equal(last[rank], results[K - 1]), "the root's own slice of the gathered block differs from its P_l"
+        assert np.array_equal(last[rank], results[(K - 1) % KEEP]), "the root's own slice of the gathered block differs from its P_l"
 
     # ---- the same timed loop with the templates first (every rank takes part: the N > 1 loop exchanges); its P_l against the direct runs'
     tf_elapsed, tf_err, tf_dom_ms, tf_dom_n, tf_dom_nc = None, None, 0.0, 0, 0
@@ -545,13 +613,13 @@ def main():
         extras = {}
         if bare_elapsed is not None:
             extras["bare_warmup_evaluations_per_s"], extras["bare_warmup_ms_per_step"] = B * world * K / bare_elapsed, bare_elapsed / K * 1e3
-            extras["bare_warmup_note"] = (f"the same {K}-step loop over {K} other draw sets, timed right behind the {W} warm-up steps asked for and BEFORE the warm-up extension "
+            extras["bare_warmup_note"] = (f"the same {K}-step loop over {len(bare_sets)} other draw sets, timed right behind the {W} warm-up steps asked for and BEFORE the warm-up extension "
                                           "(warmup_note): what the first milliseconds after idle look like; `value` is the loop in the GPU's sustained state")
         if tf_elapsed is not None:
             extras["templates_first_evaluations_per_s"], extras["templates_first_ms_per_step"] = B * world * K / tf_elapsed, tf_elapsed / K * 1e3
             extras["templates_first_note"] = ("the same timed loop with EFTB_O_PLK_DIRECT off: the 24 templates per multipole go through resummation and AP and the "
                                               "bias contraction rides in the AP epilogue (the path `value` was measured on up to round 2)"
-                                              + (f"; all {K} timed steps of the two paths agree to {tf_err:.1e} of each multipole's maximum" if tf_err is not None else ""))
+                                              + (f"; {'all' if KEEP == K else 'the last'} {KEEP} timed steps of the two paths agree to {tf_err:.1e} of each multipole's maximum" if tf_err is not None else ""))
         eng.set_latency_mode(True)
         if world == 1 and not force_comm:
             # (0) what a DEPENDENT sampler sees (reference likelihood.py:570-594 inside Model.logpost: step i + 1 needs step i's P_l): stage ->
@@ -571,7 +639,7 @@ def main():
             extras["sync_step_evaluations_per_s"], extras["sync_step_ms"] = B * K / dt1, dt1 / K * 1e3
             extras["sync_step_note"] = ("stage -> run -> P_l of the step just launched, nothing queued behind it (the engine finds the GPU idle when the step is staged and "
                                         "runs it in latency mode: one queue, P_lin read from the staging block, P_l written to mapped host memory by the AP epilogue)")
-            assert np.array_equal(out1, results[K - 1]), "dependent-sampler loop differs from the pipelined loop on the same draws"
+            assert np.array_equal(out1, results[(K - 1) % KEEP]), "dependent-sampler loop differs from the pipelined loop on the same draws"
         if not args.no_extras:
             # (1) the same kernels over inputs resident in HBM (what round 1 reported as `value`): K asynchronous runs of one batch
             d0 = sets[0]
@@ -766,43 +834,14 @@ def main():
                     check_fracs(v, f"{path}[{i_}]")
 
         check_fracs(roofline)
-        value = B * world * K / elapsed
-        valid = exchange in ("none", "rccl") and not shared_device
-        out = {
-            "metric": "theory P_l(k) evaluations/sec (single tracer, Nk=512, l=0,2,4)",
-            "value": value, "unit": "evaluations/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic (SYNTH-PLIN v1; a new draw set of `batch_per_gpu` cosmologies every step, seeds 12345 + 7919 step + 104729 rank)",
-            "config": {"workload": "cfg2: single-tracer LRG z=0.7, Nl=3 (l=0,2,4), Nk=512, IR-resum + AP, P_l via west-coast bias contraction; "
-                                   "H2D+D2H inclusive: every step stages new inputs from host memory and its P_l is fetched to host memory inside the timed region; "
-                                   f"`value` pipelines INDEPENDENT batches at depth {DEPTH} (step i's P_l is taken after step i + {DEPTH} has been handed in; steps still queued when "
-                                   f"the library's submission thread reaches them leave as one launch of up to {COALESCE} steps -- Engine(coalesce={COALESCE}) --, each fetched by itself); the rate a "
-                                   "sampler sees whose next step depends on this step's P_l is the side key sync_step_evaluations_per_s"
-                                   + ("; every step's P_l is delivered into the sampler's own page-locked results array by the copy-out behind the step (eftb_set_step_output), "
-                                      "where it is compared with the synchronous path afterwards" if OWN_OUT else "")
-                                   + ("; `value` is measured on direct-P_l runs (EFTB_O_PLK_DIRECT: the bias contraction is taken before the synthesis of the loop pieces, the "
-                                      "resummation and the AP stage, with which it commutes -- same P_l, no template block); the templates-first rate of the same loop (rounds 1-2) is "
-                                      "the side key templates_first_evaluations_per_s, and every timed step of the two is compared" if DIRECT else ""),
-                       "batch_per_gpu": B,
-                       "parallelism": (f"batch-sharded x{world}, per-step gather of P_l to rank 0 via {exchange}, rank 0 receives every step's gathered block in page-locked host memory"
-                                       if world > 1 or force_comm else "single GPU")},
-            "valid": bool(valid), "timed_steps_checked_against_sync_path": steps_checked,
-            "host_us_per_step": host_stats,
-            "warmup_steps_run": warm_steps,
-            "warmup_note": f"{W} untimed pipelined steps as asked, then the same untimed loop run continuously (chunks of {WARM_CHUNK} steps over a ring of {NRING} further draw sets) until "
-                           f"{warm_ms:.0f} ms had passed ({warm_steps} steps in all): the timed region (a few ms) otherwise runs in the state of a GPU that has just left idle -- of three "
-                           "200-step passes back to back the first takes 10 % longer per step than the others; EFTB_BENCH_PREWARM_MS=0 switches the extension off",
-            "roofline": roofline,
-        }
-        if not valid:
-            out["invalid_reason"] = ("P_l was gathered over host sockets, not RCCL" if exchange == "host-fallback" else "ranks shared one GPU") + " -- a rehearsal of the launch path, not a measurement"
+        out.update({"timed_steps_checked_against_sync_path": steps_checked, "host_us_per_step": host_stats, "roofline": roofline})
         out.update(extras)
         if not args.no_cpu_baseline:
-            # two cosmologies OF THE TIMED SETS (first of the first timed step, last of the last timed step) lead the CPU sample; the oracle's
+            # two cosmologies OF THE TIMED SETS (first of the first kept timed step, last of the last timed step) lead the CPU sample; the oracle's
             # templates of those two are compared with what the timed loop itself fetched
             pick = lambda st, w: dict(kin=sets[W + st]["kin"], Pin=sets[W + st]["Pin"][w], f=sets[W + st]["f"][w], DA=sets[W + st]["DA"][w],
                                       H=sets[W + st]["H"][w], step=st, w=w)
-            picks = [pick(0, 0), pick(K - 1, B - 1)] + [pick((3 * j) % K, (37 * j) % B) for j in range(1, 7)]
+            picks = [pick(K - KEEP, 0), pick(K - 1, B - 1)] + [pick((3 * j) % K, (37 * j) % B) for j in range(1, 7)]
             out["cpu_baseline"], templ01 = cpu_baseline(picks)
             out["speedup_vs_cpu_port"] = value / out["cpu_baseline"]["value"]
             if not args.no_extras:
@@ -815,12 +854,12 @@ def main():
             # parity of the TIMED outputs against the oracle, pointwise where |P_l| is not tiny
             worst = 0.0
             for c, templ in zip(picks[:2], templ01):
-                got = results[c["step"], c["w"]]
+                got = results[c["step"] % KEEP, c["w"]]
                 want = np.einsum("r,lrx->lx", sets[W + c["step"]]["bias"][c["w"]], templ)
                 big = np.abs(want) > 1e-3 * np.max(np.abs(want), axis=-1, keepdims=True)
                 worst = max(worst, float(np.max(np.abs(got - want)[big] / np.abs(want)[big])))
             out["max_rel_err_vs_oracle"] = worst
-            out["parity_note"] = (f"all {steps_checked} timed steps bit-identical to the synchronous eftb_eval_batch path; P_l of (step 0, cosmology 0) and "
+            out["parity_note"] = (f"{'all' if KEEP == K else 'the last'} {steps_checked} timed steps bit-identical to the synchronous eftb_eval_batch path; P_l of (step {K - KEEP}, cosmology 0) and "
                                   f"(step {K - 1}, cosmology {B - 1}) as fetched inside the timed loop against the oracle: max relative error {worst:.2e} (bar 1e-6)")
             assert worst < 1e-6, worst
         print(json.dumps(out))

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=$1; mkdir -p $OUT
 for k in $2; do for d in $3; do for c in $4; do for i in $5; do
   f=$OUT/k${k}_d${d}_c${c}_i${i}.json
-  EFTB_BENCH_DEPTH=$d EFTB_BENCH_COALESCE=$c EFTB_SUB_INFLIGHT=$i python3 bench.py --steps $k --no-cpu-baseline --no-extras > $f 2> $f.err || echo "FAILED $f"
+  EFTB_BENCH_DEPTH=$d EFTB_BENCH_COALESCE=$c EFTB_SUB_INFLIGHT=$i python3 bench.py --steps $k --full --no-cpu-baseline --no-extras > $f 2> $f.err || echo "FAILED $f"
   python3 - $f <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 K=${K:-200}
 while read -r line; do
   for rep in 1 2; do
-    env $line python3 bench.py --steps $K --no-cpu-baseline --no-extras > /tmp/es.json 2>/dev/null
+    env $line python3 bench.py --steps $K --full --no-cpu-baseline --no-extras > /tmp/es.json 2>/dev/null
     python3 - "$line" <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@
 OUT=$1; shift
 export TMPDIR=/tmp
 mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o stats -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras "$@" > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o stats -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras "$@" > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 f=$(ls "$OUT"/*kernel_stats.csv 2>/dev/null | head -1)
 [ -n "$f" ] && python3 - "$f" <<'PY'
 import csv, sys

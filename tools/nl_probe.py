@@ -1,5 +1,5 @@
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from eftpipe_amd import synth, _lib as L
 from eftpipe_amd.engine import Engine
 from eftpipe_amd.tables import EngineConfig

@@ -9,15 +9,15 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/prof
 rm -rf $OUT && mkdir -p $OUT
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o stats -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 echo "stats done"
 # one derived counter per pass where the hardware cannot collect them together (FETCH_SIZE + WRITE_SIZE is refused)
 pmc() {  # name, counters...
     local name=$1; shift
     # (one step per launch in the counter passes: EFTB_BENCH_COALESCE=1 -- the counters are then per launch of 128 cosmologies)
-    EFTB_BENCH_COALESCE=1 timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -o $name -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/$name.err
+    EFTB_BENCH_COALESCE=1 timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -o $name -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/$name.err
     echo "$name done"
 }
 pmc pmc_fetch FETCH_SIZE

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What one Engine.step call costs the sampler's thread while nothing is fetched (GPU box): the pace at which a burst of steps reaches the queue."""
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from eftpipe_amd import synth
 from eftpipe_amd.engine import Engine

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=${1:-gpurun_out/tb}
 rm -rf $OUT && mkdir -p $OUT
-EFTB_BENCH_DIRECT_ONLY=1 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 bench.py --steps ${K:-80} --no-cpu-baseline --no-extras > $OUT/bench.json 2> $OUT/err.log || { tail -5 $OUT/err.log; exit 1; }
+EFTB_BENCH_DIRECT_ONLY=1 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 bench.py --steps ${K:-80} --full --no-cpu-baseline --no-extras > $OUT/bench.json 2> $OUT/err.log || { tail -5 $OUT/err.log; exit 1; }
 f=$(ls $OUT/*kernel_trace.csv $OUT/*/*kernel_trace.csv 2>/dev/null | head -1)
 python3 - "$f" $OUT/bench.json <<'PY'
 import csv, json, sys
