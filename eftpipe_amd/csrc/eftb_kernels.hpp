@@ -43,12 +43,16 @@ __device__ __forceinline__ void xcd_decode(int ntile, int& tile, int& group) {
 // prep_rows_kernel writes the operand rows: A1 = Pin (for P11), A2 = [Pin | tail] (coefficients; also transposed, for the
 // cosmology-contiguous copy the anti-diagonal pass reads), A3 = [Pin | tail'] (IR filters), zero padded to multiples of the GEMM's K chunk.
 // One workgroup per cosmology.  A1 / A3 may be null (only the other part is wanted).  Input guard: include/eftbird.h.
+// Input grids that start above the FFTLog's xmin (LO = true): the last ntail_lo / nxtail_lo columns of A2 / A3 continue the function at the low end
+// as well, with the slope and amplitude of ITS first two samples (reference fftlog.py:140-145); wq2 then holds 4 weights (last two, first two).
 // ------------------------------------------------------------------------------------------------
+template <bool LO>
 __device__ __forceinline__ void prep_rows_body(int Nkin, int ntail, int nxtail, int KP1, int KP2, int KP3, int Bmax,
                                                         const double* __restrict__ Pin, const double* __restrict__ lnkin,
                                                         const double* __restrict__ lnxtail, const double* __restrict__ lnxxtail,
                                                         const double* __restrict__ wq2, double* __restrict__ A1, double* __restrict__ A2,
-                                                        double* __restrict__ A2T, double* __restrict__ A3, int* __restrict__ status) {
+                                                        double* __restrict__ A2T, double* __restrict__ A3, int* __restrict__ status,
+                                                        int ntail_lo, int nxtail_lo) {
     extern __shared__ double sm[];
     double* pin = sm;
     const int w = blockIdx.x, tid = threadIdx.x;
@@ -57,18 +61,27 @@ __device__ __forceinline__ void prep_rows_body(int Nkin, int ntail, int nxtail, 
         const double v = Pin[(size_t)w * Nkin + j];
         pin[j] = v;
         bad = bad || !(fabs(v) <= 1.79769313486231570815e308) || (j >= Nkin - 2 && !(v > 0.0));  // non-finite anywhere, non-positive where the logarithm is taken
+        if (LO) bad = bad || (j < 2 && !(v > 0.0));                                                 // (the low tails take it of the first two as well)
     }
     // input guard (reference fftlog.py:146-151 needs the last two samples positive): the flag sits in mapped host memory and is only written in the error case
     if (bad && status) atomicMax(status, w + 1);
     __syncthreads();
     const double dln = lnkin[Nkin - 1] - lnkin[Nkin - 2];
+    const double dlo = LO ? lnkin[1] - lnkin[0] : 0.0;
     if (A1) {
         // slope / amplitude from the last two samples (reference fftlog.py:146-151)
         const double slope = (log(pin[Nkin - 1]) - log(pin[Nkin - 2])) / dln;
         const double amp = pin[Nkin - 1] * exp(-slope * lnkin[Nkin - 1]);
+        double slo = 0.0, alo = 0.0;
+        if (LO && ntail_lo) {  // ... and from the first two (fftlog.py:140-145)
+            slo = (log(pin[1]) - log(pin[0])) / dlo;
+            alo = pin[0] * exp(-slo * lnkin[0]);
+        }
+        const int nhi = ntail - (LO ? ntail_lo : 0);
         for (int j = tid; j < KP1; j += blockDim.x) A1[(size_t)w * KP1 + j] = j < Nkin ? pin[j] : 0.0;
         for (int j = tid; j < KP2; j += blockDim.x) {
-            const double v = j < Nkin ? pin[j] : (j < Nkin + ntail ? amp * exp(slope * lnxtail[j - Nkin]) : 0.0);
+            double v = j < Nkin ? pin[j] : (j < Nkin + ntail ? amp * exp(slope * lnxtail[j - Nkin]) : 0.0);
+            if (LO && j >= Nkin + nhi && j < Nkin + ntail) v = alo * exp(slo * lnxtail[j - Nkin]);
             A2[(size_t)w * KP2 + j] = v;
             A2T[(size_t)j * Bmax + w] = v;
         }
@@ -78,17 +91,32 @@ __device__ __forceinline__ void prep_rows_body(int Nkin, int ntail, int nxtail, 
         const double q1 = pin[Nkin - 1] * wq2[1], q0 = pin[Nkin - 2] * wq2[0];
         const double slope = (log(q1) - log(q0)) / dln;
         const double amp = q1 * exp(-slope * lnkin[Nkin - 1]);
-        for (int j = tid; j < KP3; j += blockDim.x)
-            A3[(size_t)w * KP3 + j] = j < Nkin ? pin[j] : (j < Nkin + nxtail ? amp * exp(slope * lnxxtail[j - Nkin]) : 0.0);
+        double slo = 0.0, alo = 0.0;
+        if (LO && nxtail_lo) {  // the low tail continues q's first two samples
+            const double p0 = pin[0] * wq2[2], p1 = pin[1] * wq2[3];
+            slo = (log(p1) - log(p0)) / dlo;
+            alo = p0 * exp(-slo * lnkin[0]);
+        }
+        const int nhi = nxtail - (LO ? nxtail_lo : 0);
+        for (int j = tid; j < KP3; j += blockDim.x) {
+            double v = j < Nkin ? pin[j] : (j < Nkin + nxtail ? amp * exp(slope * lnxxtail[j - Nkin]) : 0.0);
+            if (LO && j >= Nkin + nhi && j < Nkin + nxtail) v = alo * exp(slo * lnxxtail[j - Nkin]);
+            A3[(size_t)w * KP3 + j] = v;
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void prep_rows_kernel(int Nkin, int ntail, int nxtail, int KP1, int KP2, int KP3, int Bmax,
-                                                        const double* __restrict__ Pin, const double* __restrict__ lnkin,
-                                                        const double* __restrict__ lnxtail, const double* __restrict__ lnxxtail,
-                                                        const double* __restrict__ wq2, double* __restrict__ A1, double* __restrict__ A2,
-                                                        double* __restrict__ A2T, double* __restrict__ A3, int* __restrict__ status) {
-    prep_rows_body(Nkin, ntail, nxtail, KP1, KP2, KP3, Bmax, Pin, lnkin, lnxtail, lnxxtail, wq2, A1, A2, A2T, A3, status);
+#define PREP_ROWS_PARAMS int Nkin, int ntail, int nxtail, int KP1, int KP2, int KP3, int Bmax, const double* __restrict__ Pin, \
+    const double* __restrict__ lnkin, const double* __restrict__ lnxtail, const double* __restrict__ lnxxtail, const double* __restrict__ wq2, \
+    double* __restrict__ A1, double* __restrict__ A2, double* __restrict__ A2T, double* __restrict__ A3, int* __restrict__ status
+#define PREP_ROWS_ARGS Nkin, ntail, nxtail, KP1, KP2, KP3, Bmax, Pin, lnkin, lnxtail, lnxxtail, wq2, A1, A2, A2T, A3, status
+
+__global__ __launch_bounds__(256) void prep_rows_kernel(PREP_ROWS_PARAMS) {
+    prep_rows_body<false>(PREP_ROWS_ARGS, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void prep_rows_lo_kernel(PREP_ROWS_PARAMS, int ntail_lo, int nxtail_lo) {
+    prep_rows_body<true>(PREP_ROWS_ARGS, ntail_lo, nxtail_lo);
 }
 
 // Q(f) of Resum.makeQ for one cosmology (qf_kernel's body; declared here for the merged front launch below)
@@ -114,18 +142,25 @@ __device__ __forceinline__ void qf_body(int w, int nq, const double* __restrict_
 
 // operand rows and Q(f) in one launch (direct-P_l runs: both are the first kernels of the front on the side stream; a launch costs the host
 // 4 us and the step is bounded by the host): workgroups [0, B) = prep_rows, [B, 2 B) = Q(f)
-__global__ __launch_bounds__(256) void prep_rows_qf_kernel(int B, int Nkin, int ntail, int nxtail, int KP1, int KP2, int KP3, int Bmax,
-                                                           const double* __restrict__ Pin, const double* __restrict__ lnkin,
-                                                           const double* __restrict__ lnxtail, const double* __restrict__ lnxxtail,
-                                                           const double* __restrict__ wq2, double* __restrict__ A1, double* __restrict__ A2,
-                                                           double* __restrict__ A2T, double* __restrict__ A3, int* __restrict__ status, int nq,
-                                                           const double* __restrict__ fgrow, const double* __restrict__ Qpoly, double* __restrict__ Q) {
+__global__ __launch_bounds__(256) void prep_rows_qf_kernel(int B, PREP_ROWS_PARAMS, int nq, const double* __restrict__ fgrow,
+                                                           const double* __restrict__ Qpoly, double* __restrict__ Q) {
     if ((int)blockIdx.x >= B) {
         qf_body(blockIdx.x - B, nq, fgrow, Qpoly, Q);
         return;
     }
-    prep_rows_body(Nkin, ntail, nxtail, KP1, KP2, KP3, Bmax, Pin, lnkin, lnxtail, lnxxtail, wq2, A1, A2, A2T, A3, status);
+    prep_rows_body<false>(PREP_ROWS_ARGS, 0, 0);
 }
+
+__global__ __launch_bounds__(256) void prep_rows_qf_lo_kernel(int B, PREP_ROWS_PARAMS, int nq, const double* __restrict__ fgrow,
+                                                              const double* __restrict__ Qpoly, double* __restrict__ Q, int ntail_lo, int nxtail_lo) {
+    if ((int)blockIdx.x >= B) {
+        qf_body(blockIdx.x - B, nq, fgrow, Qpoly, Q);
+        return;
+    }
+    prep_rows_body<true>(PREP_ROWS_ARGS, ntail_lo, nxtail_lo);
+}
+#undef PREP_ROWS_PARAMS
+#undef PREP_ROWS_ARGS
 
 // ------------------------------------------------------------------------------------------------
 // One-loop pieces in anti-diagonal form (tables.py antidiagonal_tables).  With x_n(k) = c_n k^{Pow_n} and
@@ -244,6 +279,88 @@ __global__ __launch_bounds__(64 * NW) void antidiag_kernel(int B, int Bmax, cons
     }
 }
 
+// Any other NFFT = 2 nh (128 <= nh <= 256): the same pass with nh read at run time -- a kernel of its own, so that the NFFT = 256 build above
+// keeps its code.  Grid: NPOW = 2 nh + 1 anti-diagonals; the odd cosmology groups walk j' backwards as above, so workgroups i and NPOW + i,
+// which the dispatcher deals to the same CU, bring nh + 1 - i/2 and 1 + i/2 pairs between them.
+template <int NC, int NW>
+__global__ __launch_bounds__(64 * NW) void antidiag_nh_kernel(int B, int Bmax, const double* __restrict__ coefT,
+                                                              const double2* __restrict__ AD, double2* __restrict__ S, int nh) {
+    constexpr int PB = 3, WPP = 2 * NC;  // pairs per weight block, doubles per pair
+    static_assert(PB * WPP <= 64, "one wave-load must hold a block's weights");
+    __shared__ double red[NW - 1][2 * NC][64];  // partial sums of waves 1..NW-1
+    const int npow = 2 * nh + 1, nch = nh + 1, adt = nh + 2;
+    const int grp = blockIdx.y, jp = (grp & 1) ? npow - 1 - (int)blockIdx.x : (int)blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = grp * 64 + lane;
+    const int wl = w < B ? w : B - 1;
+    const int cnt = ((2 * nh + jp) >> 1) - jp + 1;  // pairs (n, m) = (jp + t, 2 nh - t), n <= m
+    const int per = (cnt + NW - 1) / NW, t0 = wave * per, t1 = min(cnt, t0 + per);
+    const double* cr = coefT + wl;
+    const double* ci = coefT + (size_t)nch * Bmax + wl;
+    double ar[NC], ai[NC];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) ar[q] = ai[q] = 0.0;
+    if (t0 < t1) {
+        const double* adw = reinterpret_cast<const double*>(AD + ((size_t)jp * adt + t0) * NC);  // weights of pair t0 + i: adw[i WPP .. (i + 1) WPP)
+        const int nw = (t1 - t0) * WPP;
+        auto wload = [&](int blk) { return adw[min(blk * PB * WPP + lane, nw - 1)]; };
+        // (loads only -- the conjugations c_{2nh-n} = conj(c_n), c_m = conj(c_t) for m = 2 nh - t are applied where the values are consumed)
+        double xr[PB], xi[PB], yr[PB], yi[PB];
+        auto coef = [&](int t, int p) {
+            const int n = jp + t, qn = n <= nh ? n : 2 * nh - n;
+            xr[p] = cr[(size_t)qn * Bmax];
+            xi[p] = ci[(size_t)qn * Bmax];
+            yr[p] = cr[(size_t)t * Bmax];
+            yi[p] = ci[(size_t)t * Bmax];
+        };
+        double wc = wload(0);
+#pragma unroll
+        for (int p = 0; p < PB; ++p) coef(min(t0 + p, t1 - 1), p);
+        const int nblk = (t1 - t0 + PB - 1) / PB;
+        for (int blk = 0; blk < nblk; ++blk) {
+            const double wn = wload(blk + 1);  // (clamped to the chunk's last weight: the block after the last one is never consumed)
+#pragma unroll
+            for (int p = 0; p < PB; ++p) {
+                const int t = t0 + blk * PB + p;
+                const double on = t < t1 ? 1.0 : 0.0;  // pairs past the chunk's end (the last block's padding) carry no weight
+                const double xim = jp + t <= nh ? xi[p] : -xi[p], yim = -yi[p];
+                const double pr = (xr[p] * yr[p] - xim * yim) * on, pi = (xr[p] * yim + xim * yr[p]) * on;
+                // (scheduling barriers: left alone, the compiler gathers the reloads of all slots at the top of the trip and waits for every
+                // outstanding load before the first FMA -- no load would be in flight under the arithmetic)
+                __builtin_amdgcn_sched_barrier(0);
+                coef(min(t + PB, t1 - 1), p);  // the slot has been consumed: its next occupant is requested before this pair's FMAs
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int q = 0; q < NC; ++q) {
+                    const double mx = readlane_f64(wc, p * WPP + 2 * q), my = readlane_f64(wc, p * WPP + 2 * q + 1);
+                    ar[q] = fma(mx, pr, fma(-my, pi, ar[q]));
+                    ai[q] = fma(mx, pi, fma(my, pr, ai[q]));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            wc = wn;
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            red[wave - 1][2 * q][lane] = ar[q];
+            red[wave - 1][2 * q + 1][lane] = ai[q];
+        }
+    }
+    __syncthreads();
+    if (wave == 0 && w < B) {
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+#pragma unroll
+            for (int v = 0; v < NW - 1; ++v) {  // fixed order: wave 0 + wave 1 + ...
+                ar[q] += red[v][2 * q][lane];
+                ai[q] += red[v][2 * q + 1][lane];
+            }
+            S[((size_t)w * NC + q) * npow + jp] = make_double2(ar[q], ai[q]);
+        }
+    }
+}
+
 // One lane = one j' of one cosmology: sums the AD_CH partials of the nc anti-diagonal sums once, then writes
 //   blockIdx.y = 0: the nb P22 basis rows  (A22[w][BAS22][KSYN])  and the 10 P13 rows (A13[w][10][KLIN])
 //   blockIdx.y = 1: the Nl*nc weighted rows Ml[l] S_c (ACF[w][BASC][KSYN]) and the nlc Nl C11 / Cct (/ CctNNLO) rows (ALC[w][nlc Nl][KLIN])
@@ -298,6 +415,72 @@ __global__ __launch_bounds__(64) void build_rows_kernel(int sets, int Bmax, int 
             const double2 v = linvec[(size_t)(v0 + row) * NCH + n];
             const double cr = c[n], ci = n == NHALF ? 0.0 : c[NCH + n];
             double* o = out + (size_t)row * KLIN;
+            if (mp == 0) o[0] = cr * v.x - ci * v.y;
+            else {
+                o[2 * mp - 1] = cr * v.x - ci * v.y;
+                o[2 * mp] = cr * v.y + ci * v.x;
+            }
+        }
+    }
+}
+
+// Row lengths of the loop syntheses for NFFT = 2 nh: 1 + 4 nh (double sums) and 1 + 2 nh (single sums), zero padded to SYN_KPAD
+__host__ __device__ constexpr int ksyn_of(int nh) { return (4 * nh + SYN_KPAD) / SYN_KPAD * SYN_KPAD; }
+__host__ __device__ constexpr int klin_of(int nh) { return (2 * nh + SYN_KPAD) / SYN_KPAD * SYN_KPAD; }
+static_assert(ksyn_of(NHALF) == KSYN && klin_of(NHALF) == KLIN, "row lengths of the default NFFT");
+
+template <int NC>
+__global__ __launch_bounds__(64) void build_rows_nh_kernel(int sets, int Bmax, int Nl, int nlc, int nb, const double* __restrict__ coef,
+                                                            const double2* __restrict__ S, const double2* __restrict__ mlj,
+                                                            const double2* __restrict__ linvec, double* __restrict__ A22,
+                                                            double* __restrict__ A13, double* __restrict__ ACF, double* __restrict__ ALC, int nh) {
+    // five single-wave workgroups per (cosmology, half) for the 257 harmonics (round 3: as ONE workgroup of 320 threads the kernel took 58 us
+    // beside the resummation against 9 alone -- five waves need two free wave slots on one SIMD, which two resummation waves never leave);
+    // ceil((2 nh + 1) / 64) of them at other NFFT
+    const int npow = 2 * nh + 1, nch = nh + 1, ksyn = ksyn_of(nh), klin = klin_of(nh), zstride = 64 * (int)gridDim.z;
+    const int w = blockIdx.x, cf = blockIdx.y, jp = blockIdx.z * 64 + threadIdx.x;
+    if (((sets >> cf) & 1) && jp < npow) {
+        double zr[NC], zi[NC];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            zr[q] = zi[q] = 0.0;
+#pragma unroll
+            for (int ch = 0; ch < AD_CH; ++ch) {
+                const double2 v = S[(((size_t)ch * Bmax + w) * NC + q) * npow + jp];
+                zr[q] += v.x;
+                zi[q] += v.y;
+            }
+        }
+        const int o0 = jp == 0 ? 0 : 2 * jp - 1;
+        if (cf == 0) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q)
+                if (q < nb) {
+                    double* o = A22 + ((size_t)w * BAS22 + q) * ksyn;
+                    o[o0] = zr[q];
+                    if (jp) o[o0 + 1] = zi[q];
+                }
+        } else {
+            for (int l = 0; l < Nl; ++l) {
+                const double2 m = mlj[l * npow + jp];  // Bessel weight Ml[l](n + m) (reference pybird.py:1040-1046)
+#pragma unroll
+                for (int q = 0; q < NC; ++q) {
+                    double* o = ACF + ((size_t)w * BASC + l * NC + q) * ksyn;
+                    o[o0] = m.x * zr[q] - m.y * zi[q];
+                    if (jp) o[o0 + 1] = m.x * zi[q] + m.y * zr[q];
+                }
+            }
+        }
+    }
+    if ((sets >> (2 + cf)) & 1) {
+        const int nrows = cf == 0 ? 10 : nlc * Nl, v0 = cf == 0 ? 0 : 10;  // nlc = 2 (C11, Cct) or 3 (+ CctNNLO)
+        double* out = cf == 0 ? A13 + (size_t)w * 10 * klin : ALC + (size_t)w * nlc * Nl * klin;
+        const double* c = coef + (size_t)w * 2 * nch;
+        for (int e = jp; e < nrows * nch; e += zstride) {
+            const int row = e / nch, mp = e % nch, n = nh - mp;  // harmonic mp <-> coefficient n = nh - mp
+            const double2 v = linvec[(size_t)(v0 + row) * nch + n];
+            const double cr = c[n], ci = n == nh ? 0.0 : c[nch + n];
+            double* o = out + (size_t)row * klin;
             if (mp == 0) o[0] = cr * v.x - ci * v.y;
             else {
                 o[2 * mp - 1] = cr * v.x - ci * v.y;
@@ -425,6 +608,124 @@ __global__ __launch_bounds__(64) void build_rows_plk_kernel(int Bmax, int nb, co
             }
             const double cr = c[n], ci = n == NHALF ? 0.0 : c[NCH + n];
             double* o = out + (size_t)row * KLIN;
+            if (mp == 0) o[0] = cr * vx - ci * vy;
+            else {
+                o[2 * mp - 1] = cr * vx - ci * vy;
+                o[2 * mp] = cr * vy + ci * vx;
+            }
+        }
+    }
+}
+
+// build_rows_plk_kernel at any other NFFT = 2 nh (nh read at run time; ceil((2 nh + 1) / 64) workgroups per (cosmology, half))
+template <int NC>
+__global__ __launch_bounds__(64) void build_rows_plk_nh_kernel(int Bmax, int nb, const double* __restrict__ coef, const double2* __restrict__ S,
+                                                    const double2* __restrict__ mlj, const double2* __restrict__ linvec,
+                                                    const double* __restrict__ bias, const double* __restrict__ fgrow,
+                                                    const double* __restrict__ l11, const double* __restrict__ lct,
+                                                    const double* __restrict__ l22, const double* __restrict__ l13,
+                                                    const int* __restrict__ grp, const double* __restrict__ exp22,
+                                                    const double* __restrict__ expc, double* __restrict__ A22, double* __restrict__ A13,
+                                                    double* __restrict__ ACF, double* __restrict__ ALC, int nh) {
+    constexpr int NL = 3;
+    const int npow = 2 * nh + 1, nch = nh + 1, ksyn = ksyn_of(nh), klin = klin_of(nh), zstride = 64 * (int)gridDim.z;
+    __shared__ double s_cf[NL * 38];   // cf_l[b]
+    __shared__ double s_w[NL * NC];    // k space: sum_b cf_l[b] exp22[b][q] (q < nb); xi space: sum_b cf_l'[b] expc[row(l', b)][l' NC + q]
+    __shared__ double s_b[2 * NL];
+    const int w = blockIdx.x, cf = blockIdx.y, jp = blockIdx.z * 64 + threadIdx.x;
+    const double* bw = bias + (size_t)w * NROW;
+    const double f = fgrow[w];
+    for (int e = threadIdx.x; e < NL * 38; e += 64) {
+        const int l = e / 38, bq = e % 38;
+        s_cf[e] = bw[9 + grp[2 * bq]] * ipow(f, grp[2 * bq + 1]) * (bq < 28 ? l22[l * 28 + bq] : l13[l * 10 + (bq - 28)]);
+    }
+    if (threadIdx.x < 2 * NL) {
+        const int a = threadIdx.x / NL, lp = threadIdx.x % NL;
+        double v = 0.0;
+        if (a == 0)
+            for (int r = 0; r < 3; ++r) v = fma(bw[r], l11[lp * 3 + r], v);
+        else
+            for (int r = 0; r < 6; ++r) v = fma(bw[3 + r], lct[lp * 6 + r], v);
+        s_b[threadIdx.x] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NL * NC) {
+        const int l = threadIdx.x / NC, q = threadIdx.x % NC;
+        double v0 = 0.0, v1 = 0.0;
+        if (cf == 0) {
+            if (q < nb)
+                for (int b = 0; b < 28; b += 2) {
+                    v0 = fma(s_cf[l * 38 + b], exp22[b * BAS22 + q], v0);
+                    v1 = fma(s_cf[l * 38 + b + 1], exp22[(b + 1) * BAS22 + q], v1);
+                }
+        } else {
+            for (int b = 0; b < 28; b += 2) {
+                v0 = fma(s_cf[l * 38 + b], expc[(size_t)(l * 28 + b) * BASC + l * NC + q], v0);
+                v1 = fma(s_cf[l * 38 + b + 1], expc[(size_t)(l * 28 + b + 1) * BASC + l * NC + q], v1);
+            }
+            for (int b = 0; b < 10; b += 2) {
+                v0 = fma(s_cf[l * 38 + 28 + b], expc[(size_t)(NL * 28 + l * 10 + b) * BASC + l * NC + q], v0);
+                v1 = fma(s_cf[l * 38 + 29 + b], expc[(size_t)(NL * 28 + l * 10 + b + 1) * BASC + l * NC + q], v1);
+            }
+        }
+        s_w[threadIdx.x] = v0 + v1;
+    }
+    __syncthreads();
+    if (jp < npow) {
+        double zr[NC], zi[NC];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            zr[q] = zi[q] = 0.0;
+#pragma unroll
+            for (int ch = 0; ch < AD_CH; ++ch) {
+                const double2 v = S[(((size_t)ch * Bmax + w) * NC + q) * npow + jp];
+                zr[q] += v.x;
+                zi[q] += v.y;
+            }
+        }
+        const int o0 = jp == 0 ? 0 : 2 * jp - 1;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            double cr = 0.0, ci = 0.0;
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+                cr = fma(s_w[l * NC + q], zr[q], cr);
+                ci = fma(s_w[l * NC + q], zi[q], ci);
+            }
+            if (cf == 0) {
+                double* o = A22 + ((size_t)w * BAS22 + l) * ksyn;
+                o[o0] = cr;
+                if (jp) o[o0 + 1] = ci;
+            } else {
+                const double2 m = mlj[l * npow + jp];  // Bessel weight Ml[l](n + m) (reference pybird.py:1040-1046)
+                double* o = ACF + ((size_t)w * BASC + l) * ksyn;
+                o[o0] = m.x * cr - m.y * ci;
+                if (jp) o[o0 + 1] = m.x * ci + m.y * cr;
+            }
+        }
+    }
+    {   // single-sum rows: k space -> the 10 P13 rows contracted with cf_l[28 + b] (3 rows); xi space -> C11[l'] x s_b[l'], Cct[l'] x s_b[NL + l']
+        const int nrows = cf == 0 ? NL : 2 * NL;
+        double* out = cf == 0 ? A13 + (size_t)w * 10 * klin : ALC + (size_t)w * 2 * NL * klin;
+        const double* c = coef + (size_t)w * 2 * nch;
+        for (int e = jp; e < nrows * nch; e += zstride) {
+            const int row = e / nch, mp = e % nch, n = nh - mp;  // harmonic mp <-> coefficient n = nh - mp
+            double vx, vy;
+            if (cf == 0) {
+                vx = vy = 0.0;
+#pragma unroll
+                for (int b = 0; b < 10; ++b) {
+                    const double2 v = linvec[(size_t)b * nch + n];
+                    vx = fma(s_cf[row * 38 + 28 + b], v.x, vx);
+                    vy = fma(s_cf[row * 38 + 28 + b], v.y, vy);
+                }
+            } else {
+                const double2 v = linvec[(size_t)(10 + row) * nch + n];
+                vx = s_b[row] * v.x;
+                vy = s_b[row] * v.y;
+            }
+            const double cr = c[n], ci = n == nh ? 0.0 : c[nch + n];
+            double* o = out + (size_t)row * klin;
             if (mp == 0) o[0] = cr * vx - ci * vy;
             else {
                 o[2 * mp - 1] = cr * vx - ci * vy;

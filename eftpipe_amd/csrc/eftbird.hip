@@ -357,6 +357,11 @@ static inline void trace_point(eftb_engine* e, int p, hipStream_t st) {
 
 static inline size_t kpad(int n) { return (size_t)(n + SYN_KPAD - 1) / SYN_KPAD * SYN_KPAD; }  // K of a first-stage GEMM: padded like the synthesis tables
 
+// loop FFTLog size of the configuration (eftb_config.nfft, 0 = 256): nh = NFFT / 2, NPOW = 2 nh + 1 powers, NCH = nh + 1 independent coefficients
+static inline int cfg_nh(const eftb_config& c) { return c.nfft ? c.nfft / 2 : NHALF; }
+static inline int cfg_npow(const eftb_config& c) { return 2 * cfg_nh(c) + 1; }
+static inline int cfg_nch(const eftb_config& c) { return cfg_nh(c) + 1; }
+
 static size_t need_table_bytes(const eftb_config& c, int id) {
     const size_t D = sizeof(double);
     const int Nn = 2 * c.NIR * c.Na;
@@ -365,17 +370,17 @@ static size_t need_table_bytes(const eftb_config& c, int id) {
         case EFTB_T_S: return D * NS;
         case EFTB_T_LNKIN: return D * c.Nkin;
         case EFTB_T_SKT: return D * kpad(c.Nkin) * c.Nk;
-        case EFTB_T_GCT: case EFTB_T_ECT: return D * kpad(c.Nkin + c.ntail) * 2 * NCH;
+        case EFTB_T_GCT: case EFTB_T_ECT: return D * kpad(c.Nkin + c.ntail) * 2 * cfg_nch(c);
         case EFTB_T_LNXTAIL: return D * c.ntail;
-        case EFTB_T_AD: return 2 * D * (size_t)(c.nbasis + (c.with_resum ? c.nbasis13 : 0)) * NPOW * AD_T;
+        case EFTB_T_AD: return 2 * D * (size_t)(c.nbasis + (c.with_resum ? c.nbasis13 : 0)) * cfg_npow(c) * (cfg_nh(c) + 2);
         case EFTB_T_EXP22: return D * 28 * BAS22;
         case EFTB_T_EXPC: return c.with_resum ? D * (size_t)c.Nl * 38 * BASC : 0;
-        case EFTB_T_MLJ: return c.with_resum ? 2 * D * c.Nl * NPOW : 0;
-        case EFTB_T_LINVEC: return 2 * D * (size_t)(10 + (c.with_resum ? (c.with_nnlo ? 3 : 2) * c.Nl : 0)) * NCH;  // M13, Mcf11, Mcfct (, McfctNNLO)
-        case EFTB_T_SYNK: return D * (size_t)KSYN * c.Nk;
-        case EFTB_T_LINK: return D * (size_t)KLIN * c.Nk;
-        case EFTB_T_SYNS: return c.with_resum ? D * (size_t)KSYN * NS : 0;
-        case EFTB_T_LINS: return c.with_resum ? D * (size_t)KLIN * NS : 0;
+        case EFTB_T_MLJ: return c.with_resum ? 2 * D * c.Nl * cfg_npow(c) : 0;
+        case EFTB_T_LINVEC: return 2 * D * (size_t)(10 + (c.with_resum ? (c.with_nnlo ? 3 : 2) * c.Nl : 0)) * cfg_nch(c);  // M13, Mcf11, Mcfct (, McfctNNLO)
+        case EFTB_T_SYNK: return D * (size_t)ksyn_of(cfg_nh(c)) * c.Nk;
+        case EFTB_T_LINK: return D * (size_t)klin_of(cfg_nh(c)) * c.Nk;
+        case EFTB_T_SYNS: return c.with_resum ? D * (size_t)ksyn_of(cfg_nh(c)) * NS : 0;
+        case EFTB_T_LINS: return c.with_resum ? D * (size_t)klin_of(cfg_nh(c)) * NS : 0;
         case EFTB_T_L11: return D * c.Nl * 3;
         case EFTB_T_LCT: return D * c.Nl * 6;
         case EFTB_T_L22: return D * c.Nl * 28;
@@ -384,7 +389,7 @@ static size_t need_table_bytes(const eftb_config& c, int id) {
         case EFTB_T_BXT: return c.with_resum ? D * kpad(c.Nkin + c.nxtail) * 2 * NS : 0;
         case EFTB_T_TYT: return 0;  // (unused id)
         case EFTB_T_LNXXTAIL: return c.with_resum ? D * c.nxtail : 0;
-        case EFTB_T_WQLAST2: return c.with_resum ? D * 2 : 0;
+        case EFTB_T_WQLAST2: return c.with_resum ? D * (c.nxtail_lo ? 4 : 2) : 0;  // (+ the first two weights for the low tail)
         case EFTB_T_QPOLY: return c.with_resum ? D * 2 * c.Nl * c.Nl * Nn * 15 : 0;
         case EFTB_T_H: return c.with_resum ? D * c.Na * NS * c.Nk : 0;
         case EFTB_T_RSBASIS: case EFTB_T_RSBASISS: return c.with_resum ? D * RS_NB * 16 : 0;
@@ -397,7 +402,7 @@ static size_t need_table_bytes(const eftb_config& c, int id) {
         case EFTB_T_APFID: return c.with_ap ? D * 2 : 0;
         case EFTB_T_LCTN: return c.with_nnlo ? D * c.Nl * 6 : 0;
         case EFTB_T_BAO: return c.optiresum && c.with_resum ? D * (2 * NS + 4) : 0;
-        case EFTB_T_GCT2: case EFTB_T_GCT2T: return c.dual_coef ? D * kpad(c.Nkin + c.ntail) * 2 * NCH : 0;
+        case EFTB_T_GCT2: case EFTB_T_GCT2T: return c.dual_coef ? D * kpad(c.Nkin + c.ntail) * 2 * cfg_nch(c) : 0;
     }
     return 0;
 }
@@ -419,7 +424,7 @@ static size_t need_buffer_elems(const eftb_config& c, int id) {
         case EFTB_B_Q: return c.with_resum ? B * 2 * c.Nl * c.Nl * Nn : 0;
         case EFTB_B_BIAS: return B * NROW;
         case EFTB_B_PLK: return B * c.Nl * c.Nk;
-        case EFTB_B_COEF: return B * 2 * NCH;
+        case EFTB_B_COEF: return B * 2 * cfg_nch(c);
         case EFTB_B_GROWS: return B * MARG_NG1 * NROW;
         case EFTB_B_LOGP: return B * MARG_OUT;
         case EFTB_B_CCTN: return c.with_nnlo && c.with_resum ? B * c.Nl * NS : 0;
@@ -469,21 +474,36 @@ static int launch_gemm_direct(hipStream_t st, SynthBatch sb, int waves = 4) {
 static int launch_antidiag_rows(eftb_engine* e, hipStream_t st, int B, int sets, const double* coef, const double* coefT, bool contracted = false) {
     const eftb_config& c = e->c;
     const int nc = c.nbasis + (c.with_resum ? c.nbasis13 : 0);
-    const dim3 grid(NPOW, (B + 63) / 64), rgrid(B, 2, 5);  // antidiag: one workgroup of four waves per (j', 64 cosmologies); build_rows: 5 x 64 lanes per (cosmology, half)
+    const int nh = cfg_nh(c), npow = 2 * nh + 1;
+    // antidiag: one workgroup of NW waves per (j', 64 cosmologies); build_rows: ceil(NPOW / 64) x 64 lanes per (cosmology, half) -- 5 at NFFT = 256
+    const dim3 grid(npow, (B + 63) / 64), rgrid(B, 2, (npow + 63) / 64);
 #define AD_ARGS B, c.max_batch, coefT, tb<double2>(e, EFTB_T_AD), e->SAD
 #define ROW_ARGS sets, c.max_batch, c.Nl, c.with_nnlo ? 3 : 2, c.nbasis, coef, e->SAD, tb<double2>(e, EFTB_T_MLJ), tb<double2>(e, EFTB_T_LINVEC), e->A22, e->A13, \
                  e->ACF, e->ALC
-    if (nc == 9) {
+#define PLK_ARGS c.max_batch, c.nbasis, coef, e->SAD, tb<double2>(e, EFTB_T_MLJ), tb<double2>(e, EFTB_T_LINVEC), e->buf[EFTB_B_BIAS], e->buf[EFTB_B_F], \
+                 tb<double>(e, EFTB_T_L11), tb<double>(e, EFTB_T_LCT), tb<double>(e, EFTB_T_L22), tb<double>(e, EFTB_T_L13), tb<int>(e, EFTB_T_GRP), \
+                 tb<double>(e, EFTB_T_EXP22), tb<double>(e, EFTB_T_EXPC), e->A22, e->A13, e->ACF, e->ALC
+    if (nh != NHALF) {  // NFFT != 256: the kernels with the FFTLog size read at run time
+        if (nc != 9 && nc != 7)
+            return fail("loop-matrix basis of dimension %d + %d is not instantiated (expected 7 + 2)", c.nbasis, c.with_resum ? c.nbasis13 : 0);
+        if (sets & 0x10) {
+            if (nc == 9 && e->ad_waves == 2) hipLaunchKernelGGL((antidiag_nh_kernel<9, 2>), grid, dim3(128), 0, st, AD_ARGS, nh);
+            else if (nc == 9) hipLaunchKernelGGL((antidiag_nh_kernel<9, 4>), grid, dim3(256), 0, st, AD_ARGS, nh);
+            else if (e->ad_waves == 2) hipLaunchKernelGGL((antidiag_nh_kernel<7, 2>), grid, dim3(128), 0, st, AD_ARGS, nh);
+            else hipLaunchKernelGGL((antidiag_nh_kernel<7, 4>), grid, dim3(256), 0, st, AD_ARGS, nh);
+        }
+        if (contracted) trace_point(e, 11, st);
+        if (contracted && nc == 9) hipLaunchKernelGGL((build_rows_plk_nh_kernel<9>), rgrid, dim3(64), 0, st, PLK_ARGS, nh);
+        else if (nc == 9) hipLaunchKernelGGL((build_rows_nh_kernel<9>), rgrid, dim3(64), 0, st, ROW_ARGS, nh);
+        else hipLaunchKernelGGL((build_rows_nh_kernel<7>), rgrid, dim3(64), 0, st, ROW_ARGS, nh);
+    } else if (nc == 9) {
         if (contracted && WHATIF_SKIP(4)) {
         } else if ((sets & 0x10) && e->ad_waves == 2) hipLaunchKernelGGL((antidiag_kernel<9, 2>), grid, dim3(128), 0, st, AD_ARGS);
         else if (sets & 0x10) hipLaunchKernelGGL((antidiag_kernel<9, 4>), grid, dim3(256), 0, st, AD_ARGS);
         if (contracted) trace_point(e, 11, st);
         if (contracted && WHATIF_SKIP(8)) {
         } else if (contracted)  // direct-P_l runs: the rows contracted with the bias before the synthesis (3 per cosmology and space)
-            hipLaunchKernelGGL((build_rows_plk_kernel<9>), rgrid, dim3(64), 0, st, c.max_batch, c.nbasis, coef, e->SAD, tb<double2>(e, EFTB_T_MLJ),
-                               tb<double2>(e, EFTB_T_LINVEC), e->buf[EFTB_B_BIAS], e->buf[EFTB_B_F], tb<double>(e, EFTB_T_L11), tb<double>(e, EFTB_T_LCT),
-                               tb<double>(e, EFTB_T_L22), tb<double>(e, EFTB_T_L13), tb<int>(e, EFTB_T_GRP), tb<double>(e, EFTB_T_EXP22),
-                               tb<double>(e, EFTB_T_EXPC), e->A22, e->A13, e->ACF, e->ALC);
+            hipLaunchKernelGGL((build_rows_plk_kernel<9>), rgrid, dim3(64), 0, st, PLK_ARGS);
         else
         hipLaunchKernelGGL((build_rows_kernel<9>), rgrid, dim3(64), 0, st, ROW_ARGS);
     } else if (nc == 7) {
@@ -495,6 +515,7 @@ static int launch_antidiag_rows(eftb_engine* e, hipStream_t st, int B, int sets,
     }
 #undef AD_ARGS
 #undef ROW_ARGS
+#undef PLK_ARGS
     return 0;
 }
 
@@ -604,10 +625,14 @@ static int launch_pipeline_operator_plk(eftb_engine* e, int B, hipStream_t st) {
 
 static void launch_prep_rows(eftb_engine* e, hipStream_t st, int B, bool first, bool ir) {
     const eftb_config& c = e->c;
-    hipLaunchKernelGGL(prep_rows_kernel, dim3(B), dim3(256), (size_t)c.Nkin * sizeof(double), st, c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin),
-                       (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], tb<double>(e, EFTB_T_LNKIN),
-                       tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), first ? e->PA1 : nullptr, e->PA2, e->PA2T,
-                       ir ? e->PA3 : nullptr, e->status + 2 * e->status_slot);
+#define PREP_ARGS c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin), (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], \
+                  tb<double>(e, EFTB_T_LNKIN), tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), \
+                  first ? e->PA1 : nullptr, e->PA2, e->PA2T, ir ? e->PA3 : nullptr, e->status + 2 * e->status_slot
+    if (c.ntail_lo || c.nxtail_lo)  // input grid above the FFTLog's xmin: low-k tails too
+        hipLaunchKernelGGL(prep_rows_lo_kernel, dim3(B), dim3(256), (size_t)c.Nkin * sizeof(double), st, PREP_ARGS, c.ntail_lo, c.nxtail_lo);
+    else
+        hipLaunchKernelGGL(prep_rows_kernel, dim3(B), dim3(256), (size_t)c.Nkin * sizeof(double), st, PREP_ARGS);
+#undef PREP_ARGS
 }
 
 static void queue_xy(eftb_engine* e, SynthBatch& sb, int B) {  // X(s), Y(s) [B][2][80] = [Pin | tail'] (BX BY ; TX TY)
@@ -694,7 +719,7 @@ static int check_status(eftb_engine* e, const char* who, int slot = -1) {
     }
     if (!bad_in && !bad_out) return 0;
     if (bad_in)
-        return fail("%s: P_lin of cosmology %d is non-finite, or not positive at its last two samples (the FFTLog power-law extrapolation needs "
+        return fail("%s: P_lin of cosmology %d is non-finite, or not positive at its last (with a low-k tail: or first) two samples (the FFTLog power-law extrapolation needs "
                     "them positive, reference fftlog.py:146-151); the outputs of that run are invalid", who, bad_in - 1);
     return fail("%s: non-finite P_l(k) for cosmology %d (EFTB_O_CHECK_FINITE)", who, bad_out - 1);
 }
@@ -729,6 +754,8 @@ static int validate_inputs(const eftb_config& c, const char* who, int B, const d
                 if (!std::isfinite(p[j])) return fail("%s: Pin[%d][%d] is not finite", who, w, j);
         if (!(p[c.Nkin - 1] > 0.0) || !(p[c.Nkin - 2] > 0.0))
             return fail("%s: Pin[%d] must be positive at its last two samples (power-law extrapolation of the FFTLog, reference fftlog.py:146-151)", who, w);
+        if ((c.ntail_lo || c.nxtail_lo) && (!(p[0] > 0.0) || !(p[1] > 0.0)))
+            return fail("%s: Pin[%d] must be positive at its first two samples (low-k power-law extrapolation of the FFTLog, reference fftlog.py:140-145)", who, w);
         if (!std::isfinite(f[w])) return fail("%s: f[%d] is not finite", who, w);
         if (c.with_ap && (!std::isfinite(DA[w]) || !std::isfinite(H[w]) || !(DA[w] > 0.0) || !(H[w] > 0.0)))
             return fail("%s: DA[%d], H[%d] must be finite and positive", who, w, w);
@@ -885,7 +912,13 @@ static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, b
         // pybird.py:1151-1160), and X(s), Y(s) when a resummation follows in this run
         if (!front_side) fst = st;
         if (front_side && WHATIF_SKIP(1)) {
-        } else if (front_side)  // operand rows and Q(f) in one launch
+        } else if (front_side && (c.ntail_lo || c.nxtail_lo))  // operand rows (with the low-k tails) and Q(f) in one launch
+            hipLaunchKernelGGL(prep_rows_qf_lo_kernel, dim3(2 * B), dim3(256), (size_t)c.Nkin * sizeof(double), fst, B, c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin),
+                               (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], tb<double>(e, EFTB_T_LNKIN),
+                               tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), e->PA1, e->PA2, e->PA2T, e->PA3,
+                               e->status + 2 * e->status_slot, c.Nl * c.Nl * e->Nn, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QPOLY), e->buf[EFTB_B_Q],
+                               c.ntail_lo, c.nxtail_lo);
+        else if (front_side)  // operand rows and Q(f) in one launch
             hipLaunchKernelGGL(prep_rows_qf_kernel, dim3(2 * B), dim3(256), (size_t)c.Nkin * sizeof(double), fst, B, c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin),
                                (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], tb<double>(e, EFTB_T_LNKIN),
                                tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), e->PA1, e->PA2, e->PA2T, e->PA3,
@@ -894,13 +927,13 @@ static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, b
         launch_prep_rows(e, fst, B, true, xy_in_prep);
         {
             SynthBatch sb{};
-            const int KP1 = (int)kpad(c.Nkin), KP2 = (int)kpad(c.Nkin + c.ntail);
+            const int KP1 = (int)kpad(c.Nkin), KP2 = (int)kpad(c.Nkin + c.ntail), NC2 = 2 * cfg_nch(c);
             queue_synth(sb, e->PA1, 0, 1, B, KP1, tb<double>(e, EFTB_T_SKT), Nk, b[EFTB_B_P11], 0, nullptr, nullptr);
-            queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT), 2 * NCH, b[EFTB_B_COEF], 0, nullptr, nullptr);
-            queue_synth(sb, tb<double>(e, EFTB_T_ECT), KP2, 2 * NCH, 1, KP2, e->PA2T, c.max_batch, e->coefT, c.max_batch, nullptr, nullptr);
+            queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT), NC2, b[EFTB_B_COEF], 0, nullptr, nullptr);
+            queue_synth(sb, tb<double>(e, EFTB_T_ECT), KP2, NC2, 1, KP2, e->PA2T, c.max_batch, e->coefT, c.max_batch, nullptr, nullptr);
             if (c.dual_coef) {
-                queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT2), 2 * NCH, e->coef2, 0, nullptr, nullptr);
-                queue_synth(sb, tb<double>(e, EFTB_T_GCT2T), KP2, 2 * NCH, 1, KP2, e->PA2T, c.max_batch, e->coefT2, c.max_batch, nullptr, nullptr);
+                queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT2), NC2, e->coef2, 0, nullptr, nullptr);
+                queue_synth(sb, tb<double>(e, EFTB_T_GCT2T), KP2, NC2, 1, KP2, e->PA2T, c.max_batch, e->coefT2, c.max_batch, nullptr, nullptr);
             }
             if (xy_in_prep) queue_xy(e, sb, B);
             if (!(front_side && WHATIF_SKIP(2)))
@@ -949,18 +982,19 @@ static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, b
         // (only the rows in use: 7 of the 8 padded basis rows per cosmology, Nl (7 + 2) = 27 of the 32 weighted ones -- 10 % of the launch's
         // matrix-core work was padding; the padded rows of Y22 / YCF stay at their initial zeros and meet zero columns in expand_kernel)
         const int ncf = c.nbasis + (c.with_resum ? c.nbasis13 : 0);
+        const int ksyn = ksyn_of(cfg_nh(c)), klin = klin_of(cfg_nh(c));  // row lengths of this NFFT (528 / 288 at 256)
         // (direct-P_l runs: 3 contracted rows per cosmology in each of these three -- same strides, fewer rows)
-        if (k22) queue_synth(sb, e->A22, (long long)BAS22 * KSYN, B, direct ? 3 : c.nbasis, KSYN, tb<double>(e, EFTB_T_SYNK), Nk, e->Y22, (long long)BAS22 * Nk, nullptr, nullptr);
-        if (c22) queue_synth(sb, e->ACF, (long long)BASC * KSYN, B, direct ? 3 : Nl * ncf, KSYN, tb<double>(e, EFTB_T_SYNS), NS, e->YCF, (long long)BASC * NS, nullptr, nullptr);
+        if (k22) queue_synth(sb, e->A22, (long long)BAS22 * ksyn, B, direct ? 3 : c.nbasis, ksyn, tb<double>(e, EFTB_T_SYNK), Nk, e->Y22, (long long)BAS22 * Nk, nullptr, nullptr);
+        if (c22) queue_synth(sb, e->ACF, (long long)BASC * ksyn, B, direct ? 3 : Nl * ncf, ksyn, tb<double>(e, EFTB_T_SYNS), NS, e->YCF, (long long)BASC * NS, nullptr, nullptr);
         if (mask & EFTB_S_LOOPS)
-            queue_synth(sb, e->A13, 10LL * KLIN, B, direct ? 3 : 10, KLIN, tb<double>(e, EFTB_T_LINK), Nk, b[EFTB_B_P13], 10LL * Nk, b[EFTB_B_P11], nullptr);
+            queue_synth(sb, e->A13, 10LL * klin, B, direct ? 3 : 10, klin, tb<double>(e, EFTB_T_LINK), Nk, b[EFTB_B_P13], 10LL * Nk, b[EFTB_B_P11], nullptr);
         if (mask & EFTB_S_CF) {
-            const long long ag = (c.with_nnlo ? 3LL : 2LL) * Nl * KLIN;
-            queue_synth(sb, e->ALC, ag, B, Nl, KLIN, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_C11], (long long)Nl * NS, nullptr, nullptr);
-            queue_synth(sb, e->ALC + (size_t)Nl * KLIN, ag, B, Nl, KLIN, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCT], (long long)Nl * NS,
+            const long long ag = (c.with_nnlo ? 3LL : 2LL) * Nl * klin;
+            queue_synth(sb, e->ALC, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_C11], (long long)Nl * NS, nullptr, nullptr);
+            queue_synth(sb, e->ALC + (size_t)Nl * klin, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCT], (long long)Nl * NS,
                         nullptr, e->sm2);
             if (c.with_nnlo)  // makeCctNNLO (reference pybird.py:1098-1101)
-                queue_synth(sb, e->ALC + (size_t)2 * Nl * KLIN, ag, B, Nl, KLIN, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCTN], (long long)Nl * NS,
+                queue_synth(sb, e->ALC + (size_t)2 * Nl * klin, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCTN], (long long)Nl * NS,
                             nullptr, e->sm4);
         }
         {
@@ -1437,6 +1471,12 @@ int eftb_create(const eftb_config* cfg, eftb_engine** out) {
     if (c.Nk < 8 || c.Nkin < 4 || c.max_batch < 1) return fail("eftb_create: bad dimensions Nk=%d Nkin=%d max_batch=%d", c.Nk, c.Nkin, c.max_batch);
     if (c.step_batch < 0 || c.step_batch > c.max_batch) return fail("eftb_create: step_batch=%d outside [0, max_batch=%d]", c.step_batch, c.max_batch);
     if (c.nbasis < 1 || c.nbasis > 16) return fail("eftb_create: nbasis=%d outside [1, 16]", c.nbasis);
+    if (c.nfft != 0 && (c.nfft % 2 || c.nfft < 2 * NHALF || c.nfft > 512))
+        return fail("eftb_create: nfft=%d unsupported (even values from 256 to 512; 0 = 256)", c.nfft);
+    if (c.ntail < 0 || c.nxtail < 0 || c.ntail_lo < 0 || c.ntail_lo > c.ntail || c.nxtail_lo < 0 || c.nxtail_lo > c.nxtail ||
+        ((c.ntail_lo || c.nxtail_lo) && c.Nkin < 2))
+        return fail("eftb_create: tails (ntail %d, ntail_lo %d, nxtail %d, nxtail_lo %d) inconsistent", c.ntail, c.ntail_lo, c.nxtail, c.nxtail_lo);
+    if (c.nxtail_lo && !c.with_resum) return fail("eftb_create: nxtail_lo needs with_resum=1");
     if (c.nbasis > BAS22 || (c.with_resum && c.Nl * (c.nbasis + c.nbasis13) > BASC)) return fail("eftb_create: loop basis %d + %d too large", c.nbasis, c.nbasis13);
     if (c.with_resum && !((c.Nl == 3 && c.NIR == 16 && c.Na == 3) || (c.Nl == 2 && c.NIR == 8 && c.Na == 2)))
         return fail("eftb_create: (Nl, NIR, Na) = (%d, %d, %d) unsupported", c.Nl, c.NIR, c.Na);
@@ -1515,23 +1555,25 @@ int eftb_create(const eftb_config* cfg, eftb_engine** out) {
     // scratch of the anti-diagonal pipeline; padded rows / coefficients of the synthesis rows stay zero
     {
         const size_t nc = c.nbasis + (c.with_resum ? c.nbasis13 : 0);
+        // sizes of this NFFT: NCH coefficients, NPOW anti-diagonals, synthesis rows of 1 + 4 nh / 1 + 2 nh (padded)
+        const size_t nch = cfg_nch(c), npow = cfg_npow(c), ksyn = ksyn_of(cfg_nh(c)), klin = klin_of(cfg_nh(c));
         auto zalloc = [](double** p, size_t n) {
             if (hipMalloc(p, n * sizeof(double)) != hipSuccess) return 1;
             return hipMemset(*p, 0, n * sizeof(double)) != hipSuccess ? 1 : 0;
         };
-        int bad = zalloc(&e->coefT, 2 * NCH * B);
+        int bad = zalloc(&e->coefT, 2 * nch * B);
         bad |= zalloc(&e->PA1, B * kpad(c.Nkin)) | zalloc(&e->PA2, B * kpad(c.Nkin + c.ntail)) | zalloc(&e->PA2T, B * kpad(c.Nkin + c.ntail));
         if (c.with_resum) bad |= zalloc(&e->PA3, B * kpad(c.Nkin + c.nxtail));
-        if (c.dual_coef) bad |= zalloc(&e->coef2, 2 * NCH * B) | zalloc(&e->coefT2, 2 * NCH * B);
-        bad |= zalloc(reinterpret_cast<double**>(&e->SAD), 2 * (size_t)AD_CH * B * nc * NPOW);
-        bad |= zalloc(&e->A22, B * BAS22 * KSYN) | zalloc(&e->A13, B * 10 * KLIN) | zalloc(&e->Y22, B * BAS22 * c.Nk);
-        if (c.with_resum) bad |= zalloc(&e->ACF, B * BASC * KSYN) | zalloc(&e->ALC, B * (c.with_nnlo ? 3 : 2) * c.Nl * KLIN) | zalloc(&e->YCF, B * BASC * NS);
+        if (c.dual_coef) bad |= zalloc(&e->coef2, 2 * nch * B) | zalloc(&e->coefT2, 2 * nch * B);
+        bad |= zalloc(reinterpret_cast<double**>(&e->SAD), 2 * (size_t)AD_CH * B * nc * npow);
+        bad |= zalloc(&e->A22, B * BAS22 * ksyn) | zalloc(&e->A13, B * 10 * klin) | zalloc(&e->Y22, B * BAS22 * c.Nk);
+        if (c.with_resum) bad |= zalloc(&e->ACF, B * BASC * ksyn) | zalloc(&e->ALC, B * (c.with_nnlo ? 3 : 2) * c.Nl * klin) | zalloc(&e->YCF, B * BASC * NS);
         if (bad) return fail("eftb_create: out of device memory for the loop scratch");
         if (c.with_resum && c.Nl == 3 && !c.dual_coef) {  // second set of the front's outputs (direct-P_l runs, see FrontSet)
             eftb_engine::FrontSet& a = e->alt;
-            bad = zalloc(&a.coefT, 2 * NCH * B) | zalloc(&a.PA1, B * kpad(c.Nkin)) | zalloc(&a.PA2, B * kpad(c.Nkin + c.ntail)) | zalloc(&a.PA2T, B * kpad(c.Nkin + c.ntail)) |
-                  zalloc(&a.PA3, B * kpad(c.Nkin + c.nxtail)) | zalloc(reinterpret_cast<double**>(&a.SAD), 2 * (size_t)AD_CH * B * nc * NPOW) |
-                  zalloc(&a.A22, B * BAS22 * KSYN) | zalloc(&a.A13, B * 10 * KLIN) | zalloc(&a.ACF, B * BASC * KSYN) | zalloc(&a.ALC, B * (c.with_nnlo ? 3 : 2) * c.Nl * KLIN) |
+            bad = zalloc(&a.coefT, 2 * nch * B) | zalloc(&a.PA1, B * kpad(c.Nkin)) | zalloc(&a.PA2, B * kpad(c.Nkin + c.ntail)) | zalloc(&a.PA2T, B * kpad(c.Nkin + c.ntail)) |
+                  zalloc(&a.PA3, B * kpad(c.Nkin + c.nxtail)) | zalloc(reinterpret_cast<double**>(&a.SAD), 2 * (size_t)AD_CH * B * nc * npow) |
+                  zalloc(&a.A22, B * BAS22 * ksyn) | zalloc(&a.A13, B * 10 * klin) | zalloc(&a.ACF, B * BASC * ksyn) | zalloc(&a.ALC, B * (c.with_nnlo ? 3 : 2) * c.Nl * klin) |
                   zalloc(&a.P11, e->buf_elems[EFTB_B_P11]) | zalloc(&a.COEF, e->buf_elems[EFTB_B_COEF]) | zalloc(&a.XY, e->buf_elems[EFTB_B_XY]) |
                   zalloc(&a.Q, e->buf_elems[EFTB_B_Q]);
             if (bad) return fail("eftb_create: out of device memory for the second front set");

@@ -52,6 +52,9 @@ class Engine:
         c.with_nnlo = int(cfg.with_NNLO)
         c.dual_coef = int("Gc2" in t)
         c.optiresum = int(cfg.optiresum and cfg.with_resum)
+        c.nfft = 0 if cfg.NFFT == 256 else int(cfg.NFFT)   # (0: the default size, the struct's layout before the field existed)
+        c.ntail_lo = int(t["ntail_lo"])
+        c.nxtail_lo = int(t.get("nxtail_lo", 0))
         self._cconf = c
         h = C.c_void_p()
         L.check(self.lib.eftb_create(C.byref(c), C.byref(h)))
@@ -72,18 +75,19 @@ class Engine:
         # first-stage operators as GEMM operands: K-major, zero padded to a multiple of 48 rows (include/eftbird.h)
         kpad = lambda n: (n + 47) // 48 * 48
         Nkin, ntail = t["kin"].size, t["lnx_tail"].size
+        nch = t["Gc"].shape[1]   # NFFT / 2 + 1 independent coefficients (129 at NFFT = 256)
 
-        def stack_gc(G):  # [2, 129, Nkin] (+ the tail operator Ec [2, 129, ntail]) -> [KP, 258]
-            out = np.zeros((kpad(Nkin + ntail), 2 * 129))
+        def stack_gc(G, E):  # [2, NCH, Nkin] (+ the tail operator E [2, NCH, ntail]) -> [KP, 2 NCH]
+            out = np.zeros((kpad(Nkin + ntail), 2 * nch))
             for c_ in range(2):
-                out[:Nkin, c_ * 129 : (c_ + 1) * 129] = G[c_].T
-                out[Nkin : Nkin + ntail, c_ * 129 : (c_ + 1) * 129] = t["Ec"][c_].T
+                out[:Nkin, c_ * nch : (c_ + 1) * nch] = G[c_].T
+                out[Nkin : Nkin + ntail, c_ * nch : (c_ + 1) * nch] = E[c_].T
             return out
 
         skt = np.zeros((kpad(Nkin), self.Nk))
         skt[:Nkin] = t["Sk"].T
         self._set("SKT", skt)
-        gct = stack_gc(t["Gc"])
+        gct = stack_gc(t["Gc"], t["Ec"])
         self._set("GCT", gct)
         self._set("ECT", gct.T)
         self._set("LNXTAIL", t["lnx_tail"])
@@ -103,7 +107,7 @@ class Engine:
         if "bao" in t:
             self._set("BAO", t["bao"])
         if "Gc2" in t:
-            gct2 = stack_gc(t["Gc2"])
+            gct2 = stack_gc(t["Gc2"], t["Ec2"])
             self._set("GCT2", gct2)
             self._set("GCT2T", gct2.T)
         if cfg.with_resum:

@@ -96,7 +96,7 @@ _ENGINES: "weakref.WeakKeyDictionary[Common, Engine]" = weakref.WeakKeyDictionar
 
 
 _ENGINE_DEFAULTS = dict(nbinsmu=200, LambdaIR=0.2, NFFT_resum=192, resum_window=None, fft_window=0.2, kin=None,
-                        irf_soffset=1.0, irf_rescale=1.0, irf_window=None)
+                        irf_soffset=1.0, irf_rescale=1.0, irf_window=None, NFFT=256)
 _DEFAULT_KIN = np.logspace(-5, 0, 200)  # reference theory.py:562
 
 
@@ -116,7 +116,7 @@ def engine_for(co, loop_cache=None, **opts):
     if eng is not None and (eng.Nk != co.Nk or not np.array_equal(eng.k, co.k) or eng.cfg.nbinsmu != store["nbinsmu"]
                             or eng.cfg.fft_window != store["fft_window"] or not np.array_equal(eng.kin, kin_now)
                             or (eng.cfg.irf_soffset, eng.cfg.irf_rescale, eng.cfg.irf_window) != (store["irf_soffset"], store["irf_rescale"], store["irf_window"])
-                            or eng.cfg.LambdaIR != store["LambdaIR"] or eng.cfg.NFFT_resum != store["NFFT_resum"]
+                            or eng.cfg.LambdaIR != store["LambdaIR"] or eng.cfg.NFFT_resum != store["NFFT_resum"] or eng.cfg.NFFT != store["NFFT"]
                             or eng.cfg.resum_window != store["resum_window"]
                             or eng.cfg.with_NNLO != bool(co.with_NNLO) or eng.cfg.IRcutoff != co.IRcutoff or eng.cfg.kIR != co.kIR
                             or eng.cfg.optiresum != bool(co.optiresum)):
@@ -128,7 +128,7 @@ def engine_for(co, loop_cache=None, **opts):
                            nbinsmu=store["nbinsmu"], LambdaIR=store["LambdaIR"], NFFT_resum=store["NFFT_resum"], resum_window=store["resum_window"],
                            with_NNLO=bool(co.with_NNLO), IRcutoff=co.IRcutoff, kIR=co.kIR, optiresum=bool(co.optiresum),
                            fft_window=store["fft_window"], kin=None if store["kin"] is None else np.array(store["kin"], dtype=np.float64),
-                           irf_soffset=store["irf_soffset"], irf_rescale=store["irf_rescale"], irf_window=store["irf_window"])
+                           irf_soffset=store["irf_soffset"], irf_rescale=store["irf_rescale"], irf_window=store["irf_window"], NFFT=store["NFFT"])
         eng = _ENGINES[co] = Engine(cfg, max_batch=1, loop_cache=loop_cache)
     return eng
 
@@ -401,12 +401,14 @@ class NonLinear(HasLogger):
     another FFTLog configuration, or an unreadable one, is ignored with a warning and the matrices are recomputed."""
 
     def __init__(self, load=True, save=True, path="./", NFFT=256, co=common, name="pybird.nonlinear"):
-        from .tables import PYEGG_KEYS, loop_matrices, pyegg_path
+        from .tables import NFFT_MIN, PYEGG_KEYS, check_nfft, loop_matrices, pyegg_path
 
         self.set_logger(name=name)
-        if NFFT != 256:
-            raise NotImplementedError("the HIP engine is specialised for NFFT=256 (reference default)")
-        self.co = co
+        NFFT = int(NFFT)
+        if NFFT % 2 == 0 and NFFT < NFFT_MIN:  # a coarser grid would only trade accuracy for speed the device does not need
+            raise NotImplementedError(f"the HIP engine runs NFFT from {NFFT_MIN} up (reference default 256), not NFFT={NFFT}")
+        check_nfft(NFFT)                       # odd values, or above the largest size the kernels are sized for: ValueError
+        self.co, self.NFFT = co, NFFT
         self.fftsettings = dict(Nmax=NFFT, xmin=1.5e-5, xmax=1000.0, bias=-1.6)
         egg = pyegg_path(path, NFFT, co.Nl)
         cache = None
@@ -419,12 +421,12 @@ class NonLinear(HasLogger):
                 self.mpi_warning("Can't load loop matrices at %s, computing new matrices.", path)
         if cache is not None:
             try:
-                engine_for(co, loop_cache=cache)
+                engine_for(co, loop_cache=cache, NFFT=NFFT)
             except ValueError:
                 self.mpi_warning("Loaded loop matrices do not correspond to asked FFTLog configuration, computing new matrices.")
                 cache, save = None, save
         if cache is None:
-            engine_for(co)
+            engine_for(co, NFFT=NFFT)
         self.loaded = cache is not None
         if save is True and cache is None:
             try:
@@ -445,11 +447,11 @@ class NonLinear(HasLogger):
         kin, Pin = bird.kin, bird.Pin
         if IRcut:
             idx = int(np.searchsorted(kin, self.co.kIR))
-            op = FFTLogOperator(256, 1.5e-5, 1000.0, -1.6, kin[idx:], window, extrap=("padding", "extrap"))
+            op = FFTLogOperator(self.NFFT, 1.5e-5, 1000.0, -1.6, kin[idx:], window, extrap=("padding", "extrap"))
             Pin = Pin[idx:]
             kin = kin[idx:]
         else:
-            op = FFTLogOperator(256, 1.5e-5, 1000.0, -1.6, kin, window)
+            op = FFTLogOperator(self.NFFT, 1.5e-5, 1000.0, -1.6, kin, window)
         c = op.G @ Pin
         if op.high_active:
             slope = (np.log(Pin[-1]) - np.log(Pin[-2])) / (np.log(kin[-1]) - np.log(kin[-2]))

@@ -30,8 +30,15 @@ from scipy.special import legendre, spherical_jn
 from . import loopmath as lm
 
 NS = 80          # |sbird|
-NPOW = 257       # NFFT + 1 for the loop FFTLog
+NPOW = 257       # NFFT + 1 for the loop FFTLog at the default NFFT = 256 (build_tables takes the size from EngineConfig.NFFT)
 NHALF = 128
+NFFT_MIN, NFFT_MAX = 256, 512   # loop FFTLog sizes the engine supports (even values)
+
+
+def check_nfft(NFFT):
+    """The loop FFTLog sizes the device kernels run: every even NFFT from 256 to 512 (reference fftlog.py:62-63 takes any even value)."""
+    if NFFT % 2 or NFFT < NFFT_MIN or NFFT > NFFT_MAX:
+        raise ValueError(f"NFFT={NFFT} unsupported: the HIP engine takes even values from {NFFT_MIN} to {NFFT_MAX}")
 
 
 # ----------------------------------------------------------------------------- FFTLog as an operator
@@ -124,19 +131,20 @@ def antidiagonal_tables(M22b, M13b):
     serve P22 at every k and, multiplied by Ml(n + m), C22 / C13 at every s and l.  S[-j'] = conj S[j'], so only
     j' = 0..N is kept.  Exact regrouping of the same sum (verified to 1e-15 against the reference in tests).
 
-    -> AD[c, j', t] complex, t = 0..128: the symmetrised weight of the pair (n, m) = (j' + t, N - t), n <= m, of matrix c
+    -> AD[c, j', t] complex, t = 0..N/2: the symmetrised weight of the pair (n, m) = (j' + t, N - t), n <= m, of matrix c
        (M22 basis first: M[n,m] + M[m,n], or M[n,n]; then the row-broadcast M13 basis: V[n] + V[m], or V[n]); zero
-       beyond the end of the anti-diagonal."""
-    N = NPOW - 1
+       beyond the end of the anti-diagonal.  N + 1 = M22b.shape[-1] (257 at the default NFFT = 256)."""
+    npow = np.shape(M22b)[-1]
+    N = npow - 1
     mats = [np.asarray(M22b)]
     if M13b is not None:
-        mats.append(np.asarray(M13b)[:, :, None] * np.ones((1, 1, NPOW)))
+        mats.append(np.asarray(M13b)[:, :, None] * np.ones((1, 1, npow)))
     M = np.concatenate(mats)
     Ms = M + np.swapaxes(M, 1, 2)
-    idx = np.arange(NPOW)
+    idx = np.arange(npow)
     Ms[:, idx, idx] = M[:, idx, idx]
-    AD = np.zeros((M.shape[0], NPOW, NHALF + 2), dtype=complex)
-    for jp in range(NPOW):
+    AD = np.zeros((M.shape[0], npow, N // 2 + 2), dtype=complex)
+    for jp in range(npow):
         cnt = ((N + jp) >> 1) - jp + 1
         tt = np.arange(cnt)
         AD[:, jp, :cnt] = Ms[:, jp + tt, N - tt]
@@ -308,8 +316,9 @@ def loop_matrices(Nl, NFFT=256, bias=-1.6, xmin=1.5e-5, xmax=1000.0):
 def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
     """-> {name: ndarray} of every constant table, float64 / int32, C-contiguous, device layout.
     ``loop_cache``: the arrays of a reference ``pyegg*.npz`` (M22, M13, Mcf11, Mcfct are used) instead of recomputing them."""
-    if cfg.NFFT != 256:
-        raise ValueError("the HIP engine is specialised for NFFT=256 (the reference default, pybird.py:912)")
+    check_nfft(cfg.NFFT)
+    NFFT = cfg.NFFT
+    npow, nh = NFFT + 1, NFFT // 2
     Nl = cfg.Nl
     if Nl not in (2, 3):
         raise ValueError("Nl must be 2 or 3")
@@ -332,6 +341,8 @@ def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
         bao[NS + sr_idx] = tt * s[ihi] ** 2 / s[sr_idx] ** 2
         bao[2 * NS :] = [ilo, ihi, idlow, idhigh]
     Nk, Nkin = k.size, kin.size
+    if kin[0] > k[0]:  # the reference's interp1d in Bird.__init__ raises below its first sample (pybird.py:693-695): no silent extrapolation
+        raise ValueError(f"the input grid starts at kin[0]={kin[0]:.6g}, above the first k={k[0]:.6g}: P11 would be extrapolated")
     t = dict(k=k, kin=kin, s=s)
     w = lm.mu_weights(Nl)
     t.update(w)
@@ -342,7 +353,7 @@ def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
     # ---- P11 = Sk @ Pin
     t["Sk"] = np.ascontiguousarray(CubicSpline(kin, np.eye(Nkin), axis=0)(k))
 
-    # ---- loop FFTLog as an operator on Pin; only the 129 independent coefficients are kept
+    # ---- loop FFTLog as an operator on Pin; only the NFFT/2 + 1 independent coefficients are kept
     ircut = "all" if cfg.IRcutoff is True else cfg.IRcutoff
     if ircut not in (False, "all", "loop", "resum"):
         raise ValueError(f"unexpected IRcutoff option: {ircut}")
@@ -357,19 +368,27 @@ def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
         o.G = np.hstack([np.zeros((o.G.shape[0], icut), dtype=complex), o.G])
         return o
 
-    op = FFTLogOperator(256, 1.5e-5, 1000.0, -1.6, kin, cfg.fft_window)
-    if op.low_active:
-        raise ValueError("kin[0] must not exceed the FFTLog xmin=1.5e-5 (low-k extrapolation unsupported)")
-    nh = NHALF + 1
+    # (reference pybird.py:1127-1141: ("extrap", "extrap"), or ("padding", "extrap") for the IR-cut set: a grid that starts above xmin
+    # gets a low-k power-law tail on the uncut operator only)
+    op = FFTLogOperator(NFFT, 1.5e-5, 1000.0, -1.6, kin, cfg.fft_window)
+    nch = nh + 1
     # coefficient sets of the k-space (P22, P13) and xi-space (C11, Cct, C22, C13) pieces (reference pybird.py:1151-1160)
-    op_cut = cut_operator(256, 1.5e-5, 1000.0, -1.6, cfg.fft_window) if ircut else None
+    op_cut = cut_operator(NFFT, 1.5e-5, 1000.0, -1.6, cfg.fft_window) if ircut else None
     op_k = op_cut if ircut in ("all", "loop") else op
     op_s = op_cut if ircut in ("all", "resum") else op
-    t["Gc"] = np.ascontiguousarray(np.stack([op_k.G[:nh].real, op_k.G[:nh].imag]))        # [2,129,Nkin]
+    ntail_lo = op.lnx_lo.size if (op_k is op or op_s is op) else 0   # low-k tail columns, after the high-k ones
+
+    def tail_op(o):  # [2, NCH, ntail (+ ntail_lo)]: the high-k tail (the same for every operator), then this operator's low-k one
+        E = np.hstack([op.E_hi[:nch], o.E_lo[:nch] if o.low_active else np.zeros((nch, ntail_lo), complex)])
+        return np.ascontiguousarray(np.stack([E.real, E.imag]))
+
+    t["Gc"] = np.ascontiguousarray(np.stack([op_k.G[:nch].real, op_k.G[:nch].imag]))      # [2,NCH,Nkin]
+    t["Ec"] = tail_op(op_k)                                                                  # [2,NCH,Ntail]
     if op_s is not op_k:
-        t["Gc2"] = np.ascontiguousarray(np.stack([op_s.G[:nh].real, op_s.G[:nh].imag]))
-    t["Ec"] = np.ascontiguousarray(np.stack([op.E_hi[:nh].real, op.E_hi[:nh].imag]))      # [2,129,Ntail]
-    t["lnx_tail"] = op.lnx_hi
+        t["Gc2"] = np.ascontiguousarray(np.stack([op_s.G[:nch].real, op_s.G[:nch].imag]))
+        t["Ec2"] = tail_op(op_s)
+    t["lnx_tail"] = np.concatenate([op.lnx_hi, op.lnx_lo[:ntail_lo]])
+    t["ntail_lo"] = ntail_lo
     Pow = op.Pow
     nu = -0.5 * Pow
     # ---- one-loop pieces through the anti-diagonal form (see antidiagonal_tables)
@@ -377,7 +396,7 @@ def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
         if np.shape(loop_cache["Pow"]) != Pow.shape or np.any(np.asarray(loop_cache["Pow"]) != Pow):
             raise ValueError("loop-matrix cache was written for a different FFTLog configuration")
         M22, M13 = np.asarray(loop_cache["M22"]), np.asarray(loop_cache["M13"])
-        if M22.shape != (28, NPOW, NPOW) or M13.shape != (10, NPOW):
+        if M22.shape != (28, npow, npow) or M13.shape != (10, npow):
             raise ValueError("loop-matrix cache has the wrong shapes")
     else:
         M22 = lm.matrices_22(nu)
@@ -397,26 +416,26 @@ def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
             expc[Nl * 28 + l * 10 : Nl * 28 + (l + 1) * 10, l * (nb + nb13) + nb : (l + 1) * (nb + nb13)] = comb13
         t["expand_c"] = expc
         t["ad"] = antidiagonal_tables(M22[basis], M13[basis13])
-        jp = np.arange(NPOW)
+        jp = np.arange(npow)
         t["mlj"] = lm.bessel_weight(ells[:, None], -op.bias - 0.5j * op.dpow * jp[None, :] - 1.5)   # Ml depends on n + m only
-        if loop_cache is not None and np.shape(loop_cache["Mcf11"]) == (Nl, NPOW):
+        if loop_cache is not None and np.shape(loop_cache["Mcf11"]) == (Nl, npow):
             vecs += [np.asarray(loop_cache["Mcf11"]), np.asarray(loop_cache["Mcfct"])]
         else:
             vecs += [lm.bessel_weight(ells[:, None], nu[None, :]), lm.bessel_weight(ells[:, None], nu[None, :] - 1.0)]
         if cfg.with_NNLO:  # McfctNNLO (reference pybird.py:1054-1056)
-            if loop_cache is not None and np.shape(loop_cache.get("McfctNNLO")) == (Nl, NPOW):
+            if loop_cache is not None and np.shape(loop_cache.get("McfctNNLO")) == (Nl, npow):
                 vecs.append(np.asarray(loop_cache["McfctNNLO"]))
             else:
                 vecs.append(lm.bessel_weight(ells[:, None], nu[None, :] - 2.0))
-        t["syn_s"] = synthesis_table(np.log(s), -2.0 * op.bias - 6.0, op.dpow, NPOW - 1, sign=-1.0)
-        t["lin_s"] = synthesis_table(np.log(s), -op.bias - 3.0, op.dpow, NHALF, sign=+1.0)
+        t["syn_s"] = synthesis_table(np.log(s), -2.0 * op.bias - 6.0, op.dpow, NFFT, sign=-1.0)
+        t["lin_s"] = synthesis_table(np.log(s), -op.bias - 3.0, op.dpow, nh, sign=+1.0)
     else:
         t["ad"] = antidiagonal_tables(M22[basis], None)
-    t["linvec"] = np.ascontiguousarray(np.concatenate(vecs)[:, :nh])          # [10 (+ 2|3 Nl), 129] complex: M13, Mcf11, Mcfct (, McfctNNLO)
+    t["linvec"] = np.ascontiguousarray(np.concatenate(vecs)[:, :nch])         # [10 (+ 2|3 Nl), NCH] complex: M13, Mcf11, Mcfct (, McfctNNLO)
     if cfg.with_NNLO:
         t["lctn"] = np.concatenate([w["lctNNLO"], np.zeros((Nl, 3))], axis=1)  # the NNLO block keeps lctNNLO in the first 3 Pctl slots
-    t["syn_k"] = synthesis_table(np.log(k), 3.0 + 2.0 * op.bias, op.dpow, NPOW - 1, sign=+1.0)
-    t["lin_k"] = synthesis_table(np.log(k), 3.0 + op.bias, op.dpow, NHALF, sign=-1.0)
+    t["syn_k"] = synthesis_table(np.log(k), 3.0 + 2.0 * op.bias, op.dpow, NFFT, sign=+1.0)
+    t["lin_k"] = synthesis_table(np.log(k), 3.0 + op.bias, op.dpow, nh, sign=-1.0)
 
     # ---- IR-resummation
     if cfg.with_resum:
@@ -435,23 +454,24 @@ def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
             t["bao"] = bao
         # IR filters: q = Pin * exp(-k^2/L^2)/k^2 -> FFTLog(32) -> j0/j2 sums -> X, Y
         wq = np.exp(-(kin**2) / cfg.LambdaIR**2) / kin**2
+        # (reference pybird.py:1316-1335: "extrap" at both ends, the cut modes pad the low end)
         xop = (cut_operator(32, 1.5e-5, 10.0, -2.6, cfg.irf_window) if ircut in ("all", "resum")
                else FFTLogOperator(32, 1.5e-5, 10.0, -2.6, kin, cfg.irf_window))
-        if xop.low_active:
-            raise ValueError("kin[0] must not exceed 1.5e-5")
         XM = np.stack([lm.bessel_weight(2 * l, -0.5 * xop.Pow) for l in range(2)])
         XsPow = np.exp(np.outer(-xop.Pow - 3.0, np.log(s)))              # [33,Ns]
         K = lambda D: np.real(np.einsum("ln,ns,ni->lsi", XM, XsPow, D))   # [2,Ns,cols]
         soff = cfg.irf_soffset ** (-xop.Pow - 3.0)                       # X0offset: the j0 sum at s = soffset (pybird.py:1339-1346)
         Koff = lambda D: np.real(np.einsum("n,ni->i", XM[0] * soff, D))
-        body, tail = K(xop.G), K(xop.E_hi)
-        boff, toff = Koff(xop.G), Koff(xop.E_hi)
+        Ex = np.hstack([xop.E_hi, xop.E_lo])                             # the high-k tail columns, then the low-k ones
+        body, tail = K(xop.G), K(Ex)
+        boff, toff = Koff(xop.G), Koff(Ex)
         t["BX"] = np.ascontiguousarray(cfg.irf_rescale * 2.0 / 3.0 * (boff[None, :] - body[0] - body[1]) * wq[None, :])
         t["BY"] = np.ascontiguousarray(2.0 * body[1] * wq[None, :])
         t["TX"] = np.ascontiguousarray(cfg.irf_rescale * 2.0 / 3.0 * (toff[None, :] - tail[0] - tail[1]))
         t["TY"] = np.ascontiguousarray(2.0 * tail[1])
-        t["lnx_xtail"] = xop.lnx_hi
-        t["wq_last2"] = wq[-2:].copy()
+        t["lnx_xtail"] = np.concatenate([xop.lnx_hi, xop.lnx_lo])
+        t["nxtail_lo"] = xop.lnx_lo.size
+        t["wq_last2"] = np.concatenate([wq[-2:], wq[:2]]) if xop.low_active else wq[-2:].copy()
         t["Qpoly"] = lm.q_polynomials(Nl)
         t["resum_dims"] = np.array([NIR, Na, int(np.sum(~kr_mask))], dtype=np.int32)
         t.update(resum_mfma_tables(t["Qpoly"], NIR, Na))

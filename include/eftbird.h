@@ -37,8 +37,8 @@ typedef struct eftb_config {
     int32_t with_ap;       /* Alcock-Paczynski on                                       theory.py:582 */
     int32_t ap_stochastic; /* APeffect(APst=True): distort Pstl too                     pybird.py:1618 */
     int32_t nmu;           /* AP mu nodes (nbinsmu*accboost)                            pybird.py:1538 */
-    int32_t ntail;         /* high-k power-law tail length of the loop FFTLog           fftlog.py:146-151 */
-    int32_t nxtail;        /* same for the 32-point IR-filter FFTLog                    pybird.py:1293 */
+    int32_t ntail;         /* power-law tail length of the loop FFTLog (high-k columns, then the ntail_lo low-k ones)   fftlog.py:140-151 */
+    int32_t nxtail;        /* same for the 32-point IR-filter FFTLog (then the nxtail_lo low-k ones)                   pybird.py:1293 */
     int32_t nbasis;        /* dimension of the span of the 28 M22 loop matrices (7)     tables.py loop_basis */
     int32_t nbasis13;      /* dimension of the span of the 10 M13 vectors (2)           tables.py loop_basis */
     int32_t NIR, Na, Nklow;/* Resum.NIR, Resum.Na, Common.Nklow                         pybird.py:1247-1259, 560 */
@@ -50,14 +50,26 @@ typedef struct eftb_config {
     int32_t step_batch;    /* largest batch of ONE staged step (0 = max_batch).  With step_batch < max_batch, staged steps that are still queued
                               when the submission thread reaches them are launched TOGETHER, as one batch of up to max_batch cosmologies (same
                               bits per cosmology; each step is still fetched by itself).  No reference counterpart. */
+    /* appended fields (0 = the behaviour before they existed) */
+    int32_t nfft;          /* loop FFTLog size NonLinear(NFFT): even, 256..512; 0 = 256.  NCH = nfft / 2 + 1 independent coefficients,
+                              NPOW = nfft + 1 powers                                    pybird.py:907-919 */
+    int32_t ntail_lo;      /* input grids starting above the FFTLog's xmin = 1.5e-5: the last ntail_lo of the ntail tail columns continue Pin
+                              below kin[0] (slope and amplitude of its first two samples, which must then be positive)   fftlog.py:140-145 */
+    int32_t nxtail_lo;     /* same for the IR-filter FFTLog: the last nxtail_lo of the nxtail columns; EFTB_T_WQLAST2 then holds 4 weights */
 } eftb_config;
 
 /* Constant tables (built on the host by eftpipe_amd/tables.py; shapes in that file).  The first-stage operators are stored as GEMM operands,
  * K-major and zero padded to KP(n) = n rounded up to a multiple of 48 (the K chunk of the matrix-core kernel):
  *   EFTB_T_SKT [KP(Nkin)][Nk]                   P11 = Pin . SKT                                        (pybird.py:694-695)
- *   EFTB_T_GCT [KP(Nkin + ntail)][2 * 129]      FFTLog coefficients (re | im halves) = [Pin | tail] . GCT   (fftlog.py:84-166)
- *   EFTB_T_ECT [2 * 129][KP(Nkin + ntail)]      = GCT transposed: the same product with the batch as the column dimension
+ * Sizes that follow the loop FFTLog are written with NCH = nfft / 2 + 1 (129 at the default 256), NPOW = 2 NCH - 1 and NH = NCH - 1:
+ *   EFTB_T_GCT [KP(Nkin + ntail)][2 * NCH]      FFTLog coefficients (re | im halves) = [Pin | tail] . GCT   (fftlog.py:84-166)
+ *   EFTB_T_ECT [2 * NCH][KP(Nkin + ntail)]      = GCT transposed: the same product with the batch as the column dimension
  *   EFTB_T_BXT [KP(Nkin + nxtail)][2 * 80]      IR filters X | Y = [Pin | tail'] . BXT                 (pybird.py:1316-1353)
+ *   EFTB_T_GCT2, EFTB_T_GCT2T                   the layouts of GCT, ECT
+ *   EFTB_T_AD [NPOW][NH + 2][nbasis (+ nbasis13)] complex    anti-diagonal pair weights (tables.antidiagonal_tables)
+ *   EFTB_T_MLJ [Nl][NPOW] complex, EFTB_T_LINVEC [10 (+ 2|3 Nl)][NCH] complex
+ *   EFTB_T_SYNK / SYNS [KP(4 NH + 1)][Nk | 80], EFTB_T_LINK / LINS [KP(2 NH + 1)][Nk | 80]   synthesis bases (tables.synthesis_table)
+ *   EFTB_T_WQLAST2 [2] exp(-k^2/L^2)/k^2 at the last two kin (+ at the first two when nxtail_lo > 0)
  *   EFTB_T_SPCBAND [65][Nk], EFTB_T_SPLOCAL [Nk][4][4]   the AP splines in B-spline form: coefficient operator and per-interval pieces (tables.bspline_tables)
  * (EFTB_T_TYT is an unused id kept for numbering.) */
 enum eftb_table {
@@ -97,7 +109,7 @@ enum eftb_buffer {
     EFTB_B_Q,         /* [B][2][Nl][Nl][Nn]   Resum.Q                             pybird.py:1367-1380 */
     EFTB_B_BIAS,      /* [B][24]              b11(3), bct(6), bloop(12), bst(3)   parambasis.py:69-126 */
     EFTB_B_PLK,       /* [B][nl][nx]          reduce_Plk(...).sum() without Picc  parambasis.py:128-136 */
-    EFTB_B_COEF,      /* [B][2][129]          FFTLog coefficients (independent half, re/im) */
+    EFTB_B_COEF,      /* [B][2][NCH]          FFTLog coefficients (independent half, re/im) */
     EFTB_B_GROWS,     /* [B][25][24]          coefficient rows of P_NG (row 0) and dP/d(gaussian parameter) (rows 1..nG)   parambasis.py:249-316 */
     EFTB_B_LOGP,      /* [B][26]              marginalised ln P, full chi2 at the best fit, best-fit gaussian parameters  marginal.py:79-140 */
     /* with_nnlo only.  The NNLO counter-terms travel as a second template block whose Pctl slots (rows 3-5) hold PctNNLOl and
@@ -221,7 +233,8 @@ int  eftb_set_pipeline_operator(eftb_engine* e, int op_id);
 int  eftb_set_template_dims(eftb_engine* e, int nl, int nx);
 
 /* Input guards.  P_lin must be finite, and positive at its last two samples: the FFTLog extrapolates it beyond kin[-1] with the power
- * law through them (reference fftlog.py:146-151 takes their logarithm); f must be finite, DA and H finite and positive.  The entry
+ * law through them (reference fftlog.py:146-151 takes their logarithm), and, when the grid starts above the FFTLog's xmin (ntail_lo or
+ * nxtail_lo > 0), at its first two samples as well (fftlog.py:140-145); f must be finite, DA and H finite and positive.  The entry
  * points that take host inputs (eftb_eval_batch, eftb_eval_logp_batch, eftb_stage_inputs) check this before anything is copied and
  * return non-zero; for inputs placed with eftb_put the first kernel raises a flag instead and the next synchronising call (eftb_sync,
  * eftb_get, eftb_fetch_*) returns non-zero, naming the cosmology.  The reference has no such check: NaNs propagate silently there. */

@@ -905,10 +905,85 @@ def resumopt_fixture(ref):
     print("resumopt written:", {k: np.shape(v) for k, v in out.items() if np.ndim(v) > 0})
 
 
+def fftlog_fixture(ref):
+    """The loop FFTLog at NFFT = 384 / 512 and input grids that start above its xmin = 1.5e-5 through the REAL reference
+    (pybird.py:907-919, 1127-1160, 1316-1335; fftlog.py:140-151): PsCf pieces, the templates after setPsCfl / Resum.Ps / AP, and
+    for kin = logspace(-4, 0, 200) NonLinear.Coef and Resum.IRFilters.  Native k grid, synthetic P_lin of the other cases."""
+    pb = ref.pybird
+    z = 0.7
+    cos = synth.cosmology(z=z)
+    kin_lo = np.logspace(-4, 0, 200)
+    out = dict(kin=cos["kin"], Pin=cos["Pin"], f=cos["f"], DA=cos["DA"], H=cos["H"], z=z, kin_lo=kin_lo, Pin_lo=synth.plin(kin_lo),
+               bsA=BS_A, es=ES, kIR=0.004)
+    cases = {  # name: (NFFT, Nl, low-k grid, AP, Common options, what is stored)
+        "n384": (384, 3, False, True, {}, "full"), "n512": (512, 3, False, True, {}, "full"),
+        "n512l2": (512, 2, False, False, {}, "templates"), "n512cut": (512, 3, False, True, dict(IRcutoff="all", kIR=0.004), "resum"),
+        "n512nnlo": (512, 3, False, True, dict(with_NNLO=True), "resum"),
+        "lo256": (256, 3, True, True, {}, "full"), "lo512": (512, 3, True, True, {}, "full"),
+        "lo512loop": (512, 3, True, True, dict(IRcutoff="loop", kIR=0.004), "resum"),
+    }
+    for name, (NFFT, Nl, lo, ap, opts, what) in cases.items():
+        co = make_common(pb, Nl, None, **opts)
+        out["k"] = co.k
+        kin, Pin = (kin_lo, out["Pin_lo"]) if lo else (cos["kin"], cos["Pin"])
+        nl = pb.NonLinear(load=False, save=False, NFFT=NFFT, co=co)
+        bird = pb.Bird(kin, Pin, cos["f"], cos["DA"], cos["H"], z, co=co)
+        nl.PsCf(bird)
+        if what == "full":
+            for n in ("P11", "P22", "P13", "C11", "Cct"):
+                out[f"{name}_pscf_{n}"] = np.array(getattr(bird, n), copy=True)
+            out[f"{name}_pscf_C22_l0"] = bird.C22[0].copy()
+            out[f"{name}_pscf_C13_l2"] = bird.C13[1].copy()
+        if lo:
+            out[f"{name}_coef"] = nl.Coef(bird, window=0.2)
+        bird.setPsCfl()
+        if what in ("full", "templates"):
+            for n, v in stage(bird).items():
+                out[f"{name}_setpscfl_{n}"] = v
+        rs = pb.Resum(co=co)
+        if lo:
+            out[f"{name}_X"], out[f"{name}_Y"] = rs.IRFilters(bird)
+        rs.Ps(bird)
+        for n, v in stage(bird, ("P11l", "Pctl", "Ploopl") + (("PctNNLOl",) if opts.get("with_NNLO") else ())).items():
+            out[f"{name}_resum_{n}"] = v
+        if ap:
+            apo = pb.APeffect(Om_AP=synth.OM_AP, z_AP=z, co=co)
+            out["DA_AP"], out["H_AP"] = apo.DA, apo.H
+            apo.AP(bird)
+            if what == "full":
+                for n, v in stage(bird).items():
+                    out[f"{name}_ap_{n}"] = v
+        print(name, "done", flush=True)
+    # four cosmologies at NFFT = 512 on the low-k grid, for the batched tests: final templates and reduce_Plk
+    params = [dict(Om=0.29, h=0.66, ns=0.95, A=0.9), dict(Om=0.31, h=0.6777, ns=0.9611, A=1.0), dict(Om=0.33, h=0.70, ns=0.97, A=1.1),
+              dict(Om=0.345, h=0.715, ns=0.985, A=1.18)]
+    co = make_common(pb, 3, None)
+    nl = pb.NonLinear(load=False, save=False, NFFT=512, co=co)
+    rs = pb.Resum(co=co)
+    apo = pb.APeffect(Om_AP=synth.OM_AP, z_AP=z, co=co)
+    cols = {n: [] for n in ("Pin", "f", "DA", "H", "templ", "plk")}
+    for p in params:
+        Pin, f = synth.plin(kin_lo, **p), float(synth.growth_rate(p["Om"], z))
+        DA, H = float(synth.da_func(p["Om"], z)), float(synth.hubble(p["Om"], z))
+        bird = pb.Bird(kin_lo, Pin, f, DA, H, z, co=co)
+        nl.PsCf(bird)
+        bird.setPsCfl()
+        rs.Ps(bird)
+        apo.AP(bird)
+        for n, v in (("Pin", Pin), ("f", f), ("DA", DA), ("H", H)):
+            cols[n].append(v)
+        cols["templ"].append(np.concatenate([bird.P11l, bird.Pctl, bird.Ploopl, bird.Pstl], axis=1))
+        cols["plk"].append(ref.parambasis.reduce_Plk(bird, BS_A, es=ES).sum())
+    for n, v in cols.items():
+        out["batch_" + n] = np.array(v)
+    np.savez_compressed(os.path.join(GOLD, "fftlog.npz"), **out)
+    print("fftlog written:", len(out), "arrays")
+
+
 def main():
     ref = load_reference()
     os.makedirs(GOLD, exist_ok=True)
-    want = sys.argv[1:] or (["tables"] + list(CASES) + ["marg", "pyegg", "east", "fiber", "nnlo", "ircut", "opti", "wmat", "cfg3", "resumopt", "cfg5", "cfg3_nk512", "surface", "cfg5_acc4"])
+    want = sys.argv[1:] or (["tables"] + list(CASES) + ["marg", "pyegg", "east", "fiber", "nnlo", "ircut", "opti", "wmat", "cfg3", "resumopt", "cfg5", "cfg3_nk512", "surface", "cfg5_acc4", "fftlog"])
     for name in want:
         if name == "tables":
             tables_fixture(ref)
@@ -940,6 +1015,8 @@ def main():
             resumopt_fixture(ref)
         elif name == "cfg5":
             cfg5_fixture(ref)
+        elif name == "fftlog":
+            fftlog_fixture(ref)
         else:
             run_case(ref, name, CASES[name])
 
