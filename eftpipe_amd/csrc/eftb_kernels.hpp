@@ -3460,6 +3460,297 @@ __global__ __launch_bounds__(256) void marg_solve_kernel(int ndata, int nG, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Many EFT parameter draws against the templates of one cosmology (the fast / slow split of reference theory.py:829-874 EFTLeaf.calculate on
+// EFTLeafKernel's templates; likelihood.py:483-549, marginal.py:79-140).  Walker c (template entries c ntr ... c ntr + ntr - 1) owns the draws
+// [offsets[c], offsets[c + 1]).  Everything downstream of the templates is linear in the coefficient rows, so per walker the Gram matrix
+//     A_c[j][a] = T[c ntr + tau][l(a) mod nl][r][x(a)]  (column j = (tau, r); data point a of tracer tau, 0 for the other tracers),
+//     A_c[J][a] = -data[a],     W_c = A_c C^-1 A_c^T   ((J + 1)^2, symmetrised; J = 24 ntr, + 3 ntr NNLO columns (tau, 3 + j) with with_nnlo)
+// is built once (draws_gather_kernel, gemm_narrow_kernel, draws_gram_kernel), and a draw with rows R[tau][g][24] (+ R_n[tau][g][3]) costs
+//     G = R^ W_c R^^T    (R^[g][(tau, r)] = R[tau][g][r], R^[0][J] = 1, R^[g >= 1][J] = 0)
+// -- the matrix marg_solve_kernel forms as V C^-1 V^T -- and the same small algebra after it (draws_logp_kernel).
+// ------------------------------------------------------------------------------------------------
+constexpr int DRAW_MAXJ1 = 128;  // template columns of a walker + the data row (two column halves of 64 lanes)
+
+// A_c [C][J1][ndata] (one workgroup per walker; lanes over the data points, as marg_build_kernel)
+__global__ __launch_bounds__(256) void draws_gather_kernel(int nl, int nx, int ntr, int ndata, int J1, const int* __restrict__ index,
+                                                           const double* __restrict__ data, const double* __restrict__ T,
+                                                           const double* __restrict__ TN, double* __restrict__ A) {
+    const int c = blockIdx.x, J = J1 - 1;
+    double* Ac = A + (size_t)c * J1 * ndata;
+    for (int a = threadIdx.x; a < ndata; a += 256) {
+        const int l = index[a] / nx, x = index[a] % nx, tr = l / nl;  // l counts the ntr * nl multipoles of the walker's entries
+        const double* t = T + ((size_t)c * ntr * nl + l) * NROW * nx + x;
+        for (int tau = 0; tau < ntr; ++tau)
+            for (int r = 0; r < NROW; ++r) Ac[(size_t)(tau * NROW + r) * ndata + a] = tau == tr ? t[(size_t)r * nx] : 0.0;
+        if (TN) {
+            const double* tn = TN + (((size_t)c * ntr * nl + l) * NROW + 3) * nx + x;
+            for (int tau = 0; tau < ntr; ++tau)
+                for (int j = 0; j < 3; ++j) Ac[(size_t)(ntr * NROW + 3 * tau + j) * ndata + a] = tau == tr ? tn[(size_t)j * nx] : 0.0;
+        }
+        Ac[(size_t)J * ndata + a] = -data[a];
+    }
+}
+
+// W_c[i][j] = W_c[j][i] = (A_i . U_j + A_j . U_i) / 2 with U = A C^-1: one 16-lane group per entry i <= j, lanes stride the data index,
+// shuffle reduction in a fixed order (as marg_solve_kernel)
+__global__ __launch_bounds__(256) void draws_gram_kernel(int ndata, int J1, const double* __restrict__ A, const double* __restrict__ U,
+                                                         double* __restrict__ W) {
+    const int c = blockIdx.x, sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const double* Ac = A + (size_t)c * J1 * ndata;
+    const double* Uc = U + (size_t)c * J1 * ndata;
+    double* Wc = W + (size_t)c * J1 * J1;
+    for (int e = blockIdx.y * 16 + grp; e < J1 * J1; e += gridDim.y * 16) {
+        const int i = e / J1, j = e % J1;
+        if (i > j) continue;  // (uniform over the 16-lane group: the shuffles stay inside it)
+        double s0 = 0.0, s1 = 0.0;
+        for (int b = sub; b < ndata; b += 16) {
+            s0 = fma(Ac[(size_t)i * ndata + b], Uc[(size_t)j * ndata + b], s0);
+            s1 = fma(Ac[(size_t)j * ndata + b], Uc[(size_t)i * ndata + b], s1);
+        }
+#pragma unroll
+        for (int m = 8; m >= 1; m >>= 1) {
+            s0 += __shfl_xor(s0, m, 16);
+            s1 += __shfl_xor(s1, m, 16);
+        }
+        if (sub == 0) {
+            const double w = 0.5 * (s0 + s1);
+            Wc[(size_t)i * J1 + j] = w;
+            Wc[(size_t)j * J1 + i] = w;
+        }
+    }
+}
+
+// LDS written by some lanes of a wave and read by others: no workgroup barrier, only the wave's own order
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// R^[h][j] of draw Rd / Rn (column j: (tau, r) for j < 24 ntr, NNLO (tau, jj) after them, the data row at J)
+__device__ __forceinline__ double draw_coef(const double* Rd, const double* Rn, int ntr, int ng1, int J, int h, int j) {
+    if (j < ntr * NROW) return Rd[((j / NROW) * ng1 + h) * NROW + j % NROW];
+    if (j < J) {
+        const int jn = j - ntr * NROW;
+        return Rn ? Rn[((jn / 3) * ng1 + h) * 3 + jn % 3] : 0.0;
+    }
+    return h == 0 ? 1.0 : 0.0;
+}
+
+// One workgroup per (walker, share of its draws): W_c is staged in LDS once, then every wave takes one draw at a time.
+//   H = R^ W_c    lanes over the columns j (j = lane and lane + 64 with TWO), nG + 1 accumulators each; R^[g][k] wave-uniform (scalar loads)
+//   G = H R^^T    lane h (lanes 32-63: the second half of the j sum, added with one shuffle), H from the wave's LDS scratch, G back to it
+//   F2 = sym(G[1:,1:]) + sigma^-2, F1 and F0 as marg_solve_kernel; LU with partial pivoting wave-synchronously: lane i keeps row i of F2,
+//   augmented with F1[i], in registers; the pivot row is broadcast with v_readlane.  The rows are not exchanged: `pos` is the place the
+//   row would hold in a row-exchanging LU (pivot choice on ties and the sign of det follow it), the right-hand side is eliminated with the
+//   rows (= marg_solve_kernel's forward substitution, same operations in the same order), then back substitution column by column.
+// Output: the [MARG_OUT] record of the LOGP stage per draw.  LDS: W_c [J1][J1], then per wave H [nG + 1][J1] and G [nG + 1][nG + 1].
+template <bool TWO>
+__global__ __launch_bounds__(256) void draws_logp_kernel(int ntr, int nG, int J1, int jeffreys, const long long* __restrict__ offsets,
+                                                         const double* __restrict__ rows, const double* __restrict__ rowsn,
+                                                         const double* __restrict__ W, const double* __restrict__ mu,
+                                                         const double* __restrict__ sinv, double* __restrict__ out) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ng1 = nG + 1, J = J1 - 1;
+    const long long d0 = offsets[c], d1 = offsets[c + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
+    double* Ws = sm;
+    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
+    __syncthreads();
+    double* Hs = sm + J1 * J1 + wv * (ng1 * J1 + ng1 * ng1);
+    double* Gs = Hs + ng1 * J1;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        const double* Rd = rows + (size_t)d * ntr * ng1 * NROW;
+        const double* Rn = rowsn ? rowsn + (size_t)d * ntr * ng1 * 3 : nullptr;
+        // ---- H = R^ W_c
+        double h0[MARG_NG1], h1[MARG_NG1];
+#pragma unroll
+        for (int g = 0; g < MARG_NG1; ++g) h0[g] = h1[g] = 0.0;
+        const bool c0 = lane < J1, c1 = TWO && lane + 64 < J1;
+        const int kn = Rn ? J : ntr * NROW;  // (no NNLO rows: those columns have zero coefficients)
+        for (int k = 0; k < kn; ++k) {
+            const bool main = k < ntr * NROW;
+            const int tau = main ? k / NROW : (k - ntr * NROW) / 3, r = main ? k % NROW : (k - ntr * NROW) % 3, stride = main ? NROW : 3;
+            const double* rk = main ? Rd + tau * ng1 * NROW + r : Rn + tau * ng1 * 3 + r;
+            const double w0 = c0 ? Ws[k * J1 + lane] : 0.0, w1 = c1 ? Ws[k * J1 + 64 + lane] : 0.0;
+#pragma unroll
+            for (int g = 0; g < MARG_NG1; ++g)
+                if (g < ng1) {
+                    const double rv = rk[g * stride];
+                    h0[g] = fma(rv, w0, h0[g]);
+                    if (TWO) h1[g] = fma(rv, w1, h1[g]);
+                }
+        }
+        h0[0] += c0 ? Ws[J * J1 + lane] : 0.0;  // the data row: R^[0][J] = 1
+        if (TWO) h1[0] += c1 ? Ws[J * J1 + 64 + lane] : 0.0;
+#pragma unroll
+        for (int g = 0; g < MARG_NG1; ++g)
+            if (g < ng1) {
+                if (c0) Hs[g * J1 + lane] = h0[g];
+                if (c1) Hs[g * J1 + 64 + lane] = h1[g];
+            }
+        wave_lds_sync();
+        // ---- G = H R^^T: lane h sums j in [0, Jh), lane 32 + h in [Jh, J1)
+        {
+            const int h = lane & 31, half = lane >> 5, Jh = (J1 + 1) >> 1;
+            const bool hl = h < ng1;
+            double acc[MARG_NG1];
+#pragma unroll
+            for (int g = 0; g < MARG_NG1; ++g) acc[g] = 0.0;
+            for (int q = 0; q < Jh; ++q) {
+                const int j = half * Jh + q;
+                const bool jl = j < J1;
+                const double rv = (hl && jl) ? draw_coef(Rd, Rn, ntr, ng1, J, h, j) : 0.0;
+                const int jj = jl ? j : 0;
+#pragma unroll
+                for (int g = 0; g < MARG_NG1; ++g)
+                    if (g < ng1) acc[g] = fma(Hs[g * J1 + jj], rv, acc[g]);
+            }
+#pragma unroll
+            for (int g = 0; g < MARG_NG1; ++g)
+                if (g < ng1) {
+                    acc[g] += __shfl_xor(acc[g], 32);
+                    if (half == 0 && hl) Gs[g * ng1 + h] = acc[g];
+                }
+        }
+        wave_lds_sync();
+        // ---- F2 | F1 per lane (row i = lane), LU with partial pivoting
+        const bool own = lane < nG;
+        double a[MARG_MAXG], aug = 0.0;
+#pragma unroll
+        for (int j = 0; j < MARG_MAXG; ++j)
+            a[j] = (own && j < nG) ? 0.5 * (Gs[(lane + 1) * ng1 + j + 1] + Gs[(j + 1) * ng1 + lane + 1]) + (lane == j ? sinv[j] : 0.0) : 0.0;
+        if (own) aug = -Gs[(lane + 1) * ng1] + sinv[lane] * mu[lane];
+        const double f1 = aug;
+        int pos = lane, sgn = 1;
+        double logdet = 0.0, dpv[MARG_MAXG];
+        int pl[MARG_MAXG];
+#pragma unroll
+        for (int c2 = 0; c2 < MARG_MAXG; ++c2) {
+            if (c2 >= nG) continue;
+            // pivot: largest |F2[i][c2]| among the rows not yet eliminated, the first in row order on ties (marg_solve_kernel, LAPACK)
+            const bool cand = own && pos >= c2;
+            double v = fabs(a[c2]);
+            if (!(v >= 0.0)) v = -0.5;  // NaN: a total order keeps the reduction's result the same in every lane
+            if (!cand) v = -1.0;
+            int kp = cand ? pos : 1 << 20, who = lane;
+#pragma unroll
+            for (int m = 16; m >= 1; m >>= 1) {  // lanes 0-31 hold every row (nG <= 24)
+                const double v2 = __shfl_xor(v, m);
+                const int k2 = __shfl_xor(kp, m), w2 = __shfl_xor(who, m);
+                if (v2 > v || (v2 == v && k2 < kp)) {
+                    v = v2;
+                    kp = k2;
+                    who = w2;
+                }
+            }
+            const int p = __builtin_amdgcn_readlane(who, 0);
+            const int pp = __builtin_amdgcn_readlane(pos, p);
+            if (pp != c2) sgn = -sgn;
+            if (pos == c2) pos = pp;  // the row at place c2 takes the pivot row's place
+            if (lane == p) pos = c2;
+            const double dpiv = readlane_f64(a[c2], p);
+            if (dpiv < 0.0) sgn = -sgn;
+            if (dpiv == 0.0 || dpiv != dpiv) sgn = 0;
+            logdet += log(fabs(dpiv));
+            dpv[c2] = dpiv;
+            pl[c2] = p;
+            const bool elim = own && pos > c2;
+            const double m = elim ? a[c2] / dpiv : 0.0;
+#pragma unroll
+            for (int j = c2 + 1; j < MARG_MAXG; ++j)
+                if (j < nG) {
+                    const double u = readlane_f64(a[j], p);
+                    if (elim) a[j] = fma(-m, u, a[j]);
+                }
+            const double yc = readlane_f64(aug, p);
+            if (elim) aug = fma(-m, yc, aug);
+        }
+        // back substitution U b = y: b = F2^-1 F1, the best-fit Gaussian parameters
+        double b[MARG_MAXG];
+#pragma unroll
+        for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2) {
+            b[c2] = 0.0;
+            if (c2 < nG) {
+                const double bc = readlane_f64(aug, pl[c2]) / dpv[c2];
+                b[c2] = bc;
+                if (own && pos < c2) aug = fma(-a[c2], bc, aug);
+            }
+        }
+        // F1 F2^-1 F1, F0 and the full chi2 at b (row sums per lane, added in row order)
+        double bi = 0.0, srow = 0.0;
+#pragma unroll
+        for (int j = 0; j < MARG_MAXG; ++j)
+            if (j < nG) {
+                if (lane == j) bi = b[j];
+                if (own) srow = fma(b[j], Gs[(lane + 1) * ng1 + j + 1], srow);
+            }
+        const double trow = own ? bi * fma(2.0, Gs[(lane + 1) * ng1], srow) : 0.0;
+        double quad = 0.0, F0 = Gs[0], full = Gs[0];
+#pragma unroll
+        for (int i = 0; i < MARG_MAXG; ++i)
+            if (i < nG) {
+                quad = fma(readlane_f64(f1, i), b[i], quad);
+                F0 = fma(mu[i] * sinv[i], mu[i], F0);
+                full += readlane_f64(trow, i);
+            }
+        const bool ok = sgn > 0;
+        const double chi2 = -quad + F0 + (jeffreys ? 0.0 : logdet - nG * 1.8378770664093453);  // ln det(F2 / 2 pi)
+        double* o = out + (size_t)d * MARG_OUT;
+        if (lane == 0) {
+            o[0] = ok ? -0.5 * chi2 : nan;
+            o[1] = ok ? full : nan;
+        }
+        if (lane < MARG_MAXG) o[2 + lane] = own ? (ok ? bi : nan) : 0.0;
+        wave_lds_sync();  // (the next draw overwrites H and G)
+    }
+}
+
+// P_d[tau][l][x] = sum_r b_d[tau][r] T[c ntr + tau][l][r][x] (+ sum_j bn_d[tau][j] TN[c ntr + tau][l][3 + j][x]) for the draws of walker c:
+// the templates of one (walker, tracer, l, 64-wide x tile) stay in registers, the waves of the workgroup take the draws in turn, and the
+// coefficients are wave-uniform loads.  The same two FMA chains split at msplit as reduce_kernel, then the NNLO sum as reduce_nnlo_kernel:
+// the same bits.  Write-bound (8 nl nx bytes per draw and tracer).
+__global__ __launch_bounds__(256) void draws_reduce_kernel(int nx, int nl, int ntr, int msplit, int xtiles, const long long* __restrict__ offsets,
+                                                           const double* __restrict__ bias, const double* __restrict__ T,
+                                                           const double* __restrict__ biasn, const double* __restrict__ TN,
+                                                           double* __restrict__ plk) {
+    const int tile = blockIdx.x % xtiles, share = blockIdx.x / xtiles, nshare = gridDim.x / xtiles;
+    const int tau = blockIdx.y / nl, l = blockIdx.y % nl, c = blockIdx.z;
+    const int lane = threadIdx.x & 63, nw = blockDim.x >> 6, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int x = tile * 64 + lane;
+    const bool live = x < nx;
+    const size_t ent = (size_t)c * ntr + tau;
+    const double* t = T + (ent * nl + l) * NROW * nx + (live ? x : 0);
+    double tv[NROW], tn[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < NROW; ++r) tv[r] = t[(size_t)r * nx];
+    if (TN) {
+        const double* u = TN + ((ent * nl + l) * NROW + 3) * nx + (live ? x : 0);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) tn[j] = u[(size_t)j * nx];
+    }
+    const long long d1 = offsets[c + 1];
+    for (long long d = offsets[c] + (long long)share * nw + wv; d < d1; d += (long long)nshare * nw) {
+        const double* b = bias + ((size_t)d * ntr + tau) * NROW;
+        double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+        for (int r = 0; r < NROW; ++r) {
+            if (r < msplit) a0 = fma(b[r], tv[r], a0);
+            else a1 = fma(b[r], tv[r], a1);
+        }
+        double a = a0 + a1;
+        if (TN) {
+            const double* bn = biasn + ((size_t)d * ntr + tau) * 3;
+            a = a + (bn[0] * tn[0] + bn[1] * tn[1] + bn[2] * tn[2]);
+        }
+        if (live) plk[(((size_t)d * ntr + tau) * nl + l) * nx + x] = a;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Window precompute (reference window.py:262-359).  tables.py window_tables collapses the reference's per-(a, l, k)
 // FFTLog(4096) + power-law sum into  W_al(k, p) = sum_i Qt_al[i] j_{2a}(k x_i) T_l[i][p]:  window_bessel_kernel writes the
 // left factor A[a][l][k][i] = Qt_al[i] j_{2a}(k x_i), gemm_rows_kernel multiplies it with T_l on the matrix cores (one launch

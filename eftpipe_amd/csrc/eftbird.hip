@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -132,6 +133,20 @@ struct eftb_engine {
     int* like_index = nullptr;
     double *like_data = nullptr, *like_invcov = nullptr, *like_mu = nullptr, *like_sinv = nullptr;
     double *like_V = nullptr, *like_U = nullptr;  // LOGP scratch: V and U = V C^-1, packed [walkers][nG + 1][ndata]
+    // parameter draws against the current template block (eftb_draws_logp / eftb_draws_reduce).  draw_gen counts the changes of what the
+    // per-walker Gram matrices depend on (the template block, the likelihood, the tracers): every run or eftb_put that writes TEMPL / TEMPLN
+    // bumps it, and so do eftb_set_likelihood, eftb_set_tracers, eftb_set_template_dims and eftb_apply_operator.  The Gram block is rebuilt
+    // when its generation is not the current one.
+    unsigned long long draw_gen = 1, gram_gen = 0;
+    int gram_C = 0;                 // walkers the cached Gram block holds
+    bool templ_ok = false;          // the block holds templates: not after a direct-P_l run, nor once a staged step has rotated the blocks
+    bool run_direct = false;        // the synchronous run being launched took the direct-P_l path (set by launch_stages_impl)
+    size_t templ_elems = 0;         // doubles at the front of TEMPL written by the last template-producing run / eftb_put
+    double *drw_A = nullptr, *drw_U = nullptr, *drw_W = nullptr, *drw_in = nullptr, *drw_inn = nullptr, *drw_out = nullptr;  // grown on demand
+    size_t drw_A_cap = 0, drw_U_cap = 0, drw_W_cap = 0, drw_in_cap = 0, drw_inn_cap = 0, drw_out_cap = 0, drw_off_cap = 0;
+    long long* drw_off = nullptr;
+    std::vector<double> drw_host;   // eftb_draws_logp: D2H landing block [N][MARG_OUT]
+    bool drw_lds = false;           // draws_logp_kernel opted in to the large dynamic LDS
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -685,6 +700,17 @@ static void launch_ap_prefix(eftb_engine* e, hipStream_t st, int B, bool weights
 }
 
 // nnlo_pass: the linear stages (RESUM / AP / PROJECT) once more, on the NNLO block (pointers swapped in by launch_stages)
+// P_l = sum_row b_row T[l][row] as two FMA chains split at this row (the row split of ap_rows_kernel's half waves), everywhere
+static inline int reduce_msplit(const eftb_config& c) { return c.with_ap ? ((c.ap_stochastic ? NROW : 21) + 1) / 2 : NROW / 2; }
+
+// after a synchronous run: a run that writes the template block is a new generation of it (eftb_draws_*); a direct-P_l run leaves none
+static void note_templates(eftb_engine* e, int mask, int B) {
+    if (!(mask & (EFTB_S_REGROUP | EFTB_S_RESUM | EFTB_S_AP | EFTB_S_PROJECT | EFTB_K_RESUM))) return;
+    ++e->draw_gen;
+    e->templ_ok = !e->run_direct;
+    e->templ_elems = (size_t)B * e->cur_nl * NROW * e->cur_nx;
+}
+
 // the main stream picks up behind a back half that is still in flight on its own stream (see engine.back)
 static inline void join_back(eftb_engine* e) {
     if (!e->back_pending) return;
@@ -829,7 +855,7 @@ static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, b
     const bool fuse_cf = (mask & EFTB_S_REGROUP) && (mask & EFTB_S_RESUM) && c.with_resum && (Nl == 3 || !e->generic_resum) && !c.optiresum && !c.with_nnlo &&
                          !nnlo_pass && e->fuse_cf;
     // P_l = sum_row b_row T[l][row]: two FMA chains split at msplit_cfg (the row split of ap_rows_kernel's half waves), everywhere
-    const int msplit_cfg = c.with_ap ? ((c.ap_stochastic ? NROW : 21) + 1) / 2 : NROW / 2;
+    const int msplit_cfg = reduce_msplit(c);
     const bool fuse_reduce = (mask & EFTB_S_AP) && (mask & EFTB_S_REDUCE) && !(mask & (EFTB_S_PROJECT | EFTB_S_LOGP)) && c.with_ap && e->ap_mode == 0 &&
                              !c.with_nnlo && !nnlo_pass;
     // direct-P_l runs (EFTB_O_PLK_DIRECT): the bias contraction first, then resummation and AP on ONE row per multipole (regroup_plk_kernel,
@@ -852,6 +878,7 @@ static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, b
     const bool direct = e->plk_direct && direct_tail && fuse_cf && Nl == 3 && !e->generic_resum && !c.dual_coef && !e->use_graphs &&
                         (mask & EFTB_S_PREP) && (mask & EFTB_S_LOOPS) && (mask & EFTB_S_CF) && (mask & EFTB_S_REGROUP) && e->RSAS;
     const bool direct_proj = direct && (mask & EFTB_S_PROJECT);
+    if (direct) e->run_direct = true;
     e->plk_host_written = true;
     // ... and the per-s A operand of the Nl = 3 resummation (inputs only: Q(f), X, Y) is built on the side stream, off the chain
     const bool as_side = ahead && Nl == 3 && !e->generic_resum && e->RSAS2 && !direct;
@@ -1753,6 +1780,7 @@ int eftb_set_tracers(eftb_engine* e, int ntr) {
     if (!e) return fail("eftb_set_tracers: null engine");
     if (ntr < 1 || ntr > e->c.max_batch) return fail("eftb_set_tracers: %d tracers outside [1, max_batch]", ntr);
     e->ntr = ntr;
+    ++e->draw_gen;
     e->tracer_ops.clear();
     e->like_ndata = 0;  // a likelihood set for another grouping does not survive
     return 0;
@@ -1782,6 +1810,7 @@ int eftb_apply_operator(eftb_engine* e, int op_id, int B) {
     if (B < 1 || B > e->c.max_batch) return fail("eftb_apply_operator: batch %d outside [1, %d]", B, e->c.max_batch);
     HIPCHK(hipSetDevice(e->c.device));
     join_back(e);
+    ++e->draw_gen;
     if (int rc = launch_operator(e, op_id, B)) return rc;
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(le));
@@ -1804,6 +1833,7 @@ int eftb_set_template_dims(eftb_engine* e, int nl, int nx) {
     if (nl < 1 || nx < 1 || (size_t)nl * nx > (size_t)e->c.Nl * e->c.Nk) return fail("eftb_set_template_dims: bad shape [%d][24][%d]", nl, nx);
     e->cur_nl = nl;
     e->cur_nx = nx;
+    ++e->draw_gen;
     return 0;
 }
 
@@ -1932,6 +1962,7 @@ int eftb_set_likelihood(eftb_engine* e, int ndata, const int32_t* index, const d
     e->like_nG = nG;
     e->like_nl = lnl;
     e->like_nx = lnx;
+    ++e->draw_gen;
     return 0;
 }
 
@@ -1959,6 +1990,7 @@ void eftb_destroy(eftb_engine* e) {
     for (void* p : {(void*)e->APW, (void*)e->APW2, (void*)e->API, (void*)e->API2, (void*)e->APM, (void*)e->APM2}) if (p) (void)hipFree(p);
     for (auto& o : e->ops) if (o.dev) (void)hipFree(o.dev);
     for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evSnap, e->evGathered, e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
@@ -2015,6 +2047,13 @@ int eftb_put(eftb_engine* e, int id, size_t offset, const double* host, size_t c
     join_back(e);
     HIPCHK(hipMemcpyAsync(e->buf[id] + offset, host, count * sizeof(double), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    if (id == EFTB_B_TEMPL || id == EFTB_B_TEMPLN) {
+        ++e->draw_gen;
+        if (id == EFTB_B_TEMPL) {  // (the block holds templates again; what the caller wrote starts at 0 or continues what is there)
+            e->templ_elems = offset == 0 || !e->templ_ok ? offset + count : std::max(e->templ_elems, offset + count);
+            e->templ_ok = true;
+        }
+    }
     return 0;
 }
 
@@ -2042,9 +2081,11 @@ int eftb_run(eftb_engine* e, int mask, int B) {
     e->status_slot = eftb_engine::NSETS;
     e->inputs_settled = true;  // eftb_put is synchronous: the inputs of this run are in place, its first stage may start early
     e->allow_back = true;
+    e->run_direct = false;
     const int rc = run_stages(e, mask, B);
     e->inputs_settled = e->allow_back = false;
     if (rc) return rc;
+    note_templates(e, mask, B);
     HIPCHK(hipEventRecord(e->evRun[slot], e->back_pending ? e->back : e->stream));  // the run ends where its back half ran
     ++e->run_seq;
     return 0;
@@ -2068,8 +2109,10 @@ int eftb_run_timed(eftb_engine* e, int mask, int B, int repeats, float* ms) {
     HIPCHK(hipSetDevice(e->c.device));
     join_back(e);
     HIPCHK(hipEventRecord(e->ev0, e->stream));
+    e->run_direct = false;
     for (int r = 0; r < repeats; ++r)
         if (int rc = launch_stages(e, mask, B)) return rc;
+    note_templates(e, mask, B);
     HIPCHK(hipEventRecord(e->ev1, e->stream));
     HIPCHK(hipEventSynchronize(e->ev1));
     HIPCHK(hipEventElapsedTime(ms, e->ev0, e->ev1));
@@ -2097,7 +2140,10 @@ static int upload_and_launch(eftb_engine* e, const char* who, int B, const doubl
     if (c.with_resum) mask |= EFTB_S_CF | EFTB_S_RESUM;
     if (c.with_ap) mask |= EFTB_S_AP;
     if (e->pipeline_op >= 0 || !e->tracer_ops.empty()) mask |= EFTB_S_PROJECT;
-    return run_stages(e, mask, B);
+    e->run_direct = false;
+    if (int rc = run_stages(e, mask, B)) return rc;
+    note_templates(e, mask, B);
+    return 0;
 }
 
 int eftb_eval_batch(eftb_engine* e, int B, const double* Pin, const double* f, const double* DA, const double* H, double* templ,
@@ -2146,6 +2192,163 @@ int eftb_eval_logp_batch(eftb_engine* e, int B, const double* Pin, const double*
         if (best)
             for (int i = 0; i < e->like_nG; ++i) best[(size_t)w * e->like_nG + i] = o[2 + i];
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ parameter draws (fast / slow split)
+// device buffer of at least n elements: grows, never shrinks (freed by eftb_destroy); separate from every buffer of the runs
+static int grow_dev(void* pp, size_t* cap, size_t n, size_t elem = sizeof(double)) {
+    void** p = static_cast<void**>(pp);
+    if (n <= *cap) return 0;
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    HIPCHK(hipMalloc(p, n * elem));
+    *cap = n;
+    return 0;
+}
+
+// offsets (walker c owns draws [offsets[c], offsets[c + 1])) and the state of the template block; *maxcnt: the most draws one walker owns
+static int draws_check(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, long long* maxcnt) {
+    if (!e->finalized) return fail("%s: engine not finalized", who);
+    if (C < 1) return fail("%s: %d walkers", who, C);
+    if (N < 0) return fail("%s: %lld draws", who, N);
+    if (offsets[0] != 0) return fail("%s: offsets[0] = %lld, not 0", who, (long long)offsets[0]);
+    long long mx = 0;
+    for (int w = 0; w < C; ++w) {
+        if (offsets[w + 1] < offsets[w]) return fail("%s: offsets decrease at walker %d (%lld -> %lld)", who, w, (long long)offsets[w], (long long)offsets[w + 1]);
+        mx = std::max<long long>(mx, offsets[w + 1] - offsets[w]);
+    }
+    if (offsets[C] != N) return fail("%s: offsets[%d] = %lld, not the %lld draws", who, C, (long long)offsets[C], N);
+    if (!e->templ_ok)
+        return fail("%s: the current block holds no templates (the last run was a direct-P_l run, or a staged step has rotated the blocks since the "
+                    "last template-producing run / eftb_put)", who);
+    const size_t per = (size_t)e->cur_nl * NROW * e->cur_nx, have = per ? e->templ_elems / per : 0;
+    if ((size_t)C * e->ntr > have)
+        return fail("%s: %d walkers x %d tracers, but the template block holds %zu entries [%d][24][%d]", who, C, e->ntr, have, e->cur_nl, e->cur_nx);
+    *maxcnt = mx;
+    return 0;
+}
+
+// workgroups per walker: enough for its draws (per_wg at a time), about 2048 in all
+static int draw_shares(long long maxcnt, int per_wg, long long groups) {
+    const long long want = (maxcnt + per_wg - 1) / per_wg, fill = std::max(1LL, 2048 / std::max(1LL, groups));
+    return (int)std::max(1LL, std::min(want, fill));
+}
+
+int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* rows, const double* rows_nnlo, double* logp,
+                    double* fullchi2, double* best) {
+    static const char* who = "eftb_draws_logp";
+    if (e) sub_drain(e);
+    if (!e || !offsets || (N > 0 && (!rows || !logp))) return fail("%s: null argument", who);
+    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
+    long long maxcnt = 0;
+    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
+        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
+                    e->cur_nx);
+    const eftb_config& c = e->c;
+    if (rows_nnlo && !c.with_nnlo) return fail("%s: rows_nnlo needs an engine built with with_nnlo", who);
+    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1, nd = e->like_ndata;
+    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
+    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
+    const size_t lds_w = (size_t)J1 * J1 * sizeof(double), lds_wave = ((size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
+    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
+    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
+    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
+    if (N == 0) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    hipStream_t st = e->stream;
+    join_back(e);
+    if (!e->drw_lds) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->drw_lds = true;
+    }
+    if (e->gram_gen != e->draw_gen || e->gram_C < C) {  // W_c of the current block, likelihood and tracers
+        e->gram_gen = 0;
+        const size_t ae = (size_t)C * J1 * nd;
+        if (int rc = grow_dev(&e->drw_A, &e->drw_A_cap, ae)) return rc;
+        if (int rc = grow_dev(&e->drw_U, &e->drw_U_cap, ae)) return rc;
+        if (int rc = grow_dev(&e->drw_W, &e->drw_W_cap, (size_t)C * J1 * J1)) return rc;
+        hipLaunchKernelGGL(draws_gather_kernel, dim3(C), dim3(256), 0, st, e->cur_nl, e->cur_nx, ntr, nd, J1, e->like_index, e->like_data,
+                           e->buf[EFTB_B_TEMPL], c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, e->drw_A);
+        GemmDesc gd{};  // U = A C^-1 for all walkers, exactly as the LOGP stage multiplies V
+        gd.A = e->drw_A; gd.a_group = 0; gd.a_row = nd; gd.a_seg = 0; gd.rows = C * J1; gd.rows_per_group = C * J1; gd.nseg = 1; gd.kseg = nd;
+        gd.B = e->like_invcov; gd.ldb = nd; gd.ncols = nd;
+        gd.C = e->drw_U; gd.c_group = 0; gd.c_row = nd; gd.c_colgroup = 0; gd.cols_per_group = nd;
+        hipLaunchKernelGGL(gemm_narrow_kernel, dim3((gd.rows + 15) / 16, (gd.ncols + 16 * GN_MAXT - 1) / (16 * GN_MAXT)), dim3(256), 0, st, gd, GemmZ{});
+        const int gy = std::min(1024, (J1 * J1 + 63) / 64);
+        hipLaunchKernelGGL(draws_gram_kernel, dim3(C, gy), dim3(256), 0, st, nd, J1, e->drw_A, e->drw_U, e->drw_W);
+        hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+        e->gram_gen = e->draw_gen;
+        e->gram_C = C;
+    }
+    const size_t rn = (size_t)N * ntr * ng1 * NROW, rnn = (size_t)N * ntr * ng1 * 3;
+    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, rn)) return rc;
+    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
+    if (rows_nnlo)
+        if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, rnn)) return rc;
+    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->drw_in, rows, rn * sizeof(double), hipMemcpyHostToDevice, st));
+    if (rows_nnlo) HIPCHK(hipMemcpyAsync(e->drw_inn, rows_nnlo, rnn * sizeof(double), hipMemcpyHostToDevice, st));
+    const dim3 grid(C, draw_shares(maxcnt, nw, C)), block(64 * nw);
+    const size_t lds = lds_w + nw * lds_wave;
+    if (J1 > 64)
+        hipLaunchKernelGGL(draws_logp_kernel<true>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
+                           e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
+    else
+        hipLaunchKernelGGL(draws_logp_kernel<false>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
+                           e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    e->drw_host.resize((size_t)N * MARG_OUT);
+    HIPCHK(hipMemcpyAsync(e->drw_host.data(), e->drw_out, (size_t)N * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (long long d = 0; d < N; ++d) {
+        const double* o = e->drw_host.data() + (size_t)d * MARG_OUT;
+        logp[d] = o[0];
+        if (fullchi2) fullchi2[d] = o[1];
+        if (best)
+            for (int i = 0; i < nG; ++i) best[(size_t)d * nG + i] = o[2 + i];
+    }
+    return 0;
+}
+
+int eftb_draws_reduce(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* bias, const double* bias_nnlo, double* plk) {
+    static const char* who = "eftb_draws_reduce";
+    if (e) sub_drain(e);
+    if (!e || !offsets || (N > 0 && (!bias || !plk))) return fail("%s: null argument", who);
+    long long maxcnt = 0;
+    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    const eftb_config& c = e->c;
+    if (bias_nnlo && !c.with_nnlo) return fail("%s: bias_nnlo needs an engine built with with_nnlo", who);
+    if (N == 0) return 0;
+    const int ntr = e->ntr, nl = e->cur_nl, nx = e->cur_nx, xtiles = (nx + 63) / 64;
+    HIPCHK(hipSetDevice(c.device));
+    hipStream_t st = e->stream;
+    join_back(e);
+    const size_t bn = (size_t)N * ntr * NROW, bnn = (size_t)N * ntr * 3, pn = (size_t)N * ntr * nl * nx;
+    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, bn)) return rc;
+    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, pn)) return rc;
+    if (c.with_nnlo)
+        if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, bnn)) return rc;
+    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->drw_in, bias, bn * sizeof(double), hipMemcpyHostToDevice, st));
+    if (c.with_nnlo) {  // (no bias_nnlo: zeros, as the REDUCE stage of eftb_eval_batch)
+        if (bias_nnlo) HIPCHK(hipMemcpyAsync(e->drw_inn, bias_nnlo, bnn * sizeof(double), hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemsetAsync(e->drw_inn, 0, bnn * sizeof(double), st));
+    }
+    const int shares = draw_shares(maxcnt, 4, (long long)C * ntr * nl * xtiles);
+    hipLaunchKernelGGL(draws_reduce_kernel, dim3(xtiles * shares, ntr * nl, C), dim3(256), 0, st, nx, nl, ntr, reduce_msplit(c), xtiles, e->drw_off, e->drw_in,
+                       e->buf[EFTB_B_TEMPL], c.with_nnlo ? e->drw_inn : nullptr, c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, e->drw_out);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    HIPCHK(hipMemcpyAsync(plk, e->drw_out, pn * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -2648,6 +2851,8 @@ int eftb_run_staged(eftb_engine* e, int mask, int B) {
     if (!e->cpy || e->stg_slot < 0) return fail("eftb_run_staged: nothing staged (eftb_stage_inputs first)");
     if (B != e->stg_B) return fail("eftb_run_staged: batch %d, but %d cosmologies were staged", B, e->stg_B);
     HIPCHK(hipSetDevice(e->c.device));
+    e->templ_ok = false;  // (a staged step rotates the template blocks: eftb_draws_* refuse until the next template-producing run / eftb_put)
+    ++e->draw_gen;
     const unsigned long long step = e->steps_submitted;
     double* out = e->stg_out;
     e->stg_out = nullptr;   // (one step only, launched or not)

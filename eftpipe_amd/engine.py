@@ -353,9 +353,38 @@ class Engine:
             plk = np.empty((B, nl, nx))
         L.check(self.lib.eftb_eval_batch(self._h, B, L.dptr(Pin), L.dptr(f), L.dptr(DA), L.dptr(H), L.dptr(templ),
                                          L.dptr(bias), L.dptr(plk)))
+        self.dims = (nl, nx)
         if not templates:
             return plk
         return (templ, plk) if bias is not None else templ
+
+    def reduce_draws(self, bias, offsets, bias_nnlo=None, out=None):
+        """P_l for many parameter draws against the current template block (``eftb_draws_reduce``; reduce_Plk of reference
+        theory.py:829-874 EFTLeaf.calculate): walker c (template entries c * ntr ... c * ntr + ntr - 1) owns draws offsets[c] ...
+        offsets[c + 1] - 1.  bias [N, 24] ([N, ntr, 24] with tracers; ``parambasis.bias_rows_many``), bias_nnlo [N(, ntr), 3] (with_NNLO
+        engines) -> P_l [N, nl, nx] ([N, ntr, nl, nx] with tracers), the bits of the REDUCE stage.  out: an array of that shape to fill."""
+        from .marginal import _offsets
+
+        ntr, (nl, nx) = self.ntracers, self.dims
+        bias = np.ascontiguousarray(bias, dtype=np.float64)
+        N = bias.shape[0] if bias.ndim else 0
+        if bias.shape not in ((N, ntr, NROW),) + (((N, NROW),) if ntr == 1 else ()):
+            raise ValueError(f"bias must be [N, {ntr}, 24]" if ntr > 1 else "bias must be [N, 24]")
+        bn = None
+        if bias_nnlo is not None:
+            if not self.cfg.with_NNLO:
+                raise ValueError("bias_nnlo needs an engine built with with_NNLO")
+            bn = np.ascontiguousarray(bias_nnlo, dtype=np.float64)
+            if bn.shape not in ((N, ntr, 3),) + (((N, 3),) if ntr == 1 else ()):
+                raise ValueError(f"bias_nnlo must be [N, {ntr}, 3]")
+        off = _offsets(offsets)
+        shape = (N, nl, nx) if ntr == 1 else (N, ntr, nl, nx)
+        if out is None:
+            out = np.empty(shape)
+        elif out.shape != shape or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise ValueError(f"out must be a writable C-contiguous float64 array {shape}")
+        L.check(self.lib.eftb_draws_reduce(self._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(bias), L.dptr(bn), L.dptr(out)))
+        return out
 
     # ------------------------------------------------------------------ pipelined steps (double-buffered inputs / outputs)
     def stage_inputs(self, Pin, f, DA=None, H=None, bias=None, rows=None):

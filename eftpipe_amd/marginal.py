@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .parambasis import gaussian_params, gaussian_rows
+from .parambasis import _ndraws, gaussian_params, gaussian_rows, gaussian_rows_many
 
 MAXG = 24
 
@@ -43,6 +43,34 @@ def joint_gaussian_rows(bases, fs, params, names, scales):
         for i, n in enumerate(names):
             if n in own:
                 out[t, 1 + i] = r[1 + own.index(n)]
+    return out
+
+
+def joint_gaussian_rows_many(bases, fs, params, names, scales):
+    """joint_gaussian_rows for N draws: params maps each non-Gaussian parameter name to its values [N] (or one value shared by every
+    draw); fs: growth rate per tracer, one value or [N] each -> rows [N, ntr, len(names) + 1, 24], the bits of joint_gaussian_rows draw
+    for draw (the rows of MarginalLikelihood.logp_draws)."""
+    per = [np.asarray(v) for v in params.values() if np.ndim(v) >= 1] + [np.asarray(f) for f in fs if np.ndim(f) >= 1]
+    if not per:
+        raise ValueError("no per-draw values: pass arrays [N]")
+    N = _ndraws(*per)
+    if len(fs) != len(bases) or len(scales) != len(bases):
+        raise ValueError("one growth rate and one scale dict per tracer")
+    out = np.zeros((N, len(bases), len(names) + 1, 24))
+    for t, (basis, f, sc) in enumerate(zip(bases, fs, scales)):
+        if basis.get_name() == "westcoast":
+            ng = [np.stack([np.broadcast_to(np.asarray(params[x + p], dtype=np.float64), (N,)) for p in ("b1", "b2", "b4")], axis=1)
+                  for x in (basis.cross_prefix or [basis.prefix])]
+            r = gaussian_rows_many(f, ng[0], ng[1] if basis.is_cross() else None, **sc)
+            own = gaussian_params(basis.prefix, tuple(basis.cross_prefix))
+        else:
+            ng = np.stack([np.broadcast_to(np.asarray(params[basis.prefix + p], dtype=np.float64), (N,)) for p in ("b1", "b2", "bG2")], axis=1)
+            r = gaussian_rows_many(f, ng, basis="eastcoast", **sc)
+            own = basis.gaussian_params()
+        out[:, t, 0] = r[:, 0]
+        for i, n in enumerate(names):
+            if n in own:
+                out[:, t, 1 + i] = r[:, 1 + own.index(n)]
     return out
 
 
@@ -103,6 +131,32 @@ class MarginalLikelihood:
         return out[:, 0]
 
 
+    def logp_draws(self, rows, offsets, return_best=False, rows_nnlo=None):
+        """Many parameter draws against the current template block (``eftb_draws_logp``; the fast / slow split of reference
+        theory.py:829-874): walker c (template entries c * ntr ... c * ntr + ntr - 1, left by eval_logp / eval_batch / put("TEMPL")) owns
+        draws offsets[c] ... offsets[c + 1] - 1.  rows [N, ntr, nG + 1, 24] ([N, nG + 1, 24] with one tracer; ``joint_gaussian_rows_many``,
+        ``parambasis.gaussian_rows_many``), rows_nnlo [N, ntr, nG + 1, 3] (with_NNLO engines) -> ln P_marg [N] (+ full chi2 [N] and
+        best-fit Gaussian parameters [N, nG]).  Raises like the reference when det F2 <= 0."""
+        ntr, ng1 = self.eng.ntracers, self.nG + 1
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        N = rows.shape[0] if rows.ndim else 0
+        if rows.shape not in ((N, ntr, ng1, 24),) + (((N, ng1, 24),) if ntr == 1 else ()):
+            raise ValueError(f"rows must be [N, {ntr}, {ng1}, 24]")
+        rn = None
+        if rows_nnlo is not None:
+            if not self.eng.cfg.with_NNLO:
+                raise ValueError("rows_nnlo needs an engine built with with_NNLO")
+            rn = np.ascontiguousarray(rows_nnlo, dtype=np.float64)
+            if rn.shape not in ((N, ntr, ng1, 3),) + (((N, ng1, 3),) if ntr == 1 else ()):
+                raise ValueError(f"rows_nnlo must be [N, {ntr}, {ng1}, 3]")
+        off = _offsets(offsets)
+        logp, full, best = np.empty(N), np.empty(N), np.empty((N, self.nG))
+        L.check(self.eng.lib.eftb_draws_logp(self.eng._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(rows), L.dptr(rn),
+                                             L.dptr(logp), L.dptr(full), L.dptr(best)))
+        if np.any(np.isnan(logp)):
+            raise RuntimeError("det of F2ij <= 0")
+        return (logp, full, best) if return_best else logp
+
     def eval_logp(self, Pin, f, DA, H, rows, return_best=False):
         """Theory + likelihood in one call (``eftb_eval_logp_batch``): Pin [B, Nkin], f/DA/H [B], rows [B, nG + 1, 24] ->
         ln P_marg [B]; only the inputs and B floats cross PCIe.  The engine's pipeline operator must bring the templates to
@@ -115,9 +169,18 @@ class MarginalLikelihood:
         logp, full, best = np.empty(nw), np.empty(nw), np.empty((nw, self.nG))
         L.check(self.eng.lib.eftb_eval_logp_batch(self.eng._h, B, L.dptr(Pin), L.dptr(f), L.dptr(DA), L.dptr(H), L.dptr(rows),
                                                   L.dptr(logp), L.dptr(full), L.dptr(best)))
+        self.eng.dims = self.eng.out_dims()  # (the shape of the template block this run leaves)
         if np.any(np.isnan(logp)):
             raise RuntimeError("det of F2ij <= 0")
         return (logp, full, best) if return_best else logp
 
 
-__all__ = ["MarginalLikelihood", "data_index", "gaussian_params", "gaussian_rows", "joint_gaussian_rows"]
+def _offsets(offsets):
+    """walker boundaries of a draw call as int64 [C + 1] (the library checks their values)"""
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    if off.ndim != 1 or off.size < 2:
+        raise ValueError("offsets must be [C + 1]: walker c owns draws offsets[c] ... offsets[c + 1] - 1")
+    return off
+
+
+__all__ = ["MarginalLikelihood", "data_index", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_gaussian_rows", "joint_gaussian_rows_many"]

@@ -152,6 +152,137 @@ def gaussian_rows(f, ngA, ngB=None, kmA=0.7, krA=0.25, ndA=3e-4, kmB=None, krB=N
     return np.stack(rows)
 
 
+# ----------------------------------------------------------------------------- many draws at once (Engine.reduce_draws, MarginalLikelihood.logp_draws)
+# The same arithmetic as bias_vectors / gaussian_rows, element by element over N parameter draws: draw i of a *_many builder has the bits
+# of the scalar builder called with Python floats for draw i.  Per-draw powers go through _powu: numpy's array power (a square, or its own
+# vector pow) and libm's pow, which a Python float uses, differ in the last bit for some arguments.
+
+
+def _draws(x, N, name, width=None):
+    """x as float64 [N] (or [N, width]); a scalar / one row is shared by every draw"""
+    a = np.asarray(x, dtype=np.float64)
+    shape = (N,) if width is None else (N, width)
+    try:
+        return np.broadcast_to(a, shape)
+    except ValueError:
+        raise ValueError(f"{name} must be {'[N]' if width is None else f'[N, {width}]'} (N = {N}), got {a.shape}") from None
+
+
+def _powu(x, p):
+    """x ** p per element with the arithmetic of a Python float; evaluated once per distinct value (draws of one walker share its growth rate)"""
+    u, inv = np.unique(x, return_inverse=True)
+    return np.array([float(v) ** p for v in u.tolist()])[inv].reshape(x.shape)
+
+
+def _ndraws(*arrays):
+    sizes = {np.asarray(a).shape[0] for a in arrays if a is not None and np.ndim(a) >= 1}
+    if len(sizes) != 1:
+        raise ValueError(f"the per-draw arrays disagree on the number of draws: {sorted(sizes)}")
+    return sizes.pop()
+
+
+def bias_rows_many(f, bsA, bsB=None, es=(0.0, 0.0, 0.0), kmA=0.7, krA=0.25, ndA=3e-4, kmB=None, krB=None, ndB=None, counterform="westcoast"):
+    """bias_row for N draws: f [N] (or one value), bsA [N, 7], bsB [N, 7] or None, es [N, 3] or one triple -> [N, 24]."""
+    if np.ndim(bsA) != 2 or (bsB is not None and np.ndim(bsB) != 2):
+        raise ValueError("bsA / bsB must be [N, 7]")
+    N = _ndraws(bsA)
+    f = _draws(f, N, "f")
+    bsA = _draws(bsA, N, "bsA", 7)
+    bsB = bsA if bsB is None else _draws(bsB, N, "bsB", 7)
+    es = _draws(es, N, "es", 3)
+    kmB = kmA if kmB is None else kmB
+    krB = krA if krB is None else krB
+    ndB = ndA if ndB is None else ndB
+    b1A, b2A, b3A, b4A, cctA, cr1A, cr2A = bsA.T
+    b1B, b2B, b3B, b4B, cctB, cr1B, cr2B = bsB.T
+    ce0, cemono, cequad = es.T
+    b11 = [b1A * b1B, (b1A + b1B) * f, f * f]
+    if counterform not in ("westcoast", "eastcoast"):
+        raise ValueError(f"unexpected counterform: {counterform}")
+    bct = [-cctA - cctB, -(cr1A + cr1B) * f, -(cr2A + cr2B) * _powu(f, 2), 0.0, 0.0, 0.0] if counterform == "eastcoast" else [
+        b1A * cctB / kmB**2 + b1B * cctA / kmA**2,
+        b1B * cr1A / krA**2 + b1A * cr1B / krB**2,
+        b1B * cr2A / krA**2 + b1A * cr2B / krB**2,
+        (cctA / kmA**2 + cctB / kmB**2) * f,
+        (cr1A / krA**2 + cr1B / krB**2) * f,
+        (cr2A / krA**2 + cr2B / krB**2) * f,
+    ]
+    bloop = [
+        1.0, 0.5 * (b1A + b1B), 0.5 * (b2A + b2B), 0.5 * (b3A + b3B), 0.5 * (b4A + b4B), b1A * b1B,
+        0.5 * (b1A * b2B + b1B * b2A), 0.5 * (b1A * b3B + b1B * b3A), 0.5 * (b1A * b4B + b1B * b4A),
+        b2A * b2B, 0.5 * (b2A * b4B + b2B * b4A), b4A * b4B,
+    ]
+    x1 = 0.5 * (1.0 / ndA + 1.0 / ndB)
+    x2 = 0.5 * (1.0 / ndA / kmA**2 + 1.0 / ndB / kmB**2)
+    bst = [ce0 * x1, cemono * x2, cequad * x2]
+    out = np.empty((N, 24))
+    for r, v in enumerate(b11 + bct + bloop + bst):
+        out[:, r] = v
+    return out
+
+
+def gaussian_rows_many(f, ngA, ngB=None, kmA=0.7, krA=0.25, ndA=3e-4, kmB=None, krB=None, ndB=None, basis="westcoast"):
+    """gaussian_rows for N draws: f [N] (or one value), ngA [N, 3] (and ngB [N, 3] for a cross spectrum) -> [N, nG + 1, 24]."""
+    if np.ndim(ngA) != 2 or (ngB is not None and np.ndim(ngB) != 2):
+        raise ValueError("ngA / ngB must be [N, 3]")
+    N = _ndraws(ngA, ngB)
+    f = _draws(f, N, "f")
+    ngA = _draws(ngA, N, "ngA", 3)
+    zero = np.zeros(N)
+    if basis == "eastcoast":
+        if ngB is not None:
+            raise NotImplementedError("EastCoastBasis does not support cross yet")
+        b1, b2, bG2 = ngA.T
+        f2 = _powu(f, 2)
+        c0 = c2 = c4 = bGamma3 = 0.0
+        bsA = np.stack([b1, b1 + 7 / 2 * bG2, b1 + 15 * bG2 + 6 * bGamma3, 1 / 2 * b2 - 7 / 2 * bG2,
+                        c0 - f / 3 * c2 + 3 / 35 * f2 * c4, c2 - 6 / 7 * f * c4, c4 + zero], axis=1)  # eastcoast_to_bs
+        Pshot = a0 = a2 = 0.0
+        es = np.stack([Pshot + zero, a0 + 1 / 3 * a2 + zero, 2 / 3 * a2 + zero], axis=1)
+        out = np.zeros((N, 8, 24))
+        out[:, 0] = bias_rows_many(f, bsA, None, es, counterform="eastcoast", kmA=kmA, krA=krA, ndA=ndA)
+        out[:, 1, LOOP + 3], out[:, 1, LOOP + 7] = 6.0, 6.0 * b1                                        # bGamma3
+        out[:, 2, CT + 0] = -2.0                                                                       # c0
+        out[:, 3, CT + 0], out[:, 3, CT + 1] = 2 / 3 * f, -2.0 * f                                     # c2
+        out[:, 4, CT + 0], out[:, 4, CT + 1], out[:, 4, CT + 2] = -6 / 35 * f2, 12 / 7 * f2, -2.0 * f2  # c4
+        x1 = 1.0 / ndA
+        x2 = 1.0 / ndA / kmA**2
+        out[:, 5, ST + 0] = x1                                                                         # Pshot
+        out[:, 6, ST + 1] = x2                                                                         # a0
+        out[:, 7, ST + 1], out[:, 7, ST + 2] = x2 / 3, 2 * x2 / 3                                      # a2
+        return out
+    if basis != "westcoast":
+        raise ValueError(f"unexpected basis: {basis}")
+    cross = ngB is not None
+    kmB = kmA if kmB is None else kmB
+    krB = krA if krB is None else krB
+    ndB = ndA if ndB is None else ndB
+    b1A, b2A, b4A = ngA.T
+    b1B, b2B, b4B = _draws(ngB, N, "ngB", 3).T if cross else (b1A, b2A, b4A)
+    bsA = np.stack([b1A, b2A, zero, b4A, zero, zero, zero], axis=1)
+    bsB = np.stack([b1B, b2B, zero, b4B, zero, zero, zero], axis=1) if cross else None
+    out = np.zeros((N, 12 if cross else 8, 24))
+    out[:, 0] = bias_rows_many(f, bsA, bsB, (0.0, 0.0, 0.0), kmA=kmA, krA=krA, ndA=ndA, kmB=kmB, krB=krB, ndB=ndB)
+    g = 1
+    if cross:
+        for b1o, km, kr in ((b1B, kmA, krA), (b1A, kmB, krB)):
+            out[:, g, LOOP + 3], out[:, g, LOOP + 7] = 0.5, 0.5 * b1o
+            out[:, g + 1, CT + 0], out[:, g + 1, CT + 3] = b1o / km**2, f / km**2
+            out[:, g + 2, CT + 1], out[:, g + 2, CT + 4] = b1o / kr**2, f / kr**2
+            out[:, g + 3, CT + 2], out[:, g + 3, CT + 5] = b1o / kr**2, f / kr**2
+            g += 4
+    else:
+        out[:, 1, LOOP + 3], out[:, 1, LOOP + 7] = 1.0, b1A
+        out[:, 2, CT + 0], out[:, 2, CT + 3] = 2.0 * b1A / kmA**2, 2.0 * f / kmA**2
+        out[:, 3, CT + 1], out[:, 3, CT + 4] = 2.0 * b1A / krA**2, 2.0 * f / krA**2
+        out[:, 4, CT + 2], out[:, 4, CT + 5] = 2.0 * b1A / krA**2, 2.0 * f / krA**2
+        g = 5
+    x1 = 0.5 * (1.0 / ndA + 1.0 / ndB)
+    x2 = 0.5 * (1.0 / ndA / kmA**2 + 1.0 / ndB / kmB**2)
+    out[:, g, ST + 0], out[:, g + 1, ST + 1], out[:, g + 2, ST + 2] = x1, x2, x2
+    return out
+
+
 # ----------------------------------------------------------------------------- parameter bases (SURVEY 8f rank 3)
 CT, LOOP, ST = 3, 9, 21  # first template row of Pctl, Ploopl, Pstl in the 24-row order
 

@@ -270,6 +270,30 @@ int  eftb_eval_batch(eftb_engine* e, int B, const double* Pin, const double* f, 
 int  eftb_eval_logp_batch(eftb_engine* e, int B, const double* Pin, const double* f, const double* DA, const double* H,
                           const double* rows, double* logp, double* fullchi2, double* best);
 
+/* Many EFT parameter draws against the CURRENT template block (the fast / slow split of the reference: EFTLeafKernel produces the
+ * bias-independent templates once per cosmology, theory.py:557-609, and EFTLeaf.calculate contracts them with the EFT parameters of each
+ * call, theory.py:829-874; samplers drag / oversample those fast parameters at fixed cosmology).  The current block is what
+ * eftb_get(EFTB_B_TEMPL) would return now (+ EFTB_B_TEMPLN with with_nnlo): left by a synchronous template-producing run (eftb_run,
+ * eftb_eval_batch, eftb_eval_logp_batch) or by eftb_put.  Draws are grouped by walker: offsets[C + 1] (offsets[0] = 0, non-decreasing,
+ * offsets[C] = N); walker c (template entries c*ntr ... c*ntr + ntr - 1) owns draws [offsets[c], offsets[c + 1]), possibly none.
+ * Both calls are synchronous and order themselves behind earlier work (queued staged steps included), as eftb_get does.  They refuse when
+ * offsets are malformed, when C * ntr exceeds the entries the block holds, or when the block holds no templates (the last run was a direct-P_l
+ * run, EFTB_O_PLK_DIRECT, or a staged step has rotated the blocks since the last template-producing synchronous run / eftb_put).
+ *
+ * eftb_draws_logp: the marginalised log-posterior per draw (likelihood.py:483-549, marginal.py:79-140) of the likelihood set by
+ * eftb_set_likelihood, whose data index must address the block's shape.  rows PACKED [N][ntr][nG+1][24] (the rows of the LOGP stage,
+ * eftpipe_amd.parambasis.gaussian_rows per tracer), rows_nnlo [N][ntr][nG+1][3] or NULL (zeros; with_nnlo only); logp [N] (NaN where
+ * det F2 <= 0), fullchi2 [N] and best [N][nG] may be NULL.  Per walker the Gram matrix W = A C^-1 A^T of the template columns and the data
+ * row is built on the first call after the block, the likelihood or the tracers change and reused after that; a draw then costs
+ * O(nG (24 ntr)^2), independent of the data-vector length.
+ *
+ * eftb_draws_reduce: P_l per draw (reduce_Plk, parambasis.py:128-136, of EFTLeaf.calculate): bias [N][ntr][24] (the EFTB_B_BIAS coefficients
+ * per tracer), bias_nnlo [N][ntr][3] or NULL (with_nnlo only; NULL: zeros) -> plk [N][ntr][nl][nx], the same bits as the REDUCE stage of the
+ * walker's entries.  Neither call touches the buffers of the runs (device memory for the draws grows on demand, freed by eftb_destroy). */
+int  eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* rows, const double* rows_nnlo, double* logp,
+                     double* fullchi2, double* best);
+int  eftb_draws_reduce(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* bias, const double* bias_nnlo, double* plk);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

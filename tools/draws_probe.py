@@ -1,0 +1,169 @@
+#!/usr/bin/env python3
+"""Fast / slow split on one GPU: parameter draws per second through MarginalLikelihood.logp_draws (eftb_draws_logp) against the templates of
+one set of walkers, for two shapes -- the single-tracer marg.npz likelihood and the cfg 3 joint likelihood (3 tracers, 142 data points,
+14 marginalised parameters, tests/golden/cfg3.npz) -- split into
+
+    rows    host row building (parambasis.gaussian_rows_many / marginal.joint_gaussian_rows_many) for all draws
+    h2d     the rows' bytes host -> device, pageable as the call takes them (one hipMemcpy of the same array)
+    gram    first call after put("TEMPL") minus a cached call: gather + A C^-1 + A U^T of every walker
+    draws   a cached call minus h2d: draw kernel + the [N][26] records back + unpacking
+
+and, for comparison, the same number of evaluations through eval_logp (theory + likelihood per walker; Nk = 512, resummation + AP, an
+interpolation onto the data k instead of the window: a lower bound on the cost of the real thing).  GPU box.
+
+    python tools/draws_probe.py [--draws N] [--walkers C]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cfg3_util as U  # noqa: E402
+from eftpipe_amd import synth  # noqa: E402
+from eftpipe_amd import tables as TB  # noqa: E402
+from eftpipe_amd.engine import Engine  # noqa: E402
+from eftpipe_amd.marginal import MarginalLikelihood, data_index, joint_gaussian_rows_many  # noqa: E402
+from eftpipe_amd.parambasis import gaussian_rows, gaussian_rows_many  # noqa: E402
+from eftpipe_amd.tables import EngineConfig  # noqa: E402
+
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def med(fn, n=5):
+    ts = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts))
+
+
+def h2d_seconds(a):
+    """one synchronous hipMemcpy of the array (pageable, as the draw call takes it) into a device buffer of its size"""
+    import ctypes as C
+
+    hip = C.CDLL("libamdhip64.so")
+    dev = C.c_void_p()
+    if hip.hipMalloc(C.byref(dev), C.c_size_t(a.nbytes)) != 0:
+        raise RuntimeError("hipMalloc failed")
+    one = lambda: hip.hipMemcpy(dev, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), 1)  # hipMemcpyHostToDevice
+    one()
+    t = med(one)
+    hip.hipFree(dev)
+    return t
+
+
+def marg_setup(C, N, rng):
+    g = dict(np.load(os.path.join(GOLD, "marg.npz")))
+    nx = g["binned_P11l"].shape[-1]
+    eng = Engine(EngineConfig(Nl=3), max_batch=C)
+    eng.set_template_dims(3, nx)
+    T = np.concatenate([g["binned_P11l"], g["binned_Pctl"], g["binned_Ploopl"], g["binned_Pstl"]], axis=1)
+    ls = list(g["ls"])
+    index = data_index(ls, {l: slice(a, b) for l, (a, b) in zip(ls, g["masks"])}, nx)
+    like = MarginalLikelihood(eng, index, g["auto_D"], g["auto_invcov"], g["auto_loc"], g["auto_scale"])
+    templ = np.stack([T * (1.0 + 0.01 * c) for c in range(C)])
+    f, co = float(g["f"]), g["auto_co"]
+    ng = dict(zip(g["auto_ng_names"], g["auto_ng_values"]))
+    ngv = np.array([ng["b1"], ng["b2"], ng["b4"]]) + rng.normal(0, 1, (N, 3)) * [0.05, 0.3, 0.3]
+    build = lambda: gaussian_rows_many(f, ngv, None, *co[:3])
+    return eng, like, templ, build, index.size, len(g["auto_loc"])
+
+
+def cfg3_setup(C, N, rng):
+    g = dict(np.load(os.path.join(GOLD, "cfg3.npz")))
+    nb = max(U.final_templates(g, t)["P11l"].shape[-1] for t in U.TRACERS)
+    block = np.zeros((3, 3, 24, nb))
+    for i, t in enumerate(U.TRACERS):
+        ft = U.final_templates(g, t)
+        T = np.concatenate([ft[n] for n in U.NAMES], axis=1)
+        block[i, : T.shape[0], :, : T.shape[-1]] = T
+    eng = Engine(EngineConfig(Nl=3), max_batch=3 * C)
+    eng.set_tracers(3)
+    eng.set_template_dims(3, nb)
+    index = np.concatenate([data_index([int(l) for l in g[t + "_ls"]], U.masks(g, t), nb, tracer=i, nl=3) for i, t in enumerate(U.TRACERS)])
+    names = [str(n) for n in g["full_names"]]
+    like = MarginalLikelihood(eng, index, g["data_vector"], g["invcov"], np.zeros(len(names)), np.full(len(names), np.inf), jeffreys=True)
+    templ = np.concatenate([block * (1.0 + 0.01 * c) for c in range(C)])
+    p = U.params(g)
+    draws = {k: np.full(N, v) for k, v in p.items()}
+    for k in ("LRG_NGC_b1", "ELG_NGC_b1", "LRG_NGC_c2", "LRG_NGC_c4", "ELG_NGC_c2", "ELG_NGC_c4"):
+        draws[k] = p[k] + 0.05 * rng.normal(size=N)
+    for t in ("LRG_NGC_", "ELG_NGC_"):
+        draws[t + "b2"] = (draws[t + "c2"] + draws[t + "c4"]) / np.sqrt(2.0)
+        draws[t + "b4"] = (draws[t + "c2"] - draws[t + "c4"]) / np.sqrt(2.0)
+    f = [float(g[t + "_f"]) for t in U.TRACERS]
+    build = lambda: joint_gaussian_rows_many(U.bases(), f, draws, names, U.scales(g))
+    return eng, like, templ, build, index.size, len(names)
+
+
+def eval_logp_rate(ntr, ndata_per_tracer, nG, walkers=42):
+    """eval_logp walkers / s on the production grid (Nk = 512, resummation + AP), data vector of the same length per tracer"""
+    k = synth.survey_kgrid(512)
+    cfg = EngineConfig(Nl=3, k=k, with_resum=True, with_ap=True, APst=True, DA_AP=float(synth.da_func(synth.OM_AP, 0.7)), H_AP=float(synth.hubble(synth.OM_AP, 0.7)))
+    eng = Engine(cfg, max_batch=walkers * ntr)
+    nd = (ndata_per_tracer + 2) // 3
+    kdata = np.linspace(0.02, 0.2, nd)
+    op = eng.add_operator(TB.compose_operator(3, 512, binning=TB.interp_operator(k, kdata)))
+    if ntr > 1:
+        eng.set_tracers(ntr, [op] * ntr)
+    else:
+        eng.set_pipeline_operator(op)
+    index = np.concatenate([data_index([0, 2, 4], {}, nd, tracer=t, nl=3) for t in range(ntr)])
+    cos = synth.cosmology(z=0.7, Om=0.3, h=0.68)
+    B = walkers * ntr
+    Pin, f, DA, H = np.stack([cos["Pin"]] * B), np.full(B, cos["f"]), np.full(B, cos["DA"]), np.full(B, cos["H"])
+    rng = np.random.default_rng(0)
+    data = rng.normal(0, 1, index.size)
+    like = MarginalLikelihood(eng, index, data, np.eye(index.size), np.zeros(nG), np.full(nG, 2.0))
+    rows = np.zeros((B, nG + 1, 24))
+    rows[:, : min(nG, 7) + 1] = gaussian_rows(float(cos["f"]), (2.0, 0.5, 0.3), None, 0.7, 0.25, 4.5e-5)[: min(nG, 7) + 1]
+    like.eval_logp(Pin, f, DA, H, rows)
+    t = med(lambda: like.eval_logp(Pin, f, DA, H, rows), 10)
+    eng.close()
+    return walkers / t
+
+
+def probe(name, setup, C, N, ntr):
+    rng = np.random.default_rng(1)
+    eng, like, templ, build, ndata, nG = setup(C, N, rng)
+    rows = build()
+    t_rows = med(build, 3)
+    counts = np.full(C, N // C)
+    counts[: N % C] += 1
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    t_h2d = h2d_seconds(rows)
+    eng.put("TEMPL", templ)
+    like.logp_draws(rows[:64], off * 0 + np.minimum(off, 64))  # (first launch of the kernels: code objects loaded)
+    eng.put("TEMPL", templ)
+    t0 = time.perf_counter()
+    like.logp_draws(rows, off)
+    t_first = time.perf_counter() - t0
+    t_cached = med(lambda: like.logp_draws(rows, off), 5)
+    rate_eval = eval_logp_rate(ntr, ndata // ntr, nG)
+    out = {
+        "shape": name, "walkers": C, "draws": N, "tracers": ntr, "ndata": ndata, "nG": nG, "row_bytes_per_draw": rows[0].nbytes,
+        "host_rows_us_per_draw": 1e6 * t_rows / N, "h2d_us_per_draw": 1e6 * t_h2d / N, "gram_ms": 1e3 * (t_first - t_cached),
+        "draws_us_per_draw": 1e6 * (t_cached - t_h2d) / N, "call_us_per_draw": 1e6 * t_cached / N,
+        "draws_per_s_device_call": N / t_cached, "draws_per_s_end_to_end": N / (t_cached + t_rows),
+        "eval_logp_per_s": rate_eval,
+    }
+    out["speedup_end_to_end"] = out["draws_per_s_end_to_end"] / rate_eval
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--draws", type=int, default=32768)
+    ap.add_argument("--walkers", type=int, default=32)
+    a = ap.parse_args()
+    probe("marg", marg_setup, a.walkers, a.draws, 1)
+    probe("cfg3", cfg3_setup, a.walkers, a.draws, 3)
