@@ -3844,4 +3844,249 @@ __global__ __launch_bounds__(256) void stream_read_kernel(const double* __restri
     if (s == 12345.678) sink[0] = s;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Draws given as EFT parameter values: the rows are built on the device from a draw recipe (eftb_set_draw_recipe).  Entry n of the recipe
+// is one non-zero (row g, tracer tau, column r) of R^, the sum of its terms coef * f[tau]^e * theta[i] * theta[j] * theta[k]; the entries
+// are sorted by (g, tau, r) and the terms of an entry keep a fixed order, so a draw's sum does not depend on how the work is split.
+//   tab = rowstart [ng1 + 1] (first entry of row g) | ent [nnz] (tau * 32 + r) | tstart [nnz + 1] (first term of entry n) | pack [nterms]
+//         | slot [ntr * 27] (the entry of (tau, r) in row 0, or -1: draws_recipe_rows_kernel)
+//   pack = i | j << 6 | k << 12 | (tau * 7 + e) << 18, with the factor 1 at theta index P
+// ------------------------------------------------------------------------------------------------
+constexpr int RECIPE_MAXP = 32, RECIPE_MAXTERMS = 1024, RECIPE_FPOW = 7, RECIPE_MAXTR = 8;
+
+struct RecipeTab {
+    const double* coef;  // [nterms]
+    const int *rowstart, *ent, *tstart, *pack, *slot;
+    int P, nnz;
+};
+
+// th[0..P) = theta of draw d, th[P] = 1 (lanes of one wave; the caller orders the LDS accesses)
+__device__ __forceinline__ void recipe_theta(const RecipeTab& rt, const double* __restrict__ theta, long long d, int lane, double* th) {
+    if (lane <= rt.P) th[lane] = lane < rt.P ? theta[(size_t)d * rt.P + lane] : 1.0;
+}
+
+// fp[tau * 7 + e] = f[c][tau]^e, e = 0 ... 6, by repeated multiplication (one thread per tracer)
+__device__ __forceinline__ void recipe_fpow(const double* __restrict__ f, int c, int ntr, int tid, double* fp) {
+    if (tid < ntr) {
+        const double fv = f[(size_t)c * ntr + tid];
+        double p = 1.0;
+        for (int e = 0; e < RECIPE_FPOW; ++e) {
+            fp[tid * RECIPE_FPOW + e] = p;
+            p *= fv;
+        }
+    }
+}
+
+// the value of entry n: its terms summed in their order
+__device__ __forceinline__ double recipe_entry(const RecipeTab& rt, int n, const double* fp, const double* th) {
+    double s = 0.0;
+    for (int t = rt.tstart[n]; t < rt.tstart[n + 1]; ++t) {
+        const int p = rt.pack[t];
+        s += rt.coef[t] * fp[p >> 18] * th[p & 63] * th[(p >> 6) & 63] * th[(p >> 12) & 63];
+    }
+    return s;
+}
+
+// column of W_c / R^ an entry (tau * 32 + r) acts on: (tau, r) for the 24 template rows, the NNLO columns after them
+__device__ __forceinline__ int recipe_col(int ent, int ntr) {
+    const int tau = ent >> 5, r = ent & 31;
+    return r < NROW ? tau * NROW + r : ntr * NROW + 3 * tau + (r - NROW);
+}
+
+// The small algebra of one draw after G = R^ W_c R^^T (one wave; G [nG + 1][nG + 1] in the wave's LDS): F2 = sym(G[1:,1:]) + sigma^-2, F1,
+// F0, the wave-synchronous LU described at draws_logp_kernel, and the [MARG_OUT] record of the draw: the statements of draws_logp_kernel after
+// its G (that kernel keeps them inline, so its compiled code stays the one that was measured).
+__device__ __forceinline__ void draws_solve(int lane, int nG, int jeffreys, const double* Gs, const double* mu, const double* sinv, double* o) {
+    const int ng1 = nG + 1;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    // ---- F2 | F1 per lane (row i = lane), LU with partial pivoting
+    const bool own = lane < nG;
+    double a[MARG_MAXG], aug = 0.0;
+#pragma unroll
+    for (int j = 0; j < MARG_MAXG; ++j)
+        a[j] = (own && j < nG) ? 0.5 * (Gs[(lane + 1) * ng1 + j + 1] + Gs[(j + 1) * ng1 + lane + 1]) + (lane == j ? sinv[j] : 0.0) : 0.0;
+    if (own) aug = -Gs[(lane + 1) * ng1] + sinv[lane] * mu[lane];
+    const double f1 = aug;
+    int pos = lane, sgn = 1;
+    double logdet = 0.0, dpv[MARG_MAXG];
+    int pl[MARG_MAXG];
+#pragma unroll
+    for (int c2 = 0; c2 < MARG_MAXG; ++c2) {
+        if (c2 >= nG) continue;
+        // pivot: largest |F2[i][c2]| among the rows not yet eliminated, the first in row order on ties (marg_solve_kernel, LAPACK)
+        const bool cand = own && pos >= c2;
+        double v = fabs(a[c2]);
+        if (!(v >= 0.0)) v = -0.5;  // NaN: a total order keeps the reduction's result the same in every lane
+        if (!cand) v = -1.0;
+        int kp = cand ? pos : 1 << 20, who = lane;
+#pragma unroll
+        for (int m = 16; m >= 1; m >>= 1) {  // lanes 0-31 hold every row (nG <= 24)
+            const double v2 = __shfl_xor(v, m);
+            const int k2 = __shfl_xor(kp, m), w2 = __shfl_xor(who, m);
+            if (v2 > v || (v2 == v && k2 < kp)) {
+                v = v2;
+                kp = k2;
+                who = w2;
+            }
+        }
+        const int p = __builtin_amdgcn_readlane(who, 0);
+        const int pp = __builtin_amdgcn_readlane(pos, p);
+        if (pp != c2) sgn = -sgn;
+        if (pos == c2) pos = pp;  // the row at place c2 takes the pivot row's place
+        if (lane == p) pos = c2;
+        const double dpiv = readlane_f64(a[c2], p);
+        if (dpiv < 0.0) sgn = -sgn;
+        if (dpiv == 0.0 || dpiv != dpiv) sgn = 0;
+        logdet += log(fabs(dpiv));
+        dpv[c2] = dpiv;
+        pl[c2] = p;
+        const bool elim = own && pos > c2;
+        const double m = elim ? a[c2] / dpiv : 0.0;
+#pragma unroll
+        for (int j = c2 + 1; j < MARG_MAXG; ++j)
+            if (j < nG) {
+                const double u = readlane_f64(a[j], p);
+                if (elim) a[j] = fma(-m, u, a[j]);
+            }
+        const double yc = readlane_f64(aug, p);
+        if (elim) aug = fma(-m, yc, aug);
+    }
+    // back substitution U b = y: b = F2^-1 F1, the best-fit Gaussian parameters
+    double b[MARG_MAXG];
+#pragma unroll
+    for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2) {
+        b[c2] = 0.0;
+        if (c2 < nG) {
+            const double bc = readlane_f64(aug, pl[c2]) / dpv[c2];
+            b[c2] = bc;
+            if (own && pos < c2) aug = fma(-a[c2], bc, aug);
+        }
+    }
+    // F1 F2^-1 F1, F0 and the full chi2 at b (row sums per lane, added in row order)
+    double bi = 0.0, srow = 0.0;
+#pragma unroll
+    for (int j = 0; j < MARG_MAXG; ++j)
+        if (j < nG) {
+            if (lane == j) bi = b[j];
+            if (own) srow = fma(b[j], Gs[(lane + 1) * ng1 + j + 1], srow);
+        }
+    const double trow = own ? bi * fma(2.0, Gs[(lane + 1) * ng1], srow) : 0.0;
+    double quad = 0.0, F0 = Gs[0], full = Gs[0];
+#pragma unroll
+    for (int i = 0; i < MARG_MAXG; ++i)
+        if (i < nG) {
+            quad = fma(readlane_f64(f1, i), b[i], quad);
+            F0 = fma(mu[i] * sinv[i], mu[i], F0);
+            full += readlane_f64(trow, i);
+        }
+    const bool ok = sgn > 0;
+    const double chi2 = -quad + F0 + (jeffreys ? 0.0 : logdet - nG * 1.8378770664093453);  // ln det(F2 / 2 pi)
+    if (lane == 0) {
+        o[0] = ok ? -0.5 * chi2 : nan;
+        o[1] = ok ? full : nan;
+    }
+    if (lane < MARG_MAXG) o[2 + lane] = own ? (ok ? bi : nan) : 0.0;
+}
+
+// draws_logp_kernel for draws given as theta [N][P] and f [C][ntr]: the same workgroup shape (W_c in LDS once, one wave per draw at a
+// time) and the same algebra after G, but R^ only exists as the values of its nnz non-zero entries in the wave's LDS:
+//   val[n]        lanes over the entries of the recipe
+//   H = R^ W_c    row g at a time: lanes over the columns j (j = lane and lane + 64 with TWO), one FMA per non-zero of row g, the value a
+//                 broadcast LDS read; R^[0][J] = 1 stays implicit (the data row of W_c is added to row 0)
+//   G = H R^^T    lane g + 32 half holds row g of H and takes every second non-zero of row h; the halves are added with one shuffle
+// LDS: W_c [J1][J1], fp [RECIPE_MAXTR * 7], col [nnz] (ints), then per wave th [P + 1 -> 34], val [nnz], H [ng1][J1], G [ng1][ng1].
+template <bool TWO>
+__global__ __launch_bounds__(256) void draws_logp_params_kernel(int ntr, int nG, int J1, int jeffreys, RecipeTab rt, const long long* __restrict__ offsets,
+                                                                const double* __restrict__ theta, const double* __restrict__ f,
+                                                                const double* __restrict__ W, const double* __restrict__ mu,
+                                                                const double* __restrict__ sinv, double* __restrict__ out) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ng1 = nG + 1, J = J1 - 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1;
+    const long long d0 = offsets[c], d1 = offsets[c + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
+    double* Ws = sm;
+    double* fp = Ws + J1 * J1;
+    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
+    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
+    for (int n = threadIdx.x; n < nnz; n += blockDim.x) col[n] = recipe_col(rt.ent[n], ntr);
+    recipe_fpow(f, c, ntr, threadIdx.x, fp);
+    __syncthreads();
+    double* th = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp / 2 + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1);
+    double* val = th + 34;
+    double* Hs = val + nnzp;
+    double* Gs = Hs + ng1 * J1;
+    const bool c0 = lane < J1, c1 = TWO && lane + 64 < J1;
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        // ---- the non-zeros of R^ for this draw
+        recipe_theta(rt, theta, d, lane, th);
+        wave_lds_sync();
+        for (int n = lane; n < nnz; n += 64) val[n] = recipe_entry(rt, n, fp, th);
+        wave_lds_sync();
+        // ---- H = R^ W_c
+        for (int g = 0; g < ng1; ++g) {
+            double h0 = 0.0, h1 = 0.0;
+            const int n1 = rt.rowstart[g + 1];
+            for (int n = rt.rowstart[g]; n < n1; ++n) {
+                const double rv = val[n];
+                const double* wk = Ws + col[n] * J1 + lane;
+                h0 = fma(rv, c0 ? wk[0] : 0.0, h0);
+                if (TWO) h1 = fma(rv, c1 ? wk[64] : 0.0, h1);
+            }
+            if (g == 0) {  // the data row: R^[0][J] = 1
+                h0 += c0 ? Ws[J * J1 + lane] : 0.0;
+                if (TWO) h1 += c1 ? Ws[J * J1 + 64 + lane] : 0.0;
+            }
+            if (c0) Hs[g * J1 + lane] = h0;
+            if (c1) Hs[g * J1 + 64 + lane] = h1;
+        }
+        wave_lds_sync();
+        // ---- G = H R^^T over the non-zeros of row h
+        {
+            const int g = lane & 31, half = lane >> 5;
+            const double* hg = Hs + (g < ng1 ? g : 0) * J1;
+            for (int h = 0; h < ng1; ++h) {
+                double acc = 0.0;
+                const int n1 = rt.rowstart[h + 1];
+                for (int n = rt.rowstart[h] + half; n < n1; n += 2) acc = fma(hg[col[n]], val[n], acc);
+                acc += __shfl_xor(acc, 32);
+                if (h == 0) acc += hg[J];
+                if (half == 0 && g < ng1) Gs[g * ng1 + h] = acc;
+            }
+        }
+        wave_lds_sync();
+        draws_solve(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
+        wave_lds_sync();  // (the next draw overwrites th, val, H and G)
+    }
+}
+
+// The bias recipe of eftb_draws_reduce_params evaluated into the coefficient buffers of draws_reduce_kernel: bias [N][ntr][24] and, with
+// NNLO, biasn [N][ntr][3] (zero where the recipe has no entry: every coefficient is written once).  One workgroup per (walker, share of its draws), one wave per draw at a time.
+// LDS: fp [RECIPE_MAXTR * 7], then per wave th [34].
+template <bool NNLO>
+__global__ __launch_bounds__(256) void draws_recipe_rows_kernel(int ntr, RecipeTab rt, const long long* __restrict__ offsets, const double* __restrict__ theta,
+                                                                const double* __restrict__ f, double* __restrict__ bias, double* __restrict__ biasn) {
+    __shared__ double fp[RECIPE_MAXTR * RECIPE_FPOW];
+    __shared__ double ths[4][34];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long d0 = offsets[c], d1 = offsets[c + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;
+    recipe_fpow(f, c, ntr, threadIdx.x, fp);
+    __syncthreads();
+    double* th = ths[wv];
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        recipe_theta(rt, theta, d, lane, th);
+        wave_lds_sync();
+        for (int q = lane; q < ntr * (NROW + 3); q += 64) {
+            const int tau = q / (NROW + 3), r = q % (NROW + 3), n = rt.slot[q];
+            const double v = n >= 0 ? recipe_entry(rt, n, fp, th) : 0.0;
+            if (r < NROW) bias[((size_t)d * ntr + tau) * NROW + r] = v;
+            else if (NNLO) biasn[((size_t)d * ntr + tau) * 3 + (r - NROW)] = v;
+        }
+        wave_lds_sync();  // (the next draw overwrites th)
+    }
+}
+
 }  // namespace eftb

@@ -17,7 +17,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
+#include <tuple>
 #include <algorithm>
 #include <vector>
 
@@ -147,6 +149,17 @@ struct eftb_engine {
     long long* drw_off = nullptr;
     std::vector<double> drw_host;   // eftb_draws_logp: D2H landing block [N][MARG_OUT]
     bool drw_lds = false;           // draws_logp_kernel opted in to the large dynamic LDS
+    // draw recipes (eftb_set_draw_recipe): [0] of eftb_draws_logp_params, [1] of eftb_draws_reduce_params.  coef [nterms] and the int table
+    // rowstart | ent | tstart | pack | slot (RecipeTab) live on the device; set = false: none (never set, withdrawn, or dropped)
+    struct Recipe {
+        bool set = false, nnlo = false;
+        int P = 0, ng1 = 0, nterms = 0, nnz = 0, ntr_used = 0;
+        double* coef = nullptr;
+        int* tab = nullptr;
+    } recipe[2];
+    double* drw_theta = nullptr;    // theta [N][P] then f [C][ntr] of a params call
+    size_t drw_theta_cap = 0;
+    bool drwp_lds = false;          // draws_logp_params_kernel opted in to the large dynamic LDS
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -1783,6 +1796,7 @@ int eftb_set_tracers(eftb_engine* e, int ntr) {
     ++e->draw_gen;
     e->tracer_ops.clear();
     e->like_ndata = 0;  // a likelihood set for another grouping does not survive
+    e->recipe[0].set = e->recipe[1].set = false;  // nor do the draw recipes: their terms name tracers
     return 0;
 }
 
@@ -1962,6 +1976,7 @@ int eftb_set_likelihood(eftb_engine* e, int ndata, const int32_t* index, const d
     e->like_nG = nG;
     e->like_nl = lnl;
     e->like_nx = lnx;
+    e->recipe[0].set = false;  // the logp recipe belongs to the likelihood it was set for
     ++e->draw_gen;
     return 0;
 }
@@ -1990,7 +2005,8 @@ void eftb_destroy(eftb_engine* e) {
     for (void* p : {(void*)e->APW, (void*)e->APW2, (void*)e->API, (void*)e->API2, (void*)e->APM, (void*)e->APM2}) if (p) (void)hipFree(p);
     for (auto& o : e->ops) if (o.dev) (void)hipFree(o.dev);
     for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off, (void*)e->drw_theta,
+                    (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evSnap, e->evGathered, e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
@@ -2236,36 +2252,12 @@ static int draw_shares(long long maxcnt, int per_wg, long long groups) {
     return (int)std::max(1LL, std::min(want, fill));
 }
 
-int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* rows, const double* rows_nnlo, double* logp,
-                    double* fullchi2, double* best) {
-    static const char* who = "eftb_draws_logp";
-    if (e) sub_drain(e);
-    if (!e || !offsets || (N > 0 && (!rows || !logp))) return fail("%s: null argument", who);
-    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
-    long long maxcnt = 0;
-    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
-    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
-        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
-                    e->cur_nx);
+// W_c [C][J1][J1] of the current block, likelihood and tracers: built when the cached block is of another generation or holds fewer walkers
+static int draws_gram(eftb_engine* e, const char* who, int C, int J1) {
     const eftb_config& c = e->c;
-    if (rows_nnlo && !c.with_nnlo) return fail("%s: rows_nnlo needs an engine built with with_nnlo", who);
-    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1, nd = e->like_ndata;
-    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
-    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
-    const size_t lds_w = (size_t)J1 * J1 * sizeof(double), lds_wave = ((size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
-    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
-    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
-    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
-    if (N == 0) return 0;
-    HIPCHK(hipSetDevice(c.device));
+    const int ntr = e->ntr, nd = e->like_ndata;
     hipStream_t st = e->stream;
-    join_back(e);
-    if (!e->drw_lds) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        e->drw_lds = true;
-    }
-    if (e->gram_gen != e->draw_gen || e->gram_C < C) {  // W_c of the current block, likelihood and tracers
+    if (e->gram_gen != e->draw_gen || e->gram_C < C) {
         e->gram_gen = 0;
         const size_t ae = (size_t)C * J1 * nd;
         if (int rc = grow_dev(&e->drw_A, &e->drw_A_cap, ae)) return rc;
@@ -2285,6 +2277,56 @@ int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, 
         e->gram_gen = e->draw_gen;
         e->gram_C = C;
     }
+    return 0;
+}
+
+// the [N][MARG_OUT] records of a logp draw kernel -> logp [N], fullchi2 [N], best [N][nG] (synchronises the stream)
+static int draws_records(eftb_engine* e, long long N, double* logp, double* fullchi2, double* best) {
+    const int nG = e->like_nG;
+    hipStream_t st = e->stream;
+    e->drw_host.resize((size_t)N * MARG_OUT);
+    HIPCHK(hipMemcpyAsync(e->drw_host.data(), e->drw_out, (size_t)N * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (long long d = 0; d < N; ++d) {
+        const double* o = e->drw_host.data() + (size_t)d * MARG_OUT;
+        logp[d] = o[0];
+        if (fullchi2) fullchi2[d] = o[1];
+        if (best)
+            for (int i = 0; i < nG; ++i) best[(size_t)d * nG + i] = o[2 + i];
+    }
+    return 0;
+}
+
+int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* rows, const double* rows_nnlo, double* logp,
+                    double* fullchi2, double* best) {
+    static const char* who = "eftb_draws_logp";
+    if (e) sub_drain(e);
+    if (!e || !offsets || (N > 0 && (!rows || !logp))) return fail("%s: null argument", who);
+    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
+    long long maxcnt = 0;
+    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
+        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
+                    e->cur_nx);
+    const eftb_config& c = e->c;
+    if (rows_nnlo && !c.with_nnlo) return fail("%s: rows_nnlo needs an engine built with with_nnlo", who);
+    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1;
+    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
+    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
+    const size_t lds_w = (size_t)J1 * J1 * sizeof(double), lds_wave = ((size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
+    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
+    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
+    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
+    if (N == 0) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    hipStream_t st = e->stream;
+    join_back(e);
+    if (!e->drw_lds) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->drw_lds = true;
+    }
+    if (int rc = draws_gram(e, who, C, J1)) return rc;
     const size_t rn = (size_t)N * ntr * ng1 * NROW, rnn = (size_t)N * ntr * ng1 * 3;
     if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
     if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, rn)) return rc;
@@ -2304,16 +2346,7 @@ int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, 
                            e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
-    e->drw_host.resize((size_t)N * MARG_OUT);
-    HIPCHK(hipMemcpyAsync(e->drw_host.data(), e->drw_out, (size_t)N * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (long long d = 0; d < N; ++d) {
-        const double* o = e->drw_host.data() + (size_t)d * MARG_OUT;
-        logp[d] = o[0];
-        if (fullchi2) fullchi2[d] = o[1];
-        if (best)
-            for (int i = 0; i < nG; ++i) best[(size_t)d * nG + i] = o[2 + i];
-    }
+    if (int rc = draws_records(e, N, logp, fullchi2, best)) return rc;
     return 0;
 }
 
@@ -3283,3 +3316,213 @@ int eftb_window_precompute(int device, int Na, int Nl, int Nk, int nx, int Np, c
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ draws given as parameter values
+// (after every other entry point: the kernels instantiated here are emitted behind the existing ones, whose code and labels stay as they were)
+int eftb_set_draw_recipe(eftb_engine* e, int kind, int P, int ng1, int nterms, const eftb_draw_term* terms) {
+    static const char* who = "eftb_set_draw_recipe";
+    if (e) sub_drain(e);
+    if (!e) return fail("%s: null engine", who);
+    if (kind != 0 && kind != 1) return fail("%s: kind %d (0: eftb_draws_logp_params, 1: eftb_draws_reduce_params)", who, kind);
+    eftb_engine::Recipe& rc = e->recipe[kind];
+    if (nterms == 0) {
+        rc.set = false;
+        return 0;
+    }
+    if (!terms) return fail("%s: null terms", who);
+    if (P < 0 || P > RECIPE_MAXP) return fail("%s: %d parameters, at most %d", who, P, RECIPE_MAXP);
+    if (nterms < 0 || nterms > RECIPE_MAXTERMS) return fail("%s: %d terms, at most %d", who, nterms, RECIPE_MAXTERMS);
+    if (kind == 0 ? (ng1 < 1 || ng1 > MARG_NG1) : ng1 != 1) return fail("%s: ng1 = %d (kind 0: 1 ... %d, kind 1: 1)", who, ng1, MARG_NG1);
+    if (kind == 0 && !e->like_ndata) return fail("%s: the logp recipe belongs to a likelihood: needs eftb_set_likelihood first", who);
+    if (kind == 0 && ng1 != e->like_nG + 1) return fail("%s: the recipe has ng1 = %d rows, the likelihood nG + 1 = %d", who, ng1, e->like_nG + 1);
+    const int ntr = e->ntr, ncol = e->c.with_nnlo ? NROW + 3 : NROW;
+    if (ntr > RECIPE_MAXTR) return fail("%s: %d tracers, a draw recipe takes at most %d", who, ntr, RECIPE_MAXTR);
+    for (int t = 0; t < nterms; ++t) {
+        const eftb_draw_term& q = terms[t];
+        if (q.tracer < 0 || q.tracer >= ntr) return fail("%s: term %d: tracer %d outside [0, %d)", who, t, q.tracer, ntr);
+        if (q.row < 0 || q.row >= ng1) return fail("%s: term %d: row %d outside [0, %d)", who, t, q.row, ng1);
+        if (q.col < 0 || q.col >= ncol)
+            return fail("%s: term %d: column %d outside [0, %d)%s", who, t, q.col, ncol, e->c.with_nnlo ? "" : " (the NNLO columns 24 ... 26 need an engine built with with_nnlo)");
+        if (q.fpow < 0 || q.fpow >= RECIPE_FPOW) return fail("%s: term %d: f^%d, powers 0 ... %d", who, t, q.fpow, RECIPE_FPOW - 1);
+        for (int ix : {q.i, q.j, q.k})
+            if (ix < -1 || ix >= P) return fail("%s: term %d: parameter index %d outside [-1, %d)", who, t, ix, P);
+        if (!std::isfinite(q.coef)) return fail("%s: term %d: the coefficient is not finite", who, t);
+    }
+    // the order the kernels sum in: entries by (row, tracer, column); inside an entry by (fpow, i, j, k) descending indices first, then the
+    // coefficient -- independent of the order the terms arrive in
+    struct Key {
+        int row, tracer, col, fpow, ix[3];
+        double coef;
+    };
+    std::vector<Key> keys(nterms);
+    for (int t = 0; t < nterms; ++t) {
+        const eftb_draw_term& q = terms[t];
+        Key& k = keys[t];
+        k.row = q.row; k.tracer = q.tracer; k.col = q.col; k.fpow = q.fpow; k.coef = q.coef;
+        k.ix[0] = q.i; k.ix[1] = q.j; k.ix[2] = q.k;
+        std::sort(k.ix, k.ix + 3, std::greater<int>());  // (the -1 entries last)
+    }
+    std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+        return std::tie(a.row, a.tracer, a.col, a.fpow, a.ix[0], a.ix[1], a.ix[2], a.coef) < std::tie(b.row, b.tracer, b.col, b.fpow, b.ix[0], b.ix[1], b.ix[2], b.coef);
+    });
+    std::vector<int> rowstart(ng1 + 1, 0), ent, tstart, pack(nterms), slot((size_t)ntr * (NROW + 3), -1);
+    std::vector<double> coef(nterms);
+    bool nnlo = false;
+    for (int t = 0; t < nterms; ++t) {
+        const Key& k = keys[t];
+        if (t == 0 || k.row != keys[t - 1].row || k.tracer != keys[t - 1].tracer || k.col != keys[t - 1].col) {
+            if (k.row == 0) slot[(size_t)k.tracer * (NROW + 3) + k.col] = (int)ent.size();
+            ent.push_back(k.tracer * 32 + k.col);
+            tstart.push_back(t);
+            ++rowstart[k.row + 1];
+        }
+        nnlo = nnlo || k.col >= NROW;
+        auto ix = [P](int v) { return v < 0 ? P : v; };
+        pack[t] = ix(k.ix[0]) | ix(k.ix[1]) << 6 | ix(k.ix[2]) << 12 | (k.tracer * RECIPE_FPOW + k.fpow) << 18;
+        coef[t] = k.coef;
+    }
+    tstart.push_back(nterms);
+    for (int g = 0; g < ng1; ++g) rowstart[g + 1] += rowstart[g];
+    const int nnz = (int)ent.size();
+    std::vector<int> tab;
+    for (const std::vector<int>* v : {&rowstart, &ent, &tstart, &pack, &slot}) tab.insert(tab.end(), v->begin(), v->end());
+    HIPCHK(hipSetDevice(e->c.device));
+    HIPCHK(sync_all(e));  // (a params call is synchronous: nothing reads the old tables any more; as eftb_set_likelihood)
+    rc.set = false;
+    for (void* p : {(void*)rc.coef, (void*)rc.tab}) if (p) (void)hipFree(p);
+    rc.coef = nullptr;
+    rc.tab = nullptr;
+    HIPCHK(hipMalloc(&rc.coef, coef.size() * sizeof(double)));
+    HIPCHK(hipMalloc(&rc.tab, tab.size() * sizeof(int)));
+    HIPCHK(hipMemcpy(rc.coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rc.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    rc.P = P; rc.ng1 = ng1; rc.nterms = nterms; rc.nnz = nnz; rc.nnlo = nnlo; rc.ntr_used = ntr;
+    rc.set = true;
+    return 0;
+}
+
+static RecipeTab recipe_tab(const eftb_engine::Recipe& rc) {
+    RecipeTab rt{};
+    rt.coef = rc.coef;
+    rt.rowstart = rc.tab;
+    rt.ent = rt.rowstart + rc.ng1 + 1;
+    rt.tstart = rt.ent + rc.nnz;
+    rt.pack = rt.tstart + rc.nnz + 1;
+    rt.slot = rt.pack + rc.nterms;
+    rt.P = rc.P;
+    rt.nnz = rc.nnz;
+    return rt;
+}
+
+// the recipe of a params call and its inputs: refusals before anything is copied
+static int draws_params_check(eftb_engine* e, const char* who, int kind, int ng1, int C, long long N, const double* theta, const double* f) {
+    const eftb_engine::Recipe& rc = e->recipe[kind];
+    if (!rc.set) return fail("%s: no draw recipe (eftb_set_draw_recipe kind %d; eftb_set_tracers%s drops it)", who, kind, kind == 0 ? " and eftb_set_likelihood" : "");
+    if (rc.ng1 != ng1) return fail("%s: the draw recipe has ng1 = %d rows, the call needs %d", who, rc.ng1, ng1);
+    if (rc.ntr_used != e->ntr) return fail("%s: the draw recipe was set for %d tracers, the engine has %d", who, rc.ntr_used, e->ntr);
+    if (rc.nnlo && !e->c.with_nnlo) return fail("%s: the draw recipe has NNLO columns, the engine was built without with_nnlo", who);
+    for (long long q = 0; q < N * rc.P; ++q)
+        if (!std::isfinite(theta[q])) return fail("%s: theta[%lld][%d] is not finite", who, q / rc.P, (int)(q % rc.P));
+    for (int q = 0; q < C * e->ntr; ++q)
+        if (!std::isfinite(f[q])) return fail("%s: f[%d][%d] is not finite", who, q / e->ntr, q % e->ntr);
+    return 0;
+}
+
+// theta [N][P] and f [C][ntr] to the device (one buffer: theta, then f)
+static int draws_params_upload(eftb_engine* e, int P, int C, long long N, const double* theta, const double* f, const double** dtheta, const double** df) {
+    const size_t nt = (size_t)N * P, nf = (size_t)C * e->ntr;
+    if (int rc = grow_dev(&e->drw_theta, &e->drw_theta_cap, nt + nf)) return rc;
+    if (nt) HIPCHK(hipMemcpyAsync(e->drw_theta, theta, nt * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->drw_theta + nt, f, nf * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    *dtheta = e->drw_theta;
+    *df = e->drw_theta + nt;
+    return 0;
+}
+
+int eftb_draws_logp_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
+                           double* fullchi2, double* best) {
+    static const char* who = "eftb_draws_logp_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
+    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
+    long long maxcnt = 0;
+    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
+        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
+                    e->cur_nx);
+    const eftb_config& c = e->c;
+    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1;
+    if (int rc = draws_params_check(e, who, 0, ng1, C, N, theta, f)) return rc;
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
+    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
+    const int nnzp = (rcp.nnz + 1) & ~1;
+    const size_t lds_w = ((size_t)J1 * J1 + RECIPE_MAXTR * RECIPE_FPOW + nnzp / 2) * sizeof(double);
+    const size_t lds_wave = (34 + (size_t)nnzp + (size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
+    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
+    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
+    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
+    if (N == 0) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    hipStream_t st = e->stream;
+    join_back(e);
+    if (!e->drwp_lds) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_params_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_params_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->drwp_lds = true;
+    }
+    if (int rc = draws_gram(e, who, C, J1)) return rc;
+    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
+    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    const double *dtheta = nullptr, *df = nullptr;
+    if (int rc = draws_params_upload(e, rcp.P, C, N, theta, f, &dtheta, &df)) return rc;
+    const dim3 grid(C, draw_shares(maxcnt, nw, C)), block(64 * nw);
+    const size_t lds = lds_w + nw * lds_wave;
+    const RecipeTab rt = recipe_tab(rcp);
+    if (J1 > 64)
+        hipLaunchKernelGGL(draws_logp_params_kernel<true>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
+                           e->like_sinv, e->drw_out);
+    else
+        hipLaunchKernelGGL(draws_logp_params_kernel<false>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
+                           e->like_sinv, e->drw_out);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    return draws_records(e, N, logp, fullchi2, best);
+}
+
+int eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* plk) {
+    static const char* who = "eftb_draws_reduce_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta || !plk))) return fail("%s: null argument", who);
+    long long maxcnt = 0;
+    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    if (int rc = draws_params_check(e, who, 1, 1, C, N, theta, f)) return rc;
+    if (N == 0) return 0;
+    const eftb_config& c = e->c;
+    const eftb_engine::Recipe& rcp = e->recipe[1];
+    const int ntr = e->ntr, nl = e->cur_nl, nx = e->cur_nx, xtiles = (nx + 63) / 64;
+    HIPCHK(hipSetDevice(c.device));
+    hipStream_t st = e->stream;
+    join_back(e);
+    const size_t bn = (size_t)N * ntr * NROW, bnn = (size_t)N * ntr * 3, pn = (size_t)N * ntr * nl * nx;
+    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, bn)) return rc;
+    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, pn)) return rc;
+    if (c.with_nnlo)
+        if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, bnn)) return rc;
+    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    const double *dtheta = nullptr, *df = nullptr;
+    if (int rc = draws_params_upload(e, rcp.P, C, N, theta, f, &dtheta, &df)) return rc;
+    const dim3 rgrid(C, draw_shares(maxcnt, 4, C));
+    if (c.with_nnlo) hipLaunchKernelGGL(draws_recipe_rows_kernel<true>, rgrid, dim3(256), 0, st, ntr, recipe_tab(rcp), e->drw_off, dtheta, df, e->drw_in, e->drw_inn);
+    else hipLaunchKernelGGL(draws_recipe_rows_kernel<false>, rgrid, dim3(256), 0, st, ntr, recipe_tab(rcp), e->drw_off, dtheta, df, e->drw_in, nullptr);
+    const int shares = draw_shares(maxcnt, 4, (long long)C * ntr * nl * xtiles);
+    hipLaunchKernelGGL(draws_reduce_kernel, dim3(xtiles * shares, ntr * nl, C), dim3(256), 0, st, nx, nl, ntr, reduce_msplit(c), xtiles, e->drw_off, e->drw_in,
+                       e->buf[EFTB_B_TEMPL], c.with_nnlo ? e->drw_inn : nullptr, c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, e->drw_out);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    HIPCHK(hipMemcpyAsync(plk, e->drw_out, pn * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}

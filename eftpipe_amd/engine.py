@@ -386,6 +386,26 @@ class Engine:
         L.check(self.lib.eftb_draws_reduce(self._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(bias), L.dptr(bn), L.dptr(out)))
         return out
 
+    def set_reduce_recipe(self, recipe):
+        """The draw recipe of ``reduce_draws_params`` (``eftb_set_draw_recipe`` kind 1; ``parambasis.bias_draw_recipe``): one row per tracer.
+        ``set_tracers`` drops it; None withdraws it."""
+        self._reduce_recipe = _set_recipe(self, L.RECIPE_REDUCE, recipe, 1)
+
+    def reduce_draws_params(self, theta, offsets, f, out=None):
+        """``reduce_draws`` with the coefficients built on the device from parameter values (``eftb_draws_reduce_params``): theta [N, P] in
+        the order of the recipe's ``param_names``, f [C, ntr] ([C] with one tracer) the growth rate of each walker's entries
+        -> P_l [N, nl, nx] ([N, ntr, nl, nx] with tracers)."""
+        ntr, (nl, nx) = self.ntracers, self.dims
+        theta, off, f = _params_args(getattr(self, "_reduce_recipe", None), theta, offsets, f, ntr)
+        N = theta.shape[0]
+        shape = (N, nl, nx) if ntr == 1 else (N, ntr, nl, nx)
+        if out is None:
+            out = np.empty(shape)
+        elif out.shape != shape or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise ValueError(f"out must be a writable C-contiguous float64 array {shape}")
+        L.check(self.lib.eftb_draws_reduce_params(self._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f), L.dptr(out)))
+        return out
+
     # ------------------------------------------------------------------ pipelined steps (double-buffered inputs / outputs)
     def stage_inputs(self, Pin, f, DA=None, H=None, bias=None, rows=None):
         """Copy the inputs of the NEXT step into the idle input set while the current step runs (``eftb_stage_inputs``)."""
@@ -558,3 +578,36 @@ def mfma_f64_peak(device=0):
     v = C.c_double()
     L.check(lib.eftb_mfma_f64_peak(device, C.byref(v)))
     return v.value
+
+
+def _set_recipe(eng, kind, recipe, ng1):
+    """hand a ``parambasis.DrawRecipe`` to the library (None: withdraw); -> the recipe, kept for the shape checks of the params calls"""
+    if recipe is None:
+        L.check(eng.lib.eftb_set_draw_recipe(eng._h, kind, 0, ng1, 0, None))
+        return None
+    if recipe.ntr != eng.ntracers:
+        raise ValueError(f"the recipe is for {recipe.ntr} tracers, the engine has {eng.ntracers}")
+    if recipe.ng1 != ng1:
+        raise ValueError(f"the recipe has {recipe.ng1} rows, this call needs {ng1}")
+    if recipe.has_nnlo and not eng.cfg.with_NNLO:
+        raise ValueError("a recipe with NNLO columns needs an engine built with with_NNLO")
+    terms = recipe.terms()
+    L.check(eng.lib.eftb_set_draw_recipe(eng._h, kind, len(recipe.param_names), ng1, terms.size, terms.ctypes.data))
+    return recipe
+
+
+def _params_args(recipe, theta, offsets, f, ntr):
+    """theta [N, P], offsets [C + 1], f [C, ntr] of a params call as the library takes them; shape errors are raised here"""
+    from .marginal import _offsets
+
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    off = _offsets(offsets)
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    nC = off.size - 1
+    if recipe is not None and (theta.ndim != 2 or theta.shape[1] != len(recipe.param_names)):
+        raise ValueError(f"theta must be [N, {len(recipe.param_names)}] ({', '.join(recipe.param_names)})")
+    if theta.ndim != 2:
+        raise ValueError("theta must be [N, P]")
+    if f.shape not in ((nC, ntr),) + (((nC,),) if ntr == 1 else ()):
+        raise ValueError(f"f must be [{nC}, {ntr}]: one growth rate per walker and tracer")
+    return theta, off, f

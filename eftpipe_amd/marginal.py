@@ -74,6 +74,35 @@ def joint_gaussian_rows_many(bases, fs, params, names, scales):
     return out
 
 
+def joint_draw_recipe(bases, names, scales, param_names=None, with_NNLO=False):
+    """The recipe (``parambasis.DrawRecipe``) of ``joint_gaussian_rows_many(bases, fs, params, names, scales)``: theta holds the
+    non-Gaussian parameters of all tracers, each name once (a cross basis reuses its parents' entries), in the order of ``param_names``
+    (default: first appearance over the bases); f is [walkers, ntr].  Parameters a yaml derives from others stay the caller's business.
+    with_NNLO: a marginalised NNLO parameter in ``names`` (``basis.cnnloA()``) gets its row in the NNLO columns, the derivative of
+    ``nnlo_vector`` (reference parambasis.py:303-307, :429-435)."""
+    from .parambasis import _POLY_F, _compile_recipe, _poly_theta, _recipe_names, nnlo_vector
+
+    if len(scales) != len(bases):
+        raise ValueError("one scale dict per tracer")
+    names = [str(n) for n in names]
+    pn = _recipe_names(param_names, [n for b in bases for n in b.non_gaussian_params()])
+    rows = []
+    for basis, sc in zip(bases, scales):
+        v = {n: _poly_theta(pn.index(n)) for n in basis.non_gaussian_params()}
+        r = basis.gaussian_rows(_POLY_F, v, **sc)
+        west = basis.get_name() == "westcoast"
+        own = gaussian_params(basis.prefix, tuple(basis.cross_prefix)) if west else basis.gaussian_params()[:7]
+        nn = basis.cnnloA() if with_NNLO and not basis.is_cross() else []
+        out = [list(r[0]) + [0.0] * 3]
+        for n in names:
+            main = list(r[1 + own.index(n)]) if n in own else [0.0] * 24
+            unit = [1.0 if m == n else 0.0 for m in nn] + [0.0] * (2 - len(nn))
+            tail = list(nnlo_vector(_POLY_F, v[basis.prefix + "b1"], unit, sc.get("krA", 0.25), basis.counterform())) if n in nn else [0.0] * 3
+            out.append(main + tail)
+        rows.append(out)
+    return _compile_recipe(pn, rows, len(names) + 1)
+
+
 class MarginalLikelihood:
     """Gaussian likelihood of one data vector with the linear bias parameters marginalised analytically.
 
@@ -157,6 +186,29 @@ class MarginalLikelihood:
             raise RuntimeError("det of F2ij <= 0")
         return (logp, full, best) if return_best else logp
 
+    def set_draw_recipe(self, recipe):
+        """The draw recipe of ``logp_draws_params`` (``eftb_set_draw_recipe`` kind 0; ``joint_draw_recipe``): nG + 1 rows per tracer.  It
+        belongs to this likelihood: constructing another ``MarginalLikelihood`` on the engine, or ``Engine.set_tracers``, drops it."""
+        from .engine import _set_recipe
+
+        self._recipe = _set_recipe(self.eng, L.RECIPE_LOGP, recipe, self.nG + 1)
+
+    def logp_draws_params(self, theta, offsets, f, return_best=False):
+        """``logp_draws`` with the rows built on the device from parameter values (``eftb_draws_logp_params``): theta [N, P] in the order of
+        the recipe's ``param_names``, f [C, ntr] ([C] with one tracer) the growth rate of each walker's entries -> ln P_marg [N] (+ full
+        chi2 [N] and best-fit Gaussian parameters [N, nG]).  8 P bytes per draw cross PCIe instead of the rows.  Raises like the
+        reference when det F2 <= 0."""
+        from .engine import _params_args
+
+        theta, off, f = _params_args(getattr(self, "_recipe", None), theta, offsets, f, self.eng.ntracers)
+        N = theta.shape[0]
+        logp, full, best = np.empty(N), np.empty(N), np.empty((N, self.nG))
+        L.check(self.eng.lib.eftb_draws_logp_params(self.eng._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f),
+                                                    L.dptr(logp), L.dptr(full), L.dptr(best)))
+        if np.any(np.isnan(logp)):
+            raise RuntimeError("det of F2ij <= 0")
+        return (logp, full, best) if return_best else logp
+
     def eval_logp(self, Pin, f, DA, H, rows, return_best=False):
         """Theory + likelihood in one call (``eftb_eval_logp_batch``): Pin [B, Nkin], f/DA/H [B], rows [B, nG + 1, 24] ->
         ln P_marg [B]; only the inputs and B floats cross PCIe.  The engine's pipeline operator must bring the templates to
@@ -183,4 +235,4 @@ def _offsets(offsets):
     return off
 
 
-__all__ = ["MarginalLikelihood", "data_index", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_gaussian_rows", "joint_gaussian_rows_many"]
+__all__ = ["MarginalLikelihood", "data_index", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]

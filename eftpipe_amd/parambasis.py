@@ -104,6 +104,14 @@ def gaussian_params(prefix="", cross_prefix=()):
     return [prefix + p for p in GAUSSIAN + STOCHASTIC]
 
 
+def _sparse_row(pairs):
+    """24 coefficients, zero but for the (index, value) pairs; the values are floats, or the polynomials of the recipe compiler"""
+    r = np.zeros(24, dtype=object if any(isinstance(c, _Poly) for _, c in pairs) else np.float64)
+    for i, c in pairs:
+        r[i] = c
+    return r
+
+
 def gaussian_rows(f, ngA, ngB=None, kmA=0.7, krA=0.25, ndA=3e-4, kmB=None, krB=None, ndB=None, basis="westcoast"):
     """Coefficient rows over the 24 template rows (P11l[3], Pctl[6], Ploopl[12], Pstl[3]) of
 
@@ -128,13 +136,7 @@ def gaussian_rows(f, ngA, ngB=None, kmA=0.7, krA=0.25, ndA=3e-4, kmB=None, krB=N
     bsA = [b1A, b2A, 0.0, b4A, 0.0, 0.0, 0.0]
     bsB = [b1B, b2B, 0.0, b4B, 0.0, 0.0, 0.0] if cross else None
     rows = [bias_row(f, bsA, bsB, (0.0, 0.0, 0.0), kmA=kmA, krA=krA, ndA=ndA, kmB=kmB, krB=krB, ndB=ndB)]
-
-    def row(pairs):
-        r = np.zeros(24)
-        for i, c in pairs:
-            r[i] = c
-        return r
-
+    row = _sparse_row
     if cross:
         for b1o, km, kr in ((b1B, kmA, krA), (b1A, kmB, krB)):
             rows.append(row([(LOOP + 3, 0.5), (LOOP + 7, 0.5 * b1o)]))
@@ -304,13 +306,7 @@ def eastcoast_bias_row(f, b1, b2, bG2, bGamma3=0.0, c0=0.0, c2=0.0, c4=0.0, Psho
 def _eastcoast_rows(f, ng, kmA, krA, ndA):
     b1, b2, bG2 = ng
     rows = [eastcoast_bias_row(f, b1, b2, bG2, kmA=kmA, krA=krA, ndA=ndA)]
-
-    def row(pairs):
-        r = np.zeros(24)
-        for i, c in pairs:
-            r[i] = c
-        return r
-
+    row = _sparse_row
     rows.append(row([(LOOP + 3, 6.0), (LOOP + 7, 6.0 * b1)]))                                      # bGamma3
     rows.append(row([(CT + 0, -2.0)]))                                                             # c0
     rows.append(row([(CT + 0, 2 / 3 * f), (CT + 1, -2.0 * f)]))                                    # c2
@@ -500,3 +496,228 @@ def find_param_basis(name):
 
     module_name, class_name = name.rsplit(".", 1)
     return getattr(importlib.import_module(module_name), class_name)
+
+
+# ----------------------------------------------------------------------------- draw recipes (rows built on the device from parameter values)
+# A recipe is the compiled form of "how the coefficient rows follow from the parameters": every entry is a sum of monomials
+#     coef * f^e * theta[i] * theta[j] * theta[k]        (index -1: the factor 1)
+# of the per-draw parameter vector theta and the growth rate f of the (walker, tracer) entry.  The monomials are not typed a second time:
+# the scalar builders above (bias_vectors, gaussian_rows, _eastcoast_rows, nnlo_vector) only use + - * / and integer powers, so calling them
+# with _Poly values in place of floats yields the polynomials they compute (eftb_set_draw_recipe, Engine.reduce_draws_params,
+# MarginalLikelihood.logp_draws_params).
+RECIPE_MAXP, RECIPE_MAXTERMS, RECIPE_MAXDEG, RECIPE_MAXFPOW = 32, 1024, 3, 6
+
+
+class _Poly:
+    """polynomial in f and theta with float coefficients: {(e, (i, j, ...) ascending): coef}"""
+
+    __slots__ = ("m",)
+
+    def __init__(self, m=None):
+        self.m = {k: v for k, v in (m or {}).items() if v != 0.0}
+
+    @staticmethod
+    def _of(x):
+        if isinstance(x, _Poly):
+            return x
+        if isinstance(x, (int, float, np.integer, np.floating)):
+            return _Poly({(0, ()): float(x)})
+        return None
+
+    def __add__(self, o):
+        o = _Poly._of(o)
+        if o is None:
+            return NotImplemented
+        m = dict(self.m)
+        for k, v in o.m.items():
+            m[k] = m.get(k, 0.0) + v
+        return _Poly(m)
+
+    __radd__ = __add__
+
+    def __neg__(self):
+        return _Poly({k: -v for k, v in self.m.items()})
+
+    def __sub__(self, o):
+        o = _Poly._of(o)
+        return NotImplemented if o is None else self + (-o)
+
+    def __rsub__(self, o):
+        o = _Poly._of(o)
+        return NotImplemented if o is None else o + (-self)
+
+    def __mul__(self, o):
+        o = _Poly._of(o)
+        if o is None:
+            return NotImplemented
+        m = {}
+        for (e1, i1), v1 in self.m.items():
+            for (e2, i2), v2 in o.m.items():
+                k = (e1 + e2, tuple(sorted(i1 + i2)))
+                m[k] = m.get(k, 0.0) + v1 * v2
+        return _Poly(m)
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        if isinstance(o, _Poly):
+            if set(o.m) - {(0, ())} or not o.m:
+                raise ValueError("a draw recipe cannot divide by a parameter")
+            o = o.m[(0, ())]
+        if not isinstance(o, (int, float, np.integer, np.floating)):
+            return NotImplemented
+        return _Poly({k: v / float(o) for k, v in self.m.items()})
+
+    def __rtruediv__(self, o):
+        return _Poly._of(o) / self
+
+    def __pow__(self, p):
+        if not isinstance(p, (int, np.integer)) or p < 0:
+            raise ValueError("a draw recipe only takes non-negative integer powers of a parameter")
+        out = _Poly({(0, ()): 1.0})
+        for _ in range(int(p)):
+            out = out * self
+        return out
+
+
+_POLY_F = _Poly({(1, ()): 1.0})
+
+
+def _poly_theta(i):
+    return _Poly({(0, (i,)): 1.0})
+
+
+class DrawRecipe:
+    """Terms (tracer, row g, column r, coef, e, i, j, k) of the coefficient rows [ntr, ng1, 24 (+ 3 NNLO columns 24..26)]: entry
+    (tracer, g, r) is the sum of coef * f[tracer]^e * theta[i] * theta[j] * theta[k] over its terms (an index of -1: the factor 1).
+    The terms are kept sorted by (g, tracer, r, e, i, j, k) -- the order the device sums them in.  ``rows`` / ``rows_nnlo`` evaluate the
+    recipe with NumPy: the host statement of what the device computes from theta."""
+
+    def __init__(self, param_names, ntr, ng1, tracer, row, col, coef, fpow, idx):
+        self.param_names = [str(n) for n in param_names]
+        self.ntr, self.ng1 = int(ntr), int(ng1)
+        tracer, row, col, fpow = (np.asarray(a, dtype=np.int32).reshape(-1) for a in (tracer, row, col, fpow))
+        coef = np.asarray(coef, dtype=np.float64).reshape(-1)
+        idx = np.sort(np.asarray(idx, dtype=np.int32).reshape(-1, RECIPE_MAXDEG), axis=1)[:, ::-1]  # (the -1 entries last)
+        P, n = len(self.param_names), coef.size
+        if P > RECIPE_MAXP:
+            raise ValueError(f"a draw recipe takes at most {RECIPE_MAXP} parameters, got {P}")
+        if n > RECIPE_MAXTERMS:
+            raise ValueError(f"a draw recipe holds at most {RECIPE_MAXTERMS} terms, got {n}")
+        if not (tracer.size == row.size == col.size == fpow.size == idx.shape[0] == n):
+            raise ValueError("the term arrays of a draw recipe disagree on the number of terms")
+        if n and (tracer.min() < 0 or tracer.max() >= self.ntr or row.min() < 0 or row.max() >= self.ng1 or col.min() < 0 or col.max() >= 27):
+            raise ValueError("a term of the draw recipe addresses an entry outside [ntr, ng1, 27]")
+        if n and (fpow.min() < 0 or fpow.max() > RECIPE_MAXFPOW):
+            raise ValueError(f"a draw recipe takes powers of f up to {RECIPE_MAXFPOW}")
+        if n and (idx.min() < -1 or idx.max() >= P):
+            raise ValueError("a term of the draw recipe names a parameter outside theta")
+        if not np.all(np.isfinite(coef)):
+            raise ValueError("a draw recipe needs finite coefficients")
+        order = np.lexsort((idx[:, 2], idx[:, 1], idx[:, 0], fpow, col, tracer, row))
+        self.tracer, self.row, self.col, self.coef, self.fpow, self.idx = tracer[order], row[order], col[order], coef[order], fpow[order], idx[order]
+
+    @property
+    def nterms(self):
+        return self.coef.size
+
+    @property
+    def has_nnlo(self):
+        return bool(np.any(self.col >= 24))
+
+    def _eval(self, theta, f, lo, hi, magnitude=False):
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[1] != len(self.param_names):
+            raise ValueError(f"theta must be [N, {len(self.param_names)}]")
+        N = theta.shape[0]
+        f = np.asarray(f, dtype=np.float64)
+        f = np.broadcast_to(f[:, None] if f.ndim == 1 and self.ntr == 1 else f, (N, self.ntr))
+        fp = [np.ones((N, self.ntr))]
+        for _ in range(RECIPE_MAXFPOW):
+            fp.append(fp[-1] * f)
+        th = np.concatenate([theta, np.ones((N, 1))], axis=1)  # (index -1: the factor 1)
+        out = np.zeros((N, self.ntr, self.ng1, hi - lo))
+        for t, g, r, c, e, ix in zip(self.tracer, self.row, self.col, self.coef, self.fpow, self.idx):
+            if lo <= r < hi:
+                v = c * fp[e][:, t] * th[:, ix[0]] * th[:, ix[1]] * th[:, ix[2]]
+                out[:, t, g, r - lo] += np.abs(v) if magnitude else v
+        return out
+
+    def rows(self, theta, f):
+        """theta [N, P], f [N, ntr] (the growth rate of each draw's walker per tracer; [N] with one tracer) -> rows [N, ntr, ng1, 24]"""
+        return self._eval(theta, f, 0, 24)
+
+    def rows_magnitude(self, theta, f):
+        """-> the sum of the magnitudes of each entry's monomials [N, ntr, ng1, 24]: the scale of the rounding error of ``rows``.  An
+        entry far below it is a cancelling sum (the east-coast mapping enters squared: (b1 + 7/2 bG2)^2 is three monomials), whose
+        relative error, on the device as in the scalar builders, grows by that ratio."""
+        return self._eval(theta, f, 0, 24, magnitude=True)
+
+    def rows_nnlo(self, theta, f):
+        """-> the NNLO columns [N, ntr, ng1, 3]"""
+        return self._eval(theta, f, 24, 27)
+
+    def terms(self):
+        """the records of eftb_set_draw_recipe"""
+        from . import _lib as L
+
+        out = np.zeros(self.nterms, dtype=L.DRAW_TERM)
+        out["tracer"], out["row"], out["col"], out["fpow"], out["coef"] = self.tracer, self.row, self.col, self.fpow, self.coef
+        out["i"], out["j"], out["k"] = self.idx.T
+        return out
+
+
+def _compile_recipe(param_names, poly_rows, ng1):
+    """poly_rows[tracer][g]: 24 (or 27) entries, floats or _Poly -> DrawRecipe"""
+    tr, row, col, coef, fpow, idx = [], [], [], [], [], []
+    for t, rows_t in enumerate(poly_rows):
+        for g, rw in enumerate(rows_t):
+            for r, v in enumerate(rw):
+                p = _Poly._of(v)
+                if p is None:
+                    raise ValueError(f"entry ({t}, {g}, {r}) of the rows is neither a number nor a polynomial: {type(v).__name__}")
+                for (e, ix), c in sorted(p.m.items()):
+                    if len(ix) > RECIPE_MAXDEG:
+                        raise ValueError(f"entry ({t}, {g}, {r}) is of degree {len(ix)} in the parameters, a draw recipe takes up to {RECIPE_MAXDEG}")
+                    if e > RECIPE_MAXFPOW:
+                        raise ValueError(f"entry ({t}, {g}, {r}) holds f^{e}, a draw recipe takes powers of f up to {RECIPE_MAXFPOW}")
+                    tr.append(t); row.append(g); col.append(r); coef.append(c); fpow.append(e)
+                    idx.append(list(ix) + [-1] * (RECIPE_MAXDEG - len(ix)))
+    return DrawRecipe(param_names, len(poly_rows), ng1, tr, row, col, coef, fpow, idx)
+
+
+def _recipe_names(param_names, needed):
+    """theta's order: the caller's, or every needed name once in order of first appearance"""
+    if param_names is None:
+        param_names = list(dict.fromkeys(needed))
+    param_names = [str(n) for n in param_names]
+    if len(set(param_names)) != len(param_names):
+        raise ValueError("param_names repeats a name")
+    missing = [n for n in needed if n not in param_names]
+    if missing:
+        raise ValueError(f"param_names lacks {sorted(set(missing))}")
+    if len(param_names) > RECIPE_MAXP:
+        raise ValueError(f"a draw recipe takes at most {RECIPE_MAXP} parameters, got {len(param_names)}")
+    return param_names
+
+
+def bias_draw_recipe(bases, scales, with_NNLO=False, param_names=None):
+    """The recipe of ``basis.bias_row`` (``bias_rows_many``) per tracer, and of ``basis.nnlo_row`` (``nnlo_vector``) in the NNLO columns
+    with ``with_NNLO``: theta holds the full parameter set bsA() + bsB() + es() (+ cnnloA()) of every basis, each name once; one row.
+    bases / scales: one basis and one dict(kmA=, krA=, ndA=[, kmB=, ...]) per tracer (a single basis / dict: one tracer)."""
+    if not isinstance(bases, (list, tuple)):
+        bases, scales = [bases], [scales]
+    if len(scales) != len(bases):
+        raise ValueError("one scale dict per tracer")
+    own = [b.bsA() + (b.bsB() if b.is_cross() else []) + b.es() + (b.cnnloA() if with_NNLO else []) for b in bases]
+    names = _recipe_names(param_names, [n for o in own for n in o])
+    rows = []
+    for basis, sc, o in zip(bases, scales, own):
+        v = {n: _poly_theta(names.index(n)) for n in o}
+        r = list(basis.bias_row(_POLY_F, v, **sc))
+        if with_NNLO:
+            if basis.is_cross():
+                raise NotImplementedError("the NNLO counter-terms of a cross spectrum are not supported (as the reference)")
+            r += list(basis.nnlo_row(_POLY_F, v, sc.get("krA", 0.25)))
+        rows.append([r])
+    return _compile_recipe(names, rows, 1)

@@ -294,6 +294,33 @@ int  eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets,
                      double* fullchi2, double* best);
 int  eftb_draws_reduce(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* bias, const double* bias_nnlo, double* plk);
 
+/* The same draw calls fed with EFT parameter values: the coefficient rows are built on the device from a draw recipe, so a draw costs
+ * 8 P bytes of host-to-device traffic instead of its dense rows.  A recipe states every non-zero entry of the rows as a sum of monomials
+ *     coef * f^fpow * theta[i] * theta[j] * theta[k]          (an index of -1: the factor 1)
+ * of the draw's parameter vector theta[P] and the growth rate f of its walker's tracer entry (eftpipe_amd.parambasis.DrawRecipe compiles
+ * them from the scalar row builders).  A term names its entry by (tracer, row, col): row 0 ... ng1 - 1; col 0 ... 23 the template rows,
+ * 24 ... 26 the NNLO columns (with_nnlo engines only).  Limits: P <= 32, 1 <= ng1 <= 25, nterms <= 1024, fpow <= 6.
+ *
+ * eftb_set_draw_recipe validates every term, sorts the terms by (row, tracer, col, fpow, i, j, k) -- the order their sum is taken in, whatever
+ * order they arrive in -- and uploads them.  kind 0: the recipe of eftb_draws_logp_params (ng1 must be nG + 1 of the likelihood at the time
+ * of the call; eftb_set_likelihood and eftb_set_tracers drop it); kind 1: the recipe of eftb_draws_reduce_params (ng1 = 1; eftb_set_tracers
+ * drops it).  nterms = 0 withdraws the recipe.
+ *
+ * eftb_draws_logp_params / eftb_draws_reduce_params: eftb_draws_logp / eftb_draws_reduce with theta [N][P] and f [C][ntr] in place of the rows;
+ * walkers, offsets, the Gram cache, the refusals and the outputs are those of the rows calls.  No per-draw row array exists on the logp
+ * path; the reduce path evaluates the recipe into the [N][ntr][24] coefficient buffer on the device and contracts it as eftb_draws_reduce
+ * does.  Non-finite theta or f is refused before anything is copied. */
+typedef struct eftb_draw_term {
+    double  coef;
+    int32_t tracer, row, col, fpow;
+    int32_t i, j, k;  /* indices into theta, -1 for the factor 1 */
+    int32_t reserved;
+} eftb_draw_term;
+int  eftb_set_draw_recipe(eftb_engine* e, int kind, int P, int ng1, int nterms, const eftb_draw_term* terms);
+int  eftb_draws_logp_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
+                            double* fullchi2, double* best);
+int  eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* plk);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

@@ -8,6 +8,8 @@ one set of walkers, for two shapes -- the single-tracer marg.npz likelihood and 
     gram    first call after put("TEMPL") minus a cached call: gather + A C^-1 + A U^T of every walker
     draws   a cached call minus h2d: draw kernel + the [N][26] records back + unpacking
 
+the same draws through MarginalLikelihood.logp_draws_params (eftb_draws_logp_params: theta [N, P] in, the rows built on the device from the
+draw recipe) -- per call, and end to end with theta stacked from the sampler's per-parameter arrays -- with the bytes per draw over PCIe;
 and, for comparison, the same number of evaluations through eval_logp (theory + likelihood per walker; Nk = 512, resummation + AP, an
 interpolation onto the data k instead of the window: a lower bound on the cost of the real thing).  GPU box.
 
@@ -28,20 +30,24 @@ import cfg3_util as U  # noqa: E402
 from eftpipe_amd import synth  # noqa: E402
 from eftpipe_amd import tables as TB  # noqa: E402
 from eftpipe_amd.engine import Engine  # noqa: E402
-from eftpipe_amd.marginal import MarginalLikelihood, data_index, joint_gaussian_rows_many  # noqa: E402
-from eftpipe_amd.parambasis import gaussian_rows, gaussian_rows_many  # noqa: E402
+from eftpipe_amd.marginal import MarginalLikelihood, data_index, joint_draw_recipe, joint_gaussian_rows_many  # noqa: E402
+from eftpipe_amd.parambasis import WestCoastBasis, gaussian_params, gaussian_rows, gaussian_rows_many  # noqa: E402
 from eftpipe_amd.tables import EngineConfig  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
-def med(fn, n=5):
+def times(fn, n=5):
     ts = []
     for _ in range(n):
         t0 = time.perf_counter()
         fn()
         ts.append(time.perf_counter() - t0)
-    return float(np.median(ts))
+    return ts
+
+
+def med(fn, n=5):
+    return float(np.median(times(fn, n)))
 
 
 def h2d_seconds(a):
@@ -73,7 +79,9 @@ def marg_setup(C, N, rng):
     ng = dict(zip(g["auto_ng_names"], g["auto_ng_values"]))
     ngv = np.array([ng["b1"], ng["b2"], ng["b4"]]) + rng.normal(0, 1, (N, 3)) * [0.05, 0.3, 0.3]
     build = lambda: gaussian_rows_many(f, ngv, None, *co[:3])
-    return eng, like, templ, build, index.size, len(g["auto_loc"])
+    rec = joint_draw_recipe([WestCoastBasis(prefix="")], gaussian_params(""), [dict(kmA=float(co[0]), krA=float(co[1]), ndA=float(co[2]))])
+    cols = [np.ascontiguousarray(ngv[:, i]) for i in range(3)]  # (a sampler holds one array per parameter)
+    return eng, like, templ, build, index.size, len(g["auto_loc"]), (rec, lambda: np.stack(cols, axis=1), np.full(C, f))
 
 
 def cfg3_setup(C, N, rng):
@@ -100,7 +108,8 @@ def cfg3_setup(C, N, rng):
         draws[t + "b4"] = (draws[t + "c2"] - draws[t + "c4"]) / np.sqrt(2.0)
     f = [float(g[t + "_f"]) for t in U.TRACERS]
     build = lambda: joint_gaussian_rows_many(U.bases(), f, draws, names, U.scales(g))
-    return eng, like, templ, build, index.size, len(names)
+    rec = joint_draw_recipe(U.bases(), names, U.scales(g))
+    return eng, like, templ, build, index.size, len(names), (rec, lambda: np.stack([draws[n] for n in rec.param_names], axis=1), np.tile(f, (C, 1)))
 
 
 def eval_logp_rate(ntr, ndata_per_tracer, nG, walkers=42):
@@ -132,7 +141,7 @@ def eval_logp_rate(ntr, ndata_per_tracer, nG, walkers=42):
 
 def probe(name, setup, C, N, ntr):
     rng = np.random.default_rng(1)
-    eng, like, templ, build, ndata, nG = setup(C, N, rng)
+    eng, like, templ, build, ndata, nG, (rec, theta_build, fC) = setup(C, N, rng)
     rows = build()
     t_rows = med(build, 3)
     counts = np.full(C, N // C)
@@ -145,13 +154,27 @@ def probe(name, setup, C, N, ntr):
     t0 = time.perf_counter()
     like.logp_draws(rows, off)
     t_first = time.perf_counter() - t0
-    t_cached = med(lambda: like.logp_draws(rows, off), 5)
+    ts_cached = times(lambda: like.logp_draws(rows, off), 9)
+    t_cached = float(np.median(ts_cached))
+    # the params path: the same draws as theta [N, P]
+    like.set_draw_recipe(rec)
+    theta = theta_build()
+    t_theta = med(theta_build, 5)
+    lp = like.logp_draws_params(theta, off, fC)
+    agree = float(np.max(np.abs(lp / like.logp_draws(rows, off) - 1.0)))
+    ts_params = times(lambda: like.logp_draws_params(theta, off, fC), 9)
+    t_params = float(np.median(ts_params))
     rate_eval = eval_logp_rate(ntr, ndata // ntr, nG)
     out = {
         "shape": name, "walkers": C, "draws": N, "tracers": ntr, "ndata": ndata, "nG": nG, "row_bytes_per_draw": rows[0].nbytes,
         "host_rows_us_per_draw": 1e6 * t_rows / N, "h2d_us_per_draw": 1e6 * t_h2d / N, "gram_ms": 1e3 * (t_first - t_cached),
         "draws_us_per_draw": 1e6 * (t_cached - t_h2d) / N, "call_us_per_draw": 1e6 * t_cached / N,
         "draws_per_s_device_call": N / t_cached, "draws_per_s_end_to_end": N / (t_cached + t_rows),
+        "call_us_per_draw_spread": [1e6 * min(ts_cached) / N, 1e6 * max(ts_cached) / N],
+        "params_bytes_per_draw": theta[0].nbytes, "params_terms": rec.nterms, "params_theta_us_per_draw": 1e6 * t_theta / N,
+        "params_call_us_per_draw": 1e6 * t_params / N, "params_call_us_per_draw_spread": [1e6 * min(ts_params) / N, 1e6 * max(ts_params) / N],
+        "params_draws_per_s_device_call": N / t_params, "params_draws_per_s_end_to_end": N / (t_params + t_theta),
+        "params_vs_rows_max_rel_diff": agree,
         "eval_logp_per_s": rate_eval,
     }
     out["speedup_end_to_end"] = out["draws_per_s_end_to_end"] / rate_eval
