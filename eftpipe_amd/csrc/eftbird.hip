@@ -156,10 +156,17 @@ struct eftb_engine {
         int P = 0, ng1 = 0, nterms = 0, nnz = 0, ntr_used = 0;
         double* coef = nullptr;
         int* tab = nullptr;
+        // the derivative of the terms (kind 0; eftb_draws_logp_grad_params): dcoef [ndt], dtab = pstart | dent | dpack | erow (RecipeGradTab)
+        int ndt = 0;
+        double* dcoef = nullptr;
+        int* dtab = nullptr;
     } recipe[2];
     double* drw_theta = nullptr;    // theta [N][P] then f [C][ntr] of a params call
     size_t drw_theta_cap = 0;
     bool drwp_lds = false;          // draws_logp_params_kernel opted in to the large dynamic LDS
+    double* drw_grad = nullptr;     // eftb_draws_logp_grad_params: d ln P / d theta [N][P]
+    size_t drw_grad_cap = 0;
+    bool drwg_lds = false;          // draws_logp_grad_params_kernel opted in to the large dynamic LDS
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -2006,7 +2013,8 @@ void eftb_destroy(eftb_engine* e) {
     for (auto& o : e->ops) if (o.dev) (void)hipFree(o.dev);
     for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
     for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off, (void*)e->drw_theta,
-                    (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab}) if (p) (void)hipFree(p);
+                    (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab, (void*)e->recipe[0].dcoef,
+                    (void*)e->recipe[0].dtab, (void*)e->drw_grad}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evSnap, e->evGathered, e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
@@ -3384,18 +3392,57 @@ int eftb_set_draw_recipe(eftb_engine* e, int kind, int P, int ng1, int nterms, c
     tstart.push_back(nterms);
     for (int g = 0; g < ng1; ++g) rowstart[g + 1] += rowstart[g];
     const int nnz = (int)ent.size();
+    // the derivative of the sorted terms (kind 0): one record per (term, distinct theta index p in it) with the coefficient times the
+    // multiplicity of p and the two remaining indices; p outermost, the terms in their order: sorted by (p, entry, parent term)
+    std::vector<int> pstart, dent, dpack, erow;
+    std::vector<double> dcoef;
+    if (kind == 0) {
+        for (int n = 0, g = 0; n < nnz; ++n) {
+            while (n >= rowstart[g + 1]) ++g;
+            erow.push_back(g);
+        }
+        for (int p = 0; p < P; ++p) {
+            pstart.push_back((int)dent.size());
+            for (int t = 0, n = -1; t < nterms; ++t) {
+                if (n + 1 < nnz && tstart[n + 1] == t) ++n;
+                const Key& k = keys[t];
+                int mult = 0, rest[3] = {-1, -1, -1}, nr = 0;
+                for (int q = 0; q < 3; ++q) {
+                    if (k.ix[q] == p && mult++ == 0) continue;  // (the first occurrence is the factor differentiated)
+                    rest[nr++] = k.ix[q];
+                }
+                if (!mult) continue;
+                auto ix = [P](int v) { return v < 0 ? P : v; };
+                dent.push_back(n);
+                dpack.push_back(ix(rest[0]) | ix(rest[1]) << 6 | P << 12 | (k.tracer * RECIPE_FPOW + k.fpow) << 18);
+                dcoef.push_back(k.coef * mult);
+            }
+        }
+        pstart.push_back((int)dent.size());
+    }
+    std::vector<int> dtab;
+    for (const std::vector<int>* v : {&pstart, &dent, &dpack, &erow}) dtab.insert(dtab.end(), v->begin(), v->end());
     std::vector<int> tab;
     for (const std::vector<int>* v : {&rowstart, &ent, &tstart, &pack, &slot}) tab.insert(tab.end(), v->begin(), v->end());
     HIPCHK(hipSetDevice(e->c.device));
     HIPCHK(sync_all(e));  // (a params call is synchronous: nothing reads the old tables any more; as eftb_set_likelihood)
     rc.set = false;
-    for (void* p : {(void*)rc.coef, (void*)rc.tab}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)rc.coef, (void*)rc.tab, (void*)rc.dcoef, (void*)rc.dtab}) if (p) (void)hipFree(p);
     rc.coef = nullptr;
     rc.tab = nullptr;
+    rc.dcoef = nullptr;
+    rc.dtab = nullptr;
     HIPCHK(hipMalloc(&rc.coef, coef.size() * sizeof(double)));
     HIPCHK(hipMalloc(&rc.tab, tab.size() * sizeof(int)));
     HIPCHK(hipMemcpy(rc.coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(rc.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (kind == 0) {  // (a table without records still holds pstart and erow)
+        HIPCHK(hipMalloc(&rc.dcoef, std::max<size_t>(1, dcoef.size()) * sizeof(double)));
+        HIPCHK(hipMalloc(&rc.dtab, dtab.size() * sizeof(int)));
+        if (!dcoef.empty()) HIPCHK(hipMemcpy(rc.dcoef, dcoef.data(), dcoef.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(rc.dtab, dtab.data(), dtab.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    rc.ndt = (int)dcoef.size();
     rc.P = P; rc.ng1 = ng1; rc.nterms = nterms; rc.nnz = nnz; rc.nnlo = nnlo; rc.ntr_used = ntr;
     rc.set = true;
     return 0;
@@ -3525,4 +3572,68 @@ int eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* 
     HIPCHK(hipMemcpyAsync(plk, e->drw_out, pn * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ d ln P / d theta of params draws
+// (behind every other entry point, as the params calls above: the code of the existing kernels stays as it was)
+int eftb_draws_logp_grad_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
+                                double* grad, double* fullchi2, double* best) {
+    static const char* who = "eftb_draws_logp_grad_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
+    if (!grad) return fail("%s: grad == NULL (eftb_draws_logp_params is the call without the gradient)", who);
+    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
+    long long maxcnt = 0;
+    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
+        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
+                    e->cur_nx);
+    const eftb_config& c = e->c;
+    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1;
+    if (int rc = draws_params_check(e, who, 0, ng1, C, N, theta, f)) return rc;
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1, P = rcp.P;
+    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
+    const int nnzp = (rcp.nnz + 1) & ~1;
+    const size_t lds_w = ((size_t)J1 * J1 + RECIPE_MAXTR * RECIPE_FPOW + nnzp) * sizeof(double);  // W_c, fp, col and erow
+    const size_t lds_wave = (34 + (size_t)nnzp + (size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
+    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
+    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
+    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
+    if (N == 0) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    hipStream_t st = e->stream;
+    join_back(e);
+    if (!e->drwg_lds) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->drwg_lds = true;
+    }
+    if (int rc = draws_gram(e, who, C, J1)) return rc;
+    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
+    if (int rc = grow_dev(&e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
+    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    const double *dtheta = nullptr, *df = nullptr;
+    if (int rc = draws_params_upload(e, P, C, N, theta, f, &dtheta, &df)) return rc;
+    const dim3 grid(C, draw_shares(maxcnt, nw, C)), block(64 * nw);
+    const size_t lds = lds_w + nw * lds_wave;
+    const RecipeTab rt = recipe_tab(rcp);
+    RecipeGradTab gt{};
+    gt.dcoef = rcp.dcoef;
+    gt.pstart = rcp.dtab;
+    gt.dent = gt.pstart + P + 1;
+    gt.dpack = gt.dent + rcp.ndt;
+    gt.erow = gt.dpack + rcp.ndt;
+    while ((1 << gt.lgP2) < P) ++gt.lgP2;
+    if (J1 > 64)
+        hipLaunchKernelGGL(draws_logp_grad_params_kernel<true>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
+                           e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
+    else
+        hipLaunchKernelGGL(draws_logp_grad_params_kernel<false>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
+                           e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    if (P) HIPCHK(hipMemcpyAsync(grad, e->drw_grad, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    return draws_records(e, N, logp, fullchi2, best);
 }

@@ -193,20 +193,29 @@ class MarginalLikelihood:
 
         self._recipe = _set_recipe(self.eng, L.RECIPE_LOGP, recipe, self.nG + 1)
 
-    def logp_draws_params(self, theta, offsets, f, return_best=False):
+    def logp_draws_params(self, theta, offsets, f, return_best=False, grad=False):
         """``logp_draws`` with the rows built on the device from parameter values (``eftb_draws_logp_params``): theta [N, P] in the order of
         the recipe's ``param_names``, f [C, ntr] ([C] with one tracer) the growth rate of each walker's entries -> ln P_marg [N] (+ full
         chi2 [N] and best-fit Gaussian parameters [N, nG]).  8 P bytes per draw cross PCIe instead of the rows.  Raises like the
-        reference when det F2 <= 0."""
+        reference when det F2 <= 0.
+        grad=True (``eftb_draws_logp_grad_params``): d ln P_marg / d theta [N, P] in ``param_names`` order from an adjoint pass on the device
+        -> (logp, grad) or (logp, grad, full, best); ln P, full chi2 and the best fit are the bits of the call without it."""
         from .engine import _params_args
 
         theta, off, f = _params_args(getattr(self, "_recipe", None), theta, offsets, f, self.eng.ntracers)
         N = theta.shape[0]
         logp, full, best = np.empty(N), np.empty(N), np.empty((N, self.nG))
-        L.check(self.eng.lib.eftb_draws_logp_params(self.eng._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f),
-                                                    L.dptr(logp), L.dptr(full), L.dptr(best)))
+        if grad:
+            dlogp = np.empty((N, theta.shape[1]))
+            L.check(self.eng.lib.eftb_draws_logp_grad_params(self.eng._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f),
+                                                             L.dptr(logp), L.dptr(dlogp), L.dptr(full), L.dptr(best)))
+        else:
+            L.check(self.eng.lib.eftb_draws_logp_params(self.eng._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f),
+                                                        L.dptr(logp), L.dptr(full), L.dptr(best)))
         if np.any(np.isnan(logp)):
             raise RuntimeError("det of F2ij <= 0")
+        if grad:
+            return (logp, dlogp, full, best) if return_best else (logp, dlogp)
         return (logp, full, best) if return_best else logp
 
     def eval_logp(self, Pin, f, DA, H, rows, return_best=False):

@@ -657,6 +657,57 @@ class DrawRecipe:
         """-> the NNLO columns [N, ntr, ng1, 3]"""
         return self._eval(theta, f, 24, 27)
 
+    def derivative(self):
+        """The terms of d rows / d theta: for each term and each distinct theta index p in it one record (p, tracer, row, col, coef *
+        multiplicity of p in the term, fpow, idx [2]: the two remaining indices, -1 last), sorted by (p, row, tracer, col) and, inside an
+        entry, by the order the library gives the parent terms (fpow, i, j, k, coef) -- the table eftb_set_draw_recipe builds for
+        eftb_draws_logp_grad_params, whatever order the terms were handed over in."""
+        order = np.lexsort((self.coef, self.idx[:, 2], self.idx[:, 1], self.idx[:, 0], self.fpow, self.col, self.tracer, self.row))
+        rec = []
+        for p in range(len(self.param_names)):
+            for t in order:
+                ix = [int(v) for v in self.idx[t]]
+                m = ix.count(p)
+                if m:
+                    ix.remove(p)
+                    rec.append((p, self.tracer[t], self.row[t], self.col[t], self.coef[t] * m, self.fpow[t], ix))
+        out = np.zeros(len(rec), dtype=[("p", "<i4"), ("tracer", "<i4"), ("row", "<i4"), ("col", "<i4"), ("coef", "<f8"), ("fpow", "<i4"), ("idx", "<i4", (2,))])
+        for q, r in enumerate(rec):
+            out[q] = r
+        return out
+
+    def _jac(self, theta, f, lo, hi, magnitude=False):
+        theta = np.asarray(theta, dtype=np.float64)
+        P = len(self.param_names)
+        if theta.ndim != 2 or theta.shape[1] != P:
+            raise ValueError(f"theta must be [N, {P}]")
+        N = theta.shape[0]
+        f = np.asarray(f, dtype=np.float64)
+        f = np.broadcast_to(f[:, None] if f.ndim == 1 and self.ntr == 1 else f, (N, self.ntr))
+        fp = [np.ones((N, self.ntr))]
+        for _ in range(RECIPE_MAXFPOW):
+            fp.append(fp[-1] * f)
+        th = np.concatenate([theta, np.ones((N, 1))], axis=1)  # (index -1: the factor 1)
+        out = np.zeros((N, self.ntr, self.ng1, hi - lo, P))
+        for d in self.derivative():
+            if lo <= d["col"] < hi:
+                v = d["coef"] * fp[d["fpow"]][:, d["tracer"]] * th[:, d["idx"][0]] * th[:, d["idx"][1]]
+                out[:, d["tracer"], d["row"], d["col"] - lo, d["p"]] += np.abs(v) if magnitude else v
+        return out
+
+    def jacobian(self, theta, f):
+        """d rows / d theta [N, ntr, ng1, 24, P] (theta, f as ``rows``): the terms of ``derivative`` summed in their order"""
+        return self._jac(theta, f, 0, 24)
+
+    def jacobian_nnlo(self, theta, f):
+        """-> d rows_nnlo / d theta [N, ntr, ng1, 3, P]"""
+        return self._jac(theta, f, 24, 27)
+
+    def jacobian_magnitude(self, theta, f):
+        """-> the sum of the magnitudes of the monomials of each entry of ``jacobian``: the scale of its rounding error, as
+        ``rows_magnitude`` is of ``rows``"""
+        return self._jac(theta, f, 0, 24, magnitude=True)
+
     def terms(self):
         """the records of eftb_set_draw_recipe"""
         from . import _lib as L

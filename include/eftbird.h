@@ -321,6 +321,19 @@ int  eftb_draws_logp_params(eftb_engine* e, int C, long long N, const int64_t* o
                             double* fullchi2, double* best);
 int  eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* plk);
 
+/* eftb_draws_logp_params with d ln P / d theta from an adjoint pass on the device: grad [N][P] in the order of theta (required: the call
+ * without it is eftb_draws_logp_params).  ln P is the marginalised log-posterior of marginal.py:79-140 (marginalized_logp): with F2, F1,
+ * F0 as there, b = F2^-1 F1 and v = (1, b), chi2 = F0 - F1 b + [not Jeffreys] ln det(F2 / 2 pi) has
+ *     d chi2 = v^T dG v + [not Jeffreys] tr(F2^-1 dG[1:,1:]),     G = R^ W R^^T (the Gram form of eftb_draws_logp),
+ * so d chi2 / d R^ = 2 S H with S = v v^T + [not Jeffreys] blockdiag(0, F2^-1) and H = R^ W, taken at the non-zero entries of the recipe and
+ * contracted with the derivative of the recipe's monomials.  eftb_set_draw_recipe (kind 0) differentiates the sorted terms itself and keeps
+ * the derivative terms sorted by (parameter, entry, parent term) beside the recipe: whatever drops or replaces the recipe does the same to
+ * them, and the order of every sum is fixed, whatever order the terms arrived in and however the draws are split over calls.
+ * Walkers, offsets, the Gram cache and the refusals are those of eftb_draws_logp_params; logp, fullchi2 and best are its bits.  A draw
+ * with det F2 <= 0 gets NaN in all P slots of grad, as in logp. */
+int  eftb_draws_logp_grad_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
+                                 double* grad, double* fullchi2, double* best);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

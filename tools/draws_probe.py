@@ -10,6 +10,8 @@ one set of walkers, for two shapes -- the single-tracer marg.npz likelihood and 
 
 the same draws through MarginalLikelihood.logp_draws_params (eftb_draws_logp_params: theta [N, P] in, the rows built on the device from the
 draw recipe) -- per call, and end to end with theta stacked from the sampler's per-parameter arrays -- with the bytes per draw over PCIe;
+the same call with d ln P / d theta (logp_draws_params(grad=True), eftb_draws_logp_grad_params), per call and end to end, and its cost in
+forward calls (the 2 P central differences it replaces are the yardstick);
 and, for comparison, the same number of evaluations through eval_logp (theory + likelihood per walker; Nk = 512, resummation + AP, an
 interpolation onto the data k instead of the window: a lower bound on the cost of the real thing).  GPU box.
 
@@ -164,6 +166,11 @@ def probe(name, setup, C, N, ntr):
     agree = float(np.max(np.abs(lp / like.logp_draws(rows, off) - 1.0)))
     ts_params = times(lambda: like.logp_draws_params(theta, off, fC), 9)
     t_params = float(np.median(ts_params))
+    # the gradient call on the same draws
+    lpg, grad = like.logp_draws_params(theta, off, fC, grad=True)
+    assert np.array_equal(lpg, lp) and grad.shape == theta.shape
+    ts_grad = times(lambda: like.logp_draws_params(theta, off, fC, grad=True), 9)
+    t_grad = float(np.median(ts_grad))
     rate_eval = eval_logp_rate(ntr, ndata // ntr, nG)
     out = {
         "shape": name, "walkers": C, "draws": N, "tracers": ntr, "ndata": ndata, "nG": nG, "row_bytes_per_draw": rows[0].nbytes,
@@ -175,6 +182,10 @@ def probe(name, setup, C, N, ntr):
         "params_call_us_per_draw": 1e6 * t_params / N, "params_call_us_per_draw_spread": [1e6 * min(ts_params) / N, 1e6 * max(ts_params) / N],
         "params_draws_per_s_device_call": N / t_params, "params_draws_per_s_end_to_end": N / (t_params + t_theta),
         "params_vs_rows_max_rel_diff": agree,
+        "grad_bytes_back_per_draw": grad[0].nbytes, "grad_call_us_per_draw": 1e6 * t_grad / N,
+        "grad_call_us_per_draw_spread": [1e6 * min(ts_grad) / N, 1e6 * max(ts_grad) / N],
+        "grad_draws_per_s_device_call": N / t_grad, "grad_draws_per_s_end_to_end": N / (t_grad + t_theta),
+        "grad_cost_in_forward_calls": t_grad / t_params, "central_difference_cost_in_forward_calls": 2 * theta.shape[1],
         "eval_logp_per_s": rate_eval,
     }
     out["speedup_end_to_end"] = out["draws_per_s_end_to_end"] / rate_eval
