@@ -3537,13 +3537,169 @@ __device__ __forceinline__ double draw_coef(const double* Rd, const double* Rn, 
     return h == 0 ? 1.0 : 0.0;
 }
 
+// The small algebra of one draw after G = R^ W_c R^^T (one wave; G [nG + 1][nG + 1] in the wave's LDS), and the [MARG_OUT] record of the
+// draw.  Every logp draw kernel calls this one function, so the record of a draw has the same bits whichever call computed it.
+// F2 = sym(G[1:,1:]) + sigma^-2, F1 and F0 as marg_solve_kernel; LU with partial pivoting wave-synchronously: lane i keeps row i of F2,
+// augmented with F1[i], in registers; the pivot row is broadcast with v_readlane.  The rows are not exchanged: `pos` is the place the
+// row would hold in a row-exchanging LU (pivot choice on ties and the sign of det follow it), the right-hand side is eliminated with the
+// rows (= marg_solve_kernel's forward substitution, same operations in the same order), then back substitution column by column.
+// With ADJ (the gradient kernel), lane i also carries row i of the identity.  The multiplier of every eliminated row is kept in the
+// place of the entry it clears (a[c2] of a row below place c2, which nothing reads again), so the rows hold L and U of the pivoted F2.
+// Unless Jeffreys (wave-uniform: S = v v^T needs no inverse), the identity is then eliminated and substituted back with the same
+// steps, ADJ_KB columns at a time (independent chains; lane i starts with e_k[i] = [i == k]): element c2 of column k of F2^-1 ends in the
+// lane whose row holds place c2.  S is written over G (dead by then) in the wave's LDS:
+//   S[0][0] = 1, S[0][1 + k] = S[1 + k][0] = b[k], S[1 + i][1 + k] = b[i] b[k] + [not Jeffreys] F2^-1[i][k].
+// -> ok (det F2 > 0), wave-uniform
+constexpr int ADJ_KB = 4;
+
+template <bool ADJ>
+__device__ __forceinline__ bool draws_solve(int lane, int nG, int jeffreys, double* Gs, const double* mu, const double* sinv, double* o) {
+    const int ng1 = nG + 1;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    // ---- F2 | F1 per lane (row i = lane), LU with partial pivoting
+    const bool own = lane < nG;
+    double a[MARG_MAXG], aug = 0.0;
+#pragma unroll
+    for (int j = 0; j < MARG_MAXG; ++j)
+        a[j] = (own && j < nG) ? 0.5 * (Gs[(lane + 1) * ng1 + j + 1] + Gs[(j + 1) * ng1 + lane + 1]) + (lane == j ? sinv[j] : 0.0) : 0.0;
+    if (own) aug = -Gs[(lane + 1) * ng1] + sinv[lane] * mu[lane];
+    const double f1 = aug;
+    int pos = lane, sgn = 1;
+    double logdet = 0.0, dpv[MARG_MAXG];
+    int pl[MARG_MAXG];
+#pragma unroll
+    for (int c2 = 0; c2 < MARG_MAXG; ++c2) {
+        if (c2 >= nG) continue;
+        // pivot: largest |F2[i][c2]| among the rows not yet eliminated, the first in row order on ties (marg_solve_kernel, LAPACK)
+        const bool cand = own && pos >= c2;
+        double v = fabs(a[c2]);
+        if (!(v >= 0.0)) v = -0.5;  // NaN: a total order keeps the reduction's result the same in every lane
+        if (!cand) v = -1.0;
+        int kp = cand ? pos : 1 << 20, who = lane;
+#pragma unroll
+        for (int m = 16; m >= 1; m >>= 1) {  // lanes 0-31 hold every row (nG <= 24)
+            const double v2 = __shfl_xor(v, m);
+            const int k2 = __shfl_xor(kp, m), w2 = __shfl_xor(who, m);
+            if (v2 > v || (v2 == v && k2 < kp)) {
+                v = v2;
+                kp = k2;
+                who = w2;
+            }
+        }
+        const int p = __builtin_amdgcn_readlane(who, 0);
+        const int pp = __builtin_amdgcn_readlane(pos, p);
+        if (pp != c2) sgn = -sgn;
+        if (pos == c2) pos = pp;  // the row at place c2 takes the pivot row's place
+        if (lane == p) pos = c2;
+        const double dpiv = readlane_f64(a[c2], p);
+        if (dpiv < 0.0) sgn = -sgn;
+        if (dpiv == 0.0 || dpiv != dpiv) sgn = 0;
+        logdet += log(fabs(dpiv));
+        dpv[c2] = dpiv;
+        pl[c2] = p;
+        const bool elim = own && pos > c2;
+        const double m = elim ? a[c2] / dpiv : 0.0;
+#pragma unroll
+        for (int j = c2 + 1; j < MARG_MAXG; ++j)
+            if (j < nG) {
+                const double u = readlane_f64(a[j], p);
+                if (elim) a[j] = fma(-m, u, a[j]);
+            }
+        const double yc = readlane_f64(aug, p);
+        if (elim) aug = fma(-m, yc, aug);
+        if (ADJ && elim) a[c2] = m;  // (L: the cleared entry is not read again)
+    }
+    // back substitution U b = y: b = F2^-1 F1, the best-fit Gaussian parameters
+    double b[MARG_MAXG];
+#pragma unroll
+    for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2) {
+        b[c2] = 0.0;
+        if (c2 < nG) {
+            const double bc = readlane_f64(aug, pl[c2]) / dpv[c2];
+            b[c2] = bc;
+            if (own && pos < c2) aug = fma(-a[c2], bc, aug);
+        }
+    }
+    // F1 F2^-1 F1, F0 and the full chi2 at b (row sums per lane, added in row order)
+    double bi = 0.0, srow = 0.0;
+#pragma unroll
+    for (int j = 0; j < MARG_MAXG; ++j)
+        if (j < nG) {
+            if (lane == j) bi = b[j];
+            if (own) srow = fma(b[j], Gs[(lane + 1) * ng1 + j + 1], srow);
+        }
+    const double trow = own ? bi * fma(2.0, Gs[(lane + 1) * ng1], srow) : 0.0;
+    double quad = 0.0, F0 = Gs[0], full = Gs[0];
+#pragma unroll
+    for (int i = 0; i < MARG_MAXG; ++i)
+        if (i < nG) {
+            quad = fma(readlane_f64(f1, i), b[i], quad);
+            F0 = fma(mu[i] * sinv[i], mu[i], F0);
+            full += readlane_f64(trow, i);
+        }
+    const bool ok = sgn > 0;
+    const double chi2 = -quad + F0 + (jeffreys ? 0.0 : logdet - nG * 1.8378770664093453);  // ln det(F2 / 2 pi)
+    if (lane == 0) {
+        o[0] = ok ? -0.5 * chi2 : nan;
+        o[1] = ok ? full : nan;
+    }
+    if (lane < MARG_MAXG) o[2 + lane] = own ? (ok ? bi : nan) : 0.0;
+    if constexpr (ADJ) {
+        // ---- S over G: lane i < nG writes row 1 + pos, lane nG row 0
+        wave_lds_sync();  // (every read of G is done)
+        double bp = 0.0;
+#pragma unroll
+        for (int j = 0; j < MARG_MAXG; ++j)
+            if (j < nG && pos == j) bp = b[j];
+        double* srw = Gs + (own ? pos + 1 : 0) * ng1;
+        if (lane <= nG) {
+            srw[0] = own ? bp : 1.0;
+#pragma unroll
+            for (int k = 0; k < MARG_MAXG; ++k)
+                if (k < nG) srw[1 + k] = own ? bp * b[k] : b[k];
+        }
+        if (!jeffreys) {
+            double rdp[MARG_MAXG];
+#pragma unroll
+            for (int c2 = 0; c2 < MARG_MAXG; ++c2) rdp[c2] = c2 < nG ? 1.0 / dpv[c2] : 0.0;
+            for (int k0 = 0; k0 < nG; k0 += ADJ_KB) {
+                double y[ADJ_KB];
+#pragma unroll
+                for (int q = 0; q < ADJ_KB; ++q) y[q] = lane == k0 + q ? 1.0 : 0.0;
+#pragma unroll
+                for (int c2 = 0; c2 < MARG_MAXG; ++c2)
+                    if (c2 < nG) {
+                        const bool below = own && pos > c2;
+#pragma unroll
+                        for (int q = 0; q < ADJ_KB; ++q) {
+                            const double yc = readlane_f64(y[q], pl[c2]);
+                            if (below) y[q] = fma(-a[c2], yc, y[q]);
+                        }
+                    }
+#pragma unroll
+                for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2)
+                    if (c2 < nG) {
+                        const bool above = own && pos < c2;
+#pragma unroll
+                        for (int q = 0; q < ADJ_KB; ++q) {
+                            const double xc = readlane_f64(y[q], pl[c2]) * rdp[c2];
+                            if (above) y[q] = fma(-a[c2], xc, y[q]);
+                            if (pos == c2) y[q] = xc;
+                        }
+                    }
+#pragma unroll
+                for (int q = 0; q < ADJ_KB; ++q)
+                    if (own && k0 + q < nG) srw[1 + k0 + q] += y[q];
+            }
+        }
+    }
+    return ok;
+}
+
 // One workgroup per (walker, share of its draws): W_c is staged in LDS once, then every wave takes one draw at a time.
 //   H = R^ W_c    lanes over the columns j (j = lane and lane + 64 with TWO), nG + 1 accumulators each; R^[g][k] wave-uniform (scalar loads)
 //   G = H R^^T    lane h (lanes 32-63: the second half of the j sum, added with one shuffle), H from the wave's LDS scratch, G back to it
-//   F2 = sym(G[1:,1:]) + sigma^-2, F1 and F0 as marg_solve_kernel; LU with partial pivoting wave-synchronously: lane i keeps row i of F2,
-//   augmented with F1[i], in registers; the pivot row is broadcast with v_readlane.  The rows are not exchanged: `pos` is the place the
-//   row would hold in a row-exchanging LU (pivot choice on ties and the sign of det follow it), the right-hand side is eliminated with the
-//   rows (= marg_solve_kernel's forward substitution, same operations in the same order), then back substitution column by column.
+//   then draws_solve on G
 // Output: the [MARG_OUT] record of the LOGP stage per draw.  LDS: W_c [J1][J1], then per wave H [nG + 1][J1] and G [nG + 1][nG + 1].
 template <bool TWO>
 __global__ __launch_bounds__(256) void draws_logp_kernel(int ntr, int nG, int J1, int jeffreys, const long long* __restrict__ offsets,
@@ -3561,7 +3717,6 @@ __global__ __launch_bounds__(256) void draws_logp_kernel(int ntr, int nG, int J1
     __syncthreads();
     double* Hs = sm + J1 * J1 + wv * (ng1 * J1 + ng1 * ng1);
     double* Gs = Hs + ng1 * J1;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
         const double* Rd = rows + (size_t)d * ntr * ng1 * NROW;
         const double* Rn = rowsn ? rowsn + (size_t)d * ntr * ng1 * 3 : nullptr;
@@ -3617,94 +3772,7 @@ __global__ __launch_bounds__(256) void draws_logp_kernel(int ntr, int nG, int J1
                 }
         }
         wave_lds_sync();
-        // ---- F2 | F1 per lane (row i = lane), LU with partial pivoting
-        const bool own = lane < nG;
-        double a[MARG_MAXG], aug = 0.0;
-#pragma unroll
-        for (int j = 0; j < MARG_MAXG; ++j)
-            a[j] = (own && j < nG) ? 0.5 * (Gs[(lane + 1) * ng1 + j + 1] + Gs[(j + 1) * ng1 + lane + 1]) + (lane == j ? sinv[j] : 0.0) : 0.0;
-        if (own) aug = -Gs[(lane + 1) * ng1] + sinv[lane] * mu[lane];
-        const double f1 = aug;
-        int pos = lane, sgn = 1;
-        double logdet = 0.0, dpv[MARG_MAXG];
-        int pl[MARG_MAXG];
-#pragma unroll
-        for (int c2 = 0; c2 < MARG_MAXG; ++c2) {
-            if (c2 >= nG) continue;
-            // pivot: largest |F2[i][c2]| among the rows not yet eliminated, the first in row order on ties (marg_solve_kernel, LAPACK)
-            const bool cand = own && pos >= c2;
-            double v = fabs(a[c2]);
-            if (!(v >= 0.0)) v = -0.5;  // NaN: a total order keeps the reduction's result the same in every lane
-            if (!cand) v = -1.0;
-            int kp = cand ? pos : 1 << 20, who = lane;
-#pragma unroll
-            for (int m = 16; m >= 1; m >>= 1) {  // lanes 0-31 hold every row (nG <= 24)
-                const double v2 = __shfl_xor(v, m);
-                const int k2 = __shfl_xor(kp, m), w2 = __shfl_xor(who, m);
-                if (v2 > v || (v2 == v && k2 < kp)) {
-                    v = v2;
-                    kp = k2;
-                    who = w2;
-                }
-            }
-            const int p = __builtin_amdgcn_readlane(who, 0);
-            const int pp = __builtin_amdgcn_readlane(pos, p);
-            if (pp != c2) sgn = -sgn;
-            if (pos == c2) pos = pp;  // the row at place c2 takes the pivot row's place
-            if (lane == p) pos = c2;
-            const double dpiv = readlane_f64(a[c2], p);
-            if (dpiv < 0.0) sgn = -sgn;
-            if (dpiv == 0.0 || dpiv != dpiv) sgn = 0;
-            logdet += log(fabs(dpiv));
-            dpv[c2] = dpiv;
-            pl[c2] = p;
-            const bool elim = own && pos > c2;
-            const double m = elim ? a[c2] / dpiv : 0.0;
-#pragma unroll
-            for (int j = c2 + 1; j < MARG_MAXG; ++j)
-                if (j < nG) {
-                    const double u = readlane_f64(a[j], p);
-                    if (elim) a[j] = fma(-m, u, a[j]);
-                }
-            const double yc = readlane_f64(aug, p);
-            if (elim) aug = fma(-m, yc, aug);
-        }
-        // back substitution U b = y: b = F2^-1 F1, the best-fit Gaussian parameters
-        double b[MARG_MAXG];
-#pragma unroll
-        for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2) {
-            b[c2] = 0.0;
-            if (c2 < nG) {
-                const double bc = readlane_f64(aug, pl[c2]) / dpv[c2];
-                b[c2] = bc;
-                if (own && pos < c2) aug = fma(-a[c2], bc, aug);
-            }
-        }
-        // F1 F2^-1 F1, F0 and the full chi2 at b (row sums per lane, added in row order)
-        double bi = 0.0, srow = 0.0;
-#pragma unroll
-        for (int j = 0; j < MARG_MAXG; ++j)
-            if (j < nG) {
-                if (lane == j) bi = b[j];
-                if (own) srow = fma(b[j], Gs[(lane + 1) * ng1 + j + 1], srow);
-            }
-        const double trow = own ? bi * fma(2.0, Gs[(lane + 1) * ng1], srow) : 0.0;
-        double quad = 0.0, F0 = Gs[0], full = Gs[0];
-#pragma unroll
-        for (int i = 0; i < MARG_MAXG; ++i)
-            if (i < nG) {
-                quad = fma(readlane_f64(f1, i), b[i], quad);
-                F0 = fma(mu[i] * sinv[i], mu[i], F0);
-                full += readlane_f64(trow, i);
-            }
-        const bool ok = sgn > 0;
-        const double chi2 = -quad + F0 + (jeffreys ? 0.0 : logdet - nG * 1.8378770664093453);  // ln det(F2 / 2 pi)
-        double* o = out + (size_t)d * MARG_OUT;
-        if (lane == 0) {
-            o[0] = ok ? -0.5 * chi2 : nan;
-            o[1] = ok ? full : nan;
-        }
-        if (lane < MARG_MAXG) o[2 + lane] = own ? (ok ? bi : nan) : 0.0;
+        draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
         wave_lds_sync();  // (the next draw overwrites H and G)
     }
 }
@@ -3893,103 +3961,54 @@ __device__ __forceinline__ int recipe_col(int ent, int ntr) {
     return r < NROW ? tau * NROW + r : ntr * NROW + 3 * tau + (r - NROW);
 }
 
-// The small algebra of one draw after G = R^ W_c R^^T (one wave; G [nG + 1][nG + 1] in the wave's LDS): F2 = sym(G[1:,1:]) + sigma^-2, F1,
-// F0, the wave-synchronous LU described at draws_logp_kernel, and the [MARG_OUT] record of the draw: the statements of draws_logp_kernel after
-// its G (that kernel keeps them inline, so its compiled code stays the one that was measured).
-__device__ __forceinline__ void draws_solve(int lane, int nG, int jeffreys, const double* Gs, const double* mu, const double* sinv, double* o) {
-    const int ng1 = nG + 1;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    // ---- F2 | F1 per lane (row i = lane), LU with partial pivoting
-    const bool own = lane < nG;
-    double a[MARG_MAXG], aug = 0.0;
-#pragma unroll
-    for (int j = 0; j < MARG_MAXG; ++j)
-        a[j] = (own && j < nG) ? 0.5 * (Gs[(lane + 1) * ng1 + j + 1] + Gs[(j + 1) * ng1 + lane + 1]) + (lane == j ? sinv[j] : 0.0) : 0.0;
-    if (own) aug = -Gs[(lane + 1) * ng1] + sinv[lane] * mu[lane];
-    const double f1 = aug;
-    int pos = lane, sgn = 1;
-    double logdet = 0.0, dpv[MARG_MAXG];
-    int pl[MARG_MAXG];
-#pragma unroll
-    for (int c2 = 0; c2 < MARG_MAXG; ++c2) {
-        if (c2 >= nG) continue;
-        // pivot: largest |F2[i][c2]| among the rows not yet eliminated, the first in row order on ties (marg_solve_kernel, LAPACK)
-        const bool cand = own && pos >= c2;
-        double v = fabs(a[c2]);
-        if (!(v >= 0.0)) v = -0.5;  // NaN: a total order keeps the reduction's result the same in every lane
-        if (!cand) v = -1.0;
-        int kp = cand ? pos : 1 << 20, who = lane;
-#pragma unroll
-        for (int m = 16; m >= 1; m >>= 1) {  // lanes 0-31 hold every row (nG <= 24)
-            const double v2 = __shfl_xor(v, m);
-            const int k2 = __shfl_xor(kp, m), w2 = __shfl_xor(who, m);
-            if (v2 > v || (v2 == v && k2 < kp)) {
-                v = v2;
-                kp = k2;
-                who = w2;
-            }
+// The forward pass of a params draw up to G (one wave; th, val, Hs and Gs are the wave's LDS, Ws, fp and col the workgroup's): theta,
+// val[n], H = R^ W_c and G = H R^^T as described at draws_logp_params_kernel.  G is ordered for the wave's reads on return.
+template <bool TWO>
+__device__ __forceinline__ void draws_recipe_forward(const RecipeTab& rt, const double* __restrict__ theta, long long d, int lane, int ng1, int J1,
+                                                     const double* Ws, const double* fp, const int* col, double* th, double* val, double* Hs, double* Gs) {
+    const int J = J1 - 1, nnz = rt.nnz;
+    const bool c0 = lane < J1, c1 = TWO && lane + 64 < J1;
+    // ---- the non-zeros of R^ for this draw
+    recipe_theta(rt, theta, d, lane, th);
+    wave_lds_sync();
+    for (int n = lane; n < nnz; n += 64) val[n] = recipe_entry(rt, n, fp, th);
+    wave_lds_sync();
+    // ---- H = R^ W_c
+    for (int g = 0; g < ng1; ++g) {
+        double h0 = 0.0, h1 = 0.0;
+        const int n1 = rt.rowstart[g + 1];
+        for (int n = rt.rowstart[g]; n < n1; ++n) {
+            const double rv = val[n];
+            const double* wk = Ws + col[n] * J1 + lane;
+            h0 = fma(rv, c0 ? wk[0] : 0.0, h0);
+            if (TWO) h1 = fma(rv, c1 ? wk[64] : 0.0, h1);
         }
-        const int p = __builtin_amdgcn_readlane(who, 0);
-        const int pp = __builtin_amdgcn_readlane(pos, p);
-        if (pp != c2) sgn = -sgn;
-        if (pos == c2) pos = pp;  // the row at place c2 takes the pivot row's place
-        if (lane == p) pos = c2;
-        const double dpiv = readlane_f64(a[c2], p);
-        if (dpiv < 0.0) sgn = -sgn;
-        if (dpiv == 0.0 || dpiv != dpiv) sgn = 0;
-        logdet += log(fabs(dpiv));
-        dpv[c2] = dpiv;
-        pl[c2] = p;
-        const bool elim = own && pos > c2;
-        const double m = elim ? a[c2] / dpiv : 0.0;
-#pragma unroll
-        for (int j = c2 + 1; j < MARG_MAXG; ++j)
-            if (j < nG) {
-                const double u = readlane_f64(a[j], p);
-                if (elim) a[j] = fma(-m, u, a[j]);
-            }
-        const double yc = readlane_f64(aug, p);
-        if (elim) aug = fma(-m, yc, aug);
+        if (g == 0) {  // the data row: R^[0][J] = 1
+            h0 += c0 ? Ws[J * J1 + lane] : 0.0;
+            if (TWO) h1 += c1 ? Ws[J * J1 + 64 + lane] : 0.0;
+        }
+        if (c0) Hs[g * J1 + lane] = h0;
+        if (c1) Hs[g * J1 + 64 + lane] = h1;
     }
-    // back substitution U b = y: b = F2^-1 F1, the best-fit Gaussian parameters
-    double b[MARG_MAXG];
-#pragma unroll
-    for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2) {
-        b[c2] = 0.0;
-        if (c2 < nG) {
-            const double bc = readlane_f64(aug, pl[c2]) / dpv[c2];
-            b[c2] = bc;
-            if (own && pos < c2) aug = fma(-a[c2], bc, aug);
+    wave_lds_sync();
+    // ---- G = H R^^T over the non-zeros of row h
+    {
+        const int g = lane & 31, half = lane >> 5;
+        const double* hg = Hs + (g < ng1 ? g : 0) * J1;
+        for (int h = 0; h < ng1; ++h) {
+            double acc = 0.0;
+            const int n1 = rt.rowstart[h + 1];
+            for (int n = rt.rowstart[h] + half; n < n1; n += 2) acc = fma(hg[col[n]], val[n], acc);
+            acc += __shfl_xor(acc, 32);
+            if (h == 0) acc += hg[J];
+            if (half == 0 && g < ng1) Gs[g * ng1 + h] = acc;
         }
     }
-    // F1 F2^-1 F1, F0 and the full chi2 at b (row sums per lane, added in row order)
-    double bi = 0.0, srow = 0.0;
-#pragma unroll
-    for (int j = 0; j < MARG_MAXG; ++j)
-        if (j < nG) {
-            if (lane == j) bi = b[j];
-            if (own) srow = fma(b[j], Gs[(lane + 1) * ng1 + j + 1], srow);
-        }
-    const double trow = own ? bi * fma(2.0, Gs[(lane + 1) * ng1], srow) : 0.0;
-    double quad = 0.0, F0 = Gs[0], full = Gs[0];
-#pragma unroll
-    for (int i = 0; i < MARG_MAXG; ++i)
-        if (i < nG) {
-            quad = fma(readlane_f64(f1, i), b[i], quad);
-            F0 = fma(mu[i] * sinv[i], mu[i], F0);
-            full += readlane_f64(trow, i);
-        }
-    const bool ok = sgn > 0;
-    const double chi2 = -quad + F0 + (jeffreys ? 0.0 : logdet - nG * 1.8378770664093453);  // ln det(F2 / 2 pi)
-    if (lane == 0) {
-        o[0] = ok ? -0.5 * chi2 : nan;
-        o[1] = ok ? full : nan;
-    }
-    if (lane < MARG_MAXG) o[2 + lane] = own ? (ok ? bi : nan) : 0.0;
+    wave_lds_sync();
 }
 
 // draws_logp_kernel for draws given as theta [N][P] and f [C][ntr]: the same workgroup shape (W_c in LDS once, one wave per draw at a
-// time) and the same algebra after G, but R^ only exists as the values of its nnz non-zero entries in the wave's LDS:
+// time) and the same algebra after G (draws_solve), but R^ only exists as the values of its nnz non-zero entries in the wave's LDS:
 //   val[n]        lanes over the entries of the recipe
 //   H = R^ W_c    row g at a time: lanes over the columns j (j = lane and lane + 64 with TWO), one FMA per non-zero of row g, the value a
 //                 broadcast LDS read; R^[0][J] = 1 stays implicit (the data row of W_c is added to row 0)
@@ -4003,7 +4022,7 @@ __global__ __launch_bounds__(256) void draws_logp_params_kernel(int ntr, int nG,
     extern __shared__ double sm[];
     const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ng1 = nG + 1, J = J1 - 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1;
+    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
     double* Ws = sm;
@@ -4017,46 +4036,9 @@ __global__ __launch_bounds__(256) void draws_logp_params_kernel(int ntr, int nG,
     double* val = th + 34;
     double* Hs = val + nnzp;
     double* Gs = Hs + ng1 * J1;
-    const bool c0 = lane < J1, c1 = TWO && lane + 64 < J1;
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
-        // ---- the non-zeros of R^ for this draw
-        recipe_theta(rt, theta, d, lane, th);
-        wave_lds_sync();
-        for (int n = lane; n < nnz; n += 64) val[n] = recipe_entry(rt, n, fp, th);
-        wave_lds_sync();
-        // ---- H = R^ W_c
-        for (int g = 0; g < ng1; ++g) {
-            double h0 = 0.0, h1 = 0.0;
-            const int n1 = rt.rowstart[g + 1];
-            for (int n = rt.rowstart[g]; n < n1; ++n) {
-                const double rv = val[n];
-                const double* wk = Ws + col[n] * J1 + lane;
-                h0 = fma(rv, c0 ? wk[0] : 0.0, h0);
-                if (TWO) h1 = fma(rv, c1 ? wk[64] : 0.0, h1);
-            }
-            if (g == 0) {  // the data row: R^[0][J] = 1
-                h0 += c0 ? Ws[J * J1 + lane] : 0.0;
-                if (TWO) h1 += c1 ? Ws[J * J1 + 64 + lane] : 0.0;
-            }
-            if (c0) Hs[g * J1 + lane] = h0;
-            if (c1) Hs[g * J1 + 64 + lane] = h1;
-        }
-        wave_lds_sync();
-        // ---- G = H R^^T over the non-zeros of row h
-        {
-            const int g = lane & 31, half = lane >> 5;
-            const double* hg = Hs + (g < ng1 ? g : 0) * J1;
-            for (int h = 0; h < ng1; ++h) {
-                double acc = 0.0;
-                const int n1 = rt.rowstart[h + 1];
-                for (int n = rt.rowstart[h] + half; n < n1; n += 2) acc = fma(hg[col[n]], val[n], acc);
-                acc += __shfl_xor(acc, 32);
-                if (h == 0) acc += hg[J];
-                if (half == 0 && g < ng1) Gs[g * ng1 + h] = acc;
-            }
-        }
-        wave_lds_sync();
-        draws_solve(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
+        draws_recipe_forward<TWO>(rt, theta, d, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+        draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
         wave_lds_sync();  // (the next draw overwrites th, val, H and G)
     }
 }
@@ -4104,160 +4086,8 @@ struct RecipeGradTab {
     int lgP2;  // log2 of the smallest power of two >= max(P, 1): lane = share << lgP2 | p in the P sums
 };
 
-// draws_solve with lane i also carrying row i of the identity: the same statements in the same order for everything draws_solve
-// computes (the record of the draw has the forward call's bits).  Beside them the multiplier of every eliminated row is kept in the
-// place of the entry it clears (a[c2] of a row below place c2, which nothing reads again), so the rows hold L and U of the pivoted F2.
-// Unless Jeffreys (wave-uniform: S = v v^T needs no inverse), the identity is then eliminated and substituted back with the same
-// steps, ADJ_KB columns at a time (independent chains; lane i starts with e_k[i] = [i == k]): element c2 of column k of F2^-1 ends in the
-// lane whose row holds place c2.  S is written over G (dead by then) in the wave's LDS:
-//   S[0][0] = 1, S[0][1 + k] = S[1 + k][0] = b[k], S[1 + i][1 + k] = b[i] b[k] + [not Jeffreys] F2^-1[i][k].
-// -> ok (det F2 > 0), wave-uniform
-constexpr int ADJ_KB = 4;
-
-__device__ __forceinline__ bool draws_solve_adjoint(int lane, int nG, int jeffreys, double* Gs, const double* mu, const double* sinv, double* o) {
-    const int ng1 = nG + 1;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    // ---- F2 | F1 per lane (row i = lane), LU with partial pivoting
-    const bool own = lane < nG;
-    double a[MARG_MAXG], aug = 0.0;
-#pragma unroll
-    for (int j = 0; j < MARG_MAXG; ++j)
-        a[j] = (own && j < nG) ? 0.5 * (Gs[(lane + 1) * ng1 + j + 1] + Gs[(j + 1) * ng1 + lane + 1]) + (lane == j ? sinv[j] : 0.0) : 0.0;
-    if (own) aug = -Gs[(lane + 1) * ng1] + sinv[lane] * mu[lane];
-    const double f1 = aug;
-    int pos = lane, sgn = 1;
-    double logdet = 0.0, dpv[MARG_MAXG];
-    int pl[MARG_MAXG];
-#pragma unroll
-    for (int c2 = 0; c2 < MARG_MAXG; ++c2) {
-        if (c2 >= nG) continue;
-        // pivot: largest |F2[i][c2]| among the rows not yet eliminated, the first in row order on ties (marg_solve_kernel, LAPACK)
-        const bool cand = own && pos >= c2;
-        double v = fabs(a[c2]);
-        if (!(v >= 0.0)) v = -0.5;  // NaN: a total order keeps the reduction's result the same in every lane
-        if (!cand) v = -1.0;
-        int kp = cand ? pos : 1 << 20, who = lane;
-#pragma unroll
-        for (int m = 16; m >= 1; m >>= 1) {  // lanes 0-31 hold every row (nG <= 24)
-            const double v2 = __shfl_xor(v, m);
-            const int k2 = __shfl_xor(kp, m), w2 = __shfl_xor(who, m);
-            if (v2 > v || (v2 == v && k2 < kp)) {
-                v = v2;
-                kp = k2;
-                who = w2;
-            }
-        }
-        const int p = __builtin_amdgcn_readlane(who, 0);
-        const int pp = __builtin_amdgcn_readlane(pos, p);
-        if (pp != c2) sgn = -sgn;
-        if (pos == c2) pos = pp;  // the row at place c2 takes the pivot row's place
-        if (lane == p) pos = c2;
-        const double dpiv = readlane_f64(a[c2], p);
-        if (dpiv < 0.0) sgn = -sgn;
-        if (dpiv == 0.0 || dpiv != dpiv) sgn = 0;
-        logdet += log(fabs(dpiv));
-        dpv[c2] = dpiv;
-        pl[c2] = p;
-        const bool elim = own && pos > c2;
-        const double m = elim ? a[c2] / dpiv : 0.0;
-#pragma unroll
-        for (int j = c2 + 1; j < MARG_MAXG; ++j)
-            if (j < nG) {
-                const double u = readlane_f64(a[j], p);
-                if (elim) a[j] = fma(-m, u, a[j]);
-            }
-        const double yc = readlane_f64(aug, p);
-        if (elim) aug = fma(-m, yc, aug);
-        if (elim) a[c2] = m;  // (L: the cleared entry is not read again)
-    }
-    // back substitution U b = y: b = F2^-1 F1, the best-fit Gaussian parameters
-    double b[MARG_MAXG];
-#pragma unroll
-    for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2) {
-        b[c2] = 0.0;
-        if (c2 < nG) {
-            const double bc = readlane_f64(aug, pl[c2]) / dpv[c2];
-            b[c2] = bc;
-            if (own && pos < c2) aug = fma(-a[c2], bc, aug);
-        }
-    }
-    // F1 F2^-1 F1, F0 and the full chi2 at b (row sums per lane, added in row order)
-    double bi = 0.0, srow = 0.0;
-#pragma unroll
-    for (int j = 0; j < MARG_MAXG; ++j)
-        if (j < nG) {
-            if (lane == j) bi = b[j];
-            if (own) srow = fma(b[j], Gs[(lane + 1) * ng1 + j + 1], srow);
-        }
-    const double trow = own ? bi * fma(2.0, Gs[(lane + 1) * ng1], srow) : 0.0;
-    double quad = 0.0, F0 = Gs[0], full = Gs[0];
-#pragma unroll
-    for (int i = 0; i < MARG_MAXG; ++i)
-        if (i < nG) {
-            quad = fma(readlane_f64(f1, i), b[i], quad);
-            F0 = fma(mu[i] * sinv[i], mu[i], F0);
-            full += readlane_f64(trow, i);
-        }
-    const bool ok = sgn > 0;
-    const double chi2 = -quad + F0 + (jeffreys ? 0.0 : logdet - nG * 1.8378770664093453);  // ln det(F2 / 2 pi)
-    if (lane == 0) {
-        o[0] = ok ? -0.5 * chi2 : nan;
-        o[1] = ok ? full : nan;
-    }
-    if (lane < MARG_MAXG) o[2 + lane] = own ? (ok ? bi : nan) : 0.0;
-    // ---- S over G: lane i < nG writes row 1 + pos, lane nG row 0
-    wave_lds_sync();  // (every read of G is done)
-    double bp = 0.0;
-#pragma unroll
-    for (int j = 0; j < MARG_MAXG; ++j)
-        if (j < nG && pos == j) bp = b[j];
-    double* srw = Gs + (own ? pos + 1 : 0) * ng1;
-    if (lane <= nG) {
-        srw[0] = own ? bp : 1.0;
-#pragma unroll
-        for (int k = 0; k < MARG_MAXG; ++k)
-            if (k < nG) srw[1 + k] = own ? bp * b[k] : b[k];
-    }
-    if (!jeffreys) {
-        double rdp[MARG_MAXG];
-#pragma unroll
-        for (int c2 = 0; c2 < MARG_MAXG; ++c2) rdp[c2] = c2 < nG ? 1.0 / dpv[c2] : 0.0;
-        for (int k0 = 0; k0 < nG; k0 += ADJ_KB) {
-            double y[ADJ_KB];
-#pragma unroll
-            for (int q = 0; q < ADJ_KB; ++q) y[q] = lane == k0 + q ? 1.0 : 0.0;
-#pragma unroll
-            for (int c2 = 0; c2 < MARG_MAXG; ++c2)
-                if (c2 < nG) {
-                    const bool below = own && pos > c2;
-#pragma unroll
-                    for (int q = 0; q < ADJ_KB; ++q) {
-                        const double yc = readlane_f64(y[q], pl[c2]);
-                        if (below) y[q] = fma(-a[c2], yc, y[q]);
-                    }
-                }
-#pragma unroll
-            for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2)
-                if (c2 < nG) {
-                    const bool above = own && pos < c2;
-#pragma unroll
-                    for (int q = 0; q < ADJ_KB; ++q) {
-                        const double xc = readlane_f64(y[q], pl[c2]) * rdp[c2];
-                        if (above) y[q] = fma(-a[c2], xc, y[q]);
-                        if (pos == c2) y[q] = xc;
-                    }
-                }
-#pragma unroll
-            for (int q = 0; q < ADJ_KB; ++q)
-                if (own && k0 + q < nG) srw[1 + k0 + q] += y[q];
-        }
-    }
-    return ok;
-}
-
-// draws_logp_params_kernel with the gradient: the outer shape, val, H and G are that kernel's statements (the forward sums keep their
-// order), then per draw
-//   solve          draws_solve_adjoint: the record, and S over G
+// draws_logp_params_kernel with the gradient: the same outer shape and forward pass (draws_recipe_forward), then per draw
+//   solve          draws_solve<true>: the record, and S over G
 //   Rbar[n]        lanes over the entries n = (g, col): sum_h (S[g][h] + S[h][g]) H[h][col], written over val[n] (the computed F2^-1 is
 //                  symmetric up to rounding only: both halves of dG get their own factor)
 //   grad[p]        lane = share << lgP2 | p: share s of the 64 >> lgP2 takes every (64 >> lgP2)-th record of parameter p in table order,
@@ -4272,7 +4102,7 @@ __global__ __launch_bounds__(256) void draws_logp_grad_params_kernel(int ntr, in
     extern __shared__ double sm[];
     const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ng1 = nG + 1, J = J1 - 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1, P = rt.P;
+    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1, P = rt.P;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
     double* Ws = sm;
@@ -4290,48 +4120,11 @@ __global__ __launch_bounds__(256) void draws_logp_grad_params_kernel(int ntr, in
     double* val = th + 34;
     double* Hs = val + nnzp;
     double* Gs = Hs + ng1 * J1;
-    const bool c0 = lane < J1, c1 = TWO && lane + 64 < J1;
     const int pmask = (1 << gt.lgP2) - 1, gp = lane & pmask, share = lane >> gt.lgP2, nshare = 64 >> gt.lgP2;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
-        // ---- the non-zeros of R^ for this draw
-        recipe_theta(rt, theta, d, lane, th);
-        wave_lds_sync();
-        for (int n = lane; n < nnz; n += 64) val[n] = recipe_entry(rt, n, fp, th);
-        wave_lds_sync();
-        // ---- H = R^ W_c
-        for (int g = 0; g < ng1; ++g) {
-            double h0 = 0.0, h1 = 0.0;
-            const int n1 = rt.rowstart[g + 1];
-            for (int n = rt.rowstart[g]; n < n1; ++n) {
-                const double rv = val[n];
-                const double* wk = Ws + col[n] * J1 + lane;
-                h0 = fma(rv, c0 ? wk[0] : 0.0, h0);
-                if (TWO) h1 = fma(rv, c1 ? wk[64] : 0.0, h1);
-            }
-            if (g == 0) {  // the data row: R^[0][J] = 1
-                h0 += c0 ? Ws[J * J1 + lane] : 0.0;
-                if (TWO) h1 += c1 ? Ws[J * J1 + 64 + lane] : 0.0;
-            }
-            if (c0) Hs[g * J1 + lane] = h0;
-            if (c1) Hs[g * J1 + 64 + lane] = h1;
-        }
-        wave_lds_sync();
-        // ---- G = H R^^T over the non-zeros of row h
-        {
-            const int g = lane & 31, half = lane >> 5;
-            const double* hg = Hs + (g < ng1 ? g : 0) * J1;
-            for (int h = 0; h < ng1; ++h) {
-                double acc = 0.0;
-                const int n1 = rt.rowstart[h + 1];
-                for (int n = rt.rowstart[h] + half; n < n1; n += 2) acc = fma(hg[col[n]], val[n], acc);
-                acc += __shfl_xor(acc, 32);
-                if (h == 0) acc += hg[J];
-                if (half == 0 && g < ng1) Gs[g * ng1 + h] = acc;
-            }
-        }
-        wave_lds_sync();
-        const bool ok = draws_solve_adjoint(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
+        draws_recipe_forward<TWO>(rt, theta, d, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+        const bool ok = draws_solve<true>(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
         wave_lds_sync();
         // ---- Rbar at the non-zeros, over val
         for (int n = lane; n < nnz; n += 64) {

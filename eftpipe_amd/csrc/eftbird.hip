@@ -148,7 +148,7 @@ struct eftb_engine {
     size_t drw_A_cap = 0, drw_U_cap = 0, drw_W_cap = 0, drw_in_cap = 0, drw_inn_cap = 0, drw_out_cap = 0, drw_off_cap = 0;
     long long* drw_off = nullptr;
     std::vector<double> drw_host;   // eftb_draws_logp: D2H landing block [N][MARG_OUT]
-    bool drw_lds = false;           // draws_logp_kernel opted in to the large dynamic LDS
+    bool drw_lds = false;           // the draws_logp*_kernel instantiations opted in to the large dynamic LDS
     // draw recipes (eftb_set_draw_recipe): [0] of eftb_draws_logp_params, [1] of eftb_draws_reduce_params.  coef [nterms] and the int table
     // rowstart | ent | tstart | pack | slot (RecipeTab) live on the device; set = false: none (never set, withdrawn, or dropped)
     struct Recipe {
@@ -163,10 +163,8 @@ struct eftb_engine {
     } recipe[2];
     double* drw_theta = nullptr;    // theta [N][P] then f [C][ntr] of a params call
     size_t drw_theta_cap = 0;
-    bool drwp_lds = false;          // draws_logp_params_kernel opted in to the large dynamic LDS
     double* drw_grad = nullptr;     // eftb_draws_logp_grad_params: d ln P / d theta [N][P]
     size_t drw_grad_cap = 0;
-    bool drwg_lds = false;          // draws_logp_grad_params_kernel opted in to the large dynamic LDS
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -2305,57 +2303,88 @@ static int draws_records(eftb_engine* e, long long N, double* logp, double* full
     return 0;
 }
 
+// what every logp draw call refuses before it looks at its own inputs: no likelihood, draws_check, a block of another shape than the likelihood's
+static int draws_logp_check(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, long long* maxcnt) {
+    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
+    if (int rc = draws_check(e, who, C, N, offsets, maxcnt)) return rc;
+    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
+        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
+                    e->cur_nx);
+    return 0;
+}
+
+// workgroup of a logp draw kernel: J1 columns of W_c, nw waves (as many as the LDS holds beside W_c), lds bytes.  The kernel keeps
+// W_c [J1][J1] and extra_w bytes per workgroup, H [ng1][J1], G [ng1][ng1] and extra_wave bytes per wave.
+struct DrawShape {
+    int J1, nw;
+    size_t lds;
+};
+static int draws_logp_shape(eftb_engine* e, const char* who, size_t extra_w, size_t extra_wave, DrawShape* sh) {
+    const int ng1 = e->like_nG + 1, J1 = (e->c.with_nnlo ? NROW + 3 : NROW) * e->ntr + 1;
+    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
+    const size_t lds_w = (size_t)J1 * J1 * sizeof(double) + extra_w, lds_wave = ((size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double) + extra_wave;
+    int nw = 4;
+    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
+    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
+    *sh = DrawShape{J1, nw, lds_w + nw * lds_wave};
+    return 0;
+}
+
+// the large dynamic LDS for every logp draw kernel, once per engine
+static int draws_lds_optin(eftb_engine* e) {
+    if (e->drw_lds) return 0;
+    for (const void* k : {reinterpret_cast<const void*>(&draws_logp_kernel<false>), reinterpret_cast<const void*>(&draws_logp_kernel<true>),
+                          reinterpret_cast<const void*>(&draws_logp_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_params_kernel<true>),
+                          reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<false>),
+                          reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<true>)})
+        HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    e->drw_lds = true;
+    return 0;
+}
+
+// before the inputs of a logp draw call go to the device: the device and the stream, the LDS opt-in of the kernels (once), W_c, the
+// record buffer, and the offsets
+static int draws_logp_begin(eftb_engine* e, const char* who, int C, long long N, int J1, const int64_t* offsets) {
+    HIPCHK(hipSetDevice(e->c.device));
+    join_back(e);
+    if (int rc = draws_lds_optin(e)) return rc;
+    if (int rc = draws_gram(e, who, C, J1)) return rc;
+    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
+    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, e->stream));
+    return 0;
+}
+
 int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* rows, const double* rows_nnlo, double* logp,
                     double* fullchi2, double* best) {
     static const char* who = "eftb_draws_logp";
     if (e) sub_drain(e);
     if (!e || !offsets || (N > 0 && (!rows || !logp))) return fail("%s: null argument", who);
-    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
     long long maxcnt = 0;
-    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
-    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
-        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
-                    e->cur_nx);
-    const eftb_config& c = e->c;
-    if (rows_nnlo && !c.with_nnlo) return fail("%s: rows_nnlo needs an engine built with with_nnlo", who);
-    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1;
-    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
-    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
-    const size_t lds_w = (size_t)J1 * J1 * sizeof(double), lds_wave = ((size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
-    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
-    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
-    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
+    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    if (rows_nnlo && !e->c.with_nnlo) return fail("%s: rows_nnlo needs an engine built with with_nnlo", who);
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, 0, 0, &sh)) return rc;
     if (N == 0) return 0;
-    HIPCHK(hipSetDevice(c.device));
+    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets)) return rc;
+    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1, J1 = sh.J1;
     hipStream_t st = e->stream;
-    join_back(e);
-    if (!e->drw_lds) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        e->drw_lds = true;
-    }
-    if (int rc = draws_gram(e, who, C, J1)) return rc;
     const size_t rn = (size_t)N * ntr * ng1 * NROW, rnn = (size_t)N * ntr * ng1 * 3;
-    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
     if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, rn)) return rc;
-    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
     if (rows_nnlo)
         if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, rnn)) return rc;
-    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(e->drw_in, rows, rn * sizeof(double), hipMemcpyHostToDevice, st));
     if (rows_nnlo) HIPCHK(hipMemcpyAsync(e->drw_inn, rows_nnlo, rnn * sizeof(double), hipMemcpyHostToDevice, st));
-    const dim3 grid(C, draw_shares(maxcnt, nw, C)), block(64 * nw);
-    const size_t lds = lds_w + nw * lds_wave;
+    const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
     if (J1 > 64)
-        hipLaunchKernelGGL(draws_logp_kernel<true>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
+        hipLaunchKernelGGL(draws_logp_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
                            e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
     else
-        hipLaunchKernelGGL(draws_logp_kernel<false>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
+        hipLaunchKernelGGL(draws_logp_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
                            e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
-    if (int rc = draws_records(e, N, logp, fullchi2, best)) return rc;
-    return 0;
+    return draws_records(e, N, logp, fullchi2, best);
 }
 
 int eftb_draws_reduce(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* bias, const double* bias_nnlo, double* plk) {
@@ -3486,56 +3515,60 @@ static int draws_params_upload(eftb_engine* e, int P, int C, long long N, const 
     return 0;
 }
 
+// eftb_draws_logp_params (grad == nullptr: the forward kernel and its LDS layout) and eftb_draws_logp_grad_params
+static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, const double* theta, const double* f,
+                                  double* logp, double* grad, double* fullchi2, double* best) {
+    long long maxcnt = 0;
+    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    const int ntr = e->ntr, nG = e->like_nG;
+    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta, f)) return rc;
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int P = rcp.P, nnzp = (rcp.nnz + 1) & ~1;
+    DrawShape sh;  // beside W_c: fp, col [nnzp] and, with the gradient, erow [nnzp]; per wave: th [34] and val [nnzp]
+    if (int rc = draws_logp_shape(e, who, RECIPE_MAXTR * RECIPE_FPOW * sizeof(double) + (grad ? 2 : 1) * nnzp * sizeof(int), (34 + (size_t)nnzp) * sizeof(double), &sh))
+        return rc;
+    if (N == 0) return 0;
+    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets)) return rc;
+    if (grad)
+        if (int rc = grow_dev(&e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
+    const double *dtheta = nullptr, *df = nullptr;
+    if (int rc = draws_params_upload(e, P, C, N, theta, f, &dtheta, &df)) return rc;
+    hipStream_t st = e->stream;
+    const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
+    const int J1 = sh.J1;
+    const RecipeTab rt = recipe_tab(rcp);
+    if (grad) {
+        RecipeGradTab gt{};
+        gt.dcoef = rcp.dcoef;
+        gt.pstart = rcp.dtab;
+        gt.dent = gt.pstart + P + 1;
+        gt.dpack = gt.dent + rcp.ndt;
+        gt.erow = gt.dpack + rcp.ndt;
+        while ((1 << gt.lgP2) < P) ++gt.lgP2;
+        if (J1 > 64)
+            hipLaunchKernelGGL(draws_logp_grad_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
+                               e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
+        else
+            hipLaunchKernelGGL(draws_logp_grad_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
+                               e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
+    } else if (J1 > 64)
+        hipLaunchKernelGGL(draws_logp_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
+                           e->like_sinv, e->drw_out);
+    else
+        hipLaunchKernelGGL(draws_logp_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
+                           e->like_sinv, e->drw_out);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    if (grad && P) HIPCHK(hipMemcpyAsync(grad, e->drw_grad, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    return draws_records(e, N, logp, fullchi2, best);
+}
+
 int eftb_draws_logp_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
                            double* fullchi2, double* best) {
     static const char* who = "eftb_draws_logp_params";
     if (e) sub_drain(e);
     if (!e || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
-    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
-    long long maxcnt = 0;
-    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
-    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
-        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
-                    e->cur_nx);
-    const eftb_config& c = e->c;
-    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1;
-    if (int rc = draws_params_check(e, who, 0, ng1, C, N, theta, f)) return rc;
-    const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
-    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
-    const int nnzp = (rcp.nnz + 1) & ~1;
-    const size_t lds_w = ((size_t)J1 * J1 + RECIPE_MAXTR * RECIPE_FPOW + nnzp / 2) * sizeof(double);
-    const size_t lds_wave = (34 + (size_t)nnzp + (size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
-    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
-    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
-    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
-    if (N == 0) return 0;
-    HIPCHK(hipSetDevice(c.device));
-    hipStream_t st = e->stream;
-    join_back(e);
-    if (!e->drwp_lds) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_params_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_params_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        e->drwp_lds = true;
-    }
-    if (int rc = draws_gram(e, who, C, J1)) return rc;
-    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
-    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
-    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    const double *dtheta = nullptr, *df = nullptr;
-    if (int rc = draws_params_upload(e, rcp.P, C, N, theta, f, &dtheta, &df)) return rc;
-    const dim3 grid(C, draw_shares(maxcnt, nw, C)), block(64 * nw);
-    const size_t lds = lds_w + nw * lds_wave;
-    const RecipeTab rt = recipe_tab(rcp);
-    if (J1 > 64)
-        hipLaunchKernelGGL(draws_logp_params_kernel<true>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
-                           e->like_sinv, e->drw_out);
-    else
-        hipLaunchKernelGGL(draws_logp_params_kernel<false>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
-                           e->like_sinv, e->drw_out);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
-    return draws_records(e, N, logp, fullchi2, best);
+    return draws_logp_params_impl(e, who, C, N, offsets, theta, f, logp, nullptr, fullchi2, best);
 }
 
 int eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* plk) {
@@ -3575,65 +3608,11 @@ int eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* 
 }
 
 // ------------------------------------------------------------------------------------------------ d ln P / d theta of params draws
-// (behind every other entry point, as the params calls above: the code of the existing kernels stays as it was)
 int eftb_draws_logp_grad_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
                                 double* grad, double* fullchi2, double* best) {
     static const char* who = "eftb_draws_logp_grad_params";
     if (e) sub_drain(e);
     if (!e || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
     if (!grad) return fail("%s: grad == NULL (eftb_draws_logp_params is the call without the gradient)", who);
-    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
-    long long maxcnt = 0;
-    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
-    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
-        return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
-                    e->cur_nx);
-    const eftb_config& c = e->c;
-    const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1;
-    if (int rc = draws_params_check(e, who, 0, ng1, C, N, theta, f)) return rc;
-    const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int J1 = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1, P = rcp.P;
-    if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
-    const int nnzp = (rcp.nnz + 1) & ~1;
-    const size_t lds_w = ((size_t)J1 * J1 + RECIPE_MAXTR * RECIPE_FPOW + nnzp) * sizeof(double);  // W_c, fp, col and erow
-    const size_t lds_wave = (34 + (size_t)nnzp + (size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double);
-    int nw = 4;  // waves per workgroup: as many as the LDS holds beside W_c
-    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
-    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
-    if (N == 0) return 0;
-    HIPCHK(hipSetDevice(c.device));
-    hipStream_t st = e->stream;
-    join_back(e);
-    if (!e->drwg_lds) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        e->drwg_lds = true;
-    }
-    if (int rc = draws_gram(e, who, C, J1)) return rc;
-    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
-    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
-    if (int rc = grow_dev(&e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
-    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    const double *dtheta = nullptr, *df = nullptr;
-    if (int rc = draws_params_upload(e, P, C, N, theta, f, &dtheta, &df)) return rc;
-    const dim3 grid(C, draw_shares(maxcnt, nw, C)), block(64 * nw);
-    const size_t lds = lds_w + nw * lds_wave;
-    const RecipeTab rt = recipe_tab(rcp);
-    RecipeGradTab gt{};
-    gt.dcoef = rcp.dcoef;
-    gt.pstart = rcp.dtab;
-    gt.dent = gt.pstart + P + 1;
-    gt.dpack = gt.dent + rcp.ndt;
-    gt.erow = gt.dpack + rcp.ndt;
-    while ((1 << gt.lgP2) < P) ++gt.lgP2;
-    if (J1 > 64)
-        hipLaunchKernelGGL(draws_logp_grad_params_kernel<true>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
-                           e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
-    else
-        hipLaunchKernelGGL(draws_logp_grad_params_kernel<false>, grid, block, lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
-                           e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
-    if (P) HIPCHK(hipMemcpyAsync(grad, e->drw_grad, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
-    return draws_records(e, N, logp, fullchi2, best);
+    return draws_logp_params_impl(e, who, C, N, offsets, theta, f, logp, grad, fullchi2, best);
 }
