@@ -1289,144 +1289,6 @@ __global__ __launch_bounds__(256) void qf_kernel(int nq, const double* __restric
 // H folds the 192-point FFTLog of XpYp*C and the j_{2v} Bessel sum (tables.py).  Lanes along k, the s
 // range is split over blockIdx.y (partials summed by resum_sum_kernel when nchunk > 1).
 // ------------------------------------------------------------------------------------------------
-// One wave = 64 k values x one (output l, input l', a, half) block of Q x one slice of the s sum, where
-// half 0 = the X^(p+1) polynomials and half 1 = the Y X^p ones.  The NA x NIR coefficients of the block
-// stay in registers for the whole s loop and are applied by Horner, two s values at a time (2*NA
-// independent chains: v_fma_f64 has a 32-cycle dependent latency on gfx950), so the inner loop reads no
-// tables.  Partials go to part[w][chunk][l][21][k] (chunk = (l', half, slice); a = 0 fills rows 0-2, a = 1
-// rows 3-20) and are summed in a fixed order by resum_sum_kernel (deterministic, no atomics).
-template <int NL>
-__global__ __launch_bounds__(256, 2) void resum_kernel(int Nk, int Nklow, int schunk, const double* __restrict__ kk,
-                                                       const double* __restrict__ XY, const double* __restrict__ Q,
-                                                       const double* __restrict__ H, const double* __restrict__ C11,
-                                                       const double* __restrict__ Cct, const double* __restrict__ Cloopl,
-                                                       const double* __restrict__ l11, const double* __restrict__ lct,
-                                                       double* __restrict__ part, int nsplit) {
-    constexpr int NIR = (NL == 3) ? 16 : 8;
-    constexpr int NA = (NL == 3) ? 3 : 2;
-    constexpr int NN = 2 * NIR * NA;
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    const int half = blockIdx.y & 1, a = (blockIdx.y >> 1) & 1, l = blockIdx.y >> 2;
-    const int split = blockIdx.z % nsplit, lp = (blockIdx.z / nsplit) % NL, w = blockIdx.z / (nsplit * NL);
-    const bool live = (k < Nk) && (k >= Nklow);
-    const int kc = live ? k : Nklow;
-    const double k2 = kk[kc] * kk[kc];
-    double q[NA][NIR];
-    {
-        // wave-uniform values that must live in VGPRs (NA*NIR of them, beyond the SGPR file): an opaque zero
-        // keeps hipcc from turning these into scalar loads + SGPR spills
-        int vzero;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
-        const double* qa = Q + (size_t)w * 2 * NL * NL * NN + ((size_t)(a * NL + l) * NL + lp) * NN + half * NIR * NA + vzero;
-#pragma unroll
-        for (int p = 0; p < NIR; ++p)
-#pragma unroll
-            for (int v = 0; v < NA; ++v) q[v][p] = qa[p * NA + v];
-    }
-    // selection rules make ~40 % of the Q polynomials identically zero (e.g. alpha = 4 never feeds l = l' = 0):
-    // skip those Bessel orders for the whole s loop (wave-uniform branch)
-    bool nz[NA];
-#pragma unroll
-    for (int v = 0; v < NA; ++v) {
-        bool any = false;
-#pragma unroll
-        for (int p = 0; p < NIR; ++p) any = any || (q[v][p] != 0.0);
-        nz[v] = __builtin_amdgcn_readfirstlane(any ? 1 : 0) != 0;
-    }
-    double acc[18];
-#pragma unroll
-    for (int i = 0; i < 18; ++i) acc[i] = 0.0;
-    // s-dependent, wave-uniform inputs of this (w, l') staged once in LDS: X, Y, C11|Cct, Cloopl[12]
-    __shared__ double sh[15 * NS];
-    for (int e = threadIdx.x; e < 15 * NS; e += 256) {
-        const int s = e % NS, c = e / NS;
-        double v;
-        if (c < 2) v = XY[(size_t)w * 2 * NS + c * NS + s];
-        else if (c == 2) v = (a == 0 ? C11 : Cct)[((size_t)w * NL + lp) * NS + s];
-        else v = Cloopl[(((size_t)w * NL + lp) * 12 + (c - 3)) * NS + s];
-        sh[e] = v;
-    }
-    __syncthreads();
-    const int s0 = split * schunk, s1 = min(NS, s0 + schunk);
-    // the H columns of the next s pair are fetched under the current pair's Horner chains (global latency ~1 us)
-    double hnA[NA], hnB[NA];
-    {
-        const int sb0 = (s0 + 1 < s1) ? s0 + 1 : s0;
-#pragma unroll
-        for (int v = 0; v < NA; ++v) {
-            hnA[v] = H[((size_t)v * NS + s0) * Nk + kc];
-            hnB[v] = H[((size_t)v * NS + sb0) * Nk + kc];
-        }
-    }
-    for (int s = s0; s < s1; s += 2) {
-        const int sb = (s + 1 < s1) ? s + 1 : s;        // second lane of the pair (weight 0 if past the end)
-        const double wb = (s + 1 < s1) ? 1.0 : 0.0;
-        double hA[NA], hB[NA];
-#pragma unroll
-        for (int v = 0; v < NA; ++v) {
-            hA[v] = hnA[v];
-            hB[v] = hnB[v];
-        }
-        {
-            const int sn = (s + 2 < s1) ? s + 2 : s, snb = (s + 3 < s1) ? s + 3 : sn;
-#pragma unroll
-            for (int v = 0; v < NA; ++v) {
-                hnA[v] = H[((size_t)v * NS + sn) * Nk + kc];
-                hnB[v] = H[((size_t)v * NS + snb) * Nk + kc];
-            }
-        }
-        const double zA = k2 * sh[s], zB = k2 * sh[sb];
-        const double fA = half ? k2 * sh[NS + s] : zA, fB = (half ? k2 * sh[NS + sb] : zB) * wb;
-        double pA[NA], pB[NA];
-#pragma unroll
-        for (int v = 0; v < NA; ++v) {
-            pA[v] = pB[v] = 0.0;
-            if (nz[v]) {
-                // four interleaved Horner chains (even / odd powers of the two s values): v_fma_f64 latency is 32 cycles
-                const double zA2 = zA * zA, zB2 = zB * zB;
-                double eA = q[v][NIR - 2], oA = q[v][NIR - 1], eB = eA, oB = oA;
-#pragma unroll
-                for (int p = NIR - 4; p >= 0; p -= 2) {
-                    eA = fma(eA, zA2, q[v][p]);
-                    oA = fma(oA, zA2, q[v][p + 1]);
-                    eB = fma(eB, zB2, q[v][p]);
-                    oB = fma(oB, zB2, q[v][p + 1]);
-                }
-                pA[v] = fma(oA, zA, eA);
-                pB[v] = fma(oB, zB, eB);
-            }
-        }
-        double wA = 0.0, wB = 0.0;
-#pragma unroll
-        for (int v = 0; v < NA; ++v) {
-            wA = fma(hA[v], pA[v], wA);
-            wB = fma(hB[v], pB[v], wB);
-        }
-        wA *= fA;
-        wB *= fB;
-        const double cA = wA * sh[2 * NS + s], cB = wB * sh[2 * NS + sb];
-        if (a == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) acc[i] = fma(l11[lp * 3 + i], cA + cB, acc[i]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) acc[i] = fma(lct[lp * 6 + i], cA + cB, acc[i]);
-#pragma unroll
-            for (int i = 0; i < 12; ++i) acc[6 + i] = fma(wA, sh[(3 + i) * NS + s], fma(wB, sh[(3 + i) * NS + sb], acc[6 + i]));
-        }
-    }
-    if (k >= Nk) return;
-    const int nchunk = 2 * NL * nsplit, chunk = (lp * 2 + half) + 2 * NL * split;
-    double* dst = part + ((((size_t)w * nchunk + chunk) * NL + l) * 21) * Nk + k;
-    if (a == 0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) dst[(size_t)i * Nk] = live ? acc[i] : 0.0;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 18; ++i) dst[(size_t)(3 + i) * Nk] = live ? acc[i] : 0.0;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // IR-resummation on the FP64 matrix cores (Nl = 3; tables.py resum_mfma_tables).
 // All 108 polynomials  sum_p Q_a[l,l',(half,p,v)](f) z^p  of one cosmology lie in a fixed 8-dimensional space, so with
@@ -2234,7 +2096,7 @@ __global__ __launch_bounds__(320) void ap_prefix_kernel(int nmu, const double* _
 // ap_direct_kernel: the stage in the reference's own form (pybird.py:1581-1621) -- per (k, row) the nmu nodes are walked in order, the
 // spline is evaluated at k'(mu_j) in the interval the comparison k_i <= k' < k_i+1 selects (end intervals extrapolate), weighted with
 // L_l'(mu'_j) and projected on (2l+1)/2 L_l(mu_j) with the trapezoid weights.  It is the FALLBACK of the two-kernel form below for tiles
-// whose distortion crosses more knot intervals than the fast path keeps (META flag), and the whole stage with EFTB_AP_FAST=0: small
+// whose distortion crosses more knot intervals than the fast path keeps (META flag), and the whole stage with EFTB_AP_MODE=2: small
 // (no LDS, few registers), so that its launch never waits for resources when every workgroup just reads its flag and leaves.
 // Workgroup = one wave = 64 k of one cosmology, the thread walks the template rows one after the other (a light launch: 1 024 waves at
 // Nk = 512, B = 128 -- the gate must not wait for resources beside the resummation kernel); rows >= nr (Pstl unless APst) are copied through.
@@ -3257,11 +3119,6 @@ __global__ __launch_bounds__(256) void copy16_kernel(const double* __restrict__ 
     double2* d2 = reinterpret_cast<double2*>(dst);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) d2[i] = s2[i];
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) dst[n - 1] = src[n - 1];
-}
-
-// device-to-device snapshot as a kernel, for the same reason (P_l of a step, taken before the RCCL exchange on the communication stream)
-__global__ __launch_bounds__(256) void copy_kernel(const double* __restrict__ src, double* __restrict__ dst, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 // ------------------------------------------------------------------------------------------------

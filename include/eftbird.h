@@ -400,8 +400,7 @@ void  eftb_host_free(void* p);
 int  eftb_comm_unique_id(char id[128]);
 int  eftb_comm_init(eftb_engine* e, int nranks, int rank, const char id[128]);
 /* Gather EFTB_B_PLK rows [0, B) of every rank into root's device buffer (rank-major), in line behind the kernel that
- * wrote them (on the back-half stream of an overlapped run, else on the compute stream; EFTB_GATHER_ASYNC=1 moves it to a
- * communication stream instead);
+ * wrote them (on the back-half stream of an overlapped run, else on the compute stream);
  * if host_out != NULL (root only) the gathered block [nranks][B][Nl][Nx] is copied out after the gather. */
 int  eftb_gather_plk(eftb_engine* e, int B, int root, double* host_out);
 /* Pipelined multi-GPU steps (eftb_stage_inputs / eftb_run_staged / eftb_gather_plk per step, nothing waits for the step in flight): on the

@@ -66,12 +66,12 @@ def test_dropin_sequence(golden, case):
     assert hit >= 3
 
 
-def _batch_engine(B):
+def _batch_engine(B, NFFT=512):
     from eftpipe_amd.engine import Engine
     from eftpipe_amd.tables import EngineConfig
 
     z = 0.7
-    cfg = EngineConfig(Nl=3, NFFT=512, kin=np.logspace(-4, 0, 200), with_resum=True, with_ap=True,
+    cfg = EngineConfig(Nl=3, NFFT=NFFT, kin=np.logspace(-4, 0, 200), with_resum=True, with_ap=True,
                        DA_AP=float(synth.da_func(synth.OM_AP, z)), H_AP=float(synth.hubble(synth.OM_AP, z)))
     return Engine(cfg, max_batch=B)
 
@@ -98,6 +98,23 @@ def test_eval_batch_nfft512_low_k_grid(golden):
     plk_d = eng.eval_batch(Pin, f, DA, H, bias=bias, templates=False)
     for i in range(B):
         assert relerr(plk_d[i], g["batch_plk"][idx[i]]) < TOL, i
+    eng.close()
+
+
+def test_direct_plk_matches_template_path_nfft384(golden):
+    """Direct P_l at NFFT = 384, the size between the compiled-in 256 and the tested 512: nh = 192 gives the row builders a ragged last block
+    of lanes (385 harmonics in 7 blocks of 64), and B = 3 leaves 61 of the 64 lanes of the anti-diagonal pass's cosmology group on the
+    clamped index.  Held to the engine's own template path at the bar of test_gpu_direct (another order of summation: 1e-9)."""
+    g = golden("fftlog")
+    B = 3
+    eng = _batch_engine(B, NFFT=384)
+    _, Pin, f, DA, H, bias = _batch_inputs(g, B)
+    _, plk = eng.eval_batch(Pin, f, DA, H, bias=bias)
+    eng.set_plk_direct(True)
+    plk_d = eng.eval_batch(Pin, f, DA, H, bias=bias, templates=False)
+    print("NFFT 384 direct vs templates-first P_l: relerr %.3e" % relerr(plk_d, plk))
+    assert np.isfinite(plk_d).all()
+    assert relerr(plk_d, plk) < 1e-9
     eng.close()
 
 
