@@ -3409,8 +3409,10 @@ __device__ __forceinline__ double draw_coef(const double* Rd, const double* Rn, 
 // -> ok (det F2 > 0), wave-uniform
 constexpr int ADJ_KB = 4;
 
-template <bool ADJ>
-__device__ __forceinline__ bool draws_solve(int lane, int nG, int jeffreys, double* Gs, const double* mu, const double* sinv, double* o) {
+// With HESS (the Hessian kernel; needs ADJ), F2^-1 is taken under Jeffreys too and also written to Ks [nG][nG] (row: the place, as S).
+template <bool ADJ, bool HESS = false>
+__device__ __forceinline__ bool draws_solve(int lane, int nG, int jeffreys, double* Gs, const double* mu, const double* sinv, double* o,
+                                            double* Ks = nullptr) {
     const int ng1 = nG + 1;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     // ---- F2 | F1 per lane (row i = lane), LU with partial pivoting
@@ -3515,7 +3517,7 @@ __device__ __forceinline__ bool draws_solve(int lane, int nG, int jeffreys, doub
             for (int k = 0; k < MARG_MAXG; ++k)
                 if (k < nG) srw[1 + k] = own ? bp * b[k] : b[k];
         }
-        if (!jeffreys) {
+        if (HESS || !jeffreys) {
             double rdp[MARG_MAXG];
 #pragma unroll
             for (int c2 = 0; c2 < MARG_MAXG; ++c2) rdp[c2] = c2 < nG ? 1.0 / dpv[c2] : 0.0;
@@ -3546,7 +3548,10 @@ __device__ __forceinline__ bool draws_solve(int lane, int nG, int jeffreys, doub
                     }
 #pragma unroll
                 for (int q = 0; q < ADJ_KB; ++q)
-                    if (own && k0 + q < nG) srw[1 + k0 + q] += y[q];
+                    if (own && k0 + q < nG) {
+                        if (!HESS || !jeffreys) srw[1 + k0 + q] += y[q];
+                        if constexpr (HESS) Ks[pos * nG + k0 + q] = y[q];
+                    }
             }
         }
     }
@@ -4006,6 +4011,203 @@ __global__ __launch_bounds__(256) void draws_logp_grad_params_kernel(int ntr, in
             if (lane < P) grad[(size_t)d * P + lane] = ok ? -0.5 * acc : nan;
         }
         wave_lds_sync();  // (the next draw overwrites th, val, H and G)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// d2 ln P / d theta d theta of a params draw (eftb_draws_logp_hess_params).  With K = F2^-1, D_p = d R^ / d theta_p (the derivative records
+// of p: value dval, row g, column c), G_p = D_p H^T + H D_p^T and u_p = (G_p v)[1:]:
+//     d2 chi2 / d theta_p d theta_q = sum_n Rbar[n] d2 val_n / d theta_p d theta_q                                (t1: the second-derivative records)
+//                                   + sum_{n of p, m of q} dval_n dval_m (S + S^T)[g_n][g_m] W_c[c_n][c_m]        (t2)
+//                                   - 2 u_p^T K u_q  -  [not Jeffreys] sum_ij M_p[i][j] M_q[j][i],  M_p = K G_p[1:,1:]   (t3, t4)
+// and d2 ln P = -1/2 of that.  The second-derivative table of eftb_set_draw_recipe (kind 0), one record per (term, pair p <= q of theta
+// indices in it), sorted by (p, q, entry, parent term):
+//   htab = hstart [P (P + 1) / 2 + 1] (first record of pair (p, q), pairs in row order of the upper triangle) | hent [nh] | hpack [nh]
+//   hpack = i | (tau * 7 + e) << 18: the one remaining theta index (the factor 1 at index P); hcoef = coef * multiplicity
+// ------------------------------------------------------------------------------------------------
+struct RecipeHessTab {
+    const double* hcoef;  // [nh]
+    const int *hstart, *hent, *hpack;
+    int ndt, npair, lgPP;  // derivative records; pairs; log2 of the smallest power of two >= min(npair, 64): lane = share << lgPP | pair
+};
+
+// draws_logp_grad_params_kernel with the Hessian: the same forward pass, solve (draws_solve<true, true>: K also under Jeffreys, kept beside
+// S), Rbar and gradient sums, so the record and the gradient are the gradient call's bits.  Then per draw
+//   dval[t], hv    lanes over the derivative records: their values; lanes over the columns: hv = H^T v
+//   u_p, G_p       lanes over (p, i) and (p, i, j): the records of p in table order against H and hv
+//   w_q, M_p       lanes over (q, i) and (p, i, j): K u_q and K G_p[1:,1:]
+//   hess[p][q]     lane = share << lgPP | pair (64 pairs at a time): share s takes every (64 >> lgPP)-th second-derivative record (t1),
+//                  derivative record of p (t2, against every record of q), i (t3) and (i, j) (t4) of its pair; the shares are added by
+//                  an xor butterfly over the share bits.  Assignment and tree depend on the recipe alone.
+// Entry (q, p) is a copy of (p, q).  A draw with det F2 <= 0 gets NaN in all P^2 slots, as in grad and ln P.  Every loop is bounded by a
+// table size.  LDS: as the gradient kernel, then drow | dcol [ndt] (ints: row and column of every derivative record) per workgroup and
+// K [nG][nG], dval [ndt], hv [J1], u [P][nG], w [P][nG] and, unless Jeffreys, G_p and M_p [P][nG][nG] per wave.
+template <bool TWO>
+__global__ __launch_bounds__(256) void draws_logp_hess_params_kernel(int ntr, int nG, int J1, int jeffreys, RecipeTab rt, RecipeGradTab gt, RecipeHessTab ht,
+                                                                     const long long* __restrict__ offsets, const double* __restrict__ theta,
+                                                                     const double* __restrict__ f, const double* __restrict__ W,
+                                                                     const double* __restrict__ mu, const double* __restrict__ sinv,
+                                                                     double* __restrict__ out, double* __restrict__ grad, double* __restrict__ hess) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1, P = rt.P, ndt = ht.ndt, ndtp = (ndt + 1) & ~1, nG2 = nG * nG;
+    const long long d0 = offsets[c], d1 = offsets[c + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
+    double* Ws = sm;
+    double* fp = Ws + J1 * J1;
+    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
+    int* erow = col + nnzp;
+    int* drow = erow + nnzp;
+    int* dcol = drow + ndtp;
+    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
+    for (int n = threadIdx.x; n < nnz; n += blockDim.x) {
+        col[n] = recipe_col(rt.ent[n], ntr);
+        erow[n] = gt.erow[n];
+    }
+    for (int t = threadIdx.x; t < ndt; t += blockDim.x) {
+        const int n = gt.dent[t];
+        drow[t] = gt.erow[n];
+        dcol[t] = recipe_col(rt.ent[n], ntr);
+    }
+    recipe_fpow(f, c, ntr, threadIdx.x, fp);
+    __syncthreads();
+    const int gpn = jeffreys ? 0 : P * nG2;
+    double* th = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp + ndtp + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1 + nG2 + ndtp + J1 + 2 * P * nG + 2 * gpn);
+    double* val = th + 34;
+    double* Hs = val + nnzp;
+    double* Gs = Hs + ng1 * J1;
+    double* Ks = Gs + ng1 * ng1;
+    double* dval = Ks + nG2;
+    double* hv = dval + ndtp;
+    double* us = hv + J1;
+    double* ws = us + P * nG;
+    double* Gp = ws + P * nG;
+    double* Mp = Gp + gpn;
+    const int pmask = (1 << gt.lgP2) - 1, gp = lane & pmask, share = lane >> gt.lgP2, nshare = 64 >> gt.lgP2;
+    const int qmask = (1 << ht.lgPP) - 1, hshare = lane >> ht.lgPP, nhshare = 64 >> ht.lgPP;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        draws_recipe_forward<TWO>(rt, theta, d, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+        const bool ok = draws_solve<true, true>(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT, Ks);
+        wave_lds_sync();
+        // ---- Rbar at the non-zeros, over val; the values of the derivative records; hv = H^T v (v[g] = S[g][0])
+        for (int n = lane; n < nnz; n += 64) {
+            const int g = erow[n];
+            const double* hc = Hs + col[n];
+            double acc = 0.0;
+            for (int h = 0; h < ng1; ++h) acc = fma(Gs[g * ng1 + h] + Gs[h * ng1 + g], hc[h * J1], acc);
+            val[n] = acc;
+        }
+        for (int t = lane; t < ndt; t += 64) {
+            const int q = gt.dpack[t];
+            dval[t] = gt.dcoef[t] * fp[q >> 18] * th[q & 63] * th[(q >> 6) & 63];
+        }
+        for (int j = lane; j < J1; j += 64) {
+            double acc = 0.0;
+            for (int g = 0; g < ng1; ++g) acc = fma(Gs[g * ng1], Hs[g * J1 + j], acc);
+            hv[j] = acc;
+        }
+        wave_lds_sync();
+        // ---- the P sums over the derivative table (as the gradient kernel)
+        {
+            double acc = 0.0;
+            if (gp < P) {
+                const int t1 = gt.pstart[gp + 1];
+                for (int t = gt.pstart[gp] + share; t < t1; t += nshare) {
+                    const int q = gt.dpack[t];
+                    acc = fma(gt.dcoef[t] * fp[q >> 18] * th[q & 63] * th[(q >> 6) & 63], val[gt.dent[t]], acc);
+                }
+            }
+            for (int m = 32; m > pmask; m >>= 1) acc += __shfl_xor(acc, m);
+            if (lane < P) grad[(size_t)d * P + lane] = ok ? -0.5 * acc : nan;
+        }
+        // ---- u_p and G_p[1:,1:] from the records of p in table order
+        for (int e = lane; e < P * nG; e += 64) {
+            const int p = e / nG, g = e % nG + 1;
+            const double* hg = Hs + g * J1;
+            double acc = 0.0;
+            const int t1 = gt.pstart[p + 1];
+            for (int t = gt.pstart[p]; t < t1; ++t) {
+                const int gt_ = drow[t], ct = dcol[t];
+                acc = fma(dval[t], fma(Gs[gt_ * ng1], hg[ct], gt_ == g ? hv[ct] : 0.0), acc);
+            }
+            us[e] = acc;
+        }
+        for (int e = lane; e < gpn; e += 64) {
+            const int p = e / nG2, r = e % nG2, i = r / nG + 1, j = r % nG + 1;
+            const double *hi = Hs + i * J1, *hj = Hs + j * J1;
+            double acc = 0.0;
+            const int t1 = gt.pstart[p + 1];
+            for (int t = gt.pstart[p]; t < t1; ++t) {
+                const int gt_ = drow[t], ct = dcol[t];
+                acc = fma(dval[t], (gt_ == i ? hj[ct] : 0.0) + (gt_ == j ? hi[ct] : 0.0), acc);
+            }
+            Gp[e] = acc;
+        }
+        wave_lds_sync();
+        // ---- w_q = K u_q and M_p = K G_p[1:,1:]
+        for (int e = lane; e < P * nG; e += 64) {
+            const int q = e / nG, i = e % nG;
+            double acc = 0.0;
+            for (int k = 0; k < nG; ++k) acc = fma(Ks[i * nG + k], us[q * nG + k], acc);
+            ws[e] = acc;
+        }
+        for (int e = lane; e < gpn; e += 64) {
+            const int p = e / nG2, r = e % nG2, i = r / nG, j = r % nG;
+            const double* gpp = Gp + p * nG2 + j;
+            double acc = 0.0;
+            for (int k = 0; k < nG; ++k) acc = fma(Ks[i * nG + k], gpp[k * nG], acc);
+            Mp[e] = acc;
+        }
+        wave_lds_sync();
+        // ---- the P (P + 1) / 2 sums, 64 >> lgPP shares per pair
+        for (int base = 0; base < ht.npair; base += 64) {
+            const int pair = base + (lane & qmask);
+            double acc = 0.0;
+            int p = 0, q = 0;
+            if (pair < ht.npair) {
+                int r = pair;
+                while (p < P && r >= P - p) {  // (at most P steps)
+                    r -= P - p;
+                    ++p;
+                }
+                q = p + r;
+                // t1
+                const int h1 = ht.hstart[pair + 1];
+                for (int t = ht.hstart[pair] + hshare; t < h1; t += nhshare) {
+                    const int k = ht.hpack[t];
+                    acc = fma(ht.hcoef[t] * fp[k >> 18] * th[k & 63], val[ht.hent[t]], acc);
+                }
+                // t2
+                const int n1 = gt.pstart[p + 1], m0 = gt.pstart[q], m1 = gt.pstart[q + 1];
+                for (int n = gt.pstart[p] + hshare; n < n1; n += nhshare) {
+                    const int gn = drow[n];
+                    const double* wn = Ws + dcol[n] * J1;
+                    double s = 0.0;
+                    for (int m = m0; m < m1; ++m) {
+                        const int gm = drow[m];
+                        s = fma(dval[m] * (Gs[gn * ng1 + gm] + Gs[gm * ng1 + gn]), wn[dcol[m]], s);
+                    }
+                    acc = fma(dval[n], s, acc);
+                }
+                // t3
+                for (int i = hshare; i < nG; i += nhshare) acc = fma(-2.0 * us[p * nG + i], ws[q * nG + i], acc);
+                // t4
+                if (!jeffreys)
+                    for (int r2 = hshare; r2 < nG2; r2 += nhshare) {
+                        const int i = r2 / nG, j = r2 % nG;
+                        acc = fma(-Mp[p * nG2 + i * nG + j], Mp[q * nG2 + j * nG + i], acc);
+                    }
+            }
+            for (int m = 32; m > qmask; m >>= 1) acc += __shfl_xor(acc, m);
+            if (hshare == 0 && pair < ht.npair) {
+                const double hv2 = ok ? -0.5 * acc : nan;
+                hess[((size_t)d * P + p) * P + q] = hv2;
+                hess[((size_t)d * P + q) * P + p] = hv2;
+            }
+        }
+        wave_lds_sync();  // (the next draw overwrites th, val, H, G and the Hessian's scratch)
     }
 }
 

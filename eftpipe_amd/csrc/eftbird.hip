@@ -154,11 +154,18 @@ struct eftb_engine {
         int ndt = 0;
         double* dcoef = nullptr;
         int* dtab = nullptr;
+        // the second derivative of the terms (kind 0; eftb_draws_logp_hess_params): hcoef [nh], htab = hstart | hent | hpack (RecipeHessTab)
+        int nh = 0;
+        double* hcoef = nullptr;
+        int* htab = nullptr;
     } recipe[2];
     double* drw_theta = nullptr;    // theta [N][P] then f [C][ntr] of a params call
     size_t drw_theta_cap = 0;
     double* drw_grad = nullptr;     // eftb_draws_logp_grad_params: d ln P / d theta [N][P]
     size_t drw_grad_cap = 0;
+    double* drw_hess = nullptr;     // eftb_draws_logp_hess_params: d2 ln P / d theta d theta [N][P][P]
+    size_t drw_hess_cap = 0;
+    bool drw_lds_hess = false;      // the draws_logp_hess_params_kernel instantiations opted in to the large dynamic LDS
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -1962,7 +1969,7 @@ void eftb_destroy(eftb_engine* e) {
     for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
     for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off, (void*)e->drw_theta,
                     (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab, (void*)e->recipe[0].dcoef,
-                    (void*)e->recipe[0].dtab, (void*)e->drw_grad}) if (p) (void)hipFree(p);
+                    (void*)e->recipe[0].dtab, (void*)e->drw_grad, (void*)e->recipe[0].hcoef, (void*)e->recipe[0].htab, (void*)e->drw_hess}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
@@ -3374,6 +3381,38 @@ int eftb_set_draw_recipe(eftb_engine* e, int kind, int P, int ng1, int nterms, c
         }
         pstart.push_back((int)dent.size());
     }
+    // the second derivative (kind 0): one record per (term, pair p <= q of theta indices in it) with the coefficient times m_p m_q (p < q)
+    // or m_p (m_p - 1) (p = q) and the one remaining index; pairs outermost, the terms in their order: sorted by (p, q, entry, parent term)
+    std::vector<int> hstart, hent, hpack;
+    std::vector<double> hcoef;
+    if (kind == 0) {
+        for (int p = 0; p < P; ++p)
+            for (int q = p; q < P; ++q) {
+                hstart.push_back((int)hent.size());
+                for (int t = 0, n = -1; t < nterms; ++t) {
+                    if (n + 1 < nnz && tstart[n + 1] == t) ++n;
+                    const Key& k = keys[t];
+                    int mp = 0, mq = 0, rest = -1, takep = 1, takeq = 1;
+                    for (int x = 0; x < 3; ++x) {
+                        mp += k.ix[x] == p;
+                        mq += k.ix[x] == q;
+                    }
+                    const int mult = p == q ? mp * (mp - 1) : mp * mq;
+                    if (!mult) continue;
+                    for (int x = 0; x < 3; ++x) {  // (one factor theta_p and one theta_q are differentiated; what is left is at most one index)
+                        if (k.ix[x] == p && takep) { takep = 0; continue; }
+                        if (k.ix[x] == q && takeq) { takeq = 0; continue; }
+                        rest = k.ix[x];
+                    }
+                    hent.push_back(n);
+                    hpack.push_back((rest < 0 ? P : rest) | (k.tracer * RECIPE_FPOW + k.fpow) << 18);
+                    hcoef.push_back(k.coef * mult);
+                }
+            }
+        hstart.push_back((int)hent.size());
+    }
+    std::vector<int> htab;
+    for (const std::vector<int>* v : {&hstart, &hent, &hpack}) htab.insert(htab.end(), v->begin(), v->end());
     std::vector<int> dtab;
     for (const std::vector<int>* v : {&pstart, &dent, &dpack, &erow}) dtab.insert(dtab.end(), v->begin(), v->end());
     std::vector<int> tab;
@@ -3381,11 +3420,13 @@ int eftb_set_draw_recipe(eftb_engine* e, int kind, int P, int ng1, int nterms, c
     HIPCHK(hipSetDevice(e->c.device));
     HIPCHK(sync_all(e));  // (a params call is synchronous: nothing reads the old tables any more; as eftb_set_likelihood)
     rc.set = false;
-    for (void* p : {(void*)rc.coef, (void*)rc.tab, (void*)rc.dcoef, (void*)rc.dtab}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)rc.coef, (void*)rc.tab, (void*)rc.dcoef, (void*)rc.dtab, (void*)rc.hcoef, (void*)rc.htab}) if (p) (void)hipFree(p);
     rc.coef = nullptr;
     rc.tab = nullptr;
     rc.dcoef = nullptr;
     rc.dtab = nullptr;
+    rc.hcoef = nullptr;
+    rc.htab = nullptr;
     HIPCHK(hipMalloc(&rc.coef, coef.size() * sizeof(double)));
     HIPCHK(hipMalloc(&rc.tab, tab.size() * sizeof(int)));
     HIPCHK(hipMemcpy(rc.coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -3395,8 +3436,13 @@ int eftb_set_draw_recipe(eftb_engine* e, int kind, int P, int ng1, int nterms, c
         HIPCHK(hipMalloc(&rc.dtab, dtab.size() * sizeof(int)));
         if (!dcoef.empty()) HIPCHK(hipMemcpy(rc.dcoef, dcoef.data(), dcoef.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(rc.dtab, dtab.data(), dtab.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&rc.hcoef, std::max<size_t>(1, hcoef.size()) * sizeof(double)));
+        HIPCHK(hipMalloc(&rc.htab, htab.size() * sizeof(int)));
+        if (!hcoef.empty()) HIPCHK(hipMemcpy(rc.hcoef, hcoef.data(), hcoef.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(rc.htab, htab.data(), htab.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     rc.ndt = (int)dcoef.size();
+    rc.nh = (int)hcoef.size();
     rc.P = P; rc.ng1 = ng1; rc.nterms = nterms; rc.nnz = nnz; rc.nnlo = nnlo; rc.ntr_used = ntr;
     rc.set = true;
     return 0;
@@ -3440,9 +3486,10 @@ static int draws_params_upload(eftb_engine* e, int P, int C, long long N, const 
     return 0;
 }
 
-// eftb_draws_logp_params (grad == nullptr: the forward kernel and its LDS layout) and eftb_draws_logp_grad_params
+// eftb_draws_logp_params (grad == nullptr: the forward kernel and its LDS layout), eftb_draws_logp_grad_params and eftb_draws_logp_hess_params
+// (hess != nullptr, with grad: the Hessian kernel and its LDS layout)
 static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, const double* theta, const double* f,
-                                  double* logp, double* grad, double* fullchi2, double* best) {
+                                  double* logp, double* grad, double* fullchi2, double* best, double* hess = nullptr) {
     long long maxcnt = 0;
     if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt)) return rc;
     const int ntr = e->ntr, nG = e->like_nG;
@@ -3452,10 +3499,30 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
     DrawShape sh;  // beside W_c: fp, col [nnzp] and, with the gradient, erow [nnzp]; per wave: th [34] and val [nnzp]
     if (int rc = draws_logp_shape(e, who, RECIPE_MAXTR * RECIPE_FPOW * sizeof(double) + (grad ? 2 : 1) * nnzp * sizeof(int), (34 + (size_t)nnzp) * sizeof(double), &sh))
         return rc;
+    const int ndtp = (rcp.ndt + 1) & ~1;
+    if (hess) {  // beside the gradient's: drow and dcol [ndtp] per workgroup; K, dval, hv, u, w and, unless Jeffreys, G_p and M_p per wave
+        const size_t n = (size_t)nG, J1 = (size_t)sh.J1, ng1 = n + 1;
+        const size_t lds_w = (J1 * J1 + RECIPE_MAXTR * RECIPE_FPOW + nnzp + ndtp) * sizeof(double);
+        const size_t lds_wave = (34 + nnzp + ng1 * J1 + ng1 * ng1 + n * n + ndtp + J1 + 2 * P * n + (e->jeffreys ? 0 : 2 * P * n * n)) * sizeof(double);
+        int nw = 4;
+        while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
+        if (lds_w + nw * lds_wave > 160 * 1024)
+            return fail("%s: the Hessian of P = %d parameters with nG = %d and J + 1 = %d columns does not fit the LDS (%zu bytes per workgroup and %zu per wave)",
+                        who, P, nG, sh.J1, lds_w, lds_wave);
+        sh.nw = nw;
+        sh.lds = lds_w + nw * lds_wave;
+    }
     if (N == 0) return 0;
     if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets)) return rc;
+    if (hess && !e->drw_lds_hess) {
+        for (const void* k : {reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<true>)})
+            HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->drw_lds_hess = true;
+    }
     if (grad)
         if (int rc = grow_dev(&e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
+    if (hess)
+        if (int rc = grow_dev(&e->drw_hess, &e->drw_hess_cap, std::max<size_t>(1, (size_t)N * P * P))) return rc;
     const double *dtheta = nullptr, *df = nullptr;
     if (int rc = draws_params_upload(e, P, C, N, theta, f, &dtheta, &df)) return rc;
     hipStream_t st = e->stream;
@@ -3470,7 +3537,22 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
         gt.dpack = gt.dent + rcp.ndt;
         gt.erow = gt.dpack + rcp.ndt;
         while ((1 << gt.lgP2) < P) ++gt.lgP2;
-        if (J1 > 64)
+        if (hess) {
+            RecipeHessTab ht{};
+            ht.npair = P * (P + 1) / 2;
+            ht.ndt = rcp.ndt;
+            ht.hcoef = rcp.hcoef;
+            ht.hstart = rcp.htab;
+            ht.hent = ht.hstart + ht.npair + 1;
+            ht.hpack = ht.hent + rcp.nh;
+            while ((1 << ht.lgPP) < std::min(ht.npair, 64)) ++ht.lgPP;
+            if (J1 > 64)
+                hipLaunchKernelGGL(draws_logp_hess_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, e->drw_W,
+                                   e->like_mu, e->like_sinv, e->drw_out, e->drw_grad, e->drw_hess);
+            else
+                hipLaunchKernelGGL(draws_logp_hess_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, e->drw_W,
+                                   e->like_mu, e->like_sinv, e->drw_out, e->drw_grad, e->drw_hess);
+        } else if (J1 > 64)
             hipLaunchKernelGGL(draws_logp_grad_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
                                e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
         else
@@ -3485,6 +3567,7 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
     if (grad && P) HIPCHK(hipMemcpyAsync(grad, e->drw_grad, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (hess && P) HIPCHK(hipMemcpyAsync(hess, e->drw_hess, (size_t)N * P * P * sizeof(double), hipMemcpyDeviceToHost, st));
     return draws_records(e, N, logp, fullchi2, best);
 }
 
@@ -3540,4 +3623,15 @@ int eftb_draws_logp_grad_params(eftb_engine* e, int C, long long N, const int64_
     if (!e || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
     if (!grad) return fail("%s: grad == NULL (eftb_draws_logp_params is the call without the gradient)", who);
     return draws_logp_params_impl(e, who, C, N, offsets, theta, f, logp, grad, fullchi2, best);
+}
+
+// ------------------------------------------------------------------------------------------------ d2 ln P / d theta d theta of params draws
+int eftb_draws_logp_hess_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
+                                double* grad, double* hess, double* fullchi2, double* best) {
+    static const char* who = "eftb_draws_logp_hess_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
+    if (!grad) return fail("%s: grad == NULL (the Hessian call returns the gradient too)", who);
+    if (!hess) return fail("%s: hess == NULL (eftb_draws_logp_grad_params is the call without the Hessian)", who);
+    return draws_logp_params_impl(e, who, C, N, offsets, theta, f, logp, grad, fullchi2, best, hess);
 }

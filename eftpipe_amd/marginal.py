@@ -193,17 +193,27 @@ class MarginalLikelihood:
 
         self._recipe = _set_recipe(self.eng, L.RECIPE_LOGP, recipe, self.nG + 1)
 
-    def logp_draws_params(self, theta, offsets, f, return_best=False, grad=False):
+    def logp_draws_params(self, theta, offsets, f, return_best=False, grad=False, hess=False):
         """``logp_draws`` with the rows built on the device from parameter values (``eftb_draws_logp_params``): theta [N, P] in the order of
         the recipe's ``param_names``, f [C, ntr] ([C] with one tracer) the growth rate of each walker's entries -> ln P_marg [N] (+ full
         chi2 [N] and best-fit Gaussian parameters [N, nG]).  8 P bytes per draw cross PCIe instead of the rows.  Raises like the
         reference when det F2 <= 0.
         grad=True (``eftb_draws_logp_grad_params``): d ln P_marg / d theta [N, P] in ``param_names`` order from an adjoint pass on the device
-        -> (logp, grad) or (logp, grad, full, best); ln P, full chi2 and the best fit are the bits of the call without it."""
+        -> (logp, grad) or (logp, grad, full, best); ln P, full chi2 and the best fit are the bits of the call without it.
+        grad=True, hess=True (``eftb_draws_logp_hess_params``): also d2 ln P_marg / d theta d theta [N, P, P], each draw's block equal to its
+        transpose bit for bit -> (logp, grad, hess) or (logp, grad, hess, full, best); ln P, the gradient, full chi2 and the best fit are
+        the gradient call's bits.  hess=True without grad raises ValueError."""
         from .engine import _params_args
 
+        if hess and not grad:
+            raise ValueError("hess=True needs grad=True: the Hessian call returns the gradient too")
         theta, off, f = _params_args(getattr(self, "_recipe", None), theta, offsets, f, self.eng.ntracers)
         N = theta.shape[0]
+        if hess:
+            logp, dlogp, d2logp, full, best = self._draws_hess_raw(theta, off, f)
+            if np.any(np.isnan(logp)):
+                raise RuntimeError("det of F2ij <= 0")
+            return (logp, dlogp, d2logp, full, best) if return_best else (logp, dlogp, d2logp)
         logp, full, best = np.empty(N), np.empty(N), np.empty((N, self.nG))
         if grad:
             dlogp = np.empty((N, theta.shape[1]))
@@ -217,6 +227,24 @@ class MarginalLikelihood:
         if grad:
             return (logp, dlogp, full, best) if return_best else (logp, dlogp)
         return (logp, full, best) if return_best else logp
+
+    def _draws_hess_raw(self, theta, off, f):
+        """``eftb_draws_logp_hess_params`` on checked arguments -> logp, grad, hess, full, best; NaN where det F2 <= 0, nothing raised for it"""
+        N, P = theta.shape
+        logp, full, best, dlogp, d2logp = np.empty(N), np.empty(N), np.empty((N, self.nG)), np.empty((N, P)), np.empty((N, P, P))
+        L.check(self.eng.lib.eftb_draws_logp_hess_params(self.eng._h, off.size - 1, N, off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f),
+                                                         L.dptr(logp), L.dptr(dlogp), L.dptr(d2logp), L.dptr(full), L.dptr(best)))
+        return logp, dlogp, d2logp, full, best
+
+    def maximize_draws_params(self, theta0, offsets, f, **kw):
+        """Best fits over the recipe's parameters at fixed cosmology: ``newton_maximize`` fed with the Hessian call, all starts of all
+        walkers at once (theta0 [N, P], offsets and f as ``logp_draws_params``; kw: max_iter, tol) -> theta, logp, grad, hess, n_iter,
+        converged.  A point whose ln P is NaN (det F2 <= 0) is not an error here: a trial there is rejected, a start there is left where it
+        is with converged False.  Priors and bounds on theta are the sampler's business, not this call's."""
+        from .engine import _params_args
+
+        theta0, off, f = _params_args(getattr(self, "_recipe", None), theta0, offsets, f, self.eng.ntracers)
+        return newton_maximize(lambda th: self._draws_hess_raw(np.ascontiguousarray(th), off, f)[:3], theta0, **kw)
 
     def eval_logp(self, Pin, f, DA, H, rows, return_best=False):
         """Theory + likelihood in one call (``eftb_eval_logp_batch``): Pin [B, Nkin], f/DA/H [B], rows [B, nG + 1, 24] ->
@@ -244,4 +272,68 @@ def _offsets(offsets):
     return off
 
 
-__all__ = ["MarginalLikelihood", "data_index", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]
+def newton_maximize(fun, theta0, max_iter=50, tol=1e-8):
+    """Maximise ln P from M starting points at once by a Levenberg-damped Newton ascent, in NumPy.
+
+    fun(theta [M, P]) -> (logp [M], grad [M, P], hess [M, P, P]).  It is always called with all M points, the frozen ones at their
+    place and their results unused, so a device call with fixed walker offsets can stand behind it.
+    -> theta [M, P], logp [M], grad [M, P], hess [M, P, P], n_iter [M], converged [M]; n_iter counts the trial steps of a point, each
+    one evaluation of fun.
+
+    Per point and iteration (-H + lam I) delta = g is solved; lam starts at its floor 0, the pure Newton step.
+    - The trial theta + delta is accepted where ln P rises; lam then falls by 10, to 0 once below lam0 / 10.
+    - Elsewhere (ln P not higher, or ln P or a derivative NaN at the trial) the point stays and lam grows by 10, from 0 to lam0.
+      lam0 is three times the smallest |eigenvalue| of -H: the first damped step is a quarter of the Newton step along the flattest
+      direction.  Where -H + lam I is not positive definite no trial is made and lam grows to at least twice the most negative
+      eigenvalue's size.
+    - A point is converged, and frozen, when lam is 0, -H is positive definite and the Newton decrement g^T (-H)^-1 g <= tol.  That
+      last step is still taken where ln P rises by it, so ln P at the result is short of the maximum by the decrement's square, not
+      by tol / 2.  The default tol is the absolute accuracy ln P itself is pinned to (1e-10 relative at chi2 ~ 1e2).
+    - A start whose ln P or derivatives are not finite is left where it is, unconverged.
+    It is a local method: where ln P has several maxima, the one a start ends in depends on the damping.
+    Priors and bounds on theta are out of scope: they are the sampler's business."""
+    theta = np.array(theta0, dtype=np.float64)
+    if theta.ndim != 2:
+        raise ValueError("theta0 must be [M, P]")
+    M, P = theta.shape
+    finite = lambda lp, g, H: np.isfinite(lp) & np.all(np.isfinite(g), axis=1) & np.all(np.isfinite(H), axis=(1, 2))
+    logp, grad, hess = (np.array(a, dtype=np.float64) for a in fun(theta))
+    alive = finite(logp, grad, hess)
+    lam, n_iter, converged = np.zeros(M), np.zeros(M, dtype=np.int64), np.zeros(M, dtype=bool)
+    eye = np.eye(P)
+    for _ in range(max_iter):
+        act = np.nonzero(alive & ~converged)[0]
+        if act.size == 0:
+            break
+        A = -hess[act] + lam[act, None, None] * eye
+        A = 0.5 * (A + A.transpose(0, 2, 1))
+        w = np.linalg.eigvalsh(A) if P else np.ones((act.size, 1))
+        pd = w[:, 0] > 0.0
+        wh = w - lam[act, None]  # (the eigenvalues of -H)
+        lam0 = 3.0 * np.min(np.abs(wh), axis=1)
+        lam0 = np.where(lam0 > 0.0, lam0, 1e-3 * np.max(np.abs(wh), axis=1) + 1e-300)
+        delta = np.zeros((act.size, P))
+        if P and np.any(pd):
+            delta[pd] = np.linalg.solve(A[pd], grad[act][pd][:, :, None])[:, :, 0]
+        dec = np.sum(grad[act] * delta, axis=1)
+        done = pd & (lam[act] == 0.0) & (dec <= tol)
+        converged[act[done]] = True  # (after this last step, if ln P still rises by it: it halves what the decrement leaves of ln P)
+        go = pd
+        ok = np.zeros(act.size, dtype=bool)
+        if np.any(go):
+            trial = theta.copy()
+            trial[act[go]] += delta[go]
+            lp_t, g_t, H_t = (np.asarray(a, dtype=np.float64) for a in fun(trial))
+            n_iter[act[go]] += 1
+            with np.errstate(invalid="ignore"):
+                ok = go & finite(lp_t, g_t, H_t)[act] & (lp_t[act] > logp[act])
+            acc = act[ok]
+            theta[acc], logp[acc], grad[acc], hess[acc] = trial[acc], lp_t[acc], g_t[acc], H_t[acc]
+            lam[acc] = np.where(lam[acc] * 0.1 < 0.1 * lam0[ok], 0.0, lam[acc] * 0.1)
+        rej = ~ok & ~done
+        grown = np.where(lam[act] == 0.0, lam0, lam[act] * 10.0)
+        lam[act[rej]] = np.where(pd, grown, np.maximum(grown, -2.0 * wh[:, 0]))[rej]
+    return theta, logp, grad, hess, n_iter, converged
+
+
+__all__ = ["MarginalLikelihood", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]

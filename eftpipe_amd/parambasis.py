@@ -708,6 +708,64 @@ class DrawRecipe:
         ``rows_magnitude`` is of ``rows``"""
         return self._jac(theta, f, 0, 24, magnitude=True)
 
+    def second_derivative(self):
+        """The terms of d2 rows / d theta_p d theta_q: for each term and each unordered pair p <= q of theta indices in it one record (p, q,
+        tracer, row, col, coef * multiplicity, fpow, idx [1]: the one remaining index or -1), the multiplicity being m_p m_q for p < q and
+        m_p (m_p - 1) for p = q (m: how often the index occurs in the term).  Sorted by (p, q, row, tracer, col) and, inside an entry, by
+        the order the library gives the parent terms, as ``derivative`` -- the table eftb_set_draw_recipe builds for
+        eftb_draws_logp_hess_params."""
+        order = np.lexsort((self.coef, self.idx[:, 2], self.idx[:, 1], self.idx[:, 0], self.fpow, self.col, self.tracer, self.row))
+        P = len(self.param_names)
+        rec = []
+        for p in range(P):
+            for q in range(p, P):
+                for t in order:
+                    ix = [int(v) for v in self.idx[t]]
+                    m = ix.count(p) * (ix.count(p) - 1) if p == q else ix.count(p) * ix.count(q)
+                    if m:
+                        ix.remove(p)
+                        ix.remove(q)
+                        rec.append((p, q, self.tracer[t], self.row[t], self.col[t], self.coef[t] * m, self.fpow[t], ix))
+        out = np.zeros(len(rec), dtype=[("p", "<i4"), ("q", "<i4"), ("tracer", "<i4"), ("row", "<i4"), ("col", "<i4"), ("coef", "<f8"), ("fpow", "<i4"),
+                                        ("idx", "<i4", (1,))])
+        for n, r in enumerate(rec):
+            out[n] = r
+        return out
+
+    def _hess(self, theta, f, lo, hi, magnitude=False):
+        theta = np.asarray(theta, dtype=np.float64)
+        P = len(self.param_names)
+        if theta.ndim != 2 or theta.shape[1] != P:
+            raise ValueError(f"theta must be [N, {P}]")
+        N = theta.shape[0]
+        f = np.asarray(f, dtype=np.float64)
+        f = np.broadcast_to(f[:, None] if f.ndim == 1 and self.ntr == 1 else f, (N, self.ntr))
+        fp = [np.ones((N, self.ntr))]
+        for _ in range(RECIPE_MAXFPOW):
+            fp.append(fp[-1] * f)
+        th = np.concatenate([theta, np.ones((N, 1))], axis=1)  # (index -1: the factor 1)
+        out = np.zeros((N, self.ntr, self.ng1, hi - lo, P, P))
+        for d in self.second_derivative():
+            if lo <= d["col"] < hi:
+                v = d["coef"] * fp[d["fpow"]][:, d["tracer"]] * th[:, d["idx"][0]]
+                out[:, d["tracer"], d["row"], d["col"] - lo, d["p"], d["q"]] += np.abs(v) if magnitude else v
+        iu = np.triu_indices(P, 1)
+        out[..., iu[1], iu[0]] = out[..., iu[0], iu[1]]  # entry (q, p) is a copy of (p, q)
+        return out
+
+    def hessian(self, theta, f):
+        """d2 rows / d theta d theta [N, ntr, ng1, 24, P, P] (theta, f as ``rows``): the terms of ``second_derivative`` summed in their order"""
+        return self._hess(theta, f, 0, 24)
+
+    def hessian_nnlo(self, theta, f):
+        """-> d2 rows_nnlo / d theta d theta [N, ntr, ng1, 3, P, P]"""
+        return self._hess(theta, f, 24, 27)
+
+    def hessian_magnitude(self, theta, f):
+        """-> the sum of the magnitudes of the monomials of each entry of ``hessian``: the scale of its rounding error, as
+        ``jacobian_magnitude`` is of ``jacobian``"""
+        return self._hess(theta, f, 0, 24, magnitude=True)
+
     def terms(self):
         """the records of eftb_set_draw_recipe"""
         from . import _lib as L

@@ -334,6 +334,19 @@ int  eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t*
 int  eftb_draws_logp_grad_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
                                  double* grad, double* fullchi2, double* best);
 
+/* eftb_draws_logp_grad_params with d2 ln P / d theta d theta: hess [N][P][P], grad [N][P] (both required).  With K = F2^-1, D_p = d R^ / d theta_p,
+ * G_p = D_p H^T + H D_p^T, G_pq = D_pq H^T + H D_pq^T + D_p W D_q^T + D_q W D_p^T and u_p = (G_p v)[1:],
+ *     d2 chi2 / d theta_p d theta_q = sum_gh S[g][h] G_pq[g][h] - 2 u_p^T K u_q - [not Jeffreys] tr(K G_p[1:,1:] K G_q[1:,1:])
+ * (the middle term is the Schur complement of profiling b; the prior terms do not move), and d2 ln P = -1/2 of that.  eftb_set_draw_recipe
+ * (kind 0) differentiates its sorted terms a second time itself and keeps those records, sorted by (p, q, entry, parent term) with p <= q,
+ * beside the first-derivative table: whatever drops or replaces the recipe does the same to both.  The order of every sum depends on
+ * the recipe alone, however the draws are split over calls; entry (q, p) is a copy of (p, q).  Walkers, offsets, the Gram cache and the
+ * refusals are those of eftb_draws_logp_grad_params; logp, grad, fullchi2 and best are its bits.  A shape whose working set does not fit
+ * the LDS with one wave per workgroup is refused (the message names P, nG and J + 1).  A draw with det F2 <= 0 gets NaN in all P^2 slots
+ * of hess, as in grad and logp.  Nothing is iterated on the device: a Newton step on the host is eftpipe_amd.marginal.newton_maximize. */
+int  eftb_draws_logp_hess_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
+                                 double* grad, double* hess, double* fullchi2, double* best);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

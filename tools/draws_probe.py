@@ -11,7 +11,9 @@ one set of walkers, for two shapes -- the single-tracer marg.npz likelihood and 
 the same draws through MarginalLikelihood.logp_draws_params (eftb_draws_logp_params: theta [N, P] in, the rows built on the device from the
 draw recipe) -- per call, and end to end with theta stacked from the sampler's per-parameter arrays -- with the bytes per draw over PCIe;
 the same call with d ln P / d theta (logp_draws_params(grad=True), eftb_draws_logp_grad_params), per call and end to end, and its cost in
-forward calls (the 2 P central differences it replaces are the yardstick);
+forward calls (the 2 P central differences it replaces are the yardstick); the same call with d2 ln P / d theta d theta
+(logp_draws_params(grad=True, hess=True), eftb_draws_logp_hess_params), per call, and its cost in gradient calls (the 2 P gradient calls of
+a central difference are the yardstick);
 and, for comparison, the same number of evaluations through eval_logp (theory + likelihood per walker; Nk = 512, resummation + AP, an
 interpolation onto the data k instead of the window: a lower bound on the cost of the real thing).  GPU box.
 
@@ -171,6 +173,11 @@ def probe(name, setup, C, N, ntr):
     assert np.array_equal(lpg, lp) and grad.shape == theta.shape
     ts_grad = times(lambda: like.logp_draws_params(theta, off, fC, grad=True), 9)
     t_grad = float(np.median(ts_grad))
+    # the Hessian call on the same draws
+    lph, gradh, hess = like.logp_draws_params(theta, off, fC, grad=True, hess=True)
+    assert np.array_equal(lph, lp) and np.array_equal(gradh, grad) and hess.shape == theta.shape + theta.shape[1:]
+    ts_hess = times(lambda: like.logp_draws_params(theta, off, fC, grad=True, hess=True), 9)
+    t_hess = float(np.median(ts_hess))
     rate_eval = eval_logp_rate(ntr, ndata // ntr, nG)
     out = {
         "shape": name, "walkers": C, "draws": N, "tracers": ntr, "ndata": ndata, "nG": nG, "row_bytes_per_draw": rows[0].nbytes,
@@ -186,6 +193,10 @@ def probe(name, setup, C, N, ntr):
         "grad_call_us_per_draw_spread": [1e6 * min(ts_grad) / N, 1e6 * max(ts_grad) / N],
         "grad_draws_per_s_device_call": N / t_grad, "grad_draws_per_s_end_to_end": N / (t_grad + t_theta),
         "grad_cost_in_forward_calls": t_grad / t_params, "central_difference_cost_in_forward_calls": 2 * theta.shape[1],
+        "hess_bytes_back_per_draw": hess[0].nbytes, "hess_call_us_per_draw": 1e6 * t_hess / N,
+        "hess_call_us_per_draw_spread": [1e6 * min(ts_hess) / N, 1e6 * max(ts_hess) / N],
+        "hess_draws_per_s_device_call": N / t_hess, "hess_cost_in_gradient_calls": t_hess / t_grad,
+        "central_difference_cost_in_gradient_calls": 2 * theta.shape[1],
         "eval_logp_per_s": rate_eval,
     }
     out["speedup_end_to_end"] = out["draws_per_s_end_to_end"] / rate_eval
