@@ -4211,4 +4211,47 @@ __global__ __launch_bounds__(256) void draws_logp_hess_params_kernel(int ntr, in
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Draw calls against many data vectors sharing one covariance (eftb_draws_logp_params_datasets).  Only the last row and column of W_c depend
+// on the data: a group g = (walker c, data set m) gets
+//     Wg[g][:J][:J] = W_c[:J][:J],     Wg[g][i][J] = Wg[g][J][i] = (A_i . U_J + A_J . U_i) / 2,     A_J = -d_m,  U_J = -(d_m C^-1)
+// with A_c, U_c = A_c C^-1 and W_c of draws_gram and D [M][ndata], Ud = D C^-1 of eftb_set_likelihood_datasets.  One workgroup per group.  The
+// border sums are those of draws_gram_kernel for the entries (i, J), i <= J: one 16-lane group per entry, lanes stride the data index, the FMA
+// chains s0 and s1, the same xor tree; the negations are exact, so a data set equal to the likelihood's own vector gives the bits of W_c.
+// ------------------------------------------------------------------------------------------------
+template <int NT>  // threads per workgroup, a multiple of 16
+__global__ __launch_bounds__(NT) void draws_gram_groups_kernel(int ndata, int J1, const int* __restrict__ walker, const int* __restrict__ dataset,
+                                                                const double* __restrict__ A, const double* __restrict__ U,
+                                                                const double* __restrict__ W, const double* __restrict__ D,
+                                                                const double* __restrict__ Ud, double* __restrict__ Wg) {
+    const int g = blockIdx.x, sub = threadIdx.x & 15, grp = threadIdx.x >> 4, J = J1 - 1;
+    const int c = walker[g], m = dataset[g];
+    const double* Ac = A + (size_t)c * J1 * ndata;
+    const double* Uc = U + (size_t)c * J1 * ndata;
+    const double* Wc = W + (size_t)c * J1 * J1;
+    const double* dm = D + (size_t)m * ndata;
+    const double* um = Ud + (size_t)m * ndata;
+    double* Wo = Wg + (size_t)g * J1 * J1;
+    for (int e = threadIdx.x; e < J1 * J1; e += NT)
+        if (e / J1 < J && e % J1 < J) Wo[e] = Wc[e];
+    for (int i = grp; i < J1; i += NT / 16) {  // entry (i, J); i is uniform over the 16-lane group: the shuffles stay inside it
+        double s0 = 0.0, s1 = 0.0;
+        for (int b = sub; b < ndata; b += 16) {
+            const double aJ = -dm[b], uJ = -um[b];
+            s0 = fma(i < J ? Ac[(size_t)i * ndata + b] : aJ, uJ, s0);
+            s1 = fma(aJ, i < J ? Uc[(size_t)i * ndata + b] : uJ, s1);
+        }
+#pragma unroll
+        for (int q = 8; q >= 1; q >>= 1) {
+            s0 += __shfl_xor(s0, q, 16);
+            s1 += __shfl_xor(s1, q, 16);
+        }
+        if (sub == 0) {
+            const double w = 0.5 * (s0 + s1);
+            Wo[(size_t)i * J1 + J] = w;
+            Wo[(size_t)J * J1 + i] = w;
+        }
+    }
+}
+
 }  // namespace eftb

@@ -166,6 +166,16 @@ struct eftb_engine {
     double* drw_hess = nullptr;     // eftb_draws_logp_hess_params: d2 ln P / d theta d theta [N][P][P]
     size_t drw_hess_cap = 0;
     bool drw_lds_hess = false;      // the draws_logp_hess_params_kernel instantiations opted in to the large dynamic LDS
+    // data sets sharing the likelihood's covariance (eftb_set_likelihood_datasets): dset_D [M][ndata] and dset_Ud = D C^-1; dset_gen counts
+    // their changes.  eftb_draws_logp_params_datasets keeps Wg [G][J1][J1] of its last group table (grp_tab: walker [G] | dataset [G], on the
+    // host and on the device) and reuses it while draw_gen, dset_gen and the table are those it was built from (grp_draw_gen = 0: none)
+    int dset_M = 0;
+    unsigned long long dset_gen = 1, grp_draw_gen = 0, grp_dset_gen = 0;
+    double *dset_D = nullptr, *dset_Ud = nullptr, *drw_Wg = nullptr;
+    size_t dset_D_cap = 0, dset_Ud_cap = 0, drw_Wg_cap = 0, drw_gtab_cap = 0;
+    int* drw_gtab = nullptr;
+    std::vector<int> grp_tab;
+    std::vector<double> grp_f;      // f [G][ntr] of a groups call, expanded from f [C][ntr]
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -1760,6 +1770,8 @@ int eftb_set_tracers(eftb_engine* e, int ntr) {
     e->tracer_ops.clear();
     e->like_ndata = 0;  // a likelihood set for another grouping does not survive
     e->recipe[0].set = e->recipe[1].set = false;  // nor do the draw recipes: their terms name tracers
+    e->dset_M = 0;  // nor do the data sets of the groups call: they belong to the likelihood
+    ++e->dset_gen;
     return 0;
 }
 
@@ -1940,6 +1952,8 @@ int eftb_set_likelihood(eftb_engine* e, int ndata, const int32_t* index, const d
     e->like_nl = lnl;
     e->like_nx = lnx;
     e->recipe[0].set = false;  // the logp recipe belongs to the likelihood it was set for
+    e->dset_M = 0;  // and so do the data sets (eftb_set_likelihood_datasets)
+    ++e->dset_gen;
     ++e->draw_gen;
     return 0;
 }
@@ -1970,6 +1984,7 @@ void eftb_destroy(eftb_engine* e) {
     for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off, (void*)e->drw_theta,
                     (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab, (void*)e->recipe[0].dcoef,
                     (void*)e->recipe[0].dtab, (void*)e->drw_grad, (void*)e->recipe[0].hcoef, (void*)e->recipe[0].htab, (void*)e->drw_hess}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)e->dset_D, (void*)e->dset_Ud, (void*)e->drw_Wg, (void*)e->drw_gtab}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
@@ -2185,15 +2200,17 @@ static int grow_dev(void* pp, size_t* cap, size_t n, size_t elem = sizeof(double
     return 0;
 }
 
-// offsets (walker c owns draws [offsets[c], offsets[c + 1])) and the state of the template block; *maxcnt: the most draws one walker owns
-static int draws_check(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, long long* maxcnt) {
+// offsets (walker c owns draws [offsets[c], offsets[c + 1])) and the state of the template block; *maxcnt: the most draws one walker owns.
+// A groups call (eftb_draws_logp_params_datasets) passes its G groups as C, unit = "group" and nwalk, the walkers the block must hold
+static int draws_check(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, long long* maxcnt, const char* unit = "walker",
+                       int nwalk = -1) {
     if (!e->finalized) return fail("%s: engine not finalized", who);
-    if (C < 1) return fail("%s: %d walkers", who, C);
+    if (C < 1) return fail("%s: %d %ss", who, C, unit);
     if (N < 0) return fail("%s: %lld draws", who, N);
     if (offsets[0] != 0) return fail("%s: offsets[0] = %lld, not 0", who, (long long)offsets[0]);
     long long mx = 0;
     for (int w = 0; w < C; ++w) {
-        if (offsets[w + 1] < offsets[w]) return fail("%s: offsets decrease at walker %d (%lld -> %lld)", who, w, (long long)offsets[w], (long long)offsets[w + 1]);
+        if (offsets[w + 1] < offsets[w]) return fail("%s: offsets decrease at %s %d (%lld -> %lld)", who, unit, w, (long long)offsets[w], (long long)offsets[w + 1]);
         mx = std::max<long long>(mx, offsets[w + 1] - offsets[w]);
     }
     if (offsets[C] != N) return fail("%s: offsets[%d] = %lld, not the %lld draws", who, C, (long long)offsets[C], N);
@@ -2201,8 +2218,9 @@ static int draws_check(eftb_engine* e, const char* who, int C, long long N, cons
         return fail("%s: the current block holds no templates (the last run was a direct-P_l run, or a staged step has rotated the blocks since the "
                     "last template-producing run / eftb_put)", who);
     const size_t per = (size_t)e->cur_nl * NROW * e->cur_nx, have = per ? e->templ_elems / per : 0;
-    if ((size_t)C * e->ntr > have)
-        return fail("%s: %d walkers x %d tracers, but the template block holds %zu entries [%d][24][%d]", who, C, e->ntr, have, e->cur_nl, e->cur_nx);
+    if (nwalk < 0) nwalk = C;
+    if ((size_t)nwalk * e->ntr > have)
+        return fail("%s: %d walkers x %d tracers, but the template block holds %zu entries [%d][24][%d]", who, nwalk, e->ntr, have, e->cur_nl, e->cur_nx);
     *maxcnt = mx;
     return 0;
 }
@@ -2259,9 +2277,10 @@ static int draws_records(eftb_engine* e, long long N, double* logp, double* full
 }
 
 // what every logp draw call refuses before it looks at its own inputs: no likelihood, draws_check, a block of another shape than the likelihood's
-static int draws_logp_check(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, long long* maxcnt) {
+static int draws_logp_check(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, long long* maxcnt, const char* unit = "walker",
+                            int nwalk = -1) {
     if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
-    if (int rc = draws_check(e, who, C, N, offsets, maxcnt)) return rc;
+    if (int rc = draws_check(e, who, C, N, offsets, maxcnt, unit, nwalk)) return rc;
     if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
         return fail("%s: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", who, e->like_nl, e->like_nx, e->cur_nl,
                     e->cur_nx);
@@ -2298,12 +2317,12 @@ static int draws_lds_optin(eftb_engine* e) {
 }
 
 // before the inputs of a logp draw call go to the device: the device and the stream, the LDS opt-in of the kernels (once), W_c, the
-// record buffer, and the offsets
-static int draws_logp_begin(eftb_engine* e, const char* who, int C, long long N, int J1, const int64_t* offsets) {
+// record buffer, and the offsets (a groups call: C groups own the draws, W_c is wanted for nwalk walkers)
+static int draws_logp_begin(eftb_engine* e, const char* who, int C, long long N, int J1, const int64_t* offsets, int nwalk = -1) {
     HIPCHK(hipSetDevice(e->c.device));
     join_back(e);
     if (int rc = draws_lds_optin(e)) return rc;
-    if (int rc = draws_gram(e, who, C, J1)) return rc;
+    if (int rc = draws_gram(e, who, nwalk < 0 ? C : nwalk, J1)) return rc;
     if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
     if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
     HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, e->stream));
@@ -3486,12 +3505,21 @@ static int draws_params_upload(eftb_engine* e, int P, int C, long long N, const 
     return 0;
 }
 
+// the groups of eftb_draws_logp_params_datasets: group g = (walker[g], dataset[g]), every walker below nwalk, every data set below dset_M
+struct DrawGroups {
+    int nwalk;
+    const int32_t *walker, *dataset;
+};
+
+static int draws_gram_groups(eftb_engine* e, const char* who, int G, int J1, const DrawGroups& gr);  // (defined behind the last kernel instantiation of the params calls)
+
 // eftb_draws_logp_params (grad == nullptr: the forward kernel and its LDS layout), eftb_draws_logp_grad_params and eftb_draws_logp_hess_params
-// (hess != nullptr, with grad: the Hessian kernel and its LDS layout)
+// (hess != nullptr, with grad: the Hessian kernel and its LDS layout).  gr (eftb_draws_logp_params_datasets): C counts the groups, offsets and
+// f [C][ntr] are per group, and the kernels read Wg where they read W_c
 static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, const double* theta, const double* f,
-                                  double* logp, double* grad, double* fullchi2, double* best, double* hess = nullptr) {
+                                  double* logp, double* grad, double* fullchi2, double* best, double* hess = nullptr, const DrawGroups* gr = nullptr) {
     long long maxcnt = 0;
-    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt)) return rc;
+    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
     const int ntr = e->ntr, nG = e->like_nG;
     if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta, f)) return rc;
     const eftb_engine::Recipe& rcp = e->recipe[0];
@@ -3513,7 +3541,10 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
         sh.lds = lds_w + nw * lds_wave;
     }
     if (N == 0) return 0;
-    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets)) return rc;
+    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets, gr ? gr->nwalk : -1)) return rc;
+    if (gr)
+        if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
+    const double* W = gr ? e->drw_Wg : e->drw_W;
     if (hess && !e->drw_lds_hess) {
         for (const void* k : {reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<true>)})
             HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -3547,22 +3578,22 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
             ht.hpack = ht.hent + rcp.nh;
             while ((1 << ht.lgPP) < std::min(ht.npair, 64)) ++ht.lgPP;
             if (J1 > 64)
-                hipLaunchKernelGGL(draws_logp_hess_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, e->drw_W,
+                hipLaunchKernelGGL(draws_logp_hess_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, W,
                                    e->like_mu, e->like_sinv, e->drw_out, e->drw_grad, e->drw_hess);
             else
-                hipLaunchKernelGGL(draws_logp_hess_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, e->drw_W,
+                hipLaunchKernelGGL(draws_logp_hess_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, W,
                                    e->like_mu, e->like_sinv, e->drw_out, e->drw_grad, e->drw_hess);
         } else if (J1 > 64)
-            hipLaunchKernelGGL(draws_logp_grad_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
+            hipLaunchKernelGGL(draws_logp_grad_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, W,
                                e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
         else
-            hipLaunchKernelGGL(draws_logp_grad_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, e->drw_W,
+            hipLaunchKernelGGL(draws_logp_grad_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, W,
                                e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
     } else if (J1 > 64)
-        hipLaunchKernelGGL(draws_logp_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
+        hipLaunchKernelGGL(draws_logp_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, W, e->like_mu,
                            e->like_sinv, e->drw_out);
     else
-        hipLaunchKernelGGL(draws_logp_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, e->drw_W, e->like_mu,
+        hipLaunchKernelGGL(draws_logp_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, W, e->like_mu,
                            e->like_sinv, e->drw_out);
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
@@ -3634,4 +3665,103 @@ int eftb_draws_logp_hess_params(eftb_engine* e, int C, long long N, const int64_
     if (!grad) return fail("%s: grad == NULL (the Hessian call returns the gradient too)", who);
     if (!hess) return fail("%s: hess == NULL (eftb_draws_logp_grad_params is the call without the Hessian)", who);
     return draws_logp_params_impl(e, who, C, N, offsets, theta, f, logp, grad, fullchi2, best, hess);
+}
+
+// ------------------------------------------------------------------------------------------------ draws against many data vectors, one covariance
+// Wg [G][J1][J1] of a groups call, after draws_gram: kept while the template block, the likelihood, the tracers (draw_gen), the data sets
+// (dset_gen) and the group table are those it was built from.  The kernel is a template instantiated here, behind every other one, so that the
+// existing kernels keep their code and labels
+static int draws_gram_groups(eftb_engine* e, const char* who, int G, int J1, const DrawGroups& gr) {
+    if (e->grp_draw_gen == e->draw_gen && e->grp_dset_gen == e->dset_gen && e->grp_tab.size() == 2 * (size_t)G &&
+        std::equal(gr.walker, gr.walker + G, e->grp_tab.begin()) && std::equal(gr.dataset, gr.dataset + G, e->grp_tab.begin() + G))
+        return 0;
+    e->grp_draw_gen = 0;
+    const size_t need = (size_t)G * J1 * J1;
+    if (need > e->drw_Wg_cap) {
+        if (e->drw_Wg) HIPCHK(hipFree(e->drw_Wg));
+        e->drw_Wg = nullptr;
+        e->drw_Wg_cap = 0;
+        hipError_t me = hipMalloc(&e->drw_Wg, need * sizeof(double));
+        if (me != hipSuccess) {
+            (void)hipGetLastError();
+            e->drw_Wg = nullptr;
+            return fail("%s: no device memory for the Gram matrices of G = %d groups with J + 1 = %d columns (%zu bytes): %s", who, G, J1,
+                        need * sizeof(double), hipGetErrorString(me));
+        }
+        e->drw_Wg_cap = need;
+    }
+    if (int rc = grow_dev(&e->drw_gtab, &e->drw_gtab_cap, 2 * (size_t)G, sizeof(int))) return rc;
+    e->grp_tab.assign(gr.walker, gr.walker + G);
+    e->grp_tab.insert(e->grp_tab.end(), gr.dataset, gr.dataset + G);
+    HIPCHK(hipMemcpyAsync(e->drw_gtab, e->grp_tab.data(), 2 * (size_t)G * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(draws_gram_groups_kernel<256>, dim3(G), dim3(256), 0, e->stream, e->like_ndata, J1, e->drw_gtab, e->drw_gtab + G, e->drw_A, e->drw_U,
+                       e->drw_W, e->dset_D, e->dset_Ud, e->drw_Wg);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    e->grp_draw_gen = e->draw_gen;
+    e->grp_dset_gen = e->dset_gen;
+    return 0;
+}
+
+int eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data) {
+    static const char* who = "eftb_set_likelihood_datasets";
+    if (e) sub_drain(e);
+    if (!e) return fail("%s: null engine", who);
+    if (M == 0) {
+        e->dset_M = 0;
+        ++e->dset_gen;
+        return 0;
+    }
+    if (M < 0) return fail("%s: %d data sets", who, M);
+    if (!data) return fail("%s: null data", who);
+    if (!e->like_ndata) return fail("%s: the data sets share a likelihood's index, covariance and priors: needs eftb_set_likelihood first", who);
+    const int nd = e->like_ndata;
+    for (size_t q = 0; q < (size_t)M * nd; ++q)
+        if (!std::isfinite(data[q])) return fail("%s: data[%zu][%zu] is not finite", who, q / nd, q % nd);
+    HIPCHK(hipSetDevice(e->c.device));
+    join_back(e);
+    e->dset_M = 0;
+    ++e->dset_gen;
+    if (int rc = grow_dev(&e->dset_D, &e->dset_D_cap, (size_t)M * nd)) return rc;
+    if (int rc = grow_dev(&e->dset_Ud, &e->dset_Ud_cap, (size_t)M * nd)) return rc;
+    hipStream_t st = e->stream;
+    HIPCHK(hipMemcpyAsync(e->dset_D, data, (size_t)M * nd * sizeof(double), hipMemcpyHostToDevice, st));
+    GemmDesc gd{};  // Ud = D C^-1, as draws_gram multiplies A: a row of -D there is the exact negation of its row here
+    gd.A = e->dset_D; gd.a_group = 0; gd.a_row = nd; gd.a_seg = 0; gd.rows = M; gd.rows_per_group = M; gd.nseg = 1; gd.kseg = nd;
+    gd.B = e->like_invcov; gd.ldb = nd; gd.ncols = nd;
+    gd.C = e->dset_Ud; gd.c_group = 0; gd.c_row = nd; gd.c_colgroup = 0; gd.cols_per_group = nd;
+    hipLaunchKernelGGL(gemm_narrow_kernel, dim3((gd.rows + 15) / 16, (gd.ncols + 16 * GN_MAXT - 1) / (16 * GN_MAXT)), dim3(256), 0, st, gd, GemmZ{});
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    HIPCHK(hipStreamSynchronize(st));  // (the caller's array is free again)
+    e->dset_M = M;
+    return 0;
+}
+
+int eftb_draws_logp_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, const int64_t* offsets,
+                                    const double* theta, const double* f, double* logp, double* grad, double* hess, double* fullchi2, double* best) {
+    static const char* who = "eftb_draws_logp_params_datasets";
+    if (e) sub_drain(e);
+    if (!e || !walker || !dataset || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
+    if (hess && !grad) return fail("%s: hess needs grad (the Hessian kernel returns the gradient too)", who);
+    if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
+    if (!e->dset_M) return fail("%s: no data sets (eftb_set_likelihood_datasets; eftb_set_likelihood and eftb_set_tracers drop them)", who);
+    if (C < 1) return fail("%s: %d walkers", who, C);
+    if (G < 1) return fail("%s: %d groups", who, G);
+    const int ntr = e->ntr;
+    const size_t per = (size_t)e->cur_nl * NROW * e->cur_nx, have = per ? e->templ_elems / per : 0;
+    DrawGroups gr{0, walker, dataset};
+    for (int g = 0; g < G; ++g) {
+        if (walker[g] < 0 || walker[g] >= C) return fail("%s: walker[%d] = %d outside [0, %d)", who, g, walker[g], C);
+        if (dataset[g] < 0 || dataset[g] >= e->dset_M) return fail("%s: dataset[%d] = %d outside [0, %d)", who, g, dataset[g], e->dset_M);
+        if (e->templ_ok && ((size_t)walker[g] + 1) * ntr > have)
+            return fail("%s: walker[%d] = %d with %d tracers, but the template block holds %zu entries [%d][24][%d]", who, g, walker[g], ntr, have, e->cur_nl,
+                        e->cur_nx);
+        gr.nwalk = std::max(gr.nwalk, walker[g] + 1);
+    }
+    for (int q = 0; q < C * ntr; ++q)
+        if (!std::isfinite(f[q])) return fail("%s: f[%d][%d] is not finite", who, q / ntr, q % ntr);
+    e->grp_f.resize((size_t)G * ntr);  // f per group: the draw kernels read f [blockIdx.x][ntr]
+    for (int g = 0; g < G; ++g) std::copy(f + (size_t)walker[g] * ntr, f + ((size_t)walker[g] + 1) * ntr, e->grp_f.begin() + (size_t)g * ntr);
+    return draws_logp_params_impl(e, who, G, N, offsets, theta, e->grp_f.data(), logp, grad, fullchi2, best, hess, &gr);
 }

@@ -596,18 +596,26 @@ def _set_recipe(eng, kind, recipe, ng1):
     return recipe
 
 
-def _params_args(recipe, theta, offsets, f, ntr):
-    """theta [N, P], offsets [C + 1], f [C, ntr] of a params call as the library takes them; shape errors are raised here"""
-    from .marginal import _offsets
-
+def _theta_f_args(recipe, theta, f, ntr, nC=None):
+    """theta [N, P] and f [C, ntr] ([C] with one tracer) of a params call as the library takes them; nC: the walkers the offsets name
+    (None, a groups call: as many as f holds, at least one); shape errors are raised here"""
     theta = np.ascontiguousarray(theta, dtype=np.float64)
-    off = _offsets(offsets)
     f = np.ascontiguousarray(f, dtype=np.float64)
-    nC = off.size - 1
     if recipe is not None and (theta.ndim != 2 or theta.shape[1] != len(recipe.param_names)):
         raise ValueError(f"theta must be [N, {len(recipe.param_names)}] ({', '.join(recipe.param_names)})")
     if theta.ndim != 2:
         raise ValueError("theta must be [N, P]")
-    if f.shape not in ((nC, ntr),) + (((nC,),) if ntr == 1 else ()):
-        raise ValueError(f"f must be [{nC}, {ntr}]: one growth rate per walker and tracer")
+    have = f.shape[0] if f.ndim in (1, 2) and f.shape[0] >= 1 else -1
+    want = have if nC is None else nC
+    if f.shape not in ((want, ntr),) + (((want,),) if ntr == 1 else ()):
+        raise ValueError(f"f must be [{'C' if nC is None else nC}, {ntr}]: one growth rate per walker and tracer")
+    return theta, f
+
+
+def _params_args(recipe, theta, offsets, f, ntr):
+    """theta [N, P], offsets [C + 1], f [C, ntr] of a params call as the library takes them; shape errors are raised here"""
+    from .marginal import _offsets
+
+    off = _offsets(offsets)
+    theta, f = _theta_f_args(recipe, theta, f, ntr, off.size - 1)
     return theta, off, f

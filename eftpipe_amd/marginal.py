@@ -193,7 +193,20 @@ class MarginalLikelihood:
 
         self._recipe = _set_recipe(self.eng, L.RECIPE_LOGP, recipe, self.nG + 1)
 
-    def logp_draws_params(self, theta, offsets, f, return_best=False, grad=False, hess=False):
+    def set_datasets(self, data):
+        """Data vectors that share this likelihood's index, covariance, priors and Jeffreys switch (``eftb_set_likelihood_datasets``): data
+        [M, ndata], e.g. mock realisations; ``None`` withdraws them.  ``logp_draws_params`` and ``maximize_draws_params`` score draws
+        against them through ``groups=``.  They belong to this likelihood: constructing another ``MarginalLikelihood`` on the engine, or
+        ``Engine.set_tracers``, drops them.  Every other call keeps the one data vector the likelihood was constructed with."""
+        if data is None:
+            L.check(self.eng.lib.eftb_set_likelihood_datasets(self.eng._h, 0, None))
+            return
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] != self.index.size:
+            raise ValueError(f"data must be [M, {self.index.size}]: M >= 1 data vectors of the likelihood's length")
+        L.check(self.eng.lib.eftb_set_likelihood_datasets(self.eng._h, data.shape[0], L.dptr(data)))
+
+    def logp_draws_params(self, theta, offsets, f, return_best=False, grad=False, hess=False, groups=None):
         """``logp_draws`` with the rows built on the device from parameter values (``eftb_draws_logp_params``): theta [N, P] in the order of
         the recipe's ``param_names``, f [C, ntr] ([C] with one tracer) the growth rate of each walker's entries -> ln P_marg [N] (+ full
         chi2 [N] and best-fit Gaussian parameters [N, nG]).  8 P bytes per draw cross PCIe instead of the rows.  Raises like the
@@ -202,11 +215,22 @@ class MarginalLikelihood:
         -> (logp, grad) or (logp, grad, full, best); ln P, full chi2 and the best fit are the bits of the call without it.
         grad=True, hess=True (``eftb_draws_logp_hess_params``): also d2 ln P_marg / d theta d theta [N, P, P], each draw's block equal to its
         transpose bit for bit -> (logp, grad, hess) or (logp, grad, hess, full, best); ln P, the gradient, full chi2 and the best fit are
-        the gradient call's bits.  hess=True without grad raises ValueError."""
+        the gradient call's bits.  hess=True without grad raises ValueError.
+        groups=(walker [G], dataset [G]) (``eftb_draws_logp_params_datasets``; ``set_datasets`` first): group g scores its draws
+        offsets[g] ... offsets[g + 1] - 1 against the templates of walker[g] and data set dataset[g]; offsets is then [G + 1], f stays
+        [C, ntr] per walker.  Groups come in any order and may repeat a walker or a data set.  Returns as without it; a group whose data set
+        is the likelihood's own vector returns the bits of the call without ``groups``."""
         from .engine import _params_args
 
         if hess and not grad:
             raise ValueError("hess=True needs grad=True: the Hessian call returns the gradient too")
+        if groups is not None:
+            theta, off, f, wk, ds = _groups_args(getattr(self, "_recipe", None), theta, offsets, f, self.eng.ntracers, groups)
+            logp, dlogp, d2logp, full, best = self._draws_groups_raw(theta, off, f, wk, ds, grad, hess)
+            if np.any(np.isnan(logp)):
+                raise RuntimeError("det of F2ij <= 0")
+            out = (logp,) + ((dlogp,) if grad else ()) + ((d2logp,) if hess else ()) + ((full, best) if return_best else ())
+            return out if len(out) > 1 else logp
         theta, off, f = _params_args(getattr(self, "_recipe", None), theta, offsets, f, self.eng.ntracers)
         N = theta.shape[0]
         if hess:
@@ -236,13 +260,32 @@ class MarginalLikelihood:
                                                          L.dptr(logp), L.dptr(dlogp), L.dptr(d2logp), L.dptr(full), L.dptr(best)))
         return logp, dlogp, d2logp, full, best
 
-    def maximize_draws_params(self, theta0, offsets, f, **kw):
+    def _draws_groups_raw(self, theta, off, f, wk, ds, grad=True, hess=True):
+        """``eftb_draws_logp_params_datasets`` on checked arguments -> logp, grad (or None), hess (or None), full, best; NaN where det F2 <= 0,
+        nothing raised for it"""
+        N, P = theta.shape
+        logp, full, best = np.empty(N), np.empty(N), np.empty((N, self.nG))
+        dlogp = np.empty((N, P)) if grad else None
+        d2logp = np.empty((N, P, P)) if hess else None
+        i32p = C.POINTER(C.c_int32)
+        nC = f.shape[0]
+        L.check(self.eng.lib.eftb_draws_logp_params_datasets(self.eng._h, nC, wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p), N,
+                                                             off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f), L.dptr(logp), L.dptr(dlogp),
+                                                             L.dptr(d2logp), L.dptr(full), L.dptr(best)))
+        return logp, dlogp, d2logp, full, best
+
+    def maximize_draws_params(self, theta0, offsets, f, groups=None, **kw):
         """Best fits over the recipe's parameters at fixed cosmology: ``newton_maximize`` fed with the Hessian call, all starts of all
         walkers at once (theta0 [N, P], offsets and f as ``logp_draws_params``; kw: max_iter, tol) -> theta, logp, grad, hess, n_iter,
         converged.  A point whose ln P is NaN (det F2 <= 0) is not an error here: a trial there is rejected, a start there is left where it
-        is with converged False.  Priors and bounds on theta are the sampler's business, not this call's."""
+        is with converged False.  Priors and bounds on theta are the sampler's business, not this call's.
+        groups=(walker [G], dataset [G]) as in ``logp_draws_params``: the starts of group g climb the posterior of data set dataset[g] --
+        the best fits of many mocks in one call."""
         from .engine import _params_args
 
+        if groups is not None:
+            theta0, off, f, wk, ds = _groups_args(getattr(self, "_recipe", None), theta0, offsets, f, self.eng.ntracers, groups)
+            return newton_maximize(lambda th: self._draws_groups_raw(np.ascontiguousarray(th), off, f, wk, ds)[:3], theta0, **kw)
         theta0, off, f = _params_args(getattr(self, "_recipe", None), theta0, offsets, f, self.eng.ntracers)
         return newton_maximize(lambda th: self._draws_hess_raw(np.ascontiguousarray(th), off, f)[:3], theta0, **kw)
 
@@ -270,6 +313,28 @@ def _offsets(offsets):
     if off.ndim != 1 or off.size < 2:
         raise ValueError("offsets must be [C + 1]: walker c owns draws offsets[c] ... offsets[c + 1] - 1")
     return off
+
+
+def _groups_args(recipe, theta, offsets, f, ntr, groups):
+    """theta [N, P], offsets [G + 1], f [C, ntr] and groups = (walker [G], dataset [G]) of a groups call as the library takes them; shape
+    errors are raised here, the values (a walker or data set out of range) are the library's to refuse"""
+    try:
+        wk, ds = groups
+    except (TypeError, ValueError):
+        raise ValueError("groups must be (walker [G], dataset [G])") from None
+    wk, ds = np.asarray(wk), np.asarray(ds)
+    if wk.ndim != 1 or wk.shape != ds.shape or wk.size < 1:
+        raise ValueError("groups must be (walker [G], dataset [G]): two integer arrays of one length G >= 1")
+    for a in (wk, ds):
+        if a.dtype.kind not in "iu" or np.any(a != a.astype(np.int32)):
+            raise ValueError("groups must be (walker [G], dataset [G]): integers")
+    from .engine import _theta_f_args
+
+    theta, f = _theta_f_args(recipe, theta, f, ntr)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    if off.ndim != 1 or off.size != wk.size + 1:
+        raise ValueError(f"offsets must be [{wk.size + 1}]: group g owns draws offsets[g] ... offsets[g + 1] - 1")
+    return theta, off, f.reshape(-1, ntr), np.ascontiguousarray(wk, dtype=np.int32), np.ascontiguousarray(ds, dtype=np.int32)
 
 
 def newton_maximize(fun, theta0, max_iter=50, tol=1e-8):

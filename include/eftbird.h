@@ -347,6 +347,27 @@ int  eftb_draws_logp_grad_params(eftb_engine* e, int C, long long N, const int64
 int  eftb_draws_logp_hess_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* logp,
                                  double* grad, double* hess, double* fullchi2, double* best);
 
+/* Many data vectors sharing one covariance (mock realisations, pipeline validation, coverage tests), scored against the same templates.
+ * A data set is one of M vectors data[M][ndata]; all share the index, invcov, priors and Jeffreys switch of the likelihood set by
+ * eftb_set_likelihood, which must come first.  Only the last row and column of the Gram matrix W depend on the data: with U = A C^-1 of the
+ * walker's template columns (eftb_draws_logp) and Ud = data C^-1,
+ *     W[j][J] = W[J][j] = -(A_j . Ud_m + U_j . d_m) / 2,     W[J][J] = d_m . Ud_m,     W[:J][:J] as for the likelihood's own vector.
+ * eftb_set_likelihood_datasets uploads the data sets and computes Ud once (the multiplication eftb_draws_logp applies to A); M = 0 withdraws
+ * them, and eftb_set_likelihood and eftb_set_tracers drop them, as they drop the kind-0 recipe.  Non-finite data is refused before anything is
+ * copied.  The LOGP stage, eftb_eval_logp_batch and the rows call eftb_draws_logp keep the likelihood's one vector. */
+int  eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data);
+/* eftb_draws_logp_params, eftb_draws_logp_grad_params (grad != NULL) or eftb_draws_logp_hess_params (grad and hess != NULL; hess needs grad)
+ * per GROUP instead of per walker: group g = (walker[g] in [0, C), dataset[g] in [0, M)) owns the draws [offsets[g], offsets[g + 1]),
+ * possibly none; offsets[G + 1] as for the walkers of the other calls.  Groups come in any order and may repeat a walker or a data set.
+ * theta [N][P]; f [C][ntr] stays per walker.  Per group the (J + 1)^2 matrix Wg = the walker's W with the border of its data set is built by
+ * one small kernel (8 (J + 1)^2 bytes per group, grown on demand; 2 (J + 1) dot products of length ndata) and kept until the template block,
+ * the likelihood, the tracers, the data sets or the group table (walker, dataset) change; the kernels, records, outputs and refusals are those
+ * of the three params calls.  A group whose data set equals the likelihood's own vector bit for bit returns the bits of those calls.  Refused,
+ * naming the index: a walker outside [0, C) or beyond the template block, a data set outside [0, M), a call with no data sets set.  The
+ * Gram cache of the other draw calls is shared, not disturbed: they return the same bits before and after. */
+int  eftb_draws_logp_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, const int64_t* offsets,
+                                     const double* theta, const double* f, double* logp, double* grad, double* hess, double* fullchi2, double* best);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

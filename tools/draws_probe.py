@@ -18,6 +18,17 @@ and, for comparison, the same number of evaluations through eval_logp (theory + 
 interpolation onto the data k instead of the window: a lower bound on the cost of the real thing).  GPU box.
 
     python tools/draws_probe.py [--draws N] [--walkers C]
+
+--datasets M: many data vectors sharing one covariance (MarginalLikelihood.set_datasets, ``groups=``) instead, for both
+shapes, 1 walker x M data sets x --draws draws per group (default 1024 in this mode), Hessian calls, medians of cached calls:
+
+    (a) groups   one logp_draws_params(grad=True, hess=True, groups=...) call over the M groups
+    (b) loop     the same job without data sets: per data vector a new MarginalLikelihood, set_draw_recipe, one call
+    (c) plain    one call without groups with the same total draws on the one walker: the ceiling
+
+On a tree without set_datasets (a) is skipped, so that the same file times (b) and (c) on the parent commit.
+
+    python tools/draws_probe.py --datasets M [--draws N]
 """
 import argparse
 import json
@@ -85,7 +96,8 @@ def marg_setup(C, N, rng):
     build = lambda: gaussian_rows_many(f, ngv, None, *co[:3])
     rec = joint_draw_recipe([WestCoastBasis(prefix="")], gaussian_params(""), [dict(kmA=float(co[0]), krA=float(co[1]), ndA=float(co[2]))])
     cols = [np.ascontiguousarray(ngv[:, i]) for i in range(3)]  # (a sampler holds one array per parameter)
-    return eng, like, templ, build, index.size, len(g["auto_loc"]), (rec, lambda: np.stack(cols, axis=1), np.full(C, f))
+    lk = (g["auto_D"], g["auto_invcov"], g["auto_loc"], g["auto_scale"], False)  # (data, invcov, loc, scale, jeffreys: the likelihood's own arguments)
+    return eng, like, templ, build, index.size, len(g["auto_loc"]), (rec, lambda: np.stack(cols, axis=1), np.full(C, f)), lk
 
 
 def cfg3_setup(C, N, rng):
@@ -113,7 +125,8 @@ def cfg3_setup(C, N, rng):
     f = [float(g[t + "_f"]) for t in U.TRACERS]
     build = lambda: joint_gaussian_rows_many(U.bases(), f, draws, names, U.scales(g))
     rec = joint_draw_recipe(U.bases(), names, U.scales(g))
-    return eng, like, templ, build, index.size, len(names), (rec, lambda: np.stack([draws[n] for n in rec.param_names], axis=1), np.tile(f, (C, 1)))
+    lk = (g["data_vector"], g["invcov"], np.zeros(len(names)), np.full(len(names), np.inf), True)
+    return eng, like, templ, build, index.size, len(names), (rec, lambda: np.stack([draws[n] for n in rec.param_names], axis=1), np.tile(f, (C, 1))), lk
 
 
 def eval_logp_rate(ntr, ndata_per_tracer, nG, walkers=42):
@@ -145,7 +158,7 @@ def eval_logp_rate(ntr, ndata_per_tracer, nG, walkers=42):
 
 def probe(name, setup, C, N, ntr):
     rng = np.random.default_rng(1)
-    eng, like, templ, build, ndata, nG, (rec, theta_build, fC) = setup(C, N, rng)
+    eng, like, templ, build, ndata, nG, (rec, theta_build, fC), _ = setup(C, N, rng)
     rows = build()
     t_rows = med(build, 3)
     counts = np.full(C, N // C)
@@ -205,10 +218,63 @@ def probe(name, setup, C, N, ntr):
     return out
 
 
+def probe_datasets(name, setup, M, n, repeats=9):
+    """(a), (b), (c) of the module docstring for one shape; n draws per group"""
+    rng = np.random.default_rng(1)
+    eng, like, templ, _, ndata, nG, (rec, theta_build, fC), (data, invcov, loc, scale, jeff) = setup(1, M * n, rng)
+    eng.put("TEMPL", templ)
+    theta = theta_build()
+    chol = np.linalg.cholesky(np.linalg.inv(invcov))
+    Ds = np.stack([data] + [data + chol @ np.random.default_rng(100 + m).standard_normal(ndata) for m in range(1, M)])
+    off = n * np.arange(M + 1, dtype=np.int64)
+    kw = dict(grad=True, hess=True)
+    like.set_draw_recipe(rec)
+    plain = lambda: like.logp_draws_params(theta, [0, M * n], fC, **kw)
+    plain()
+    ts_c = times(plain, repeats)
+    out = {"shape": name, "datasets": M, "draws_per_group": n, "ndata": ndata, "nG": nG, "P": theta.shape[1],
+           "plain_ms": 1e3 * float(np.median(ts_c)), "plain_ms_spread": [1e3 * min(ts_c), 1e3 * max(ts_c)]}
+    if hasattr(like, "set_datasets"):
+        groups = (np.zeros(M, dtype=np.int32), np.arange(M, dtype=np.int32))
+        like.set_datasets(Ds)
+        call = lambda: like.logp_draws_params(theta, off, fC, groups=groups, **kw)
+        t0 = time.perf_counter()
+        got = call()
+        t_first = time.perf_counter() - t0
+        ts_a = times(call, repeats)
+        out.update({"groups_ms": 1e3 * float(np.median(ts_a)), "groups_ms_spread": [1e3 * min(ts_a), 1e3 * max(ts_a)],
+                    "groups_first_call_ms": 1e3 * t_first, "groups_Wg_bytes": 8 * M * (eng.ntracers * 24 + 1) ** 2})
+        t0 = time.perf_counter()
+        like.set_datasets(Ds)
+        out["set_datasets_ms"] = 1e3 * (time.perf_counter() - t0)
+
+    def loop():
+        res = []
+        for m in range(M):
+            lk = MarginalLikelihood(eng, like.index, Ds[m], invcov, loc, scale, jeffreys=jeff)
+            lk.set_draw_recipe(rec)
+            res.append(lk.logp_draws_params(theta[off[m] : off[m + 1]], [0, n], fC, **kw))
+        return res
+
+    res = loop()
+    if "groups_ms" in out:
+        assert all(np.allclose(np.concatenate([r[i] for r in res]), got[i], rtol=1e-9, atol=0) for i in (0,))
+    ts_b = times(loop, repeats)
+    out.update({"loop_ms": 1e3 * float(np.median(ts_b)), "loop_ms_spread": [1e3 * min(ts_b), 1e3 * max(ts_b)]})
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--draws", type=int, default=32768)
+    ap.add_argument("--draws", type=int, default=None)
     ap.add_argument("--walkers", type=int, default=32)
+    ap.add_argument("--datasets", type=int, default=0, help="M data vectors sharing the covariance: time the groups call, the per-vector loop and the plain call")
     a = ap.parse_args()
-    probe("marg", marg_setup, a.walkers, a.draws, 1)
-    probe("cfg3", cfg3_setup, a.walkers, a.draws, 3)
+    if a.datasets:
+        probe_datasets("marg", marg_setup, a.datasets, a.draws or 1024)
+        probe_datasets("cfg3", cfg3_setup, a.datasets, a.draws or 1024)
+    else:
+        probe("marg", marg_setup, a.walkers, a.draws or 32768, 1)
+        probe("cfg3", cfg3_setup, a.walkers, a.draws or 32768, 3)
