@@ -165,7 +165,6 @@ struct eftb_engine {
     size_t drw_grad_cap = 0;
     double* drw_hess = nullptr;     // eftb_draws_logp_hess_params: d2 ln P / d theta d theta [N][P][P]
     size_t drw_hess_cap = 0;
-    bool drw_lds_hess = false;      // the draws_logp_hess_params_kernel instantiations opted in to the large dynamic LDS
     // data sets sharing the likelihood's covariance (eftb_set_likelihood_datasets): dset_D [M][ndata] and dset_Ud = D C^-1; dset_gen counts
     // their changes.  eftb_draws_logp_params_datasets keeps Wg [G][J1][J1] of its last group table (grp_tab: walker [G] | dataset [G], on the
     // host and on the device) and reuses it while draw_gen, dset_gen and the table are those it was built from (grp_draw_gen = 0: none)
@@ -493,17 +492,16 @@ static void launch_synth(hipStream_t st, const SynthBatch& sb) {
 }
 
 // the same batch on gemm_direct_kernel (one wave per 16 x 32 tile, no LDS): for problems with few rows -- the first-stage products
-static int launch_gemm_direct(hipStream_t st, SynthBatch sb) {
+// (every K a multiple of 16: plan_stages)
+static void launch_gemm_direct(hipStream_t st, SynthBatch sb) {
     int end = 0;
     for (int i = 0; i < sb.n; ++i) {
         SynthDesc& d = sb.p[i];
-        if (d.K % 16) return fail("eftb_run: K = %d of a first-stage product is not a multiple of 16", d.K);
         d.wgx = (d.X + 31) / 32;
         end += d.wgx * ((d.M + 15) / 16);
         d.wg_end = end;
     }
     if (sb.n) hipLaunchKernelGGL((gemm_direct_kernel<4>), dim3(end), dim3(256), 0, st, sb);  // four waves split K
-    return 0;
 }
 
 // one of a pair of entry points onto the same body: the FFTLog size compiled in at NFFT = 256 (no size argument), read at run time otherwise
@@ -514,8 +512,8 @@ static void launch_nh(void (*fixed)(P...), void (*any)(P..., int), int nh, dim3 
 }
 
 // anti-diagonal sums of every loop matrix for the batch (shared by the k-space and the xi-space pieces), then the
-// synthesis rows selected by `sets` (build_rows_kernel)
-static int launch_antidiag_rows(eftb_engine* e, hipStream_t st, int B, int sets, const double* coef, const double* coefT, bool contracted = false) {
+// synthesis rows selected by `sets` (build_rows_kernel); the basis is 7 + 2 or 7 (plan_stages)
+static void launch_antidiag_rows(eftb_engine* e, hipStream_t st, int B, int sets, const double* coef, const double* coefT, bool contracted = false) {
     const eftb_config& c = e->c;
     const int nc = c.nbasis + (c.with_resum ? c.nbasis13 : 0);
     const int nh = cfg_nh(c), npow = 2 * nh + 1;
@@ -527,8 +525,6 @@ static int launch_antidiag_rows(eftb_engine* e, hipStream_t st, int B, int sets,
 #define PLK_ARGS c.max_batch, c.nbasis, coef, e->SAD, tb<double2>(e, EFTB_T_MLJ), tb<double2>(e, EFTB_T_LINVEC), e->buf[EFTB_B_BIAS], e->buf[EFTB_B_F], \
                  tb<double>(e, EFTB_T_L11), tb<double>(e, EFTB_T_LCT), tb<double>(e, EFTB_T_L22), tb<double>(e, EFTB_T_L13), tb<int>(e, EFTB_T_GRP), \
                  tb<double>(e, EFTB_T_EXP22), tb<double>(e, EFTB_T_EXPC), e->A22, e->A13, e->ACF, e->ALC
-    if (nc != 9 && nc != 7)
-        return fail("loop-matrix basis of dimension %d + %d is not instantiated (expected 7 + 2)", c.nbasis, c.with_resum ? c.nbasis13 : 0);
     if ((sets & 0x10) && !(contracted && WHATIF_SKIP(4))) {  // two waves per workgroup: two free wave slots on a CU are found sooner than four
         if (nc == 9) launch_nh(antidiag_kernel<9, 2>, antidiag_nh_kernel<9, 2>, nh, grid, dim3(128), st, AD_ARGS);
         else launch_nh(antidiag_kernel<7, 2>, antidiag_nh_kernel<7, 2>, nh, grid, dim3(128), st, AD_ARGS);
@@ -541,7 +537,6 @@ static int launch_antidiag_rows(eftb_engine* e, hipStream_t st, int B, int sets,
 #undef AD_ARGS
 #undef ROW_ARGS
 #undef PLK_ARGS
-    return 0;
 }
 
 // out[w][a][r][x] = sum_{l,k} T[w][l][r][k] * opT[(l,k)][(a,x)] on the FP64 matrix cores; the block changes shape
@@ -660,6 +655,20 @@ static void launch_prep_rows(eftb_engine* e, hipStream_t st, int B, bool first, 
 #undef PREP_ARGS
 }
 
+// the front of a direct-P_l run on the side stream: all operand rows and Q(f) in one launch (with the low-k tails where the grid has them)
+static void launch_prep_rows_qf(eftb_engine* e, hipStream_t st, int B) {
+    const eftb_config& c = e->c;
+#define PRQ_ARGS B, c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin), (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], \
+                 tb<double>(e, EFTB_T_LNKIN), tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), e->PA1, e->PA2, e->PA2T, e->PA3, \
+                 e->status + 2 * e->status_slot, c.Nl * c.Nl * e->Nn, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QPOLY), e->buf[EFTB_B_Q]
+    if (WHATIF_SKIP(1)) return;
+    if (c.ntail_lo || c.nxtail_lo)
+        hipLaunchKernelGGL(prep_rows_qf_lo_kernel, dim3(2 * B), dim3(256), (size_t)c.Nkin * sizeof(double), st, PRQ_ARGS, c.ntail_lo, c.nxtail_lo);
+    else
+        hipLaunchKernelGGL(prep_rows_qf_kernel, dim3(2 * B), dim3(256), (size_t)c.Nkin * sizeof(double), st, PRQ_ARGS);
+#undef PRQ_ARGS
+}
+
 static void queue_xy(eftb_engine* e, SynthBatch& sb, int B) {  // X(s), Y(s) [B][2][80] = [Pin | tail'] (BX BY ; TX TY)
     const eftb_config& c = e->c;
     queue_synth(sb, e->PA3, 0, 1, B, (int)kpad(c.Nkin + c.nxtail), tb<double>(e, EFTB_T_BXT), 2 * NS, e->buf[EFTB_B_XY], 0, nullptr, nullptr);
@@ -672,7 +681,7 @@ static void launch_irfilter(eftb_engine* e, hipStream_t st, int B, bool xy = tru
         launch_prep_rows(e, st, B, false, true);
         SynthBatch sb{};
         queue_xy(e, sb, B);
-        (void)launch_gemm_direct(st, sb);
+        launch_gemm_direct(st, sb);
     }
     hipLaunchKernelGGL(qf_kernel, dim3(B), dim3(256), 0, st, c.Nl * c.Nl * e->Nn, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QPOLY), e->buf[EFTB_B_Q]);
 }
@@ -829,44 +838,44 @@ static void timer_end(eftb_engine* e, hipStream_t st, int tslot) {
     if (tslot >= 0 && hipEventRecord(e->evT1[tslot], st) == hipSuccess) e->timer_busy[tslot] = true;
 }
 
-static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, bool nnlo_inline = false) {
+// with_NNLO: CctNNLO rides in the resummation records of the first pass when the batch is large enough for unsplit s sums (the main kernel then
+// accumulates PctNNLOl beside Pctl: no second resummation)
+static inline bool nnlo_fusable(const eftb_engine* e) {
     const eftb_config& c = e->c;
-    e->launch_B = B;
-    hipStream_t st = e->stream;
-    const int Nk = c.Nk, Nl = c.Nl;
-    double** b = e->buf;
-    // every configuration error is raised before the first launch: no half-issued run is left behind on the look-ahead stream
-    if ((mask & (EFTB_S_CF | EFTB_K_C22)) && !c.with_resum) return fail("eftb_run: stage CF needs with_resum=1");
-    if ((mask & (EFTB_S_RESUM | EFTB_K_RESUM)) && !c.with_resum) return fail("eftb_run: stage RESUM needs with_resum=1");
-    if ((mask & EFTB_S_AP) && !c.with_ap) return fail("eftb_run: stage AP needs with_ap=1");
-    if ((mask & EFTB_S_PROJECT) && e->tracer_ops.empty() && e->pipeline_op < 0) return fail("eftb_run: stage PROJECT needs eftb_set_pipeline_operator");
-    if ((mask & EFTB_S_LOGP) && !e->like_ndata) return fail("eftb_run: stage LOGP needs eftb_set_likelihood");
-    if ((mask & (EFTB_S_PROJECT | EFTB_S_LOGP)) && (B % e->ntr)) return fail("eftb_run: batch %d is not a multiple of the %d tracers per likelihood point", B, e->ntr);
+    return c.with_resum && c.Nl == 3 && e->resum_splits == 1 && !c.optiresum;
+}
+
+// The layout of one launch_stages_impl call: every decision that follows from the mask, the configuration and the engine's state as the call
+// finds it (plan_stages).  The stage functions read it and decide nothing of the kind themselves.  NOT in here: the pointers a run swaps (RSA /
+// RSA2, APP / APP2, the FrontSet, T3) and the event slots (back_step, rs_step, front_step) -- those are read where they are used, after the swaps.
+struct StagePlan {
+    // nnlo_pass: the linear stages (RESUM / AP / PROJECT) once more, on the NNLO block (pointers swapped in by launch_stages)
+    // nnlo_inline (launch_stages): this call carries the NNLO block through regrouping, resummation (fused accumulator), AP and REDUCE itself
+    bool nnlo_pass, nnlo_inline;
     // The IR filters / Q(f) and the AP prefix sums depend on the inputs only: when they are part of a longer stage set they
     // run on a side stream beside the (latency-bound) loop path and are joined right before their consumers.
-    const bool side_ir = !nnlo_pass && (mask & EFTB_S_RESUM) && c.with_resum && (mask & (EFTB_S_PREP | EFTB_S_LOOPS | EFTB_S_CF | EFTB_S_REGROUP));
-    const bool side_ap0 = !nnlo_pass && (mask & EFTB_S_AP) && c.with_ap && (mask & (EFTB_S_PREP | EFTB_S_LOOPS | EFTB_S_CF | EFTB_S_REGROUP | EFTB_S_RESUM));
+    // side_ap = side_ap0 && !direct (direct-P_l runs take the AP stage as the node quadrature on one row: no prefix sums, no knot weights)
+    bool side_ir, side_ap0, side_ap;
+    // with_NNLO: CctNNLO rides in the resummation records of the first pass when the batch is large enough for unsplit s sums (nnlo_fusable; not
+    // in the NNLO pass itself): the main kernel accumulates PctNNLOl beside Pctl (no second pass)
+    bool nnlo_fused;
     // cross-run overlap of the front half (see engine.pre): only for asynchronous runs whose inputs are already in place
-    // with_NNLO: CctNNLO rides in the resummation records of the first pass when the batch is large enough for unsplit s sums
-    const bool nnlo_fused = c.with_nnlo && c.with_resum && Nl == 3 && e->resum_splits == 1 && !c.optiresum;
     // (with_NNLO steps stay on one stream: with only the front half overlapped they measured 0.66 ms per 128 against 0.64 ms in line)
-    // nnlo_inline (launch_stages): this call carries the NNLO block through regrouping, resummation (fused accumulator), AP and REDUCE itself
-    const bool pre_side = (mask & EFTB_S_PREP) && (mask & EFTB_S_REGROUP) && e->prep_overlap && e->inputs_settled && !e->use_graphs && !nnlo_pass &&
-                          (!c.with_nnlo || nnlo_inline);
-    const bool ap_side = pre_side && e->ap_overlap && e->allow_back && (mask & EFTB_S_RESUM) && (mask & EFTB_S_AP);
-    if (!ap_side) join_back(e);
+    bool pre_side;
+    // ... and of the back half (spline, AP, reduce) on its own stream beside the next run's resummation (see engine.back)
+    bool ap_side;
     // three-stream runs keep the regrouping and the operand build of the resummation on the look-ahead stream as well: the main stream
     // then carries nothing but the resummation kernels, back to back
-    const bool ahead = ap_side && e->RSA2;
-    const int bslot = e->back_step & 1;  // evBack[bslot] was recorded two runs ago
-    const bool xy_in_prep = (mask & EFTB_S_PREP) && (mask & EFTB_S_RESUM) && c.with_resum && !nnlo_pass;  // X, Y ride with the first-stage GEMMs
+    bool ahead;
+    bool xy_in_prep;  // X, Y ride with the first-stage GEMMs
     // whole-pipeline runs regroup C22 / C13 into the resummation records directly (resum_prep_kernel): no regroup_cf_kernel, no Cloopl
     // buffer on the way (EFTB_B_CLOOPL then keeps what the last stand-alone REGROUP stage left there)
-    const bool fuse_cf = (mask & EFTB_S_REGROUP) && (mask & EFTB_S_RESUM) && c.with_resum && !c.optiresum && !c.with_nnlo && !nnlo_pass;
-    // P_l = sum_row b_row T[l][row]: two FMA chains split at msplit_cfg (the row split of ap_rows_kernel's half waves), everywhere
-    const int msplit_cfg = reduce_msplit(c);
-    const bool fuse_reduce = (mask & EFTB_S_AP) && (mask & EFTB_S_REDUCE) && !(mask & (EFTB_S_PROJECT | EFTB_S_LOGP)) && c.with_ap && e->ap_mode == 0 &&
-                             !c.with_nnlo && !nnlo_pass;
+    bool fuse_cf;
+    // P_l = sum_row b_row T[l][row]: two FMA chains split at msplit (the row split of ap_rows_kernel's half waves), everywhere
+    int msplit;
+    // REDUCE directly behind the AP stage: the bias contraction rides in the epilogue of ap_rows_kernel (and of the fallback tiles'
+    // ap_direct_kernel), in the summation order of reduce_kernel(msplit) -- no separate pass over the 33 MB of AP output
+    bool fuse_reduce;
     // direct-P_l runs (EFTB_O_PLK_DIRECT): the bias contraction first, then resummation and AP on ONE row per multipole (regroup_plk_kernel,
     // resum_prep_plk_kernel, resum_plk_kernel, spline / ap_rows on row 0); the template block is not produced
     // (only runs that also hold PREP, LOOPS and CF: the front of a direct run leaves CONTRACTED rows in Y22 / P13 / YCF / C11 / CCT, which is what
@@ -875,123 +884,222 @@ static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, b
     // alike: reference window.py:371-415, binning.py:131-162, chained.py:56-68 -- the operator takes ONE row per cosmology instead of 24) unless an
     // operator keeps a second matrix for the stochastic rows; and on every k grid (the AP stage of a direct run is the moment form on B-spline
     // pieces, which needs neither the knot-weight tables nor their grid limit).  LOGP runs stay templates-first: they need 1 + n_G contracted rows.
-    bool proj_plk = true;  // every operator of the PROJECT stage can act on the contracted row
+    bool proj_plk;  // every operator of the PROJECT stage can act on the contracted row
+    bool direct_tail, direct, direct_proj;
+    // ... and the per-s A operand of the Nl = 3 resummation (inputs only: Q(f), X, Y) is built on the side stream, off the chain
+    bool as_side;
+    // ... whose front runs a step ahead on the side stream (see FrontSet)
+    bool front_side;
+    // row counts of the configuration: the loop-matrix basis (7 + 2), the row lengths of the synthesis tables at this NFFT (528 / 288 at 256), the
+    // rows of a template block that go through the AP stage
+    int ncf, ksyn, klin, ap_nr;
+};
+
+// rows of one AP pass over a block.  nn: the NNLO block carries only the three counter-term rows 3-5 of every multipole: spline and AP touch
+// those alone
+struct ApRows {
+    bool dir, red;
+    int nr, rlo, rsel, msplit;
+};
+static ApRows ap_rows_of(const eftb_engine* e, const StagePlan& p, bool nn) {
+    const bool moments = e->ap_mode == 1;  // (works on whole blocks: the NNLO block's zero rows stay zero)
+    ApRows a;
+    a.dir = p.direct && !nn;  // direct-P_l runs: row 0 of every (cosmology, l) block is the only one that goes through the stage
+    a.red = p.fuse_reduce && !nn;
+    a.nr = a.dir ? 1 : nn ? (moments ? 21 : 6) : p.ap_nr;
+    // rows the spline data is needed for: [rlo, rlo + rsel) of every (cosmology, l) -- the counter-term rows of the NNLO block; on the fast
+    // path only the rows the stage distorts (Pstl passes through unless APst: 21 of 24 rows)
+    a.rlo = nn && !moments ? 3 : 0;
+    a.rsel = a.dir ? 1 : nn && !moments ? 3 : (e->ap_mode == 0 ? a.nr : NROW);
+    a.msplit = a.red ? p.msplit : (a.rlo + a.nr + 1) / 2;  // rows [rlo, msplit) / [msplit, nr) to the two half waves
+    return a;
+}
+
+// Fills the plan and does nothing else: no HIP call, no write to the engine.  Every configuration error of a run is raised here, before the
+// first launch: no half-issued run is left behind on the look-ahead streams.  (What stays with its stage: the shape of the template block as
+// PROJECT and LOGP find it, which the stages in front of them set.)
+static int plan_stages(const eftb_engine* e, int mask, int B, bool nnlo_pass, bool nnlo_inline, StagePlan* p) {
+    const eftb_config& c = e->c;
+    const int Nk = c.Nk, Nl = c.Nl;
+    if ((mask & (EFTB_S_CF | EFTB_K_C22)) && !c.with_resum) return fail("eftb_run: stage CF needs with_resum=1");
+    if ((mask & (EFTB_S_RESUM | EFTB_K_RESUM)) && !c.with_resum) return fail("eftb_run: stage RESUM needs with_resum=1");
+    if ((mask & EFTB_K_IRFILTER) && !(mask & EFTB_S_RESUM) && !c.with_resum) return fail("eftb_run: EFTB_K_IRFILTER needs with_resum=1");
+    if ((mask & EFTB_S_AP) && !c.with_ap) return fail("eftb_run: stage AP needs with_ap=1");
+    if ((mask & EFTB_S_PROJECT) && e->tracer_ops.empty() && e->pipeline_op < 0) return fail("eftb_run: stage PROJECT needs eftb_set_pipeline_operator");
+    if ((mask & EFTB_S_LOGP) && !e->like_ndata) return fail("eftb_run: stage LOGP needs eftb_set_likelihood");
+    if ((mask & (EFTB_S_PROJECT | EFTB_S_LOGP)) && (B % e->ntr)) return fail("eftb_run: batch %d is not a multiple of the %d tracers per likelihood point", B, e->ntr);
+    if ((mask & EFTB_S_LOGP) && (size_t)e->ntr * (e->like_nG + 1) * NROW * sizeof(double) > 64 * 1024)
+        return fail("eftb_run: stage LOGP: %d tracers x %d rows do not fit the coefficient block in LDS", e->ntr, e->like_nG + 1);
+    p->nnlo_pass = nnlo_pass;
+    p->nnlo_inline = nnlo_inline;
+    p->ncf = c.nbasis + (c.with_resum ? c.nbasis13 : 0);
+    p->ksyn = ksyn_of(cfg_nh(c));
+    p->klin = klin_of(cfg_nh(c));
+    p->ap_nr = c.ap_stochastic ? NROW : 21;
+    if ((mask & (EFTB_S_LOOPS | EFTB_S_CF | EFTB_K_P22 | EFTB_K_C22)) && p->ncf != 9 && p->ncf != 7)
+        return fail("loop-matrix basis of dimension %d + %d is not instantiated (expected 7 + 2)", c.nbasis, c.with_resum ? c.nbasis13 : 0);
+    p->side_ir = !nnlo_pass && (mask & EFTB_S_RESUM) && c.with_resum && (mask & (EFTB_S_PREP | EFTB_S_LOOPS | EFTB_S_CF | EFTB_S_REGROUP));
+    p->side_ap0 = !nnlo_pass && (mask & EFTB_S_AP) && c.with_ap && (mask & (EFTB_S_PREP | EFTB_S_LOOPS | EFTB_S_CF | EFTB_S_REGROUP | EFTB_S_RESUM));
+    p->nnlo_fused = c.with_nnlo && nnlo_fusable(e) && !nnlo_pass;
+    p->pre_side = (mask & EFTB_S_PREP) && (mask & EFTB_S_REGROUP) && e->prep_overlap && e->inputs_settled && !e->use_graphs && !nnlo_pass &&
+                  (!c.with_nnlo || nnlo_inline);
+    p->ap_side = p->pre_side && e->ap_overlap && e->allow_back && (mask & EFTB_S_RESUM) && (mask & EFTB_S_AP);
+    p->ahead = p->ap_side && e->RSA2;
+    p->xy_in_prep = (mask & EFTB_S_PREP) && (mask & EFTB_S_RESUM) && c.with_resum && !nnlo_pass;
+    p->fuse_cf = (mask & EFTB_S_REGROUP) && (mask & EFTB_S_RESUM) && c.with_resum && !c.optiresum && !c.with_nnlo && !nnlo_pass;
+    p->msplit = reduce_msplit(c);
+    p->fuse_reduce = (mask & EFTB_S_AP) && (mask & EFTB_S_REDUCE) && !(mask & (EFTB_S_PROJECT | EFTB_S_LOGP)) && c.with_ap && e->ap_mode == 0 &&
+                     !c.with_nnlo && !nnlo_pass;
+    p->proj_plk = true;
     if (mask & EFTB_S_PROJECT) {
         auto one = [&](int id) { return id >= 0 && id < (int)e->ops.size() && e->ops[id].st_op < 0 && e->ops[id].nl_in == Nl && e->ops[id].nx_in == Nk; };
-        if (e->tracer_ops.empty()) proj_plk = one(e->pipeline_op);
+        if (e->tracer_ops.empty()) p->proj_plk = one(e->pipeline_op);
         else
-            for (int t = 0; t < e->ntr; ++t) proj_plk = proj_plk && one(e->tracer_ops[t]) && e->ops[e->tracer_ops[t]].nl_out == e->ops[e->tracer_ops[0]].nl_out &&
-                                                        e->ops[e->tracer_ops[t]].nx_out == e->ops[e->tracer_ops[0]].nx_out;
+            for (int t = 0; t < e->ntr; ++t) p->proj_plk = p->proj_plk && one(e->tracer_ops[t]) && e->ops[e->tracer_ops[t]].nl_out == e->ops[e->tracer_ops[0]].nl_out &&
+                                                           e->ops[e->tracer_ops[t]].nx_out == e->ops[e->tracer_ops[0]].nx_out;
     }
-    const bool direct_tail = (mask & EFTB_S_AP) && (mask & EFTB_S_REDUCE) && !(mask & EFTB_S_LOGP) && c.with_ap && !c.with_nnlo && !nnlo_pass && proj_plk && e->PLK0;
-    const bool direct = e->plk_direct && direct_tail && fuse_cf && Nl == 3 && !c.dual_coef && !e->use_graphs &&
-                        (mask & EFTB_S_PREP) && (mask & EFTB_S_LOOPS) && (mask & EFTB_S_CF) && (mask & EFTB_S_REGROUP) && e->RSAS;
-    const bool direct_proj = direct && (mask & EFTB_S_PROJECT);
-    if (direct) e->run_direct = true;
-    e->plk_host_written = true;
-    // ... and the per-s A operand of the Nl = 3 resummation (inputs only: Q(f), X, Y) is built on the side stream, off the chain
-    const bool as_side = ahead && Nl == 3 && e->RSAS2 && !direct;
-    // ... whose front runs a step ahead on the side stream (see FrontSet)
-    const bool front_side = direct && ahead && e->alt.A22 && (mask & EFTB_S_PREP) && (mask & (EFTB_S_LOOPS | EFTB_S_CF)) && xy_in_prep;
-    hipStream_t fst = st;  // where the front's kernels go
-    const bool side_ap = side_ap0 && !direct;  // (direct-P_l runs take the AP stage as the node quadrature on one row: no prefix sums, no knot weights)
-    if ((side_ir || side_ap) && !pre_side) {
-        if (hipEventRecord(e->evFork, st) != hipSuccess || hipStreamWaitEvent(e->side, e->evFork, 0) != hipSuccess)
-            return fail("eftb_run: stream fork failed");
-        if (side_ir) launch_irfilter(e, e->side, B, !xy_in_prep);
-        if (hipEventRecord(e->evJoin, e->side) != hipSuccess) return fail("eftb_run: stream join failed");
-        if (side_ap) launch_ap_prefix(e, e->side, B);
-        if (hipEventRecord(e->evJoinAP, e->side) != hipSuccess) return fail("eftb_run: stream join failed");
+    p->direct_tail = (mask & EFTB_S_AP) && (mask & EFTB_S_REDUCE) && !(mask & EFTB_S_LOGP) && c.with_ap && !c.with_nnlo && !nnlo_pass && p->proj_plk && e->PLK0;
+    p->direct = e->plk_direct && p->direct_tail && p->fuse_cf && Nl == 3 && !c.dual_coef && !e->use_graphs &&
+                (mask & EFTB_S_PREP) && (mask & EFTB_S_LOOPS) && (mask & EFTB_S_CF) && (mask & EFTB_S_REGROUP) && e->RSAS;
+    p->direct_proj = p->direct && (mask & EFTB_S_PROJECT);
+    p->as_side = p->ahead && Nl == 3 && e->RSAS2 && !p->direct;
+    p->front_side = p->direct && p->ahead && e->alt.A22 && (mask & EFTB_S_PREP) && (mask & (EFTB_S_LOOPS | EFTB_S_CF)) && p->xy_in_prep;
+    p->side_ap = p->side_ap0 && !p->direct;
+    // K of the first-stage products (gemm_direct_kernel: four waves split K in steps of 16): P11 and the coefficients, X and Y
+    const bool xy = p->xy_in_prep || ((mask & (EFTB_S_RESUM | EFTB_K_IRFILTER)) && !nnlo_pass);
+    for (int K : {(mask & EFTB_S_PREP) ? (int)kpad(c.Nkin) : 0, (mask & EFTB_S_PREP) ? (int)kpad(c.Nkin + c.ntail) : 0, xy ? (int)kpad(c.Nkin + c.nxtail) : 0})
+        if (K % 16) return fail("eftb_run: K = %d of a first-stage product is not a multiple of 16", K);
+    // the AP passes of this call on the fast path (the main block or, in the NNLO pass, the NNLO block; in line: both)
+    for (int pass = 0; pass < ((mask & EFTB_S_AP) && e->ap_mode == 0 ? (nnlo_inline ? 2 : 1) : 0); ++pass) {
+        const ApRows a = ap_rows_of(e, *p, pass ? true : nnlo_pass);
+        const int nh = (a.nr - a.rlo + 1) / 2;
+        if (!a.dir && (a.rlo + 2 * nh > NROW || a.msplit - a.rlo > nh || a.nr - a.msplit > nh || (nh != 2 && nh != 11 && nh != 12)))
+            return fail("eftb_run: AP rows [%d, %d) split at %d do not fit the window layouts built into ap_rows_kernel", a.rlo, a.nr, a.msplit);
     }
-    bool joined = !side_ir, joined_ap = !side_ap;
-    if (mask & EFTB_S_PREP) {
-        hipStream_t st0 = st;
-        if (front_side) {
-            // the front of this run goes to the side stream, into the set the run before the previous one used (its readers -- syntheses,
-            // contraction, operand build -- have signalled evFrontFree); the rest of the chain (pre stream) picks up at the syntheses
-            st = e->pre;
-            eftb_engine::FrontSet& a = e->alt;
-            std::swap(e->PA1, a.PA1); std::swap(e->PA2, a.PA2); std::swap(e->PA2T, a.PA2T); std::swap(e->PA3, a.PA3); std::swap(e->coefT, a.coefT);
-            std::swap(e->A22, a.A22); std::swap(e->A13, a.A13); std::swap(e->ACF, a.ACF); std::swap(e->ALC, a.ALC); std::swap(e->SAD, a.SAD);
-            std::swap(b[EFTB_B_P11], a.P11); std::swap(b[EFTB_B_COEF], a.COEF); std::swap(b[EFTB_B_XY], a.XY); std::swap(b[EFTB_B_Q], a.Q);
-            ++e->epoch;  // (graphs captured earlier hold the other set's pointers)
-            fst = e->side;
-            if (hipStreamWaitEvent(fst, e->evFrontFree[e->front_step & 1], 0) != hipSuccess) return fail("eftb_run: stream wait failed");
-            if (!e->prev_front_side && hipStreamWaitEvent(fst, e->evInFree, 0) != hipSuccess) return fail("eftb_run: stream wait failed");
-            joined = joined_ap = true;  // (X, Y, Q(f) reach the rest of the chain with evFront; no AP tables in a direct run)
-        } else if (pre_side) {
-            st = e->pre;
-            if (hipStreamWaitEvent(st, e->evInFree, 0) != hipSuccess) return fail("eftb_run: stream wait failed");
-            // (X, Y of the previous run are also read by its operand build on the side stream, which evInFree does not cover)
-            if (as_side && hipStreamWaitEvent(st, e->evAS, 0) != hipSuccess) return fail("eftb_run: stream wait failed");
-            // the input-only kernels (IR filters / Q(f); AP prefix sums and knot weights) get their own low-priority stream beside the front
-            // half: X, Y, Q are free since the previous run built its resummation operands (evInFree); the AP tables alternate between two
-            // sets because the previous run's AP reads its own late (the set written here was last read two runs ago: evBack)
-            if (side_ir || side_ap) {
-                if (hipStreamWaitEvent(e->side, e->evInFree, 0) != hipSuccess) return fail("eftb_run: stream wait failed");
-                if (side_ir) launch_irfilter(e, e->side, B, !xy_in_prep);
-                if (hipEventRecord(e->evJoin, e->side) != hipSuccess) return fail("eftb_run: stream join failed");
-                if (side_ap) {
-                    std::swap(e->APP, e->APP2);
-                    std::swap(e->APR, e->APR2);
-                    std::swap(e->APW, e->APW2);
-                    std::swap(e->API, e->API2);
-                    std::swap(e->APM, e->APM2);
-                    if (ap_side && hipStreamWaitEvent(e->side, e->evBack[bslot], 0) != hipSuccess) return fail("eftb_run: stream wait failed");  // its reader
-                    launch_ap_prefix(e, e->side, B);
-                }
-                if (hipEventRecord(e->evJoinAP, e->side) != hipSuccess) return fail("eftb_run: stream join failed");
-            }
+    return 0;
+}
+
+// The cursor of a run through the five streams: where the chain's next kernel goes (st), where the front's kernels go (fst), and whether the
+// chain has picked up what the side stream produced (joined: X, Y, Q(f); joined_ap: the AP tables)
+struct StageRun {
+    eftb_engine* e;
+    int mask, B;
+    StagePlan p;
+    hipStream_t st, fst;
+    bool joined, joined_ap;
+    // `to` goes on behind what `from` holds so far (what: fork / join)
+    int hand_over(hipEvent_t ev, hipStream_t from, hipStream_t to, const char* what) const {
+        return hipEventRecord(ev, from) != hipSuccess || hipStreamWaitEvent(to, ev, 0) != hipSuccess ? fail("eftb_run: stream %s failed", what) : 0;
+    }
+    int wait_on(hipStream_t s, hipEvent_t ev, const char* what = "wait") const {
+        return hipStreamWaitEvent(s, ev, 0) != hipSuccess ? fail("eftb_run: stream %s failed", what) : 0;
+    }
+    int record(hipEvent_t ev, hipStream_t s, const char* what = "event record") const {
+        return hipEventRecord(ev, s) != hipSuccess ? fail("eftb_run: %s failed", what) : 0;
+    }
+};
+
+// the input-only kernels (IR filters / Q(f); AP prefix sums and knot weights) on the side stream, behind whatever the caller made it wait for
+static int fork_side(StageRun& r) {
+    eftb_engine* e = r.e;
+    const StagePlan& p = r.p;
+    if (p.side_ir) launch_irfilter(e, e->side, r.B, !p.xy_in_prep);
+    if (int rc = r.record(e->evJoin, e->side, "stream join")) return rc;
+    if (p.side_ap) {
+        if (p.pre_side) {
+            // the AP tables alternate between two sets because the previous run's AP reads its own late (the set written here was last read
+            // two runs ago: evBack)
+            std::swap(e->APP, e->APP2);
+            std::swap(e->APR, e->APR2);
+            std::swap(e->APW, e->APW2);
+            std::swap(e->API, e->API2);
+            std::swap(e->APM, e->APM2);
+            if (p.ap_side)  // its reader
+                if (int rc = r.wait_on(e->side, e->evBack[e->back_step & 1])) return rc;
         }
-        // operand rows, then every first-stage product in one launch on the matrix cores: P11, the FFTLog coefficients (and their
-        // cosmology-contiguous transpose for the anti-diagonal pass), the second coefficient set of IRcutoff "loop" / "resum" (reference
-        // pybird.py:1151-1160), and X(s), Y(s) when a resummation follows in this run
-        if (!front_side) fst = st;
-        if (front_side && WHATIF_SKIP(1)) {
-        } else if (front_side && (c.ntail_lo || c.nxtail_lo))  // operand rows (with the low-k tails) and Q(f) in one launch
-            hipLaunchKernelGGL(prep_rows_qf_lo_kernel, dim3(2 * B), dim3(256), (size_t)c.Nkin * sizeof(double), fst, B, c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin),
-                               (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], tb<double>(e, EFTB_T_LNKIN),
-                               tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), e->PA1, e->PA2, e->PA2T, e->PA3,
-                               e->status + 2 * e->status_slot, c.Nl * c.Nl * e->Nn, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QPOLY), e->buf[EFTB_B_Q],
-                               c.ntail_lo, c.nxtail_lo);
-        else if (front_side)  // operand rows and Q(f) in one launch
-            hipLaunchKernelGGL(prep_rows_qf_kernel, dim3(2 * B), dim3(256), (size_t)c.Nkin * sizeof(double), fst, B, c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin),
-                               (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], tb<double>(e, EFTB_T_LNKIN),
-                               tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), e->PA1, e->PA2, e->PA2T, e->PA3,
-                               e->status + 2 * e->status_slot, c.Nl * c.Nl * e->Nn, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QPOLY), e->buf[EFTB_B_Q]);
-        else
-        launch_prep_rows(e, fst, B, true, xy_in_prep);
-        {
-            SynthBatch sb{};
-            const int KP1 = (int)kpad(c.Nkin), KP2 = (int)kpad(c.Nkin + c.ntail), NC2 = 2 * cfg_nch(c);
-            queue_synth(sb, e->PA1, 0, 1, B, KP1, tb<double>(e, EFTB_T_SKT), Nk, b[EFTB_B_P11], 0, nullptr, nullptr);
-            queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT), NC2, b[EFTB_B_COEF], 0, nullptr, nullptr);
-            queue_synth(sb, tb<double>(e, EFTB_T_ECT), KP2, NC2, 1, KP2, e->PA2T, c.max_batch, e->coefT, c.max_batch, nullptr, nullptr);
-            if (c.dual_coef) {
-                queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT2), NC2, e->coef2, 0, nullptr, nullptr);
-                queue_synth(sb, tb<double>(e, EFTB_T_GCT2T), KP2, NC2, 1, KP2, e->PA2T, c.max_batch, e->coefT2, c.max_batch, nullptr, nullptr);
-            }
-            if (xy_in_prep) queue_xy(e, sb, B);
-            if (!(front_side && WHATIF_SKIP(2)))
-                if (int rc = launch_gemm_direct(fst, sb)) return rc;
-            if (front_side) trace_point(e, 10, fst);
+        launch_ap_prefix(e, e->side, r.B);
+    }
+    return r.record(e->evJoinAP, e->side, "stream join");
+}
+
+// PREP: operand rows, then every first-stage product in one launch on the matrix cores: P11, the FFTLog coefficients (and their
+// cosmology-contiguous transpose for the anti-diagonal pass), the second coefficient set of IRcutoff "loop" / "resum" (reference
+// pybird.py:1151-1160), and X(s), Y(s) when a resummation follows in this run
+static int stage_prep(StageRun& r) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    const StagePlan& p = r.p;
+    const int B = r.B;
+    double** b = e->buf;
+    if (!(r.mask & EFTB_S_PREP)) return 0;
+    const hipStream_t st0 = r.st;
+    if (p.front_side) {
+        // the front of this run goes to the side stream, into the set the run before the previous one used (its readers -- syntheses,
+        // contraction, operand build -- have signalled evFrontFree); the rest of the chain (pre stream) picks up at the syntheses
+        r.st = e->pre;
+        eftb_engine::FrontSet& a = e->alt;
+        std::swap(e->PA1, a.PA1); std::swap(e->PA2, a.PA2); std::swap(e->PA2T, a.PA2T); std::swap(e->PA3, a.PA3); std::swap(e->coefT, a.coefT);
+        std::swap(e->A22, a.A22); std::swap(e->A13, a.A13); std::swap(e->ACF, a.ACF); std::swap(e->ALC, a.ALC); std::swap(e->SAD, a.SAD);
+        std::swap(b[EFTB_B_P11], a.P11); std::swap(b[EFTB_B_COEF], a.COEF); std::swap(b[EFTB_B_XY], a.XY); std::swap(b[EFTB_B_Q], a.Q);
+        ++e->epoch;  // (graphs captured earlier hold the other set's pointers)
+        r.fst = e->side;
+        if (int rc = r.wait_on(r.fst, e->evFrontFree[e->front_step & 1])) return rc;
+        if (!e->prev_front_side)
+            if (int rc = r.wait_on(r.fst, e->evInFree)) return rc;
+        r.joined = r.joined_ap = true;  // (X, Y, Q(f) reach the rest of the chain with evFront; no AP tables in a direct run)
+    } else if (p.pre_side) {
+        r.st = e->pre;
+        if (int rc = r.wait_on(r.st, e->evInFree)) return rc;
+        // (X, Y of the previous run are also read by its operand build on the side stream, which evInFree does not cover)
+        if (p.as_side)
+            if (int rc = r.wait_on(r.st, e->evAS)) return rc;
+        // the input-only kernels get their own low-priority stream beside the front half: X, Y, Q are free since the previous run built its
+        // resummation operands (evInFree)
+        if (p.side_ir || p.side_ap) {
+            if (int rc = r.wait_on(e->side, e->evInFree)) return rc;
+            if (int rc = fork_side(r)) return rc;
         }
-        if (as_side) {  // behind the AP tables on the side stream; the set written here was last read by the resummation two runs ago
-            if (xy_in_prep && (hipEventRecord(e->evXY, st) != hipSuccess || hipStreamWaitEvent(e->side, e->evXY, 0) != hipSuccess))
-                return fail("eftb_run: stream join failed");
-            std::swap(e->RSAS, e->RSAS2);
-            if (hipStreamWaitEvent(e->side, e->evRsDone[e->rs_step & 1], 0) != hipSuccess) return fail("eftb_run: stream wait failed");
-            launch_resum_as(e, e->side, B);
-            if (hipEventRecord(e->evAS, e->side) != hipSuccess) return fail("eftb_run: event record failed");
+    }
+    if (!p.front_side) r.fst = r.st;
+    if (p.front_side) launch_prep_rows_qf(e, r.fst, B);  // operand rows and Q(f) in one launch
+    else launch_prep_rows(e, r.fst, B, true, p.xy_in_prep);
+    {
+        SynthBatch sb{};
+        const int KP1 = (int)kpad(c.Nkin), KP2 = (int)kpad(c.Nkin + c.ntail), NC2 = 2 * cfg_nch(c);
+        queue_synth(sb, e->PA1, 0, 1, B, KP1, tb<double>(e, EFTB_T_SKT), c.Nk, b[EFTB_B_P11], 0, nullptr, nullptr);
+        queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT), NC2, b[EFTB_B_COEF], 0, nullptr, nullptr);
+        queue_synth(sb, tb<double>(e, EFTB_T_ECT), KP2, NC2, 1, KP2, e->PA2T, c.max_batch, e->coefT, c.max_batch, nullptr, nullptr);
+        if (c.dual_coef) {
+            queue_synth(sb, e->PA2, 0, 1, B, KP2, tb<double>(e, EFTB_T_GCT2), NC2, e->coef2, 0, nullptr, nullptr);
+            queue_synth(sb, tb<double>(e, EFTB_T_GCT2T), KP2, NC2, 1, KP2, e->PA2T, c.max_batch, e->coefT2, c.max_batch, nullptr, nullptr);
         }
-        if (!pre_side) st = st0;
+        if (p.xy_in_prep) queue_xy(e, sb, B);
+        if (!(p.front_side && WHATIF_SKIP(2))) launch_gemm_direct(r.fst, sb);
+        if (p.front_side) trace_point(e, 10, r.fst);
+    }
+    if (p.as_side) {  // behind the AP tables on the side stream; the set written here was last read by the resummation two runs ago
+        if (p.xy_in_prep)
+            if (int rc = r.hand_over(e->evXY, r.st, e->side, "join")) return rc;
+        std::swap(e->RSAS, e->RSAS2);
+        if (int rc = r.wait_on(e->side, e->evRsDone[e->rs_step & 1])) return rc;
+        launch_resum_as(e, e->side, B);
+        if (int rc = r.record(e->evAS, e->side)) return rc;
     }
     // with pre_side the whole front half (first stage, anti-diagonal sums, rows, syntheses, expansions: inputs -> P22, P13, C11, Cct, CC)
     // stays on the `pre` stream; the main stream picks up at the regrouping
-    hipStream_t st_main = e->stream;
-    if ((mask & (EFTB_S_CF | EFTB_K_C22)) && !c.with_resum) return fail("eftb_run: stage CF needs with_resum=1");
-    // the anti-diagonal sums serve both the k-space and the xi-space pieces: one pass, then the synthesis rows of
-    // whatever is requested (bit 0/1: quadratic rows of k / xi space, bit 2/3: single-sum rows, bit 4: the sums themselves)
+    if (!p.pre_side) r.st = st0;
+    return 0;
+}
+
+// LOOPS / CF: the anti-diagonal sums serve both the k-space and the xi-space pieces: one pass, then the synthesis rows of
+// whatever is requested (bit 0/1: quadratic rows of k / xi space, bit 2/3: single-sum rows, bit 4: the sums themselves); every synthesis of the
+// requested pieces in one launch, then both expansions in one launch
+static int stage_loops(StageRun& r) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    const StagePlan& p = r.p;
+    const int mask = r.mask, B = r.B, Nk = c.Nk, Nl = c.Nl;
+    double** b = e->buf;
     if (mask & (EFTB_S_LOOPS | EFTB_S_CF | EFTB_K_P22 | EFTB_K_C22)) {
         int sets = 0x10;
         if (mask & (EFTB_S_LOOPS | EFTB_K_P22)) sets |= 0x1;
@@ -999,359 +1107,419 @@ static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, b
         if (mask & (EFTB_S_CF | EFTB_K_C22)) sets |= 0x2;
         if (mask & EFTB_S_CF) sets |= 0x8;
         if (!c.dual_coef) {
-            if (int rc = launch_antidiag_rows(e, front_side ? fst : st, B, sets, b[EFTB_B_COEF], e->coefT, direct)) return rc;
-            if (front_side) trace_point(e, 1, fst);
-            if (front_side && (hipEventRecord(e->evFront, fst) != hipSuccess || hipStreamWaitEvent(st, e->evFront, 0) != hipSuccess))
-                return fail("eftb_run: stream join failed");
-            if (front_side) trace_point(e, 2, st);
+            launch_antidiag_rows(e, p.front_side ? r.fst : r.st, B, sets, b[EFTB_B_COEF], e->coefT, p.direct);
+            if (p.front_side) {
+                trace_point(e, 1, r.fst);
+                if (int rc = r.hand_over(e->evFront, r.fst, r.st, "join")) return rc;
+                trace_point(e, 2, r.st);
+            }
         } else {  // k-space rows from the first coefficient set, xi-space rows from the second (the sums are recomputed in between)
-            if (sets & 0x5)
-                if (int rc = launch_antidiag_rows(e, st, B, (sets & 0x5) | 0x10, b[EFTB_B_COEF], e->coefT)) return rc;
-            if (sets & 0xa)
-                if (int rc = launch_antidiag_rows(e, st, B, (sets & 0xa) | 0x10, e->coef2, e->coefT2)) return rc;
+            if (sets & 0x5) launch_antidiag_rows(e, r.st, B, (sets & 0x5) | 0x10, b[EFTB_B_COEF], e->coefT);
+            if (sets & 0xa) launch_antidiag_rows(e, r.st, B, (sets & 0xa) | 0x10, e->coef2, e->coefT2);
         }
     }
-    {
-        // every synthesis of the requested pieces in one launch, then both expansions in one launch
-        SynthBatch sb{};
-        const bool k22 = mask & (EFTB_S_LOOPS | EFTB_K_P22), c22 = mask & (EFTB_S_CF | EFTB_K_C22);
-        // (only the rows in use: 7 of the 8 padded basis rows per cosmology, Nl (7 + 2) = 27 of the 32 weighted ones -- 10 % of the launch's
-        // matrix-core work was padding; the padded rows of Y22 / YCF stay at their initial zeros and meet zero columns in expand_kernel)
-        const int ncf = c.nbasis + (c.with_resum ? c.nbasis13 : 0);
-        const int ksyn = ksyn_of(cfg_nh(c)), klin = klin_of(cfg_nh(c));  // row lengths of this NFFT (528 / 288 at 256)
-        // (direct-P_l runs: 3 contracted rows per cosmology in each of these three -- same strides, fewer rows)
-        if (k22) queue_synth(sb, e->A22, (long long)BAS22 * ksyn, B, direct ? 3 : c.nbasis, ksyn, tb<double>(e, EFTB_T_SYNK), Nk, e->Y22, (long long)BAS22 * Nk, nullptr, nullptr);
-        if (c22) queue_synth(sb, e->ACF, (long long)BASC * ksyn, B, direct ? 3 : Nl * ncf, ksyn, tb<double>(e, EFTB_T_SYNS), NS, e->YCF, (long long)BASC * NS, nullptr, nullptr);
-        if (mask & EFTB_S_LOOPS)
-            queue_synth(sb, e->A13, 10LL * klin, B, direct ? 3 : 10, klin, tb<double>(e, EFTB_T_LINK), Nk, b[EFTB_B_P13], 10LL * Nk, b[EFTB_B_P11], nullptr);
-        if (mask & EFTB_S_CF) {
-            const long long ag = (c.with_nnlo ? 3LL : 2LL) * Nl * klin;
-            queue_synth(sb, e->ALC, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_C11], (long long)Nl * NS, nullptr, nullptr);
-            queue_synth(sb, e->ALC + (size_t)Nl * klin, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCT], (long long)Nl * NS,
-                        nullptr, e->sm2);
-            if (c.with_nnlo)  // makeCctNNLO (reference pybird.py:1098-1101)
-                queue_synth(sb, e->ALC + (size_t)2 * Nl * klin, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCTN], (long long)Nl * NS,
-                            nullptr, e->sm4);
-        }
-        {
-            const int tslot = (mask & EFTB_S_REGROUP) ? timer_begin(e, st, 1) : -1;
-            if (direct && WHATIF_SKIP(16)) {
-            } else launch_synth(st, sb);
-            timer_end(e, st, tslot);
-        }
-        if ((k22 || c22) && !direct) {  // (direct-P_l runs contract the basis rows themselves: regroup_plk_kernel, resum_prep_plk_kernel)
-            const int n22 = k22 ? ((Nk + 63) / 64) * ((28 + EXP_RPB - 1) / EXP_RPB) * B : 0;
-            const int ncf = c22 ? ((NS + 63) / 64) * ((Nl * 38 + EXP_RPB - 1) / EXP_RPB) * B : 0;
-            hipLaunchKernelGGL(expand_kernel, dim3(n22 + ncf), dim3(64), 0, st, n22, Nk, B, e->Y22, tb<double>(e, EFTB_T_EXP22), b[EFTB_B_P22], Nl * 38,
-                               e->YCF, c22 ? tb<double>(e, EFTB_T_EXPC) : nullptr, b[EFTB_B_CC]);
-        }
+    const hipStream_t st = r.st;
+    SynthBatch sb{};
+    const bool k22 = mask & (EFTB_S_LOOPS | EFTB_K_P22), c22 = mask & (EFTB_S_CF | EFTB_K_C22);
+    // (only the rows in use: 7 of the 8 padded basis rows per cosmology, Nl (7 + 2) = 27 of the 32 weighted ones -- 10 % of the launch's
+    // matrix-core work was padding; the padded rows of Y22 / YCF stay at their initial zeros and meet zero columns in expand_kernel)
+    const int ksyn = p.ksyn, klin = p.klin;
+    // (direct-P_l runs: 3 contracted rows per cosmology in each of these three -- same strides, fewer rows)
+    if (k22) queue_synth(sb, e->A22, (long long)BAS22 * ksyn, B, p.direct ? 3 : c.nbasis, ksyn, tb<double>(e, EFTB_T_SYNK), Nk, e->Y22, (long long)BAS22 * Nk, nullptr, nullptr);
+    if (c22) queue_synth(sb, e->ACF, (long long)BASC * ksyn, B, p.direct ? 3 : Nl * p.ncf, ksyn, tb<double>(e, EFTB_T_SYNS), NS, e->YCF, (long long)BASC * NS, nullptr, nullptr);
+    if (mask & EFTB_S_LOOPS)
+        queue_synth(sb, e->A13, 10LL * klin, B, p.direct ? 3 : 10, klin, tb<double>(e, EFTB_T_LINK), Nk, b[EFTB_B_P13], 10LL * Nk, b[EFTB_B_P11], nullptr);
+    if (mask & EFTB_S_CF) {
+        const long long ag = (c.with_nnlo ? 3LL : 2LL) * Nl * klin;
+        queue_synth(sb, e->ALC, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_C11], (long long)Nl * NS, nullptr, nullptr);
+        queue_synth(sb, e->ALC + (size_t)Nl * klin, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCT], (long long)Nl * NS,
+                    nullptr, e->sm2);
+        if (c.with_nnlo)  // makeCctNNLO (reference pybird.py:1098-1101)
+            queue_synth(sb, e->ALC + (size_t)2 * Nl * klin, ag, B, Nl, klin, tb<double>(e, EFTB_T_LINS), NS, b[EFTB_B_CCTN], (long long)Nl * NS,
+                        nullptr, e->sm4);
     }
-    if (pre_side && !ahead) {
-        if (hipEventRecord(e->evPrep, st) != hipSuccess || hipStreamWaitEvent(st_main, e->evPrep, 0) != hipSuccess) return fail("eftb_run: stream join failed");
-        st = st_main;
+    const int tslot = (mask & EFTB_S_REGROUP) ? timer_begin(e, st, 1) : -1;
+    if (!(p.direct && WHATIF_SKIP(16))) launch_synth(st, sb);
+    timer_end(e, st, tslot);
+    if ((k22 || c22) && !p.direct) {  // (direct-P_l runs contract the basis rows themselves: regroup_plk_kernel, resum_prep_plk_kernel)
+        const int n22 = k22 ? ((Nk + 63) / 64) * ((28 + EXP_RPB - 1) / EXP_RPB) * B : 0;
+        const int ncf = c22 ? ((NS + 63) / 64) * ((Nl * 38 + EXP_RPB - 1) / EXP_RPB) * B : 0;
+        hipLaunchKernelGGL(expand_kernel, dim3(n22 + ncf), dim3(64), 0, st, n22, Nk, B, e->Y22, tb<double>(e, EFTB_T_EXP22), b[EFTB_B_P22], Nl * 38,
+                           e->YCF, c22 ? tb<double>(e, EFTB_T_EXPC) : nullptr, b[EFTB_B_CC]);
     }
-    if (ap_side) {
+    return 0;
+}
+
+// REGROUP: the template block from P11, P22, P13 (and Cloopl from CC unless the resummation regroups it itself)
+static int stage_regroup(StageRun& r) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    const StagePlan& p = r.p;
+    const int B = r.B, Nk = c.Nk, Nl = c.Nl;
+    double** b = e->buf;
+    if (p.pre_side && !p.ahead) {
+        if (int rc = r.hand_over(e->evPrep, r.st, e->stream, "join")) return rc;
+        r.st = e->stream;
+    }
+    if (p.ap_side) {
         // regroup into the block the run before the previous one left its AP output in (its readers are done: evBack)
-        if (hipStreamWaitEvent(st, e->evBack[bslot], 0) != hipSuccess) return fail("eftb_run: stream wait failed");
+        if (int rc = r.wait_on(r.st, e->evBack[e->back_step & 1])) return rc;
         std::swap(b[EFTB_B_TEMPL], e->T3);
-        if (nnlo_inline) std::swap(b[EFTB_B_TEMPLN], e->T3N);
+        if (p.nnlo_inline) std::swap(b[EFTB_B_TEMPLN], e->T3N);
     }
-    if (mask & EFTB_S_REGROUP) {
-        if (direct) {  // (regroup_plk rides in the launch of the operand build below: back_prep_plk_kernel)
-        } else
+    if (!(r.mask & EFTB_S_REGROUP)) return 0;
+    const hipStream_t st = r.st;
+    if (!p.direct)  // (regroup_plk rides in the launch of the operand build of the resummation: back_prep_plk_kernel)
         hipLaunchKernelGGL(regroup_kernel, dim3((Nk + 255) / 256, B, Nl), dim3(256), 0, st, Nk, Nl, tb<double>(e, EFTB_T_K), b[EFTB_B_F],
                            b[EFTB_B_P11], b[EFTB_B_P22], b[EFTB_B_P13], tb<double>(e, EFTB_T_L11), tb<double>(e, EFTB_T_LCT),
                            tb<double>(e, EFTB_T_L22), tb<double>(e, EFTB_T_L13), tb<int>(e, EFTB_T_GRP), b[EFTB_B_TEMPL]);
-        if (c.with_nnlo)
-            hipLaunchKernelGGL(nnlo_rows_kernel, dim3((Nk + 255) / 256, B, Nl), dim3(256), 0, st, Nk, Nl, tb<double>(e, EFTB_T_K), b[EFTB_B_P11],
-                               tb<double>(e, EFTB_T_LCTN), b[EFTB_B_TEMPLN]);
-        if (c.with_resum && !fuse_cf)
-            hipLaunchKernelGGL(regroup_cf_kernel, dim3(12, Nl, B), dim3(128), 0, st, Nl, b[EFTB_B_F], b[EFTB_B_CC], tb<double>(e, EFTB_T_L22),
-                               tb<double>(e, EFTB_T_L13), tb<int>(e, EFTB_T_GRP), b[EFTB_B_CLOOPL]);
-        // nothing later in this run reads the front half's outputs (P11, coefficients, P22, P13, CC; C11 / Cct only if a resummation
-        // follows): the next run's front half may overwrite them from here on
-        if (!(mask & EFTB_S_RESUM) && !e->use_graphs && !nnlo_pass && hipEventRecord(e->evInFree, st) != hipSuccess)
-            return fail("eftb_run: event record failed");
+    if (c.with_nnlo)
+        hipLaunchKernelGGL(nnlo_rows_kernel, dim3((Nk + 255) / 256, B, Nl), dim3(256), 0, st, Nk, Nl, tb<double>(e, EFTB_T_K), b[EFTB_B_P11],
+                           tb<double>(e, EFTB_T_LCTN), b[EFTB_B_TEMPLN]);
+    if (c.with_resum && !p.fuse_cf)
+        hipLaunchKernelGGL(regroup_cf_kernel, dim3(12, Nl, B), dim3(128), 0, st, Nl, b[EFTB_B_F], b[EFTB_B_CC], tb<double>(e, EFTB_T_L22),
+                           tb<double>(e, EFTB_T_L13), tb<int>(e, EFTB_T_GRP), b[EFTB_B_CLOOPL]);
+    // nothing later in this run reads the front half's outputs (P11, coefficients, P22, P13, CC; C11 / Cct only if a resummation
+    // follows): the next run's front half may overwrite them from here on
+    if (!(r.mask & EFTB_S_RESUM) && !e->use_graphs && !p.nnlo_pass)
+        if (int rc = r.record(e->evInFree, st)) return rc;
+    return 0;
+}
+
+// RESUM (EFTB_K_IRFILTER / EFTB_K_RESUM: its two halves alone): operands from Q(f), X, Y and the CF pieces, then the main kernel
+static int stage_resum(StageRun& r) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    const StagePlan& p = r.p;
+    const int mask = r.mask, B = r.B, Nk = c.Nk, Nl = c.Nl;
+    double** b = e->buf;
+    if ((mask & EFTB_K_IRFILTER) && !(mask & EFTB_S_RESUM)) launch_irfilter(e, r.st, B);
+    if (!(mask & (EFTB_S_RESUM | EFTB_K_RESUM))) return 0;
+    hipStream_t st = r.st;
+    const bool full = mask & EFTB_S_RESUM;  // EFTB_K_RESUM alone: only the main kernel, on the operands of an earlier full run
+    const bool direct = p.direct, nnlo_pass = p.nnlo_pass;
+    if (full && !p.side_ir && !nnlo_pass) launch_irfilter(e, st, B);  // X, Y, Q(f) of the first pass stay valid
+    if (!r.joined) {
+        if (int rc = r.wait_on(st, e->evJoin, "join")) return rc;
+        r.joined = true;
     }
-    if ((mask & EFTB_K_IRFILTER) && !(mask & EFTB_S_RESUM)) {
-        if (!c.with_resum) return fail("eftb_run: EFTB_K_IRFILTER needs with_resum=1");
-        launch_irfilter(e, st, B);
+    const double *c11 = b[EFTB_B_C11], *cct = b[EFTB_B_CCT], *cloopl = b[EFTB_B_CLOOPL];
+    if (c.optiresum && full) {  // Resum.extractBAO (reference pybird.py:1382-1400) into scratch: the stage inputs stay as the CF stage left them
+        double *x11 = e->XB, *xct = x11 + (size_t)c.max_batch * Nl * NS, *xl = xct + (size_t)c.max_batch * Nl * NS;
+        hipLaunchKernelGGL(extract_bao_kernel, dim3(B * Nl), dim3(128), 0, st, tb<double>(e, EFTB_T_BAO), c11, x11);
+        hipLaunchKernelGGL(extract_bao_kernel, dim3(B * Nl), dim3(128), 0, st, tb<double>(e, EFTB_T_BAO), cct, xct);
+        hipLaunchKernelGGL(extract_bao_kernel, dim3(B * Nl * 12), dim3(128), 0, st, tb<double>(e, EFTB_T_BAO), cloopl, xl);
+        c11 = x11; cct = xct; cloopl = xl;
     }
-    if (mask & (EFTB_S_RESUM | EFTB_K_RESUM)) {
-        if (!c.with_resum) return fail("eftb_run: stage RESUM needs with_resum=1");
-        const bool full = mask & EFTB_S_RESUM;  // EFTB_K_RESUM alone: only the main kernel, on the operands of an earlier full run
-        if (full && !side_ir && !nnlo_pass) launch_irfilter(e, st, B);  // X, Y, Q(f) of the first pass stay valid
-        if (!joined) {
-            if (hipStreamWaitEvent(st, e->evJoin, 0) != hipSuccess) return fail("eftb_run: stream join failed");
-            joined = true;
-        }
-        const double *c11 = b[EFTB_B_C11], *cct = b[EFTB_B_CCT], *cloopl = b[EFTB_B_CLOOPL];
-        if (c.optiresum && full) {  // Resum.extractBAO (reference pybird.py:1382-1400) into scratch: the stage inputs stay as the CF stage left them
-            double *x11 = e->XB, *xct = x11 + (size_t)c.max_batch * Nl * NS, *xl = xct + (size_t)c.max_batch * Nl * NS;
-            hipLaunchKernelGGL(extract_bao_kernel, dim3(B * Nl), dim3(128), 0, st, tb<double>(e, EFTB_T_BAO), c11, x11);
-            hipLaunchKernelGGL(extract_bao_kernel, dim3(B * Nl), dim3(128), 0, st, tb<double>(e, EFTB_T_BAO), cct, xct);
-            hipLaunchKernelGGL(extract_bao_kernel, dim3(B * Nl * 12), dim3(128), 0, st, tb<double>(e, EFTB_T_BAO), cloopl, xl);
-            c11 = x11; cct = xct; cloopl = xl;
-        }
-        // matrix-core form: polynomials as [80 | 32 x 8] x [8 x 16 points] MFMAs, one wave = 16 k x one slice of the s sum
-        // with_nnlo, large batches: CctNNLO rides in the records and the main kernel accumulates PctNNLOl beside Pctl (no second pass)
-        const bool fused_nnlo = nnlo_fused && !nnlo_pass;
+    // matrix-core form: polynomials as [80 | 32 x 8] x [8 x 16 points] MFMAs, one wave = 16 k x one slice of the s sum
 #define RP_ARGS e->Nn, c.NIR, c.Na, b[EFTB_B_Q], tb<double>(e, EFTB_T_RSBASISS), tb<int>(e, EFTB_T_RSROWS), b[EFTB_B_XY], c11, cct, cloopl, e->RSA, e->RSC, \
-            fused_nnlo ? b[EFTB_B_CCTN] : nullptr, fuse_cf ? b[EFTB_B_CC] : nullptr, b[EFTB_B_F], tb<double>(e, EFTB_T_L22), tb<double>(e, EFTB_T_L13), \
-            tb<int>(e, EFTB_T_GRP)
-        const dim3 rpgrid(B, fuse_cf ? 5 : 1);  // the fused regrouping is 38 conditional terms per record entry: spread over five workgroups
-        const int rslot = e->rs_step & 1;
-        if (ahead) {  // the operand set written here was last read by the resummation two runs ago
-            std::swap(e->RSA, e->RSA2);
-            std::swap(e->RSC, e->RSC2);
-            if (direct) std::swap(e->RSAS, e->RSAS2);  // (here the coefficient table of resum_plk_kernel)
-            if (hipStreamWaitEvent(st, e->evRsDone[rslot], 0) != hipSuccess) return fail("eftb_run: stream wait failed");
-        }
-        if (full && direct) {
-            constexpr int nparts = 5;  // slices of the s range per cosmology (2 ... 10 measured the same since the coefficient part keeps Q(f) in registers: 20-22 us alone at 512 per launch, 8 at 128)
-            const int nsl = (NS + nparts - 1) / nparts;
-            const size_t plds = ((size_t)2 * 3 * nsl + 2 * nsl) * sizeof(double);
-            const int nkx = (Nk + 255) / 256, nreg = nkx * B;   // (regroup: one workgroup per (256 k, cosmology), all three l)
-            if (!WHATIF_SKIP(32))
+        p.nnlo_fused ? b[EFTB_B_CCTN] : nullptr, p.fuse_cf ? b[EFTB_B_CC] : nullptr, b[EFTB_B_F], tb<double>(e, EFTB_T_L22), tb<double>(e, EFTB_T_L13), \
+        tb<int>(e, EFTB_T_GRP)
+    const dim3 rpgrid(B, p.fuse_cf ? 5 : 1);  // the fused regrouping is 38 conditional terms per record entry: spread over five workgroups
+    const int rslot = e->rs_step & 1;
+    if (p.ahead) {  // the operand set written here was last read by the resummation two runs ago
+        std::swap(e->RSA, e->RSA2);
+        std::swap(e->RSC, e->RSC2);
+        if (direct) std::swap(e->RSAS, e->RSAS2);  // (here the coefficient table of resum_plk_kernel)
+        if (int rc = r.wait_on(st, e->evRsDone[rslot])) return rc;
+    }
+    if (full && direct) {
+        constexpr int nparts = 5;  // slices of the s range per cosmology (2 ... 10 measured the same since the coefficient part keeps Q(f) in registers: 20-22 us alone at 512 per launch, 8 at 128)
+        const int nsl = (NS + nparts - 1) / nparts;
+        const size_t plds = ((size_t)2 * 3 * nsl + 2 * nsl) * sizeof(double);
+        const int nkx = (Nk + 255) / 256, nreg = nkx * B;   // (regroup: one workgroup per (256 k, cosmology), all three l)
+        if (!WHATIF_SKIP(32))
             hipLaunchKernelGGL(back_prep_plk_kernel, dim3(nreg + nparts * B), dim3(BPP_THREADS), plds, st, nreg, nkx, B, nparts, Nk, Nl, tb<double>(e, EFTB_T_K), b[EFTB_B_P11], e->Y22,
                                b[EFTB_B_P13], tb<double>(e, EFTB_T_L11), tb<double>(e, EFTB_T_LCT), b[EFTB_B_BIAS], b[EFTB_B_TEMPL], c.ap_stochastic ? 1 : 0,
                                e->Nn, c.NIR, c.Na, b[EFTB_B_Q], b[EFTB_B_XY], c11, cct, e->YCF, e->RSAS);
-            trace_point(e, 3, st);
-            if (front_side) {  // the last reader of this run's front set
-                if (hipEventRecord(e->evFrontFree[e->front_step & 1], st) != hipSuccess) return fail("eftb_run: event record failed");
-                ++e->front_step;
-            }
+        trace_point(e, 3, st);
+        if (p.front_side) {  // the last reader of this run's front set
+            if (int rc = r.record(e->evFrontFree[e->front_step & 1], st)) return rc;
+            ++e->front_step;
         }
-        else if (full && Nl == 3 && !as_side) launch_resum_as(e, st, B);  // (in line: X, Y, Q(f) are in place behind evJoin)
-        if (full && direct) {
-        } else
-        if (full && Nl == 3) hipLaunchKernelGGL((resum_prep_kernel<3>), rpgrid, dim3(256), 0, st, RP_ARGS);
-        else if (full) hipLaunchKernelGGL((resum_prep_kernel<2>), rpgrid, dim3(256), 0, st, RP_ARGS);
+    } else if (full) {
+        if (Nl == 3 && !p.as_side) launch_resum_as(e, st, B);  // (in line: X, Y, Q(f) are in place behind evJoin)
+        if (Nl == 3) hipLaunchKernelGGL((resum_prep_kernel<3>), rpgrid, dim3(256), 0, st, RP_ARGS);
+        else hipLaunchKernelGGL((resum_prep_kernel<2>), rpgrid, dim3(256), 0, st, RP_ARGS);
+    }
 #undef RP_ARGS
-        // C11 / Cct / Cloopl now live in the per-s records: the next run's front half may overwrite its outputs (see the regrouping)
-        if (full && (mask & EFTB_S_REGROUP) && !e->use_graphs && !nnlo_pass && hipEventRecord(e->evInFree, st) != hipSuccess)
-            return fail("eftb_run: event record failed");
-        if (ahead) {
-            if (hipEventRecord(e->evPrep, st) != hipSuccess || hipStreamWaitEvent(st_main, e->evPrep, 0) != hipSuccess) return fail("eftb_run: stream join failed");
-            if (as_side && full && hipStreamWaitEvent(st_main, e->evAS, 0) != hipSuccess) return fail("eftb_run: stream join failed");
-            st = st_main;
-        }
-        if (direct) trace_point(e, 4, st);
-        const int tslot = full ? timer_begin(e, st, 0) : -1;
-        const int kblocks = (Nk - c.Nklow + 63) / 64;
-        int nsplit = 1;
-        while (!direct && nsplit < e->resum_splits && (size_t)kblocks * 4 * B * nsplit < 2048) nsplit *= 2;
-        const int schunk = (NS + nsplit - 1) / nsplit;
+    // C11 / Cct / Cloopl now live in the per-s records: the next run's front half may overwrite its outputs (see the regrouping)
+    if (full && (mask & EFTB_S_REGROUP) && !e->use_graphs && !nnlo_pass)
+        if (int rc = r.record(e->evInFree, st)) return rc;
+    if (p.ahead) {
+        if (int rc = r.hand_over(e->evPrep, st, e->stream, "join")) return rc;
+        if (p.as_side && full)
+            if (int rc = r.wait_on(e->stream, e->evAS, "join")) return rc;
+        st = r.st = e->stream;
+    }
+    if (direct) trace_point(e, 4, st);
+    const int tslot = full ? timer_begin(e, st, 0) : -1;
+    const int kblocks = (Nk - c.Nklow + 63) / 64;
+    int nsplit = 1;
+    while (!direct && nsplit < e->resum_splits && (size_t)kblocks * 4 * B * nsplit < 2048) nsplit *= 2;
+    const int schunk = (NS + nsplit - 1) / nsplit;
 #define RM_ARGS Nk, c.Nklow, schunk, tb<double>(e, EFTB_T_K), tb<double>(e, EFTB_T_H), tb<double>(e, EFTB_T_RSBASIS), Nl == 3 ? e->RSAS : e->RSA, e->RSC, tb<double>(e, EFTB_T_L11), \
-            tb<double>(e, nnlo_pass ? EFTB_T_LCTN : EFTB_T_LCT), b[EFTB_B_TEMPL], e->part, nsplit
-        const int nkb = (Nk - (c.Nklow & ~15) + 63) / 64;  // Nl = 3: k tiles aligned to 16, (k block, cosmology) decoded from a flat index
-        if (direct) {
-            // four k per lane, four slices of the s range (round 4, same-box sweep of six shapes: 34.9 us alone at B = 128 / 105 at 384; 4 x 2, the
-            // round-3 shape: 39.0 / 120; 2 x 4: 38.6 / 117; 8 x 1: 57 / 117; 8 x 2: 58 / 153; 8 x 4: 49 / 134)
-            const int nkd = (Nk + 64 * 4 - 1) / (64 * 4);
-            if (kblocks > 0 && !WHATIF_SKIP(64))
-                hipLaunchKernelGGL((resum_plk_kernel<4, 4>), dim3(nkd * 3 * B), dim3(192 * 4), 0, st, Nk, c.Nklow, tb<double>(e, EFTB_T_K), tb<double>(e, EFTB_T_H),
-                                   e->RSAS, b[EFTB_B_TEMPL], nkd);
-        } else if (kblocks > 0 && Nl == 3 && fused_nnlo)
-            hipLaunchKernelGGL((resum_mfma_kernel<true>), dim3(nkb * B, 1, nsplit), dim3(256), 0, st, RM_ARGS, tb<double>(e, EFTB_T_LCTN), b[EFTB_B_TEMPLN], nkb);
-        else if (kblocks > 0 && Nl == 3)
-            hipLaunchKernelGGL((resum_mfma_kernel<false>), dim3(nkb * B, 1, nsplit), dim3(256), 0, st, RM_ARGS, nullptr, nullptr, nkb);
-        else if (kblocks > 0) hipLaunchKernelGGL(resum_mfma2_kernel, dim3(kblocks, B, nsplit), dim3(256), 0, st, RM_ARGS);
+        tb<double>(e, nnlo_pass ? EFTB_T_LCTN : EFTB_T_LCT), b[EFTB_B_TEMPL], e->part, nsplit
+    const int nkb = (Nk - (c.Nklow & ~15) + 63) / 64;  // Nl = 3: k tiles aligned to 16, (k block, cosmology) decoded from a flat index
+    if (direct) {
+        // four k per lane, four slices of the s range (round 4, same-box sweep of six shapes: 34.9 us alone at B = 128 / 105 at 384; 4 x 2, the
+        // round-3 shape: 39.0 / 120; 2 x 4: 38.6 / 117; 8 x 1: 57 / 117; 8 x 2: 58 / 153; 8 x 4: 49 / 134)
+        const int nkd = (Nk + 64 * 4 - 1) / (64 * 4);
+        if (kblocks > 0 && !WHATIF_SKIP(64))
+            hipLaunchKernelGGL((resum_plk_kernel<4, 4>), dim3(nkd * 3 * B), dim3(192 * 4), 0, st, Nk, c.Nklow, tb<double>(e, EFTB_T_K), tb<double>(e, EFTB_T_H),
+                               e->RSAS, b[EFTB_B_TEMPL], nkd);
+    } else if (kblocks > 0 && Nl == 3 && p.nnlo_fused)
+        hipLaunchKernelGGL((resum_mfma_kernel<true>), dim3(nkb * B, 1, nsplit), dim3(256), 0, st, RM_ARGS, tb<double>(e, EFTB_T_LCTN), b[EFTB_B_TEMPLN], nkb);
+    else if (kblocks > 0 && Nl == 3)
+        hipLaunchKernelGGL((resum_mfma_kernel<false>), dim3(nkb * B, 1, nsplit), dim3(256), 0, st, RM_ARGS, nullptr, nullptr, nkb);
+    else if (kblocks > 0) hipLaunchKernelGGL(resum_mfma2_kernel, dim3(kblocks, B, nsplit), dim3(256), 0, st, RM_ARGS);
 #undef RM_ARGS
-        if (nsplit > 1)
-            hipLaunchKernelGGL(resum_sum_kernel, dim3((Nk + 255) / 256, 21 * Nl, B), dim3(256), 0, st, Nk, Nl, nsplit, e->part, b[EFTB_B_TEMPL]);
-        timer_end(e, st, tslot);
-        if (direct) trace_point(e, 5, st);
-        if (ahead) {
-            if (hipEventRecord(e->evRsDone[rslot], st) != hipSuccess) return fail("eftb_run: event record failed");
-            ++e->rs_step;
-        }
+    if (nsplit > 1)
+        hipLaunchKernelGGL(resum_sum_kernel, dim3((Nk + 255) / 256, 21 * Nl, B), dim3(256), 0, st, Nk, Nl, nsplit, e->part, b[EFTB_B_TEMPL]);
+    timer_end(e, st, tslot);
+    if (direct) trace_point(e, 5, st);
+    if (p.ahead) {
+        if (int rc = r.record(e->evRsDone[rslot], st)) return rc;
+        ++e->rs_step;
     }
-    if (ap_side) {
-        // (with the operands built ahead the resummation's own event -- recorded right behind it on this stream -- is the fork point: one
-        // event record less on the host's path)
-        if (ahead && (mask & EFTB_S_RESUM)) {
-            if (hipStreamWaitEvent(e->back, e->evRsDone[(e->rs_step + 1) & 1], 0) != hipSuccess) return fail("eftb_run: stream fork failed");
-        } else if (hipEventRecord(e->evResum, st) != hipSuccess || hipStreamWaitEvent(e->back, e->evResum, 0) != hipSuccess) return fail("eftb_run: stream fork failed");
-        st = e->back;
+    return 0;
+}
+
+// the AP stage of a direct-P_l run: the contracted row `in` -> P_l, in one of three forms
+static void ap_pass_plk(StageRun& r, const double* in) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    const int B = r.B, Nk = c.Nk;
+    const hipStream_t st = r.st;
+    double** b = e->buf;
+    // (a PROJECT stage follows: the stage leaves P_l in PLK0 and the operator writes the final block)
+    double* const plk_dst = r.p.direct_proj ? e->PLK0 : b[EFTB_B_PLK];
+    double* const plk_hst = r.p.direct_proj ? nullptr : e->plk_host_out;
+    // (the tables between the nodes and the spline data: the quadrature weights and Legendre values, or the mu prefix sums and roots)
+#define APK_ARGS(...) Nk, c.nmu, tb<double>(e, EFTB_T_K), b[EFTB_B_DA], b[EFTB_B_H], tb<double>(e, EFTB_T_APFID), tb<double>(e, EFTB_T_MU), __VA_ARGS__, e->SD, \
+                      tb<double>(e, EFTB_T_SPLOCAL), in, b[EFTB_B_BIAS], plk_dst, plk_hst, e->check_finite ? e->status + 2 * e->status_slot + 1 : nullptr, \
+                      c.ap_stochastic ? NROW : 21
+    const bool nodes = e->ap_plk_nodes, fused = !nodes && e->ap_plk_fused;
+    // moment form on the contracted row (ap_plk_mom_kernel): the mu prefix sums of this cosmology batch (a function of DA, H alone) in
+    // line in front of it -- the stage is ~20 us of latency-bound launches either way, and in line it needs no second set of sums
+    if (!nodes && !fused) launch_ap_prefix(e, st, B, false);
+    const int tslot = timer_begin(e, st, 2);
+    if (nodes) {  // the node quadrature on the contracted row (ap_plk_kernel); nothing else of the stage runs
+        const size_t lds = ((size_t)Nk + (size_t)c.nmu * 8 + 3 * APD_WMAX * 4 + 3 * 3 * 64) * sizeof(double);
+        hipLaunchKernelGGL((ap_plk_kernel<3>), dim3(((Nk + 63) / 64) * B), dim3(256), lds, st, APK_ARGS(tb<double>(e, EFTB_T_WMU), tb<double>(e, EFTB_T_LEGMU)));
+    } else if (fused) {
+        // moment form with everything in LDS (ap_plk_fused_kernel): prefix sums, pieces and the walk in one launch
+        const size_t lds = ((size_t)((Nk + 1) & ~1) + (size_t)c.nmu * (2 + 2 * 3) + 36 * 16 + (size_t)(c.nmu + 1) * 36 + (size_t)(Nk - 1) * 3 * 4) * sizeof(double);
+        // one workgroup of eight waves per cosmology (22.3 us alone at B = 128, 40 at 384; two workgroups of four waves measured 22.7 / 61 -- the
+        // LDS tables allow one workgroup per CU either way)
+        if (!WHATIF_SKIP(256))
+            hipLaunchKernelGGL((ap_plk_fused_kernel<3, 8>), dim3(B), dim3(512), lds, st, APK_ARGS(tb<double>(e, EFTB_T_WMU), tb<double>(e, EFTB_T_LEGMU)));
+        trace_point(e, 7, st);
+    } else {
+        const size_t lds = ((size_t)Nk + c.nmu + 3 * 3 * 64) * sizeof(double);
+        hipLaunchKernelGGL((ap_plk_mom_kernel<3>), dim3(((Nk + 63) / 64) * B), dim3(256), lds, st, APK_ARGS(e->APP, e->APR));
     }
-    if (mask & EFTB_S_AP) {
-        if (!c.with_ap) return fail("eftb_run: stage AP needs with_ap=1");
-        // one AP pass over a template block: *pin -> *palt, then the two trade places.  nn: the NNLO block carries only the three
-        // counter-term rows 3-5 of every multipole: spline and AP touch those alone
-        auto ap_pass = [&](bool nn, double** pin, double** palt) -> int {
-            const bool moments = e->ap_mode == 1;  // (works on whole blocks: the NNLO block's zero rows stay zero)
-            const bool dir = direct && !nn;  // direct-P_l runs: row 0 of every (cosmology, l) block is the only one that goes through the stage
-            const int nr = dir ? 1 : nn ? (moments ? 21 : 6) : (c.ap_stochastic ? NROW : 21);
-            // rows the spline data is needed for: [rlo, rlo + rsel) of every (cosmology, l) -- the counter-term rows of the NNLO block; on the fast
-            // path only the rows the stage distorts (Pstl passes through unless APst: 21 of 24 rows)
-            const int rlo = nn && !moments ? 3 : 0, rsel = dir ? 1 : nn && !moments ? 3 : (e->ap_mode == 0 ? nr : NROW);
-            const int nseries = B * Nl * rsel;
-            if (dir) trace_point(e, 6, st);
-            {
-                const int kt = (Nk + 63) / 64;
-                int ysplit = std::max(1, std::min((nseries + 15) / 16, 1024 / kt));  // ~4 workgroups per CU, each sweeping its share of the series
-                if (ysplit >= 8) ysplit &= ~7;  // shares in multiples of 8: the k tiles of a share then sit on one XCD (xcd_decode)
-                // (the fast path keeps the splines as B-spline coefficients -- one number per knot; the moment / quadrature forms as knot slopes)
-                if (!(dir && WHATIF_SKIP(128)))
-                hipLaunchKernelGGL(spline_kernel, dim3(kt * ysplit), dim3(256), 0, st, Nk, nseries, rlo, rsel, *pin, tb<double>(e, e->ap_mode == 0 || dir ? EFTB_T_SPCBAND : EFTB_T_SPBAND), e->SD);
-            }
-            // (a PROJECT stage follows: the stage leaves P_l in PLK0 and the operator writes the final block)
-            double* const plk_dst = direct_proj ? e->PLK0 : b[EFTB_B_PLK];
-            double* const plk_hst = direct_proj ? nullptr : e->plk_host_out;
-            if (dir && e->ap_plk_nodes) {  // the node quadrature on the contracted row (ap_plk_kernel); nothing else of the stage runs
-                const size_t lds = ((size_t)Nk + (size_t)c.nmu * 8 + 3 * APD_WMAX * 4 + 3 * 3 * 64) * sizeof(double);
-                const int tslot = timer_begin(e, st, 2);
-                hipLaunchKernelGGL((ap_plk_kernel<3>), dim3(((Nk + 63) / 64) * B), dim3(256), lds, st, Nk, c.nmu, tb<double>(e, EFTB_T_K), b[EFTB_B_DA], b[EFTB_B_H],
-                                   tb<double>(e, EFTB_T_APFID), tb<double>(e, EFTB_T_MU), tb<double>(e, EFTB_T_WMU), tb<double>(e, EFTB_T_LEGMU), e->SD,
-                                   tb<double>(e, EFTB_T_SPLOCAL), *pin, b[EFTB_B_BIAS], plk_dst, plk_hst,
-                                   e->check_finite ? e->status + 2 * e->status_slot + 1 : nullptr, c.ap_stochastic ? NROW : 21);
-                timer_end(e, st, tslot);
-                std::swap(*pin, *palt);
-                return 0;
-            }
-            if (dir && e->ap_plk_fused) {
-                // moment form with everything in LDS (ap_plk_fused_kernel): prefix sums, pieces and the walk in one launch, two workgroups per cosmology
-                const size_t lds = ((size_t)((Nk + 1) & ~1) + (size_t)c.nmu * (2 + 2 * 3) + 36 * 16 + (size_t)(c.nmu + 1) * 36 + (size_t)(Nk - 1) * 3 * 4) * sizeof(double);
-                const int tslot = timer_begin(e, st, 2);
-#define APF_ARGS Nk, c.nmu, tb<double>(e, EFTB_T_K), b[EFTB_B_DA], b[EFTB_B_H], tb<double>(e, EFTB_T_APFID), tb<double>(e, EFTB_T_MU), tb<double>(e, EFTB_T_WMU),   \
-                 tb<double>(e, EFTB_T_LEGMU), e->SD, tb<double>(e, EFTB_T_SPLOCAL), *pin, b[EFTB_B_BIAS], plk_dst, plk_hst,                                      \
-                 e->check_finite ? e->status + 2 * e->status_slot + 1 : nullptr, c.ap_stochastic ? NROW : 21
-                // one workgroup of eight waves per cosmology (22.3 us alone at B = 128, 40 at 384; two workgroups of four waves measured 22.7 / 61 -- the
-                // LDS tables allow one workgroup per CU either way)
-                if (!WHATIF_SKIP(256)) hipLaunchKernelGGL((ap_plk_fused_kernel<3, 8>), dim3(B), dim3(512), lds, st, APF_ARGS);
-#undef APF_ARGS
-                trace_point(e, 7, st);
-                timer_end(e, st, tslot);
-                std::swap(*pin, *palt);
-                return 0;
-            }
-            if (dir) {
-                // moment form on the contracted row (ap_plk_mom_kernel): the mu prefix sums of this cosmology batch (a function of DA, H alone) in
-                // line in front of it -- the stage is ~20 us of latency-bound launches either way, and in line it needs no second set of sums
-                launch_ap_prefix(e, st, B, false);
-                const size_t lds = ((size_t)Nk + c.nmu + 3 * 3 * 64) * sizeof(double);
-                const int tslot = timer_begin(e, st, 2);
-                hipLaunchKernelGGL((ap_plk_mom_kernel<3>), dim3(((Nk + 63) / 64) * B), dim3(256), lds, st, Nk, c.nmu, tb<double>(e, EFTB_T_K), b[EFTB_B_DA], b[EFTB_B_H],
-                                   tb<double>(e, EFTB_T_APFID), tb<double>(e, EFTB_T_MU), e->APP, e->APR, e->SD, tb<double>(e, EFTB_T_SPLOCAL), *pin, b[EFTB_B_BIAS],
-                                   plk_dst, plk_hst, e->check_finite ? e->status + 2 * e->status_slot + 1 : nullptr, c.ap_stochastic ? NROW : 21);
-                timer_end(e, st, tslot);
-                std::swap(*pin, *palt);
-                return 0;
-            }
-            // prefix sums over mu per cosmology (side stream when possible), then interval moments by differences x cubic coefficients
-            if (!side_ap && !nn) launch_ap_prefix(e, st, B);
-            if (!joined_ap) {
-                if (hipStreamWaitEvent(st, e->evJoinAP, 0) != hipSuccess) return fail("eftb_run: stream join failed");
-                joined_ap = true;
-            }
-            if (moments) {
-                const dim3 apgrid((Nk + 63) / 64, B, 3);
-                const size_t aplds = ((size_t)Nk + c.nmu + (size_t)4 * Nl * ((nr + 2) / 3) * 64) * sizeof(double);
+#undef APK_ARGS
+    timer_end(e, st, tslot);
+}
+
+// one AP pass over a template block: *pin -> *palt, then the two trade places (nn: see ApRows)
+static int ap_pass(StageRun& r, bool nn, double** pin, double** palt) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    const StagePlan& p = r.p;
+    const int B = r.B, Nk = c.Nk, Nl = c.Nl;
+    const hipStream_t st = r.st;
+    double** b = e->buf;
+    const ApRows a = ap_rows_of(e, p, nn);
+    const int nr = a.nr, rlo = a.rlo, msplit = a.msplit;
+    const int nseries = B * Nl * a.rsel;
+    if (a.dir) trace_point(e, 6, st);
+    {
+        const int kt = (Nk + 63) / 64;
+        int ysplit = std::max(1, std::min((nseries + 15) / 16, 1024 / kt));  // ~4 workgroups per CU, each sweeping its share of the series
+        if (ysplit >= 8) ysplit &= ~7;  // shares in multiples of 8: the k tiles of a share then sit on one XCD (xcd_decode)
+        // (the fast path keeps the splines as B-spline coefficients -- one number per knot; the moment / quadrature forms as knot slopes)
+        if (!(a.dir && WHATIF_SKIP(128)))
+            hipLaunchKernelGGL(spline_kernel, dim3(kt * ysplit), dim3(256), 0, st, Nk, nseries, rlo, a.rsel, *pin, tb<double>(e, e->ap_mode == 0 || a.dir ? EFTB_T_SPCBAND : EFTB_T_SPBAND), e->SD);
+    }
+    if (a.dir) {
+        ap_pass_plk(r, *pin);
+        std::swap(*pin, *palt);
+        return 0;
+    }
+    // prefix sums over mu per cosmology (side stream when possible), then interval moments by differences x cubic coefficients
+    if (!p.side_ap && !nn) launch_ap_prefix(e, st, B);
+    if (!r.joined_ap) {
+        if (int rc = r.wait_on(st, e->evJoinAP, "join")) return rc;
+        r.joined_ap = true;
+    }
+    if (e->ap_mode == 1) {
+        const dim3 apgrid((Nk + 63) / 64, B, 3);
+        const size_t aplds = ((size_t)Nk + c.nmu + (size_t)4 * Nl * ((nr + 2) / 3) * 64) * sizeof(double);
 #define APM_ARGS Nk, c.nmu, tb<double>(e, EFTB_T_K), b[EFTB_B_DA], b[EFTB_B_H], tb<double>(e, EFTB_T_APFID), tb<double>(e, EFTB_T_MU), e->APP, e->APR, *pin, e->SD, *palt
-                if (Nl == 3 && nr == 21) hipLaunchKernelGGL((ap_moments_kernel<3, 21, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
-                else if (Nl == 3) hipLaunchKernelGGL((ap_moments_kernel<3, NROW, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
-                else if (nr == 21) hipLaunchKernelGGL((ap_moments_kernel<2, 21, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
-                else hipLaunchKernelGGL((ap_moments_kernel<2, NROW, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
+        if (Nl == 3 && nr == 21) hipLaunchKernelGGL((ap_moments_kernel<3, 21, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
+        else if (Nl == 3) hipLaunchKernelGGL((ap_moments_kernel<3, NROW, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
+        else if (nr == 21) hipLaunchKernelGGL((ap_moments_kernel<2, 21, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
+        else hipLaunchKernelGGL((ap_moments_kernel<2, NROW, 3>), apgrid, dim3(256), aplds, st, APM_ARGS);
 #undef APM_ARGS
-                std::swap(*pin, *palt);
-                return 0;
-            }
-            // REDUCE directly behind the AP stage: the bias contraction rides in the epilogue of ap_rows_kernel (and of the fallback tiles'
-            // ap_direct_kernel), in the summation order of reduce_kernel(msplit) -- no separate pass over the 33 MB of AP output
-            const bool red = fuse_reduce && !nn;
-            const int msplit = red ? msplit_cfg : (rlo + nr + 1) / 2;  // rows [rlo, msplit) / [msplit, nr) to the two half waves
-            const double* rb = red ? b[EFTB_B_BIAS] : nullptr;
-            double* rp = red ? b[EFTB_B_PLK] : nullptr;
-            double* rph = red ? e->plk_host_out : nullptr;
-            int* rflag = red && e->check_finite ? e->status + 2 * e->status_slot + 1 : nullptr;
-            if (e->ap_mode == 0) {
-                // banded product of the knot weights with the spline data; rows outside [rlo, nr) are copied through
-                const int kt2 = 2 * ((Nk + 63) / 64), nh = (nr - rlo + 1) / 2, nre = 2 * nh;
-                const size_t lds = 0;  // (the window is a static array: 37 KB at most)
-                if (rlo + nre > NROW || msplit - rlo > nh || nr - msplit > nh || (nh != 2 && nh != 11 && nh != 12))
-                    return fail("eftb_run: AP rows [%d, %d) split at %d do not fit the window layouts built into ap_rows_kernel", rlo, nr, msplit);
+        std::swap(*pin, *palt);
+        return 0;
+    }
+    // REDUCE directly behind the AP stage (fuse_reduce): the epilogue's bias, destinations and flag
+    const double* rb = a.red ? b[EFTB_B_BIAS] : nullptr;
+    double* rp = a.red ? b[EFTB_B_PLK] : nullptr;
+    double* rph = a.red ? e->plk_host_out : nullptr;
+    int* rflag = a.red && e->check_finite ? e->status + 2 * e->status_slot + 1 : nullptr;
+    if (e->ap_mode == 0) {
+        // banded product of the knot weights with the spline data; rows outside [rlo, nr) are copied through
+        // (nh = 2, 11 or 12 rows per half wave: the window layouts built into ap_rows_kernel, checked by plan_stages)
+        const int kt2 = 2 * ((Nk + 63) / 64), nh = (nr - rlo + 1) / 2;
+        const size_t lds = 0;  // (the window is a static array: 37 KB at most)
 #define APR_ARGS Nk, rlo, nr, msplit, b[EFTB_B_DA], b[EFTB_B_H], tb<double>(e, EFTB_T_APFID), e->APW, e->API, e->APM, *pin, e->SD, *palt, rb, rp, rph, rflag
 #define APR_LAUNCH(NLV, NHV) hipLaunchKernelGGL((ap_rows_kernel<NLV, NHV, 2>), dim3(kt2 * B), dim3(64 * NLV), lds, st, APR_ARGS)  // (ring of two knots' weights in flight)
-                if (Nl == 3 && nh == 11) APR_LAUNCH(3, 11);
-                else if (Nl == 3 && nh == 12) APR_LAUNCH(3, 12);
-                else if (Nl == 3) APR_LAUNCH(3, 2);
-                else if (nh == 11) APR_LAUNCH(2, 11);
-                else if (nh == 12) APR_LAUNCH(2, 12);
-                else APR_LAUNCH(2, 2);
+        if (Nl == 3 && nh == 11) APR_LAUNCH(3, 11);
+        else if (Nl == 3 && nh == 12) APR_LAUNCH(3, 12);
+        else if (Nl == 3) APR_LAUNCH(3, 2);
+        else if (nh == 11) APR_LAUNCH(2, 11);
+        else if (nh == 12) APR_LAUNCH(2, 12);
+        else APR_LAUNCH(2, 2);
 #undef APR_LAUNCH
 #undef APR_ARGS
-            }
-            // the reference's own quadrature: every tile (EFTB_AP_MODE=2), or only the tiles the fast path flagged (strong distortions)
-            {
-                const bool gated = e->ap_mode == 0;
-                const int4* gate = gated ? e->APM : nullptr;
-                const dim3 dgrid(((Nk + 63) / 64) * B);
+    }
+    // the reference's own quadrature: every tile (EFTB_AP_MODE=2), or only the tiles the fast path flagged (strong distortions)
+    const bool gated = e->ap_mode == 0;
+    const int4* gate = gated ? e->APM : nullptr;
+    const dim3 dgrid(((Nk + 63) / 64) * B);
 #define APD_ARGS Nk, c.nmu, rlo, nr, tb<double>(e, EFTB_T_K), b[EFTB_B_DA], b[EFTB_B_H], tb<double>(e, EFTB_T_APFID), tb<double>(e, EFTB_T_MU), tb<double>(e, EFTB_T_WMU), \
                  tb<double>(e, EFTB_T_LEGMU), e->APR, *pin, e->SD, *palt, gate, rb, rp, rph, msplit, rflag, tb<double>(e, EFTB_T_SPLOCAL)
-                if (gated && Nl == 3) hipLaunchKernelGGL((ap_direct_kernel<3, true>), dgrid, dim3(64), 0, st, APD_ARGS);
-                else if (gated) hipLaunchKernelGGL((ap_direct_kernel<2, true>), dgrid, dim3(64), 0, st, APD_ARGS);
-                else if (Nl == 3) hipLaunchKernelGGL((ap_direct_kernel<3, false>), dgrid, dim3(64), 0, st, APD_ARGS);
-                else hipLaunchKernelGGL((ap_direct_kernel<2, false>), dgrid, dim3(64), 0, st, APD_ARGS);
+    if (gated && Nl == 3) hipLaunchKernelGGL((ap_direct_kernel<3, true>), dgrid, dim3(64), 0, st, APD_ARGS);
+    else if (gated) hipLaunchKernelGGL((ap_direct_kernel<2, true>), dgrid, dim3(64), 0, st, APD_ARGS);
+    else if (Nl == 3) hipLaunchKernelGGL((ap_direct_kernel<3, false>), dgrid, dim3(64), 0, st, APD_ARGS);
+    else hipLaunchKernelGGL((ap_direct_kernel<2, false>), dgrid, dim3(64), 0, st, APD_ARGS);
 #undef APD_ARGS
-            }
-            std::swap(*pin, *palt);
-            return 0;
-        };
-        if (int rc = ap_pass(nnlo_pass, &e->buf[EFTB_B_TEMPL], &e->Talt)) return rc;
-        if (nnlo_inline)
-            if (int rc = ap_pass(true, &e->buf[EFTB_B_TEMPLN], &e->TaltN)) return rc;
+    std::swap(*pin, *palt);
+    return 0;
+}
+
+// AP: the back half moves to its own stream in three-stream runs; one pass over the block (and one over the NNLO block it carries in line)
+static int stage_ap(StageRun& r) {
+    eftb_engine* e = r.e;
+    const StagePlan& p = r.p;
+    if (p.ap_side) {
+        // (with the operands built ahead the resummation's own event -- recorded right behind it on this stream -- is the fork point: one
+        // event record less on the host's path)
+        const bool rs_event = p.ahead && (r.mask & EFTB_S_RESUM);
+        if (int rc = rs_event ? r.wait_on(e->back, e->evRsDone[(e->rs_step + 1) & 1], "fork") : r.hand_over(e->evResum, r.st, e->back, "fork")) return rc;
+        r.st = e->back;
     }
-    if (mask & EFTB_S_REGROUP) {
-        e->cur_nl = Nl;
-        e->cur_nx = Nk;
+    if (!(r.mask & EFTB_S_AP)) return 0;
+    if (int rc = ap_pass(r, p.nnlo_pass, &e->buf[EFTB_B_TEMPL], &e->Talt)) return rc;
+    if (p.nnlo_inline)
+        if (int rc = ap_pass(r, true, &e->buf[EFTB_B_TEMPLN], &e->TaltN)) return rc;
+    return 0;
+}
+
+// PROJECT: the pipeline operator(s) on the template block, or on the one row per cosmology a direct-P_l run carries
+static int stage_project(StageRun& r) {
+    eftb_engine* e = r.e;
+    if (r.mask & EFTB_S_REGROUP) {  // the block as the stages so far leave it
+        e->cur_nl = e->c.Nl;
+        e->cur_nx = e->c.Nk;
     }
-    if (direct_proj) {
-        if (int rc = launch_pipeline_operator_plk(e, B, st)) return rc;
+    if (r.p.direct_proj) {
+        if (int rc = launch_pipeline_operator_plk(e, r.B, r.st)) return rc;
         e->plk_host_written = false;  // (the operator writes device memory only: whoever wants P_l in host memory copies it behind the launch)
-    } else if (mask & EFTB_S_PROJECT) {
-        e->opstream = st;
-        const int rc = launch_pipeline_operator(e, B);
+    } else if (r.mask & EFTB_S_PROJECT) {
+        e->opstream = r.st;
+        const int rc = launch_pipeline_operator(e, r.B);
         e->opstream = nullptr;
         if (rc) return rc;
     }
-    if (mask & EFTB_S_LOGP) {
-        if (!e->like_ndata) return fail("eftb_run: stage LOGP needs eftb_set_likelihood");
-        if (B % e->ntr) return fail("eftb_run: batch %d is not a multiple of the %d tracers per likelihood point", B, e->ntr);
-        if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
-            return fail("eftb_run: stage LOGP: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", e->like_nl,
-                        e->like_nx, e->cur_nl, e->cur_nx);
-        const int nw = B / e->ntr, ng1 = e->like_nG + 1, nd = e->like_ndata;
-        const size_t lds = (size_t)e->ntr * ng1 * NROW * sizeof(double);
-        if (lds > 64 * 1024) return fail("eftb_run: stage LOGP: %d tracers x %d rows do not fit the coefficient block in LDS", e->ntr, ng1);
-        // V (residual and derivatives on the data vector) per walker, U = V C^-1 for all walkers in one matrix-core GEMM, then the
-        // (nG + 1)^2 products and the small dense solve per walker
-        hipLaunchKernelGGL(marg_build_kernel, dim3(nw), dim3(256), lds, st, e->cur_nl, e->cur_nx, e->ntr, nd, e->like_nG, e->like_index, e->like_data,
-                           b[EFTB_B_GROWS], b[EFTB_B_TEMPL], c.with_nnlo ? b[EFTB_B_GROWSN] : nullptr, c.with_nnlo ? b[EFTB_B_TEMPLN] : nullptr,
-                           e->like_V);
-        GemmDesc gd{};
-        gd.A = e->like_V; gd.a_group = 0; gd.a_row = nd; gd.a_seg = 0; gd.rows = nw * ng1; gd.rows_per_group = nw * ng1; gd.nseg = 1; gd.kseg = nd;
-        gd.B = e->like_invcov; gd.ldb = nd; gd.ncols = nd;
-        gd.C = e->like_U; gd.c_group = 0; gd.c_row = nd; gd.c_colgroup = 0; gd.cols_per_group = nd;
-        hipLaunchKernelGGL(gemm_narrow_kernel, dim3((gd.rows + 15) / 16, (gd.ncols + 16 * GN_MAXT - 1) / (16 * GN_MAXT)), dim3(256), 0, st, gd, GemmZ{});
-        hipLaunchKernelGGL(marg_solve_kernel, dim3(nw), dim3(256), 0, st, nd, e->like_nG, e->jeffreys, e->like_mu, e->like_sinv, e->like_V, e->like_U,
-                           b[EFTB_B_LOGP]);
-    }
-    if ((mask & EFTB_S_REDUCE) && !fuse_reduce && !direct)
-        hipLaunchKernelGGL(reduce_kernel, dim3((e->cur_nx + 255) / 256, e->cur_nl, B), dim3(256), 0, st, e->cur_nx, e->cur_nl, msplit_cfg, b[EFTB_B_BIAS],
+    return 0;
+}
+
+// out [rows][ndata] = A [rows][ndata] C^-1 with the likelihood's inverse covariance, on the matrix cores (LOGP stage: V, draw calls: the gathered
+// templates, data sets: D -- one and the same product, so that a row of -D there is the exact negation of its row here)
+static void launch_times_invcov(eftb_engine* e, hipStream_t st, const double* A, int rows, double* out) {
+    const int nd = e->like_ndata;
+    GemmDesc gd{};
+    gd.A = A; gd.a_group = 0; gd.a_row = nd; gd.a_seg = 0; gd.rows = rows; gd.rows_per_group = rows; gd.nseg = 1; gd.kseg = nd;
+    gd.B = e->like_invcov; gd.ldb = nd; gd.ncols = nd;
+    gd.C = out; gd.c_group = 0; gd.c_row = nd; gd.c_colgroup = 0; gd.cols_per_group = nd;
+    hipLaunchKernelGGL(gemm_narrow_kernel, dim3((gd.rows + 15) / 16, (gd.ncols + 16 * GN_MAXT - 1) / (16 * GN_MAXT)), dim3(256), 0, st, gd, GemmZ{});
+}
+
+// LOGP: V (residual and derivatives on the data vector) per walker, U = V C^-1 for all walkers in one matrix-core GEMM, then the
+// (nG + 1)^2 products and the small dense solve per walker
+static int stage_logp(StageRun& r) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    double** b = e->buf;
+    if (!(r.mask & EFTB_S_LOGP)) return 0;
+    if (e->cur_nl != e->like_nl || e->cur_nx != e->like_nx)
+        return fail("eftb_run: stage LOGP: the likelihood's data index addresses templates [%d][24][%d], the block is [%d][24][%d]", e->like_nl,
+                    e->like_nx, e->cur_nl, e->cur_nx);
+    const int nw = r.B / e->ntr, ng1 = e->like_nG + 1, nd = e->like_ndata;
+    const size_t lds = (size_t)e->ntr * ng1 * NROW * sizeof(double);  // (the coefficient block: at most 64 KB, plan_stages)
+    hipLaunchKernelGGL(marg_build_kernel, dim3(nw), dim3(256), lds, r.st, e->cur_nl, e->cur_nx, e->ntr, nd, e->like_nG, e->like_index, e->like_data,
+                       b[EFTB_B_GROWS], b[EFTB_B_TEMPL], c.with_nnlo ? b[EFTB_B_GROWSN] : nullptr, c.with_nnlo ? b[EFTB_B_TEMPLN] : nullptr,
+                       e->like_V);
+    launch_times_invcov(e, r.st, e->like_V, nw * ng1, e->like_U);
+    hipLaunchKernelGGL(marg_solve_kernel, dim3(nw), dim3(256), 0, r.st, nd, e->like_nG, e->jeffreys, e->like_mu, e->like_sinv, e->like_V, e->like_U,
+                       b[EFTB_B_LOGP]);
+    return 0;
+}
+
+// REDUCE: P_l = sum_row b_row T[l][row], unless the AP stage did it in its epilogue (fuse_reduce) or the run contracted first (direct)
+static int stage_reduce(StageRun& r) {
+    eftb_engine* e = r.e;
+    const eftb_config& c = e->c;
+    double** b = e->buf;
+    if (!(r.mask & EFTB_S_REDUCE)) return 0;
+    if (!r.p.fuse_reduce && !r.p.direct)
+        hipLaunchKernelGGL(reduce_kernel, dim3((e->cur_nx + 255) / 256, e->cur_nl, r.B), dim3(256), 0, r.st, e->cur_nx, e->cur_nl, r.p.msplit, b[EFTB_B_BIAS],
                            b[EFTB_B_TEMPL], b[EFTB_B_PLK], c.with_nnlo ? nullptr : e->plk_host_out, e->check_finite && !c.with_nnlo ? e->status + 2 * e->status_slot + 1 : nullptr);
-    if ((mask & EFTB_S_REDUCE) && c.with_nnlo)
-        hipLaunchKernelGGL(reduce_nnlo_kernel, dim3((e->cur_nx + 255) / 256, e->cur_nl, B), dim3(256), 0, st, e->cur_nx, e->cur_nl, b[EFTB_B_BIASN],
+    if (c.with_nnlo)
+        hipLaunchKernelGGL(reduce_nnlo_kernel, dim3((e->cur_nx + 255) / 256, e->cur_nl, r.B), dim3(256), 0, r.st, e->cur_nx, e->cur_nl, b[EFTB_B_BIASN],
                            b[EFTB_B_TEMPLN], b[EFTB_B_PLK], e->check_finite ? e->status + 2 * e->status_slot + 1 : nullptr);
-    if (!(mask & EFTB_S_REGROUP) && !e->use_graphs && !nnlo_pass && hipEventRecord(e->evInFree, st) != hipSuccess) return fail("eftb_run: event record failed");
-    if (ap_side) {
-        if (hipEventRecord(e->evBack[bslot], st) != hipSuccess) return fail("eftb_run: event record failed");
+    return 0;
+}
+
+// what the next run waits for: the inputs are free (unless the regrouping or the resummation said so already), the back half is done
+static int stage_tail(StageRun& r) {
+    eftb_engine* e = r.e;
+    if (!(r.mask & EFTB_S_REGROUP) && !e->use_graphs && !r.p.nnlo_pass)
+        if (int rc = r.record(e->evInFree, r.st)) return rc;
+    if (r.p.ap_side) {
+        if (int rc = r.record(e->evBack[e->back_step & 1], r.st)) return rc;
         ++e->back_step;
         e->back_pending = true;
     }
-    if (mask & EFTB_S_PREP) e->prev_front_side = front_side;
+    if (r.mask & EFTB_S_PREP) e->prev_front_side = r.p.front_side;
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(le));
+    return 0;
+}
+
+// One run of the stages in `mask` over B cosmologies: the plan, then the stages in their order.  Each stage function launches on the cursor's
+// stream and moves the cursor where its part of the layout says (StageRun); launch_stages, run_stages and issue_group call this.
+static int launch_stages_impl(eftb_engine* e, int mask, int B, bool nnlo_pass, bool nnlo_inline = false) {
+    e->launch_B = B;
+    StageRun r{e, mask, B, StagePlan{}, e->stream, e->stream, false, false};
+    if (int rc = plan_stages(e, mask, B, nnlo_pass, nnlo_inline, &r.p)) return rc;
+    const StagePlan& p = r.p;
+    if (!p.ap_side) join_back(e);
+    if (p.direct) e->run_direct = true;
+    e->plk_host_written = true;
+    r.joined = !p.side_ir;
+    r.joined_ap = !p.side_ap;
+    if ((p.side_ir || p.side_ap) && !p.pre_side) {  // (overlapped runs fork inside stage_prep, behind the waits of the look-ahead)
+        if (int rc = r.hand_over(e->evFork, r.st, e->side, "fork")) return rc;
+        if (int rc = fork_side(r)) return rc;
+    }
+    for (int (*stage)(StageRun&) : {stage_prep, stage_loops, stage_regroup, stage_resum, stage_ap, stage_project, stage_logp, stage_reduce, stage_tail})
+        if (int rc = stage(r)) return rc;
     return 0;
 }
 
@@ -1364,9 +1532,8 @@ static int launch_stages(eftb_engine* e, int mask, int B) {
     // everything but the tail, then the linear stages again with the NNLO operands swapped in, then LOGP / REDUCE.
     // whole-pipeline steps without PROJECT / LOGP take the three-stream layout: the NNLO block has its own three rotating blocks and
     // follows the main block through every stage inside one call
-    const bool fused0 = c.with_resum && c.Nl == 3 && e->resum_splits == 1 && !c.optiresum;
     const int whole = EFTB_S_PREP | EFTB_S_REGROUP | EFTB_S_RESUM | EFTB_S_AP;
-    if (fused0 && c.with_ap && (mask & whole) == whole && !(mask & (EFTB_S_PROJECT | EFTB_S_LOGP)) && e->prep_overlap && e->ap_overlap && e->inputs_settled &&
+    if (nnlo_fusable(e) && c.with_ap && (mask & whole) == whole && !(mask & (EFTB_S_PROJECT | EFTB_S_LOGP)) && e->prep_overlap && e->ap_overlap && e->inputs_settled &&
         e->allow_back && !e->use_graphs && e->T3N && e->nnlo_inline)
         return launch_stages_impl(e, mask, B, false, true);
     const int tail = mask & (EFTB_S_LOGP | EFTB_S_REDUCE);
@@ -1386,14 +1553,19 @@ static int launch_stages(eftb_engine* e, int mask, int B) {
     e->cur_nl = in_nl;
     e->cur_nx = in_nx;
     // large batches at Nl = 3 accumulate PctNNLOl inside the resummation kernel of the first pass: only AP / PROJECT are left for the block
-    const bool fused = c.with_resum && c.Nl == 3 && e->resum_splits == 1 && !c.optiresum;
-    const int lin2 = fused ? (lin & ~EFTB_S_RESUM) : lin;
+    const int lin2 = nnlo_fusable(e) ? (lin & ~EFTB_S_RESUM) : lin;
     const int rc = lin2 ? launch_stages_impl(e, lin2, B, true) : 0;
     swap_in();  // the same swaps undo themselves
     e->cur_nl = out_nl;
     e->cur_nx = out_nx;
     if (rc) return rc;
     return tail ? launch_stages_impl(e, tail, B, false) : 0;
+}
+
+// the likelihood's device arrays (eftb_set_likelihood replaces them, eftb_destroy drops them)
+static void free_likelihood(eftb_engine* e) {
+    for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
+    e->like_index = nullptr; e->like_data = e->like_invcov = e->like_mu = e->like_sinv = e->like_V = e->like_U = nullptr;
 }
 
 static void drop_graphs(eftb_engine* e) {
@@ -1928,8 +2100,7 @@ int eftb_set_likelihood(eftb_engine* e, int ndata, const int32_t* index, const d
         }
     HIPCHK(hipSetDevice(e->c.device));
     HIPCHK(sync_all(e));  // a likelihood stage of an overlapped run may still be reading the old tables on the back-half stream
-    for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
-    e->like_index = nullptr; e->like_data = e->like_invcov = e->like_mu = e->like_sinv = e->like_V = e->like_U = nullptr;
+    free_likelihood(e);
     {
         const size_t vb = (size_t)(e->c.max_batch / e->ntr + 1) * (nG + 1) * ndata * sizeof(double);
         HIPCHK(hipMalloc(&e->like_V, vb));
@@ -1980,7 +2151,7 @@ void eftb_destroy(eftb_engine* e) {
     e->gathered = nullptr;  // (one of gathered2)
     for (void* p : {(void*)e->APW, (void*)e->APW2, (void*)e->API, (void*)e->API2, (void*)e->APM, (void*)e->APM2}) if (p) (void)hipFree(p);
     for (auto& o : e->ops) if (o.dev) (void)hipFree(o.dev);
-    for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
+    free_likelihood(e);
     for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off, (void*)e->drw_theta,
                     (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab, (void*)e->recipe[0].dcoef,
                     (void*)e->recipe[0].dtab, (void*)e->drw_grad, (void*)e->recipe[0].hcoef, (void*)e->recipe[0].htab, (void*)e->drw_hess}) if (p) (void)hipFree(p);
@@ -2244,11 +2415,7 @@ static int draws_gram(eftb_engine* e, const char* who, int C, int J1) {
         if (int rc = grow_dev(&e->drw_W, &e->drw_W_cap, (size_t)C * J1 * J1)) return rc;
         hipLaunchKernelGGL(draws_gather_kernel, dim3(C), dim3(256), 0, st, e->cur_nl, e->cur_nx, ntr, nd, J1, e->like_index, e->like_data,
                            e->buf[EFTB_B_TEMPL], c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, e->drw_A);
-        GemmDesc gd{};  // U = A C^-1 for all walkers, exactly as the LOGP stage multiplies V
-        gd.A = e->drw_A; gd.a_group = 0; gd.a_row = nd; gd.a_seg = 0; gd.rows = C * J1; gd.rows_per_group = C * J1; gd.nseg = 1; gd.kseg = nd;
-        gd.B = e->like_invcov; gd.ldb = nd; gd.ncols = nd;
-        gd.C = e->drw_U; gd.c_group = 0; gd.c_row = nd; gd.c_colgroup = 0; gd.cols_per_group = nd;
-        hipLaunchKernelGGL(gemm_narrow_kernel, dim3((gd.rows + 15) / 16, (gd.ncols + 16 * GN_MAXT - 1) / (16 * GN_MAXT)), dim3(256), 0, st, gd, GemmZ{});
+        launch_times_invcov(e, st, e->drw_A, C * J1, e->drw_U);  // U = A C^-1 for all walkers, exactly as the LOGP stage multiplies V
         const int gy = std::min(1024, (J1 * J1 + 63) / 64);
         hipLaunchKernelGGL(draws_gram_kernel, dim3(C, gy), dim3(256), 0, st, nd, J1, e->drw_A, e->drw_U, e->drw_W);
         hipError_t le = hipGetLastError();
@@ -2309,8 +2476,8 @@ static int draws_lds_optin(eftb_engine* e) {
     if (e->drw_lds) return 0;
     for (const void* k : {reinterpret_cast<const void*>(&draws_logp_kernel<false>), reinterpret_cast<const void*>(&draws_logp_kernel<true>),
                           reinterpret_cast<const void*>(&draws_logp_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_params_kernel<true>),
-                          reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<false>),
-                          reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<true>)})
+                          reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<true>),
+                          reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<true>)})
         HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     e->drw_lds = true;
     return 0;
@@ -3545,11 +3712,6 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
     if (gr)
         if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
     const double* W = gr ? e->drw_Wg : e->drw_W;
-    if (hess && !e->drw_lds_hess) {
-        for (const void* k : {reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<true>)})
-            HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        e->drw_lds_hess = true;
-    }
     if (grad)
         if (int rc = grow_dev(&e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
     if (hess)
@@ -3726,11 +3888,7 @@ int eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data) {
     if (int rc = grow_dev(&e->dset_Ud, &e->dset_Ud_cap, (size_t)M * nd)) return rc;
     hipStream_t st = e->stream;
     HIPCHK(hipMemcpyAsync(e->dset_D, data, (size_t)M * nd * sizeof(double), hipMemcpyHostToDevice, st));
-    GemmDesc gd{};  // Ud = D C^-1, as draws_gram multiplies A: a row of -D there is the exact negation of its row here
-    gd.A = e->dset_D; gd.a_group = 0; gd.a_row = nd; gd.a_seg = 0; gd.rows = M; gd.rows_per_group = M; gd.nseg = 1; gd.kseg = nd;
-    gd.B = e->like_invcov; gd.ldb = nd; gd.ncols = nd;
-    gd.C = e->dset_Ud; gd.c_group = 0; gd.c_row = nd; gd.c_colgroup = 0; gd.cols_per_group = nd;
-    hipLaunchKernelGGL(gemm_narrow_kernel, dim3((gd.rows + 15) / 16, (gd.ncols + 16 * GN_MAXT - 1) / (16 * GN_MAXT)), dim3(256), 0, st, gd, GemmZ{});
+    launch_times_invcov(e, st, e->dset_D, M, e->dset_Ud);  // Ud = D C^-1, as draws_gram multiplies A: a row of -D there is the exact negation of its row here
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
     HIPCHK(hipStreamSynchronize(st));  // (the caller's array is free again)
