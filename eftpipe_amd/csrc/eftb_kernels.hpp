@@ -2650,8 +2650,8 @@ __global__ __launch_bounds__(256) void ap_plk_kernel(int Nk, int nmu, const doub
                                                      const double* __restrict__ LOCAL, const double* __restrict__ T, const double* __restrict__ bias,
                                                      double* __restrict__ Plk, double* __restrict__ PlkHost, int* __restrict__ nonfinite, int direct0) {
     extern __shared__ double sm[];
-    double* s_k = sm;                           // [Nk] the k grid (every interval search below is an LDS walk)
-    double* s_node = s_k + Nk;                  // [nmu][8]
+    double* s_k = sm;                           // [Nk] (+ 1 if odd) the k grid (every interval search below is an LDS walk)
+    double* s_node = s_k + ((Nk + 1) & ~1);     // [nmu][8]  (16-byte aligned for an odd Nk too: read and written 32 bytes at a time, like s_pp behind it)
     double* s_pp = s_node + (size_t)nmu * 8;    // [NL][APD_WMAX][4]
     double* s_red = s_pp + NL * APD_WMAX * 4;   // [3][NL][64]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3119,6 +3119,11 @@ __global__ __launch_bounds__(256) void copy16_kernel(const double* __restrict__ 
     double2* d2 = reinterpret_cast<double2*>(dst);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) d2[i] = s2[i];
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) dst[n - 1] = src[n - 1];
+}
+
+// the same with 8 bytes per lane: for a source or destination that is only 8-byte aligned (an odd row length and a step that starts at an odd row)
+__global__ __launch_bounds__(256) void copy8_kernel(const double* __restrict__ src, double* __restrict__ dst, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 // ------------------------------------------------------------------------------------------------

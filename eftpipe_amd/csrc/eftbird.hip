@@ -14,6 +14,7 @@
 #include <mutex>
 #include <thread>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1305,7 +1306,7 @@ static void ap_pass_plk(StageRun& r, const double* in) {
     if (!nodes && !fused) launch_ap_prefix(e, st, B, false);
     const int tslot = timer_begin(e, st, 2);
     if (nodes) {  // the node quadrature on the contracted row (ap_plk_kernel); nothing else of the stage runs
-        const size_t lds = ((size_t)Nk + (size_t)c.nmu * 8 + 3 * APD_WMAX * 4 + 3 * 3 * 64) * sizeof(double);
+        const size_t lds = ((size_t)((Nk + 1) & ~1) + (size_t)c.nmu * 8 + 3 * APD_WMAX * 4 + 3 * 3 * 64) * sizeof(double);
         hipLaunchKernelGGL((ap_plk_kernel<3>), dim3(((Nk + 63) / 64) * B), dim3(256), lds, st, APK_ARGS(tb<double>(e, EFTB_T_WMU), tb<double>(e, EFTB_T_LEGMU)));
     } else if (fused) {
         // moment form with everything in LDS (ap_plk_fused_kernel): prefix sums, pieces and the walk in one launch
@@ -2796,9 +2797,15 @@ static int issue_group(eftb_engine* e, const eftb_engine::SubCmd* cmds, int n, b
         // the DMA engine, in line behind the launch's last kernel (same-box A/B over 200 steps: 0.091-0.096 ms per step against 0.102-0.104 with
         // copy16_kernel -- the what-if runs priced the kernel's PCIe stores at a fifth of the step; EFTB_PLK_DMA=0 brings the kernel back)
         const bool dma = e->plk_dma || !plk_direct;
+        // (16 bytes per lane only where both ends are 16-byte aligned: with an odd row length the later steps of a launch start at odd offsets)
+        auto launch_copy = [&](const double* src, double* dst, size_t count) {
+            if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0)
+                hipLaunchKernelGGL(copy16_kernel, dim3(copy_wgs), dim3(256), 0, st, src, dst, count);
+            else hipLaunchKernelGGL(copy8_kernel, dim3(copy_wgs), dim3(256), 0, st, src, dst, count);
+        };
         if (WHATIF_SKIP(512)) return 0;   // (what-if: P_l stays on the device)
         if (WHATIF_SKIP(2048) && e->PLK0) {   // (what-if: the copy kernel with a device destination -- the stream holds it, PCIe does not)
-            hipLaunchKernelGGL(copy16_kernel, dim3(copy_wgs), dim3(256), 0, st, e->buf[EFTB_B_PLK], e->PLK0, (size_t)Bt * per);
+            launch_copy(e->buf[EFTB_B_PLK], e->PLK0, (size_t)Bt * per);
             return 0;
         }
         for (int j = 0; j < n; ++j)
@@ -2814,7 +2821,7 @@ static int issue_group(eftb_engine* e, const eftb_engine::SubCmd* cmds, int n, b
             const double* src = e->buf[EFTB_B_PLK] + (size_t)row * per;
             double* dst = cmds[j].out ? cmds[j].out : e->plk_host[q] + (size_t)row * per;
             if (dma) HIPCHK(hipMemcpyAsync(dst, src, (size_t)rows * per * sizeof(double), hipMemcpyDeviceToHost, st));
-            else hipLaunchKernelGGL(copy16_kernel, dim3(copy_wgs), dim3(256), 0, st, src, dst, (size_t)rows * per);
+            else launch_copy(src, dst, (size_t)rows * per);
             row += rows;
             j = j1;
         }

@@ -21,7 +21,7 @@ CASE_FLAGS = {
 
 
 def oracle_config(g, name, **over):
-    fl = CASE_FLAGS[name]
+    fl = dict(resum=True, ap=True) if name.startswith("kgrid_") else CASE_FLAGS[name]  # (tools/make_fixtures.py kgrids: resum + AP on every grid)
     native = g["k"].size == 50
     cfg = OracleConfig(
         Nl=int(g["Nl"]), k=None if native else g["k"], kmA=0.7, krA=0.25, ndA=4.5e-5,

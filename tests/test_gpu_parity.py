@@ -112,12 +112,13 @@ def test_final_nk2048(golden):
 
 @pytest.mark.parametrize("name,APst,mode", [("caseE", False, None), ("caseD", False, None), ("caseD", True, None), ("caseF", False, None),
                                             ("caseD", False, "1"), ("caseD", True, "1"), ("caseE", False, "1"), ("caseD", False, "2"),
-                                            ("caseF", False, "0")])
+                                            ("caseF", False, "0"), ("kgrid_from002", False, None), ("kgrid_kmax04", False, None)])
 def test_ap_extreme_distortions(golden, monkeypatch, name, APst, mode):
     """AP stage alone over a batch of strong distortions: many knot intervals crossed (rising and falling k'(mu)),
     extrapolation past both ends of the k grid, the identity, and the isotropic F = 1 case.  mode: the engine's choice (knot weights +
     banded product with the quadrature fallback for tiles it cannot hold; interval moments at Nk = 2048) or one form forced through
-    EFTB_AP_MODE (0 weights / fallback, 1 interval moments, 2 the reference's quadrature everywhere)."""
+    EFTB_AP_MODE (0 weights / fallback, 1 interval moments, 2 the reference's quadrature everywhere).  kgrid_from002 starts at k = 0.02 (no low-k
+    points: the falling k'(mu) leaves the grid at its lower end from the first tile on), kgrid_kmax04 is the drop-in's grid for kmax = 0.4."""
     from eftpipe_amd import _lib as L
 
     if mode is not None:

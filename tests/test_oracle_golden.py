@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+from eftpipe_amd import synth
 from oracle import tables as T
 from oracle.engine import OracleEngine, da_func, hubble
 from oracle.fftlog import FFTLogGrid
@@ -395,3 +396,31 @@ def test_cfg3_nk512_oracle_ap_stage_other_redshift(golden):
     st = eng.evaluate(g["kin"], g[t + "_Pin"], float(g[t + "_f"]), float(g[t + "_DA"]), float(g[t + "_H"]), pairwise=True)
     for n in U.NAMES:
         assert relerr(st[n], g[f"{t}_ap_{n}"]) < TOL, n
+
+
+KGRIDS = ["kmax04", "kmax05", "from002", "lowdense", "odd77", "nk8", "densemid", "finetail", "s753", "s754", "s755"]
+
+
+@pytest.mark.parametrize("name", KGRIDS)
+def test_kgrid_fixtures(golden, name):
+    """Oracle == reference on the k grids off the usual outline (tests/golden/kgrid_<name>.npz, tools/make_fixtures.py kgrids; what each grid
+    is there for: tests/test_kgrids.py): the templates in front of and behind the AP stage and the contracted multipoles, at Nl = 3 and,
+    where the fixture has it, at Nl = 2."""
+    from oracle import OracleConfig
+
+    g = golden("kgrid_" + name)
+    f = float(g["f"])
+    for Nl, pre in ((3, ""), (2, "nl2_")):
+        if pre + "plk_auto" not in g:
+            continue
+        eng = OracleEngine(OracleConfig(Nl=Nl, k=g["k"], kmA=0.7, krA=0.25, ndA=4.5e-5, with_resum=True, with_ap=True, Om_AP=synth.OM_AP,
+                                        z_AP=float(g["z"])))
+        assert np.array_equal(eng.k, g["k"])
+        assert np.isclose(eng.DA_fid, g["DA_AP"], rtol=1e-14) and np.isclose(eng.H_fid, g["H_AP"], rtol=1e-15)
+        taps = {}
+        st = eng.evaluate(g["kin"], g["Pin"], f, float(g["DA"]), float(g["H"]), taps=taps)
+        for n in ("P11l", "Pctl", "Ploopl"):
+            assert relerr(taps["resum"][n], g[pre + "resum_" + n]) < TOL, (Nl, n)
+        for n in ("P11l", "Pctl", "Ploopl", "Pstl"):
+            assert relerr(st[n], g[pre + "ap_" + n]) < TOL, (Nl, n)
+        assert relerr(eng.reduce_plk(f, st, list(g["bsA"]), es=tuple(g["es"])), g[pre + "plk_auto"]) < TOL, Nl

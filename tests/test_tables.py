@@ -62,6 +62,54 @@ def test_device_algebra_matches_oracle(golden, name, resum, ap):
             assert relerr(st[n], g["ap_" + n]) < 1e-9, n
 
 
+@pytest.mark.parametrize("name", ["kmax04", "kmax05", "from002", "lowdense", "odd77", "nk8", "densemid", "finetail"])
+def test_device_algebra_matches_oracle_on_other_kgrids(golden, name):
+    """The chain of test_device_algebra_matches_oracle on the k grids off the usual outline (tests/golden/kgrid_<name>.npz, Nk <= 405; what each
+    grid is there for: tests/test_kgrids.py): Nklow = 0 ... 31, odd Nk, Nk = 8, kmax = 0.25 ... 0.5 -- at Nl = 3 and, where the fixture
+    has it, at Nl = 2; the matrix-core form of the resummation and the contracted form of direct-P_l runs where the tables carry them."""
+    from oracle import OracleConfig, OracleEngine
+    from oracle.engine import da_func, hubble
+
+    g = golden("kgrid_" + name)
+    f, DA, H, z = float(g["f"]), float(g["DA"]), float(g["H"]), float(g["z"])
+    for Nl, pre in ((3, ""), (2, "nl2_")):
+        if pre + "plk_auto" not in g:
+            continue
+        t = build_tables(EngineConfig(Nl=Nl, k=g["k"], with_resum=True, with_ap=True, DA_AP=da_func(synth.OM_AP, z), H_AP=hubble(synth.OM_AP, z)))
+        eng = OracleEngine(OracleConfig(Nl=Nl, k=g["k"], kmA=0.7, krA=0.25, ndA=4.5e-5, with_resum=True, with_ap=True, Om_AP=synth.OM_AP, z_AP=z))
+        taps = {}
+        eng.evaluate(g["kin"], g["Pin"], f, DA, H, taps=taps)
+        st = E.pscf(t, g["Pin"], with_cf=True)
+        for n in ("P11", "P22", "P13", "C11", "Cct", "C22", "C13"):
+            assert relerr(st[n], taps["pscf"][n]) < 1e-9, (Nl, n)
+        st.update(E.setpscfl(t, f, st, with_cf=True))
+        for n in ("P11l", "Pctl", "Ploopl", "Pstl", "Cloopl"):
+            assert relerr(st[n], taps["setpscfl"][n]) < 1e-9, (Nl, n)
+        st = E.resum(t, f, g["Pin"], st)
+        assert relerr(st["X"], taps["resum"]["X"]) < 1e-10 and relerr(st["Y"], taps["resum"]["Y"]) < 1e-10
+        for n in ("P11l", "Pctl", "Ploopl"):
+            assert relerr(st[n], taps["resum"][n]) < 1e-9, (Nl, n)
+            assert relerr(st[n], g[pre + "resum_" + n]) < 1e-9, (Nl, n)
+        if "rs_rows" in t:  # matrix-core form of the stage
+            pre_rs = {n: taps["setpscfl"][n] for n in ("P11l", "Pctl", "Ploopl", "Cloopl")}
+            pre_rs.update(C11=taps["pscf"]["C11"], Cct=taps["pscf"]["Cct"])
+            alt = E.resum_mfma(t, f, g["Pin"], pre_rs)
+            for n in ("P11l", "Pctl", "Ploopl"):
+                assert relerr(alt[n], taps["resum"][n]) < 1e-9, (Nl, n)
+            zz = t["k"][:, None] ** 2 * alt["X"][None, :]
+            assert zz.max() < 2 * 8.0  # the scaled variable of the polynomial basis stays O(1): 11.1 at kmax = 0.5
+            if Nl == 3:  # direct-P_l runs: the contracted correction against the reference's template corrections contracted afterwards
+                bias = np.random.default_rng(3).normal(size=24)
+                dref = sum(np.einsum("i,lik->lk", bias[sl], taps["resum"][n] - taps["setpscfl"][n])
+                           for n, sl in (("P11l", slice(0, 3)), ("Pctl", slice(3, 9)), ("Ploopl", slice(9, 21))))
+                assert relerr(E.resum_plk(t, f, g["Pin"], pre_rs, bias), dref) < 1e-9
+        names = ("P11l", "Pctl", "Ploopl")
+        st = E.ap(t, DA, H, st, names)
+        for n in names:
+            assert relerr(st[n], taps["ap"][n]) < 1e-9, (Nl, n)
+            assert relerr(st[n], g[pre + "ap_" + n]) < 1e-9, (Nl, n)
+
+
 def test_banded_spline_operator_matches_scipy():
     from scipy.interpolate import CubicSpline
 

@@ -6,6 +6,7 @@ does (reference theory.py:557-609).  Only inputs + outputs are stored (data, no 
 
     python tools/make_fixtures.py            # all cases
     python tools/make_fixtures.py caseD      # one case
+    python tools/make_fixtures.py kgrids     # the eleven kgrid_<name>.npz files (kgrid_odd77: one of them)
 """
 from __future__ import annotations
 
@@ -980,10 +981,86 @@ def fftlog_fixture(ref):
     print("fftlog written:", len(out), "arrays")
 
 
+# ----------------------------------------------------------------------------- k grids off the usual outline
+# Every other fixture has k[0] = 0.001, k[-1] = 0.3 and 7 points below 0.02.  These eleven grids each sit on one edge the launcher or a kernel
+# branches on (tests/test_kgrids.py restates what each one is for and checks the stored k against it).  None = the grid of Common(kmax=...).
+KGRIDS = {
+    "kmax04": (0.4, None),
+    "kmax05": (0.5, None),
+    "from002": (0.3, lambda: np.linspace(0.02, 0.3, 100)),
+    "lowdense": (0.3, lambda: np.linspace(0.001, 0.25, 301)),
+    "odd77": (0.3, lambda: np.concatenate([np.linspace(0.002, 0.0199, 20), np.linspace(0.02, 0.35, 57)])),
+    "nk8": (0.3, lambda: np.linspace(0.01, 0.2, 8)),
+    "densemid": (0.3, lambda: np.concatenate([np.linspace(0.005, 0.2, 400)[:-1], np.linspace(0.2, 0.3, 6)])),
+    "finetail": (0.3, lambda: np.concatenate([np.linspace(0.005, 0.29, 58), [0.2901, 0.2902]])),
+    "s753": (0.3, lambda: synth.survey_kgrid(753)),
+    "s754": (0.3, lambda: synth.survey_kgrid(754)),
+    "s755": (0.3, lambda: synth.survey_kgrid(755)),
+}
+KGRID_NL2_MAX_NK = 104
+
+
+def save_npz_reproducible(path, arrays):
+    """np.savez_compressed with fixed member timestamps, so that the same arrays give the same file bytes."""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for name, val in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue())
+
+
+def kgrid_fixture(ref, name):
+    """One tests/golden/kgrid_<name>.npz: what run_case(final_only=True) stores for a resum + AP case, plus the templates in front of the AP
+    stage; at Nl = 3, and for the grids with Nk <= 104 also at Nl = 2 under an `nl2_` prefix.  The cosmology is synth.cosmology(z=0.7) with
+    DA * 1.03 and H * 0.97, so that k'(mu) crosses knots and leaves the grid at its upper end."""
+    pb = ref.pybird
+    z = 0.7
+    kmax, grid = KGRIDS[name]
+    cos = synth.cosmology(z=z)
+    DA, H = cos["DA"] * 1.03, cos["H"] * 0.97
+    out = dict(kin=cos["kin"], Pin=cos["Pin"], f=cos["f"], DA=DA, H=H, z=z, Nl=3, bsA=BS_A, es=ES)
+    for Nl in (3, 2):
+        co = pb.Common(Nl=Nl, kmax=kmax, kmA=0.7, krA=0.25, ndA=4.5e-5)
+        if grid is not None:
+            k = np.asarray(grid(), dtype=np.float64)
+            co.k, co.Nk = k, k.size
+            co.kr = k[0.02 <= k]
+            co.Nkr = co.kr.size
+            co.Nklow = co.Nk - co.Nkr
+        if Nl == 2 and co.Nk > KGRID_NL2_MAX_NK:
+            break
+        pre = "" if Nl == 3 else "nl2_"
+        out["k"] = co.k
+        nl = pb.NonLinear(load=False, save=False, co=co)
+        bird = pb.Bird(cos["kin"], cos["Pin"], cos["f"], DA, H, z, co=co)
+        nl.PsCf(bird)
+        bird.setPsCfl()
+        pb.Resum(co=co).Ps(bird)
+        for n, v in stage(bird, ("P11l", "Pctl", "Ploopl")).items():
+            out[pre + "resum_" + n] = v
+        ap = pb.APeffect(Om_AP=synth.OM_AP, z_AP=z, co=co)
+        out["DA_AP"], out["H_AP"] = ap.DA, ap.H
+        ap.AP(bird)
+        for n, v in stage(bird).items():
+            out[pre + "ap_" + n] = v
+        out[pre + "plk_auto"] = ref.parambasis.reduce_Plk(bird, BS_A, es=ES).sum()
+    path = os.path.join(GOLD, "kgrid_" + name + ".npz")
+    save_npz_reproducible(path, out)
+    k = out["k"]
+    print("kgrid_" + name, "written: Nk", k.size, "Nklow", int((k < 0.02).sum()), "nl2" if "nl2_plk_auto" in out else "", os.path.getsize(path), "bytes",
+          flush=True)
+
+
 def main():
     ref = load_reference()
     os.makedirs(GOLD, exist_ok=True)
-    want = sys.argv[1:] or (["tables"] + list(CASES) + ["marg", "pyegg", "east", "fiber", "nnlo", "ircut", "opti", "wmat", "cfg3", "resumopt", "cfg5", "cfg3_nk512", "surface", "cfg5_acc4", "fftlog"])
+    want = sys.argv[1:] or (["tables"] + list(CASES) + ["marg", "pyegg", "east", "fiber", "nnlo", "ircut", "opti", "wmat", "cfg3", "resumopt", "cfg5", "cfg3_nk512", "surface", "cfg5_acc4", "fftlog", "kgrids"])
     for name in want:
         if name == "tables":
             tables_fixture(ref)
@@ -1017,6 +1094,11 @@ def main():
             cfg5_fixture(ref)
         elif name == "fftlog":
             fftlog_fixture(ref)
+        elif name == "kgrids":
+            for grid in KGRIDS:
+                kgrid_fixture(ref, grid)
+        elif name.startswith("kgrid_"):
+            kgrid_fixture(ref, name[len("kgrid_"):])
         else:
             run_case(ref, name, CASES[name])
 
