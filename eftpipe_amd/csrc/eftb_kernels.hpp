@@ -1625,26 +1625,33 @@ __global__ __launch_bounds__(256, 2) void resum_mfma_kernel(int Nk, int Nklow, i
 
 // ------------------------------------------------------------------------------------------------
 // IR-resummation of direct-P_l runs (EFTB_O_PLK_DIRECT; Nl = 3).  With the bias contraction taken first the correction of P_l is
-//     dP_l(k) = k^2 sum_s sum_v H_v(k,s) D_lv(k^2 X(s) / RS_ZS; s),
-//     D_lv(t; s) = sum_p t^p RS_ZS^p sum_l' sum_a g_a[l'](s) ( delta(v,l') X(s) Q_a[l,l',(0,p,v)] + Y(s) Q_a[l,l',(1,p,v)] ),
+//     dP_l(k) = k^2 sum_s sum_v H_v(k,s) D_lv(k^2 X(s); s),
+//     D_lv(z; s) = sum_p z^p sum_l' sum_a g_a[l'](s) ( delta(v,l') X(s) Q_a[l,l',(0,p,v)] + Y(s) Q_a[l,l',(1,p,v)] ),
 //     g_0[l'](s) = C11[l'](s) sum_i b_i l11[l'][i],    g_1[l'](s) = Cct[l'](s) sum_i b_3+i lct[l'][i] + sum_i b_9+i Cloopl[l'][i](s)
 // (reference pybird.py:1413-1464 contracted with parambasis.py:42-136): nine polynomials of degree 15 per s whose coefficients are the same
-// for every k -- scalar operands.  resum_prep_plk_kernel builds them per cosmology (CF[w][s][160]: [l][v][p], then X(s) / RS_ZS), with
-// the regrouping of C22 / C13 into Cloopl (pybird.py:805-846) folded into g_1; resum_plk_kernel is one wave = (64 k, one l): per s three
-// Horner chains with scalar coefficients and three FMAs -- 49 FP64 vector instructions per (64 k, l, s), no matrix cores (nine rows would
-// leave a 16-row tile half empty and the basis polynomials would cost more than the Horner chains).
+// for every k.  All of them lie in one 8-dimensional space with a closed-form basis (tables.py resum_plk_tables): with u = -z / 2
+//     sum_p q_p z^p = -1/2 sum_j c_j b_j(u),   b_0 = sum_{p<16} u^p / (p+1)!,   b_j = u^(j-1) e_{16-j}(u)  (j = 1..7),   e_n = sum_{m<=n} u^m / m!
+// and the eight b_j fall out of ONE Horner evaluation of e_16: h_16 = 1/16!, h_m = h_{m+1} u + 1/m! gives h_m = sum_i u^i / (m+i)!, so
+//     b_0 = h_1,   b_j = u^(j-1) h_0 - u^16 h_{17-j}.
+// The basis costs 37 FP64 instructions per (k, s) and is shared by the nine (l, v): each is an 8-term dot product with SCALAR coefficients
+// W[l][v][j](s) and one FMA with H_v -- 118 instructions per (k, s) where nine Horner chains of degree 15 took 162.  resum_prep_plk_kernel
+// builds the records per cosmology (CF[w][s][80]: W [l][v][j] with the -1/2 folded in, then -X(s) / 2) from Q_e(f), the coordinates c_j of
+// Q(f) (qf_body on the table QEpoly), with the regrouping of C22 / C13 into Cloopl (pybird.py:805-846) folded into g_1.
 // ------------------------------------------------------------------------------------------------
-constexpr int RSD_REC = 160;  // doubles per (cosmology, s): 9 x 16 coefficients, X / RS_ZS, pad
+constexpr int RSD_NB = 8;    // basis functions
+constexpr int RSD_REC = 80;  // doubles per (cosmology, s): 9 x 8 coefficients, -X / 2, pad
+constexpr int RSD_NN = 2 * RSD_NB * 3;  // Q_e(f) entries per (a, l, l'): [half][j][v]
+constexpr int RSD_KPL = 2, RSD_SH = 8;  // the shape resum_plk_kernel is launched in: k per lane, slices of the s range
 
-__device__ __forceinline__ void resum_prep_plk_body(int w, int part, int nparts, int NN, int NIR, int Na, const double* __restrict__ Q,
+__device__ __forceinline__ void resum_prep_plk_body(int w, int part, int nparts, const double* __restrict__ Q,
                                                     const double* __restrict__ XY, const double* __restrict__ C11, const double* __restrict__ Cct,
                                                     const double* __restrict__ YCF, double* __restrict__ CF) {
     // grid (cosmology, slice of the s range).  g_0[l'](s) = C11[w][l'][s], g_1[l'](s) = Cct[w][l'][s] + YCF[w][l'][s]: all three already carry their
-    // bias coefficients (build_rows_plk_kernel contracted the rows before the synthesis).  A thread owns ONE entry c = (l, v, p) of the record
-    // and walks every second s of the slice: its eight Q(f) values sit in registers, g, X and Y of the slice in LDS (broadcast reads) -- the
+    // bias coefficients (build_rows_plk_kernel contracted the rows before the synthesis).  A thread owns ONE entry c = (l, v, j) of the record
+    // and walks every fourth s of the slice: its eight Q_e(f) values sit in registers, g, X and Y of the slice in LDS (broadcast reads) -- the
     // first form (entries x s flattened over the workgroup, X / Y from global memory inside the loop, Q(f) in LDS) took ten dependent global
     // loads per thread: 29 us alone at 512 cosmologies per launch, a third of them in a second round of workgroups
-    constexpr int NL = 3;
+    constexpr int NL = 3, Na = 3, NN = RSD_NN;
     const int ns = (NS + nparts - 1) / nparts, s0 = part * ns, s1 = min(NS, s0 + ns), nsl = s1 - s0;
     extern __shared__ double sm[];
     double* s_g = sm;                  // [2][NL][ns] g_a[l'](s0 + .)
@@ -1655,9 +1662,9 @@ __device__ __forceinline__ void resum_prep_plk_body(int w, int part, int nparts,
         s_g[(NL + lp) * ns + sl] = Cct[((size_t)w * NL + lp) * NS + s] + YCF[((size_t)w * BASC + lp) * NS + s];
     }
     for (int e = threadIdx.x; e < 2 * nsl; e += blockDim.x) s_xy[(e / nsl) * ns + e % nsl] = XY[(size_t)w * 2 * NS + (size_t)(e / nsl) * NS + s0 + e % nsl];
-    const int c = threadIdx.x % RSD_REC, half = threadIdx.x / RSD_REC, nhalf = blockDim.x / RSD_REC;
-    const int l = c / 48, vv = (c / 16) % 3, p = c % 16;
-    const bool poly = c < 144 && p < NIR;
+    const int c = threadIdx.x % RSD_REC, quarter = threadIdx.x / RSD_REC, nquarter = blockDim.x / RSD_REC;
+    const int l = c / (3 * RSD_NB), vv = (c / RSD_NB) % 3, j = c % RSD_NB;
+    const bool poly = c < 9 * RSD_NB;
     double qy[2][NL], qx[2] = {0.0, 0.0};
 #pragma unroll
     for (int a = 0; a < 2; ++a)   // device Q[a]: 0 = the C11 series, 1 = the Cct / Cloopl series
@@ -1665,15 +1672,14 @@ __device__ __forceinline__ void resum_prep_plk_body(int w, int part, int nparts,
         for (int lp = 0; lp < NL; ++lp) {
             qy[a][lp] = 0.0;
             if (poly) {
-                const double* qq = Q + (size_t)w * 2 * NL * NL * NN + ((a * NL + l) * NL + lp) * NN + p * Na + vv;
-                qy[a][lp] = qq[NIR * Na];
+                const double* qq = Q + (size_t)w * 2 * NL * NL * NN + ((a * NL + l) * NL + lp) * NN + j * Na + vv;
+                qy[a][lp] = qq[RSD_NB * Na];
                 if (lp == vv) qx[a] = qq[0];
             }
         }
     __syncthreads();
-    if (half >= nhalf) return;
     double* dst = CF + ((size_t)w * NS + s0) * RSD_REC + c;
-    for (int sl = half; sl < nsl; sl += nhalf) {
+    for (int sl = quarter; sl < nsl; sl += nquarter) {
         double v = 0.0;
         if (poly) {
             const double x = s_xy[sl], y = s_xy[ns + sl];
@@ -1685,9 +1691,9 @@ __device__ __forceinline__ void resum_prep_plk_body(int w, int part, int nparts,
                     if (lp == vv) term = fma(x, qx[a], term);
                     v = fma(s_g[(a * NL + lp) * ns + sl], term, v);
                 }
-            v = ldexp(v, 3 * p);  // RS_ZS^p, RS_ZS = 8
-        } else if (c == 144) {
-            v = s_xy[sl] * (1.0 / RS_ZS);
+            v *= -0.5;
+        } else if (c == 9 * RSD_NB) {
+            v = -0.5 * s_xy[sl];
         }
         dst[(size_t)sl * RSD_REC] = v;
     }
@@ -1695,12 +1701,12 @@ __device__ __forceinline__ void resum_prep_plk_body(int w, int part, int nparts,
 
 // One launch for the two light kernels between the syntheses and the resummation of a direct-P_l run (a launch costs the host 4 us and the step is
 // bounded by the host): workgroups [0, nreg) = regroup_plk (k tile, cosmology, l), the rest = resum_prep_plk (cosmology, slice of the s range)
-constexpr int BPP_THREADS = 2 * RSD_REC;   // 320: the coefficient part's (entry, half of the s slice); the regrouping part uses the first 256
+constexpr int BPP_THREADS = 4 * RSD_REC;   // 320: the coefficient part's (entry, quarter of the s slice); the regrouping part uses the first 256
 __global__ __launch_bounds__(BPP_THREADS) void back_prep_plk_kernel(int nreg, int nkx, int B, int nparts, int Nk, int Nl, const double* __restrict__ kk,
                                                             const double* __restrict__ P11, const double* __restrict__ Y22,
                                                             const double* __restrict__ P13, const double* __restrict__ l11,
                                                             const double* __restrict__ lct, const double* __restrict__ bias, double* __restrict__ T,
-                                                            int stoch0, int NN, int NIR, int Na, const double* __restrict__ Q,
+                                                            int stoch0, const double* __restrict__ Q,
                                                             const double* __restrict__ XY, const double* __restrict__ C11,
                                                             const double* __restrict__ Cct, const double* __restrict__ YCF, double* __restrict__ CF) {
     const int id = blockIdx.x;
@@ -1708,14 +1714,24 @@ __global__ __launch_bounds__(BPP_THREADS) void back_prep_plk_kernel(int nreg, in
         regroup_plk_body(id % nkx, id / nkx, Nk, Nl, kk, P11, Y22, P13, l11, lct, bias, T, stoch0);
     } else {
         const int j = id - nreg;
-        resum_prep_plk_body(j % B, j / B, nparts, NN, NIR, Na, Q, XY, C11, Cct, YCF, CF);
+        resum_prep_plk_body(j % B, j / B, nparts, Q, XY, C11, Cct, YCF, CF);
     }
 }
 
 // FP64 vector operations with one scalar (wave-uniform) operand, spelled out
-__device__ __forceinline__ double sop_fma(double a, double b, double c) {
+__device__ __forceinline__ double sop_fma(double a, double b, double c) {   // a b + c, c scalar
     double r;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+}
+__device__ __forceinline__ double sop_fmas(double a, double b, double c) {  // a b + c, b scalar
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ double sop_fnmas(double a, double b, double c) {  // c - a b, b scalar
+    double r;
+    asm("v_fma_f64 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
     return r;
 }
 __device__ __forceinline__ double sop_mul(double a, double c) {
@@ -1723,89 +1739,152 @@ __device__ __forceinline__ double sop_mul(double a, double c) {
     asm("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(c));
     return r;
 }
-__device__ __forceinline__ double sop_add(double a, double c) {
-    double r;
-    asm("v_add_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(c));
-    return r;
-}
 
-// workgroup = 3 SH waves = (v, slice of the s range) of one (64 KPL k, l, cosmology): a lane owns KPL k (64 apart), so a wave runs KPL
-// independent Horner chains per s on ONE set of 16 scalar coefficients -- at one k per lane and with the wait for a set in front of the step
-// that requests the next one, the scalar loads, not the FP64 pipe, set the pace (66-71 us) -- sums H_v D_lv over its s in registers, and the
-// 3 SH partial sums meet in LDS at the end, added in wave order.  KPL = 2, SH = 2: 9 216 equal waves = nine per SIMD.
+// 1 / m!, m = 0 ... 16: the Horner coefficients of e_16.  A 64-bit constant cannot be a literal operand, so each one the loop uses is a scalar
+// register pair (sop_fma) -- 1, 1, 1/2 are inline constants and 1/15! sits in a vector pair.  (The other way, the constants as per-s Horner
+// coefficients in k^2 riding in the record, was not built: it adds 16 scalar loads per s to a kernel whose remaining waits are scalar loads.
+// With the ring below the thirteen pairs no longer all fit beside it: the compiler keeps some in lanes of a vector register, 27 v_readlane /
+// v_writelane per s step -- still the faster form, 29.3 us alone at 128 cosmologies against 31.1 with sets of eight and every constant resident.)
+__host__ __device__ constexpr double rsd_inv_fact(int m) {
+    double f = 1.0;
+    for (int i = 2; i <= m; ++i) f *= i;
+    return 1.0 / f;
+}
+#define RSD_F(m) rsd_inv_fact(m)
+
+// workgroup = SH waves = slices of the s range of one (64 KPL k, cosmology): a lane owns KPL k (64 apart), and a wave owns ALL nine (l, v) of
+// its (k, s) points -- the eight basis values of a point live in registers and serve nine dot products (shared between waves through LDS
+// each value would be read back for a single FMA: a CU's LDS returns 16 doubles per clock against 64 FP64 lanes).  Per s a wave reads its 72
+// scalar coefficients through a ring of two sets of sixteen (two dot products each) and one of eight: a set is requested at least two dot
+// products (36 FP64 instructions per k) before it is read and waited for where it is first used (scalar loads return out of order: a wait
+// is always for all of them, so it must not sit behind the requests of the next set) -- four waits per s; with sets of eight, ten waits
+// per s and one dot product of cover, four resident waves did not hide the loads (31.1 us alone against 29.3).  The SH partial sums of the three l meet in LDS at the end and are added in wave order: no atomics, the result
+// does not depend on timing.  KPL = 2, SH = 8: 4 096 equal waves per 128 cosmologies = four per SIMD.
 template <int KPL, int SH>
-__global__ __launch_bounds__(192 * SH) void resum_plk_kernel(int Nk, int Nklow, const double* __restrict__ kk, const double* __restrict__ H,
-                                                             const double* __restrict__ CF, double* __restrict__ T, int KT) {
-    constexpr int NL = 3, NSH = NS / SH;  // (NS = 80: NSH even for SH = 1, 2, 4)
-    __shared__ double s_part[3 * SH - 1][KPL][64];
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (wave-uniform: the coefficient loads stay scalar)
-    const int v = wv % 3, sh = wv / 3;
-    // workgroup -> (k tile of 64 KPL, l, cosmology); the 3 KT workgroups of a cosmology sit on one XCD (its coefficient table passes through one L2)
-    int t3, w;
-    xcd_decode(KT * NL, t3, w);
-    const int kt = t3 / NL, l = t3 % NL;
+__global__ __launch_bounds__(64 * SH, 4) void resum_plk_kernel(int Nk, int Nklow, const double* __restrict__ kk, const double* __restrict__ H,
+                                                               const double* __restrict__ CF, double* __restrict__ T, int KT) {
+    constexpr int NL = 3, NV = 3, NSH = NS / SH;
+    static_assert(NS % (2 * SH) == 0, "two s steps per trip");
+    __shared__ double s_part[SH - 1][NL][KPL][64];
+    const int lane = threadIdx.x & 63, sh = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (wave-uniform: the coefficient loads stay scalar)
+    // workgroup -> (k tile of 64 KPL, cosmology); the KT workgroups of a cosmology sit on one XCD (its coefficient table passes through one L2)
+    int kt, w;
+    xcd_decode(KT, kt, w);
     int k[KPL];
-    double k2[KPL], acc[KPL], h[KPL];
-    const double* hp = H + ((size_t)v * NS + sh * NSH) * Nk;
+    double k2[KPL], acc[NL][KPL], h[NV][KPL];
+    const double* hp = H + (size_t)sh * NSH * Nk;
+    const size_t hv = (size_t)NS * Nk;
     unsigned ho[KPL];
 #pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-        k[j] = kt * 64 * KPL + 64 * j + lane;
-        const int kc = k[j] < Nklow ? Nklow : (k[j] < Nk ? k[j] : Nk - 1);  // lanes outside [Nklow, Nk) compute on a clamped k and store nothing
-        k2[j] = kk[kc] * kk[kc];
-        ho[j] = (unsigned)kc;
-        h[j] = hp[ho[j]];
-        acc[j] = 0.0;
-    }
-    const double* cf = CF + ((size_t)w * NS + sh * NSH) * RSD_REC + l * 48 + v * 16;  // wave-uniform: scalar loads; X / RS_ZS sits at [144] of the record
-    const int xo = 144 - l * 48 - v * 16;
-    // two steps per trip with two coefficient sets: the set a step reads was requested one step earlier and is waited for where it is first
-    // used (scalar loads return out of order: a wait is always for all of them, so it must not sit behind the requests of the next set)
-    double ca[16], cb[16], xa = cf[xo], xb;
+    for (int i = 0; i < KPL; ++i) {
+        k[i] = kt * 64 * KPL + 64 * i + lane;
+        const int kc = k[i] < Nklow ? Nklow : (k[i] < Nk ? k[i] : Nk - 1);  // lanes outside [Nklow, Nk) compute on a clamped k and store nothing
+        k2[i] = kk[kc] * kk[kc];
+        ho[i] = (unsigned)kc;
 #pragma unroll
-    for (int p = 0; p < 16; ++p) ca[p] = cf[p];
-#define RSD_STEP(C, X, CN, XN, MORE)                                                                        \
+        for (int v = 0; v < NV; ++v) h[v][i] = hp[v * hv + ho[i]];
+#pragma unroll
+        for (int l = 0; l < NL; ++l) acc[l][i] = 0.0;
+    }
+    const double* cf = CF + ((size_t)w * NS + sh * NSH) * RSD_REC;  // wave-uniform: scalar loads; -X / 2 sits at [72] of the record
+    const double f15 = RSD_F(15);
+    // the ring: two sets of sixteen coefficients = two (l, v) each, and one of eight for the ninth
+    double ca[2 * RSD_NB], cb[2 * RSD_NB], cc[RSD_NB], xa = cf[9 * RSD_NB];
+#pragma unroll
+    for (int j = 0; j < 2 * RSD_NB; ++j) ca[j] = cf[j];
+    double b[KPL][RSD_NB], hn[NV][KPL];
+    // the dot product of (l, v) = Q with the basis, times H_v, into the sum of l; its eight coefficients start at CUR[O]
+#define RSD_MAC(CUR, O, Q)                                                                                  \
     do {                                                                                                    \
-        asm volatile("" ::"s"(C[0]), "s"(X)); /* the wait for this step's set: in front of the next requests */ \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-        cf += (MORE) ? RSD_REC : 0;                                                                         \
+        double d[KPL];                                                                                      \
+        _Pragma("unroll") for (int i = 0; i < KPL; ++i) d[i] = sop_mul(b[i][0], CUR[O]);                    \
+        _Pragma("unroll") for (int j = 1; j < RSD_NB; ++j)                                                  \
+            _Pragma("unroll") for (int i = 0; i < KPL; ++i) d[i] = sop_fmas(b[i][j], CUR[(O) + j], d[i]);   \
+        _Pragma("unroll") for (int i = 0; i < KPL; ++i) acc[(Q) / NV][i] = fma(h[(Q) % NV][i], d[i], acc[(Q) / NV][i]); \
+    } while (0)
+#define RSD_WAIT(...)                                                                                       \
+    asm volatile("" ::__VA_ARGS__); /* the wait for a set: in front of the next requests */                 \
+    __builtin_amdgcn_sched_barrier(0)
+    // one s.  On entry ca holds the sets (l, v) = 0, 1 and xa the scalar -X(s) / 2, requested during the previous step
+#define RSD_STEP(MORE)                                                                                      \
+    do {                                                                                                    \
+        RSD_WAIT("s"(ca[0]), "s"(xa));                                                                      \
+        const double* cfn = cf + ((MORE) ? RSD_REC : 0);                                                    \
         hp += (MORE) ? Nk : 0;                                                                              \
-        _Pragma("unroll") for (int p = 0; p < 16; ++p) CN[p] = cf[p];                                       \
-        XN = cf[xo];                                                                                        \
-        double hn[KPL];                                                                                     \
-        _Pragma("unroll") for (int j = 0; j < KPL; ++j) hn[j] = hp[ho[j]];                                  \
+        _Pragma("unroll") for (int j = 0; j < 2 * RSD_NB; ++j) cb[j] = cf[2 * RSD_NB + j];                  \
+        _Pragma("unroll") for (int i = 0; i < KPL; ++i)                                                     \
+            _Pragma("unroll") for (int v = 0; v < NV; ++v) hn[v][i] = hp[v * hv + ho[i]];                   \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
-        /* Horner with the coefficients as SCALAR addends (v_fma_f64 v, v, v, s: left to itself hipcc picks v_fmac_f64 and moves */ \
-        /* every coefficient into a vector register pair first) */                                          \
-        double t[KPL], d[KPL];                                                                              \
-        _Pragma("unroll") for (int j = 0; j < KPL; ++j) {                                                   \
-            t[j] = sop_mul(k2[j], X);                                                                       \
-            d[j] = sop_add(sop_mul(t[j], C[15]), C[14]);                                                    \
+        _Pragma("unroll") for (int i = 0; i < KPL; ++i) {                                                   \
+            const double u = sop_mul(k2[i], xa);                                                            \
+            double g[17];                                                                                   \
+            g[15] = sop_fmas(u, RSD_F(16), f15);                                                            \
+            _Pragma("unroll") for (int m = 14; m >= 3; --m) g[m] = sop_fma(g[m + 1], u, RSD_F(m));          \
+            g[2] = fma(g[3], u, 0.5);                                                                       \
+            g[1] = fma(g[2], u, 1.0);                                                                       \
+            g[0] = fma(g[1], u, 1.0);                                                                       \
+            const double u2 = u * u, u3 = u2 * u, u4 = u2 * u2, u5 = u4 * u, u6 = u4 * u2, u8 = u4 * u4, u16 = u8 * u8; \
+            const double pw[7] = {1.0, u, u2, u3, u4, u5, u6};                                              \
+            b[i][0] = g[1];                                                                                 \
+            b[i][1] = sop_fnmas(u16, RSD_F(16), g[0]);                                                      \
+            _Pragma("unroll") for (int j = 2; j < RSD_NB; ++j) {                                            \
+                const double t = u16 * g[17 - j];                                                           \
+                b[i][j] = fma(pw[j - 1], g[0], -t);                                                         \
+            }                                                                                               \
         }                                                                                                   \
-        _Pragma("unroll") for (int p = 13; p >= 0; --p)                                                     \
-            _Pragma("unroll") for (int j = 0; j < KPL; ++j) d[j] = sop_fma(d[j], t[j], C[p]);               \
-        _Pragma("unroll") for (int j = 0; j < KPL; ++j) acc[j] = fma(h[j], d[j], acc[j]);                   \
+        RSD_MAC(ca, 0, 0);                                                                                  \
+        RSD_MAC(ca, RSD_NB, 1);                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
-        _Pragma("unroll") for (int j = 0; j < KPL; ++j) h[j] = hn[j];                                       \
+        RSD_WAIT("s"(cb[0]));                                                                               \
+        _Pragma("unroll") for (int j = 0; j < 2 * RSD_NB; ++j) ca[j] = cf[4 * RSD_NB + j];                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        RSD_MAC(cb, 0, 2);                                                                                  \
+        RSD_MAC(cb, RSD_NB, 3);                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        RSD_WAIT("s"(ca[0]));                                                                               \
+        _Pragma("unroll") for (int j = 0; j < 2 * RSD_NB; ++j) cb[j] = cf[6 * RSD_NB + j];                  \
+        _Pragma("unroll") for (int j = 0; j < RSD_NB; ++j) cc[j] = cf[8 * RSD_NB + j];                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        RSD_MAC(ca, 0, 4);                                                                                  \
+        RSD_MAC(ca, RSD_NB, 5);                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        RSD_WAIT("s"(cb[0]), "s"(cc[0]));                                                                   \
+        _Pragma("unroll") for (int j = 0; j < 2 * RSD_NB; ++j) ca[j] = cfn[j];                              \
+        xa = cfn[9 * RSD_NB];                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        RSD_MAC(cb, 0, 6);                                                                                  \
+        RSD_MAC(cb, RSD_NB, 7);                                                                             \
+        RSD_MAC(cc, 0, 8);                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        cf = cfn;                                                                                           \
+        _Pragma("unroll") for (int i = 0; i < KPL; ++i)                                                     \
+            _Pragma("unroll") for (int v = 0; v < NV; ++v) h[v][i] = hn[v][i];                              \
     } while (0)
     for (int s = 0; s < NSH; s += 2) {
-        RSD_STEP(ca, xa, cb, xb, true);
-        RSD_STEP(cb, xb, ca, xa, s + 2 < NSH);
+        RSD_STEP(true);
+        RSD_STEP(s + 2 < NSH);
     }
+#undef RSD_WAIT
 #undef RSD_STEP
-    if (wv > 0) {
+#undef RSD_MAC
+#undef RSD_F
+    if (sh > 0) {
 #pragma unroll
-        for (int j = 0; j < KPL; ++j) s_part[wv - 1][j][lane] = acc[j];
+        for (int l = 0; l < NL; ++l)
+#pragma unroll
+            for (int i = 0; i < KPL; ++i) s_part[sh - 1][l][i][lane] = acc[l][i];
     }
     __syncthreads();
-    if (wv > 0) return;
+    if (sh > 0) return;
 #pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-        double a = acc[j];
+    for (int l = 0; l < NL; ++l)
 #pragma unroll
-        for (int q = 0; q < 3 * SH - 1; ++q) a += s_part[q][j][lane];
-        if (k[j] < Nk && k[j] >= Nklow) T[(((size_t)w * NL + l) * NROW) * Nk + k[j]] += k2[j] * a;
-    }
+        for (int i = 0; i < KPL; ++i) {
+            double a = acc[l][i];
+#pragma unroll
+            for (int q = 0; q < SH - 1; ++q) a += s_part[q][l][i][lane];
+            if (k[i] < Nk && k[i] >= Nklow) T[(((size_t)w * NL + l) * NROW) * Nk + k[i]] += k2[i] * a;
+        }
 }
 
 // The same scheme for Nl = 2 (NIR = 8, Na = 2): the polynomials have degree 7, so the monomials of t = z / RS_ZS are the basis

@@ -441,6 +441,7 @@ static size_t need_table_bytes(const eftb_config& c, int id) {
         case EFTB_T_LCTN: return c.with_nnlo ? D * c.Nl * 6 : 0;
         case EFTB_T_BAO: return c.optiresum && c.with_resum ? D * (2 * NS + 4) : 0;
         case EFTB_T_GCT2: case EFTB_T_GCT2T: return c.dual_coef ? D * kpad(c.Nkin + c.ntail) * 2 * cfg_nch(c) : 0;
+        case EFTB_T_QEPOLY: return c.with_resum && c.Nl == 3 ? D * 2 * c.Nl * c.Nl * RSD_NN * 15 : 0;  // (direct-P_l runs: Q(f) in the closed-form basis)
     }
     return 0;
 }
@@ -661,7 +662,7 @@ static void launch_prep_rows_qf(eftb_engine* e, hipStream_t st, int B) {
     const eftb_config& c = e->c;
 #define PRQ_ARGS B, c.Nkin, c.ntail, c.nxtail, (int)kpad(c.Nkin), (int)kpad(c.Nkin + c.ntail), (int)kpad(c.Nkin + c.nxtail), c.max_batch, e->buf[EFTB_B_PIN], \
                  tb<double>(e, EFTB_T_LNKIN), tb<double>(e, EFTB_T_LNXTAIL), tb<double>(e, EFTB_T_LNXXTAIL), tb<double>(e, EFTB_T_WQLAST2), e->PA1, e->PA2, e->PA2T, e->PA3, \
-                 e->status + 2 * e->status_slot, c.Nl * c.Nl * e->Nn, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QPOLY), e->buf[EFTB_B_Q]
+                 e->status + 2 * e->status_slot, c.Nl * c.Nl * RSD_NN, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QEPOLY), e->buf[EFTB_B_Q]
     if (WHATIF_SKIP(1)) return;
     if (c.ntail_lo || c.nxtail_lo)
         hipLaunchKernelGGL(prep_rows_qf_lo_kernel, dim3(2 * B), dim3(256), (size_t)c.Nkin * sizeof(double), st, PRQ_ARGS, c.ntail_lo, c.nxtail_lo);
@@ -676,7 +677,9 @@ static void queue_xy(eftb_engine* e, SynthBatch& sb, int B) {  // X(s), Y(s) [B]
 }
 
 // Resum.IRFilters + Resum.makeQ: X, Y (operand rows + one GEMM, unless the first stage of this run already produced them) and Q(f)
-static void launch_irfilter(eftb_engine* e, hipStream_t st, int B, bool xy = true) {
+// (a direct-P_l run reads Q(f) in the closed-form basis of its resummation: Q_e(f), 48 entries per (a, l, l') where Q(f) has 96 -- each run
+// evaluates the block that its own resummation reads)
+static void launch_irfilter(eftb_engine* e, hipStream_t st, int B, bool xy = true, bool direct = false) {
     const eftb_config& c = e->c;
     if (xy) {
         launch_prep_rows(e, st, B, false, true);
@@ -684,7 +687,8 @@ static void launch_irfilter(eftb_engine* e, hipStream_t st, int B, bool xy = tru
         queue_xy(e, sb, B);
         launch_gemm_direct(st, sb);
     }
-    hipLaunchKernelGGL(qf_kernel, dim3(B), dim3(256), 0, st, c.Nl * c.Nl * e->Nn, e->buf[EFTB_B_F], tb<double>(e, EFTB_T_QPOLY), e->buf[EFTB_B_Q]);
+    hipLaunchKernelGGL(qf_kernel, dim3(B), dim3(256), 0, st, c.Nl * c.Nl * (direct ? RSD_NN : e->Nn), e->buf[EFTB_B_F],
+                       tb<double>(e, direct ? EFTB_T_QEPOLY : EFTB_T_QPOLY), e->buf[EFTB_B_Q]);
 }
 
 static int timer_begin(eftb_engine* e, hipStream_t st, int kind);
@@ -1004,7 +1008,7 @@ struct StageRun {
 static int fork_side(StageRun& r) {
     eftb_engine* e = r.e;
     const StagePlan& p = r.p;
-    if (p.side_ir) launch_irfilter(e, e->side, r.B, !p.xy_in_prep);
+    if (p.side_ir) launch_irfilter(e, e->side, r.B, !p.xy_in_prep, p.direct);
     if (int rc = r.record(e->evJoin, e->side, "stream join")) return rc;
     if (p.side_ap) {
         if (p.pre_side) {
@@ -1199,7 +1203,7 @@ static int stage_resum(StageRun& r) {
     hipStream_t st = r.st;
     const bool full = mask & EFTB_S_RESUM;  // EFTB_K_RESUM alone: only the main kernel, on the operands of an earlier full run
     const bool direct = p.direct, nnlo_pass = p.nnlo_pass;
-    if (full && !p.side_ir && !nnlo_pass) launch_irfilter(e, st, B);  // X, Y, Q(f) of the first pass stay valid
+    if (full && !p.side_ir && !nnlo_pass) launch_irfilter(e, st, B, true, direct);  // X, Y, Q(f) of the first pass stay valid
     if (!r.joined) {
         if (int rc = r.wait_on(st, e->evJoin, "join")) return rc;
         r.joined = true;
@@ -1232,7 +1236,7 @@ static int stage_resum(StageRun& r) {
         if (!WHATIF_SKIP(32))
             hipLaunchKernelGGL(back_prep_plk_kernel, dim3(nreg + nparts * B), dim3(BPP_THREADS), plds, st, nreg, nkx, B, nparts, Nk, Nl, tb<double>(e, EFTB_T_K), b[EFTB_B_P11], e->Y22,
                                b[EFTB_B_P13], tb<double>(e, EFTB_T_L11), tb<double>(e, EFTB_T_LCT), b[EFTB_B_BIAS], b[EFTB_B_TEMPL], c.ap_stochastic ? 1 : 0,
-                               e->Nn, c.NIR, c.Na, b[EFTB_B_Q], b[EFTB_B_XY], c11, cct, e->YCF, e->RSAS);
+                               b[EFTB_B_Q], b[EFTB_B_XY], c11, cct, e->YCF, e->RSAS);
         trace_point(e, 3, st);
         if (p.front_side) {  // the last reader of this run's front set
             if (int rc = r.record(e->evFrontFree[e->front_step & 1], st)) return rc;
@@ -1263,11 +1267,12 @@ static int stage_resum(StageRun& r) {
         tb<double>(e, nnlo_pass ? EFTB_T_LCTN : EFTB_T_LCT), b[EFTB_B_TEMPL], e->part, nsplit
     const int nkb = (Nk - (c.Nklow & ~15) + 63) / 64;  // Nl = 3: k tiles aligned to 16, (k block, cosmology) decoded from a flat index
     if (direct) {
-        // four k per lane, four slices of the s range (round 4, same-box sweep of six shapes: 34.9 us alone at B = 128 / 105 at 384; 4 x 2, the
-        // round-3 shape: 39.0 / 120; 2 x 4: 38.6 / 117; 8 x 1: 57 / 117; 8 x 2: 58 / 153; 8 x 4: 49 / 134)
-        const int nkd = (Nk + 64 * 4 - 1) / (64 * 4);
+        // two k per lane, eight slices of the s range: a wave owns all nine (l, v) of its points, a workgroup one (128 k, cosmology).  Alone at
+        // B = 128 (rocprofv3, same machine and session, sets of eight coefficients): <2,8> 31.1 us, <2,10> 44.3, <2,5> 43.2, <2,4> 51.8, <1,8> 52.1;
+        // <2,8> with sets of sixteen, the form that runs: 29.3; the Horner kernel it replaces, <4,4> of 3 SH waves per (256 k, l): 35.4
+        const int nkd = (Nk + 64 * RSD_KPL - 1) / (64 * RSD_KPL);
         if (kblocks > 0 && !WHATIF_SKIP(64))
-            hipLaunchKernelGGL((resum_plk_kernel<4, 4>), dim3(nkd * 3 * B), dim3(192 * 4), 0, st, Nk, c.Nklow, tb<double>(e, EFTB_T_K), tb<double>(e, EFTB_T_H),
+            hipLaunchKernelGGL((resum_plk_kernel<RSD_KPL, RSD_SH>), dim3(nkd * B), dim3(64 * RSD_SH), 0, st, Nk, c.Nklow, tb<double>(e, EFTB_T_K), tb<double>(e, EFTB_T_H),
                                e->RSAS, b[EFTB_B_TEMPL], nkd);
     } else if (kblocks > 0 && Nl == 3 && p.nnlo_fused)
         hipLaunchKernelGGL((resum_mfma_kernel<true>), dim3(nkb * B, 1, nsplit), dim3(256), 0, st, RM_ARGS, tb<double>(e, EFTB_T_LCTN), b[EFTB_B_TEMPLN], nkb);

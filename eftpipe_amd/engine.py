@@ -125,6 +125,8 @@ class Engine:
             self._set("LNXXTAIL", t["lnx_xtail"])
             self._set("WQLAST2", t["wq_last2"])
             self._set("QPOLY", t["Qpoly"])
+            if "QEpoly" in t:
+                self._set("QEPOLY", t["QEpoly"])
             self._set("H", t["H"].transpose(0, 2, 1))
             if "rs_rows" in t:
                 self._set("RSBASIS", t["rs_basis"])

@@ -475,6 +475,8 @@ def build_tables(cfg: EngineConfig, loop_cache=None) -> dict:
         t["Qpoly"] = lm.q_polynomials(Nl)
         t["resum_dims"] = np.array([NIR, Na, int(np.sum(~kr_mask))], dtype=np.int32)
         t.update(resum_mfma_tables(t["Qpoly"], NIR, Na))
+        if Nl == 3:
+            t.update(resum_plk_tables(t["Qpoly"], NIR, Na))
 
     # ---- AP
     if cfg.with_ap:
@@ -552,6 +554,79 @@ def resum_mfma_tables(Qpoly, NIR, Na):
     if np.any(nz[::-1] & ~used):
         raise ValueError("resummation table has entries outside the (v = l' | half 1) slot pattern")
     return dict(rs_basis=V8, rs_basis_scaled=np.ascontiguousarray(V8 * scale[None, :]), rs_rows=rows.reshape(-1))
+
+
+RSE_TOL = 1e-9  # resum_plk_tables: largest accepted miss of a reconstructed coefficient p = 8 ... 15, relative to that coefficient (q_tables.npz: 7.3e-11)
+
+
+def resum_plk_tables(Qpoly, NIR, Na):
+    """Table of the direct-P_l resummation (resum_plk_kernel, Nl = 3): every polynomial in a closed-form basis of the 8-dimensional space.
+
+    R(p) = q_p (p+1)! (-2)^(p+1) is a polynomial of degree <= 7 in p (see resum_mfma_tables).  Written in the falling factorials of m = p + 1,
+    R = sum_j c_j m (m-1) ... (m-j+1), j = 0..7, and with u = -z / 2,
+        sum_p q_p z^p = -1/2 sum_j c_j b_j(u),   b_0 = sum_{p<16} u^p / (p+1)!,   b_j = u^(j-1) e_{16-j}(u),   e_n(u) = sum_{m<=n} u^m / m!
+    -- eight functions that fall out of one Horner evaluation of e_16 (resum_basis).  The coordinates c_j come from the table coefficients
+    p = 0..7 by exact rational interpolation, rounded once (a float least-squares fit of all sixteen leaves 5e-8); the coefficients p = 8..15
+    they imply must reproduce the table to RSE_TOL each, else this raises.
+
+    -> QEpoly [2, Nl * Nl * 2 * 8 * Na, nf]: the layout of Qpoly with the coordinate j in the place of the power p; rse_worst [1]: the largest
+       miss of a reconstructed coefficient."""
+    from fractions import Fraction
+    from math import factorial
+
+    Nl, NB = 3, RS_NB
+    if NIR != 16:
+        raise ValueError("resum_plk_tables: Nl = 3 (NIR = 16) only")
+    nf = Qpoly.shape[-1]
+    Qr = Qpoly.reshape(2, Nl, Nl, 2, NIR, Na, nf)
+    rows = np.ascontiguousarray(Qr.transpose(0, 1, 2, 3, 5, 6, 4)).reshape(-1, NIR)       # (table, l, l', half, v, f-power) x p
+    unit = [Fraction(factorial(p + 1) * (-2) ** (p + 1)) for p in range(NIR)]              # R(p) = q_p unit[p]
+    ff = lambda m, j: Fraction(factorial(m) // factorial(m - j)) if m >= j else Fraction(0)  # m (m-1) ... (m-j+1)
+    # inverse of F[p][j] = ff(p + 1, j), p, j = 0..7, by Gauss-Jordan elimination in rationals
+    A = [[ff(p + 1, j) for j in range(NB)] + [Fraction(int(i == p)) for i in range(NB)] for p in range(NB)]
+    for c in range(NB):
+        piv = next(r for r in range(c, NB) if A[r][c] != 0)
+        A[c], A[piv] = A[piv], A[c]
+        A[c] = [x / A[c][c] for x in A[c]]
+        for r in range(NB):
+            if r != c and A[r][c] != 0:
+                A[r] = [x - A[r][c] * y for x, y in zip(A[r], A[c])]
+    Finv = [row[NB:] for row in A]
+    out = np.zeros((rows.shape[0], NB))
+    worst = 0.0
+    for i in np.flatnonzero(np.abs(rows).max(axis=1) > 0):
+        R = [Fraction(float(rows[i, p])) * unit[p] for p in range(NB)]
+        c = [sum((Finv[j][p] * R[p] for p in range(NB)), Fraction(0)) for j in range(NB)]
+        out[i] = [float(x) for x in c]
+        for p in range(NB, NIR):
+            want = float(rows[i, p])
+            got = float(sum((c[j] * ff(p + 1, j) for j in range(NB)), Fraction(0)) / unit[p])
+            if want != 0.0:
+                worst = max(worst, abs(got - want) / abs(want))
+            elif got != 0.0:
+                worst = np.inf
+    if not worst <= RSE_TOL:
+        raise ValueError(f"resummation polynomials leave the closed-form basis: a coefficient p >= {NB} is missed by {worst:.2e} of itself (bound {RSE_TOL:.0e})")
+    QE = out.reshape(2, Nl, Nl, 2, Na, nf, NB).transpose(0, 1, 2, 3, 6, 4, 5)             # table, l, l', half, j, v, f-power
+    return dict(QEpoly=np.ascontiguousarray(QE).reshape(2, Nl * Nl * 2 * NB * Na, nf), rse_worst=np.array([worst]))
+
+
+def resum_basis(u):
+    """The eight basis functions b_j(u) of resum_plk_tables in float64, by the recurrence of resum_plk_kernel (operation for operation, FMAs as
+    two roundings): h_16 = 1/16!, h_m = h_{m+1} u + 1/m!  (h_m = sum_i u^i / (m+i)!),  b_0 = h_1,  b_j = u^(j-1) h_0 - u^16 h_{17-j}.   u [...] -> [8, ...]"""
+    from math import factorial
+
+    u = np.asarray(u, dtype=np.float64)
+    h = [None] * 17
+    h[16] = np.full_like(u, 1.0 / factorial(16))
+    for m in range(15, -1, -1):
+        h[m] = h[m + 1] * u + 1.0 / factorial(m)
+    u2 = u * u
+    u3, u4 = u2 * u, u2 * u2
+    u5, u6, u8 = u4 * u, u4 * u2, u4 * u4
+    u16 = u8 * u8
+    pw = [np.ones_like(u), u, u2, u3, u4, u5, u6]
+    return np.stack([h[1]] + [pw[j - 1] * h[0] - u16 * h[17 - j] for j in range(1, 8)])
 
 
 def resum_block(tau, jg, slot):

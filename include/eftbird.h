@@ -85,6 +85,7 @@ enum eftb_table {
                          bao(s) = C(s) - a(s) C(s[i_lo]) - b(s) C(s[i_hi]), 0 elsewhere     Resum.extractBAO pybird.py:1382-1400 */
     EFTB_T_GCT2,      /* dual_coef: FFTLog operator of the xi-space coefficients (layout of EFTB_T_GCT) */
     EFTB_T_GCT2T,     /* dual_coef: its transpose (layout of EFTB_T_ECT) */
+    EFTB_T_QEPOLY,    /* Nl = 3: [2][Nl Nl 2 8 Na][15] Q(f) of direct-P_l runs in the closed-form basis (tables.py resum_plk_tables; layout of EFTB_T_QPOLY) */
     EFTB_T_COUNT
 };
 

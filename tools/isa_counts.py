@@ -146,6 +146,49 @@ def analyse(asm_text):
     return out
 
 
+BENCH_ALIAS = "resum_plk_kernel<4,4>"   # the key under which bench.py prices the resummation of a direct-P_l step
+BENCH_WAVE_TRIPS = 3 * 2 * 12 * 10      # ... and the wave-trips per cosmology it multiplies the loop's flops by (Nk = 512, NS = 80)
+
+
+def resum_plk_shape():
+    """(KPL, SH) of the resum_plk_kernel instantiation that eftbird.hip launches (RSD_KPL, RSD_SH in eftb_kernels.hpp)"""
+    with open(os.path.join(CSRC, "eftb_kernels.hpp")) as fh:
+        m = re.search(r"constexpr int RSD_KPL = (\d+), RSD_SH = (\d+);", fh.read())
+    return int(m.group(1)), int(m.group(2))
+
+
+def resum_plk_wave_trips(kpl, sh, Nk=512, NS=80):
+    """wave-trips of the hot loop per cosmology: workgroups of sh waves per (64 kpl k, cosmology), two s per trip"""
+    return (Nk + 64 * kpl - 1) // (64 * kpl) * sh * (NS // sh // 2)
+
+
+def alias_resum_plk(res):
+    """bench.py (which is fixed) looks the direct resummation up as resum_plk_kernel<4,4> and multiplies the hot loop's flops per wave and trip by
+    720 wave-trips per cosmology, the geometry of the kernel that carried that name.  The kernel that runs has another geometry, so the entry
+    under that key describes the REAL kernel with its per-trip counts rescaled: x 720 they give the FP64 flops one cosmology's resummation
+    executes.  The real kernel keeps an entry under its own name, unscaled."""
+    kpl, sh = resum_plk_shape()
+    real_name = f"resum_plk_kernel<{kpl},{sh}>"
+    real = res[real_name]
+    loop = max(real["loops"], key=lambda b: b["valu_f64"])
+    trips = resum_plk_wave_trips(kpl, sh)
+    scale = trips / BENCH_WAVE_TRIPS
+    scaled = dict(loop)
+    for key in ("mfma", "valu_f64", "valu_other", "vmem", "lds", "smem", "salu", "wait", "other", "flops_per_wave_trip", "mfma_flops_per_wave_trip"):
+        scaled[key] = loop[key] * scale
+    scaled["f64_ops"] = {op: n * scale for op, n in loop["f64_ops"].items()}
+    alias = {k: v for k, v in real.items() if k != "loops"}
+    alias["loops"] = [scaled]
+    alias["note"] = (f"alias of {real_name} for bench.py: the kernel that runs is {real_name} -- workgroups of {sh} waves per (64 x {kpl} k, cosmology), a wave owns all "
+                     f"nine (l, v) of its points, {trips} wave-trips of the hot loop per cosmology at Nk = 512, NS = 80 (two s per trip), "
+                     f"{loop['valu_f64']} FP64 vector instructions = {loop['flops_per_wave_trip']} flops per wave and trip.  The per-trip counts here are those "
+                     f"times {trips}/{BENCH_WAVE_TRIPS}, so that bench.py's {BENCH_WAVE_TRIPS} wave-trips per cosmology give the flops the kernel executes; "
+                     f"the resources and `whole` (the count over the kernel's whole text) are the real kernel's, unscaled")
+    alias["alias_of"], alias["scale"] = real_name, scale
+    alias["unscaled"] = {"valu_f64": loop["valu_f64"], "flops_per_wave_trip": loop["flops_per_wave_trip"], "f64_ops": loop["f64_ops"], "wave_trips_per_cosmology": trips}
+    res[BENCH_ALIAS] = alias
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(CSRC, "isa_counts.json"))
@@ -160,6 +203,7 @@ def main():
             emit_asm(p)
             text = open(p).read()
     res = analyse(text)
+    alias_resum_plk(res)
     res["_source_hash"] = source_hash()
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1, sort_keys=True)

@@ -97,7 +97,7 @@ gy = {(int(r["Start_Timestamp"]), int(r["End_Timestamp"])): int(r["Grid_Size_X"]
 ALGO = {
     "eftb::resum_mfma_kernel": f"H table 3*80*{NK}*8 = {3 * 80 * NK * 8 / 1e6:.1f} MB (L2-resident, re-read per cosmology) + per-s records {B * 80 * 48 * 8 / 1e6:.1f} MB + per-s operand "
                                f"{B * 80 * 512 * 8 / 1e6:.1f} MB + template read-modify-write 2*{B}*63*{NK}*8 = {2 * B * 63 * NK * 8 / 1e6:.0f} MB",
-    "eftb::resum_plk_kernel": f"H table {3 * 80 * NK * 8 / 1e6:.1f} MB (L2-resident) + coefficient table {B * 80 * 160 * 8 / 1e6:.1f} MB (scalar loads) + P_l read-modify-write "
+    "eftb::resum_plk_kernel": f"H table {3 * 80 * NK * 8 / 1e6:.1f} MB (L2-resident) + coefficient table {B * 80 * 80 * 8 / 1e6:.1f} MB (scalar loads) + P_l read-modify-write "
                               f"2*{B}*3*{NK}*8 = {2 * B * 3 * NK * 8 / 1e6:.1f} MB",
     "eftb::ap_plk_kernel": f"B-spline coefficients of the contracted rows {B * 3 * NK * 8 / 1e6:.1f} MB + per-interval matrices {NK * 16 * 8 / 1e6:.2f} MB (L2) + stochastic rows and P_l "
                            f"{B * 3 * 4 * NK * 8 / 1e6:.1f} MB (P_l to mapped host memory)",
