@@ -4338,4 +4338,160 @@ __global__ __launch_bounds__(NT) void draws_gram_groups_kernel(int ndata, int J1
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Samples of the marginalised parameters of a params draw (eftb_draws_sample_params).  Given theta they are exactly Gaussian,
+//     b | theta, data ~ N(b^ = F2^-1 F1, F2^-1)      (with and without Jeffreys, which only drops ln det F2 from the marginal),
+// so with the upper Cholesky factor F2 = U^T U and standard normals z of the caller, b = b^ + U^-1 z has that law: cov(U^-1 z) = U^-1 U^-T.
+// draws_logp_params_kernel's outer shape and forward pass (draws_recipe_forward), then per draw
+//   record         draws_solve<false>: the same function, so ln P, full chi2 and b^ are the bits of eftb_draws_logp_params; G stays in the LDS
+//   Cholesky       wave-synchronous, on F2 as draws_solve's first statement forms it: lane i < nG keeps row i in registers, no pivot search
+//                  and no row exchange.  Column c: the pivot a_c[c] is broadcast from lane c, r = sqrt(pivot); the rows i > c eliminate
+//                  with m = a_i[c] / pivot, a_i[j] = fma(-m, a_c[j], a_i[j]) (j > c); row c becomes U[c][j] = a_c[j] / r (j >= c).
+//                  A pivot that is not > 0 (NaN included) marks the draw failed, wave-uniformly
+//   samples        ADJ_KB at a time, independent chains as the F2^-1 columns of draws_solve<true>: lane i starts with y = z[d][s][i];
+//                  for c = nG - 1 ... 0: x_c = y of lane c / U[c][c], lanes i < c take y = fma(-U[i][c], x_c, y); b[s][i] = b^[i] + x_i.
+//                  The chains never mix: a sample's bits depend neither on S, nor on its place in the chunk, the split into calls or the wave
+//   chi2(b[s])     draws_solve's `full` formula G[0][0] + 2 b . G[1:,0] + b^T G[1:,1:] b in the same row order (z = 0: the bits of the record's)
+//   coefficients   (coef != null) coef[d][s][tau][r] = R^[0][(tau, r)] + sum_g b[s][g - 1] R^[g][(tau, r)] over the entries val[n] of the recipe
+//                  in table order: lanes over the 27 ntr slots, zero where the recipe has no entry, every coefficient written once (as
+//                  draws_recipe_rows_kernel); the 24 template coefficients to coef [N S][ntr][24], the NNLO ones to coefn [N S][ntr][3]
+// A failed draw (det F2 <= 0 of draws_solve, or a pivot <= 0) gets NaN in all S samples, their chi2 and its coefficient rows; its record is
+// what draws_solve wrote.  LDS: as draws_logp_grad_params_kernel (erow after col), and per wave bs [ADJ_KB][nG] after G.
+// ------------------------------------------------------------------------------------------------
+template <bool TWO>
+__global__ __launch_bounds__(256) void draws_sample_params_kernel(int ntr, int nG, int J1, int jeffreys, int S, RecipeTab rt, const int* __restrict__ erow_tab,
+                                                                  const long long* __restrict__ offsets, const double* __restrict__ theta,
+                                                                  const double* __restrict__ f, const double* __restrict__ W,
+                                                                  const double* __restrict__ mu, const double* __restrict__ sinv,
+                                                                  const double* __restrict__ z, double* __restrict__ out, double* __restrict__ bsamp,
+                                                                  double* __restrict__ chi2samp, double* __restrict__ coef, double* __restrict__ coefn) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1;
+    const long long d0 = offsets[c], d1 = offsets[c + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
+    double* Ws = sm;
+    double* fp = Ws + J1 * J1;
+    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
+    int* erow = col + nnzp;
+    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
+    for (int n = threadIdx.x; n < nnz; n += blockDim.x) {
+        col[n] = recipe_col(rt.ent[n], ntr);
+        erow[n] = erow_tab[n];
+    }
+    recipe_fpow(f, c, ntr, threadIdx.x, fp);
+    __syncthreads();
+    double* th = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1 + ADJ_KB * nG);
+    double* val = th + 34;
+    double* Hs = val + nnzp;
+    double* Gs = Hs + ng1 * J1;
+    double* bs = Gs + ng1 * ng1;
+    const bool own = lane < nG;
+    const int nslot = ntr * (NROW + 3);
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        double* o = out + (size_t)d * MARG_OUT;
+        draws_recipe_forward<TWO>(rt, theta, d, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+        bool good = draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, o);
+        // ---- F2 = U^T U: lane i ends with row i of U
+        double a[MARG_MAXG], dg[MARG_MAXG];
+#pragma unroll
+        for (int j = 0; j < MARG_MAXG; ++j)
+            a[j] = (own && j < nG) ? 0.5 * (Gs[(lane + 1) * ng1 + j + 1] + Gs[(j + 1) * ng1 + lane + 1]) + (lane == j ? sinv[j] : 0.0) : 0.0;
+#pragma unroll
+        for (int c2 = 0; c2 < MARG_MAXG; ++c2) {
+            dg[c2] = 1.0;
+            if (c2 < nG) {
+                const double piv = readlane_f64(a[c2], c2);
+                if (!(piv > 0.0)) good = false;
+                const double r = sqrt(piv);
+                const bool elim = own && lane > c2;
+                const double m = elim ? a[c2] / piv : 0.0;
+#pragma unroll
+                for (int j = c2; j < MARG_MAXG; ++j)
+                    if (j < nG) {
+                        const double u = readlane_f64(a[j], c2);
+                        if (elim && j > c2) a[j] = fma(-m, u, a[j]);
+                        if (lane == c2) a[j] = u / r;
+                    }
+                dg[c2] = readlane_f64(a[c2], c2);  // U[c2][c2]
+            }
+        }
+        const double bhat = own ? o[2 + lane] : 0.0;  // (this lane's own store in draws_solve)
+        for (int s0 = 0; s0 < S; s0 += ADJ_KB) {
+            // ---- U x = z, ADJ_KB samples at a time
+            double y[ADJ_KB];
+#pragma unroll
+            for (int q = 0; q < ADJ_KB; ++q) y[q] = (own && s0 + q < S) ? z[((size_t)d * S + s0 + q) * nG + lane] : 0.0;
+#pragma unroll
+            for (int c2 = MARG_MAXG - 1; c2 >= 0; --c2)
+                if (c2 < nG) {
+                    const bool above = own && lane < c2;
+#pragma unroll
+                    for (int q = 0; q < ADJ_KB; ++q) {
+                        const double xc = readlane_f64(y[q], c2) / dg[c2];
+                        if (above) y[q] = fma(-a[c2], xc, y[q]);
+                        if (lane == c2) y[q] = xc;
+                    }
+                }
+            double bi[ADJ_KB];
+#pragma unroll
+            for (int q = 0; q < ADJ_KB; ++q) {
+                bi[q] = bhat + y[q];
+                if (own) {
+                    bs[q * nG + lane] = bi[q];
+                    if (s0 + q < S) bsamp[((size_t)d * S + s0 + q) * nG + lane] = good ? bi[q] : nan;
+                }
+            }
+            wave_lds_sync();
+            // ---- chi2 at b[s] (row sums per lane, added in row order, as draws_solve)
+#pragma unroll
+            for (int q = 0; q < ADJ_KB; ++q) {
+                double srow = 0.0;
+#pragma unroll
+                for (int j = 0; j < MARG_MAXG; ++j)
+                    if (j < nG && own) srow = fma(bs[q * nG + j], Gs[(lane + 1) * ng1 + j + 1], srow);
+                const double trow = own ? bi[q] * fma(2.0, Gs[(lane + 1) * ng1], srow) : 0.0;
+                double full = Gs[0];
+#pragma unroll
+                for (int i = 0; i < MARG_MAXG; ++i)
+                    if (i < nG) full += readlane_f64(trow, i);
+                if (lane == 0 && s0 + q < S) chi2samp[(size_t)d * S + s0 + q] = good ? full : nan;
+            }
+            // ---- the coefficient rows of the samples: lanes over the slots (tau, r), the entries of the recipe in table order
+            if (coef) {
+                for (int q0 = 0; q0 < nslot; q0 += 64) {
+                    const int sl = q0 + lane, tau = sl / (NROW + 3), r = sl % (NROW + 3);
+                    const int cq = sl < nslot ? recipe_col(tau * 32 + r, ntr) : -1;
+                    double acc[ADJ_KB];
+#pragma unroll
+                    for (int q = 0; q < ADJ_KB; ++q) acc[q] = 0.0;
+                    for (int n = 0; n < nnz; ++n) {
+                        const int g = erow[n];
+                        const double v = val[n];
+                        const bool mine = col[n] == cq;
+#pragma unroll
+                        for (int q = 0; q < ADJ_KB; ++q) {
+                            const double bg = g ? bs[q * nG + g - 1] : 1.0;
+                            if (mine) acc[q] = fma(bg, v, acc[q]);
+                        }
+                    }
+                    if (sl < nslot) {
+#pragma unroll
+                        for (int q = 0; q < ADJ_KB; ++q)
+                            if (s0 + q < S) {
+                                const size_t row = ((size_t)d * S + s0 + q) * ntr + tau;
+                                if (r < NROW) coef[row * NROW + r] = good ? acc[q] : nan;
+                                else if (coefn) coefn[row * 3 + (r - NROW)] = good ? acc[q] : nan;
+                            }
+                    }
+                }
+            }
+            wave_lds_sync();  // (the next chunk overwrites bs)
+        }
+        wave_lds_sync();  // (the next draw overwrites th, val, H and G)
+    }
+}
+
 }  // namespace eftb

@@ -176,6 +176,13 @@ struct eftb_engine {
     int* drw_gtab = nullptr;
     std::vector<int> grp_tab;
     std::vector<double> grp_f;      // f [G][ntr] of a groups call, expanded from f [C][ntr]
+    // eftb_draws_sample_params: z and b [N][S][nG], chi2 [N][S], the coefficient rows [N S][ntr][24] / [N S][ntr][3], P_l [N S][ntr][nl][nx]
+    // and the offsets times S of the reduce launch; grown on demand
+    double *smp_z = nullptr, *smp_b = nullptr, *smp_chi2 = nullptr, *smp_coef = nullptr, *smp_coefn = nullptr, *smp_plk = nullptr;
+    size_t smp_z_cap = 0, smp_b_cap = 0, smp_chi2_cap = 0, smp_coef_cap = 0, smp_coefn_cap = 0, smp_plk_cap = 0, smp_off_cap = 0;
+    long long* smp_off = nullptr;
+    std::vector<long long> smp_off_host;
+    bool smp_lds = false;           // the draws_sample_params_kernel instantiations opted in to the large dynamic LDS
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -2162,6 +2169,7 @@ void eftb_destroy(eftb_engine* e) {
                     (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab, (void*)e->recipe[0].dcoef,
                     (void*)e->recipe[0].dtab, (void*)e->drw_grad, (void*)e->recipe[0].hcoef, (void*)e->recipe[0].htab, (void*)e->drw_hess}) if (p) (void)hipFree(p);
     for (void* p : {(void*)e->dset_D, (void*)e->dset_Ud, (void*)e->drw_Wg, (void*)e->drw_gtab}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)e->smp_z, (void*)e->smp_b, (void*)e->smp_chi2, (void*)e->smp_coef, (void*)e->smp_coefn, (void*)e->smp_plk, (void*)e->smp_off}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
@@ -3908,30 +3916,163 @@ int eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data) {
     return 0;
 }
 
-int eftb_draws_logp_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, const int64_t* offsets,
-                                    const double* theta, const double* f, double* logp, double* grad, double* hess, double* fullchi2, double* best) {
-    static const char* who = "eftb_draws_logp_params_datasets";
-    if (e) sub_drain(e);
-    if (!e || !walker || !dataset || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
-    if (hess && !grad) return fail("%s: hess needs grad (the Hessian kernel returns the gradient too)", who);
+// the group table of a data-sets call (gr->walker and gr->dataset [G] of the caller): refusals, gr->nwalk, and f [C][ntr] expanded to grp_f [G][ntr]
+static int draws_groups_check(eftb_engine* e, const char* who, int C, int G, const double* f, DrawGroups* gr) {
+    const int32_t *walker = gr->walker, *dataset = gr->dataset;
     if (!e->like_ndata) return fail("%s: needs eftb_set_likelihood", who);
     if (!e->dset_M) return fail("%s: no data sets (eftb_set_likelihood_datasets; eftb_set_likelihood and eftb_set_tracers drop them)", who);
     if (C < 1) return fail("%s: %d walkers", who, C);
     if (G < 1) return fail("%s: %d groups", who, G);
     const int ntr = e->ntr;
     const size_t per = (size_t)e->cur_nl * NROW * e->cur_nx, have = per ? e->templ_elems / per : 0;
-    DrawGroups gr{0, walker, dataset};
+    gr->nwalk = 0;
     for (int g = 0; g < G; ++g) {
         if (walker[g] < 0 || walker[g] >= C) return fail("%s: walker[%d] = %d outside [0, %d)", who, g, walker[g], C);
         if (dataset[g] < 0 || dataset[g] >= e->dset_M) return fail("%s: dataset[%d] = %d outside [0, %d)", who, g, dataset[g], e->dset_M);
         if (e->templ_ok && ((size_t)walker[g] + 1) * ntr > have)
             return fail("%s: walker[%d] = %d with %d tracers, but the template block holds %zu entries [%d][24][%d]", who, g, walker[g], ntr, have, e->cur_nl,
                         e->cur_nx);
-        gr.nwalk = std::max(gr.nwalk, walker[g] + 1);
+        gr->nwalk = std::max(gr->nwalk, walker[g] + 1);
     }
     for (int q = 0; q < C * ntr; ++q)
         if (!std::isfinite(f[q])) return fail("%s: f[%d][%d] is not finite", who, q / ntr, q % ntr);
     e->grp_f.resize((size_t)G * ntr);  // f per group: the draw kernels read f [blockIdx.x][ntr]
     for (int g = 0; g < G; ++g) std::copy(f + (size_t)walker[g] * ntr, f + ((size_t)walker[g] + 1) * ntr, e->grp_f.begin() + (size_t)g * ntr);
+    return 0;
+}
+
+int eftb_draws_logp_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, const int64_t* offsets,
+                                    const double* theta, const double* f, double* logp, double* grad, double* hess, double* fullchi2, double* best) {
+    static const char* who = "eftb_draws_logp_params_datasets";
+    if (e) sub_drain(e);
+    if (!e || !walker || !dataset || !offsets || !f || (N > 0 && (!theta || !logp))) return fail("%s: null argument", who);
+    if (hess && !grad) return fail("%s: hess needs grad (the Hessian kernel returns the gradient too)", who);
+    DrawGroups gr{0, walker, dataset};
+    if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
     return draws_logp_params_impl(e, who, G, N, offsets, theta, e->grp_f.data(), logp, grad, fullchi2, best, hess, &gr);
+}
+
+// ------------------------------------------------------------------------------------------------ samples of the marginalised parameters
+// device buffer of at least n elements for eftb_draws_sample_params (as grow_dev; a failed allocation names the shape that asked for it)
+static int sample_grow(const char* who, void* pp, size_t* cap, size_t n, size_t elem, const char* what, long long N, int S, int nG) {
+    void** p = static_cast<void**>(pp);
+    if (n <= *cap) return 0;
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    hipError_t me = hipMalloc(p, n * elem);
+    if (me != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail("%s: no device memory for %s of N = %lld draws x S = %d samples with nG = %d (%zu bytes): %s", who, what, N, S, nG, n * elem,
+                    hipGetErrorString(me));
+    }
+    *cap = n;
+    return 0;
+}
+
+// eftb_draws_sample_params and eftb_draws_sample_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group, no plk): the
+// checks, W_c, uploads and records of draws_logp_params_impl around draws_sample_params_kernel, then draws_reduce_kernel on the [N S]
+// coefficient rows where plk is asked for.  The kernel is a template instantiated here, behind every other one, so that the existing kernels
+// keep their code and labels
+static int draws_sample_params_impl(eftb_engine* e, const char* who, int C, long long N, int S, const int64_t* offsets, const double* theta, const double* f,
+                                    const double* z, double* logp, double* fullchi2, double* best, double* bsamp, double* chi2samp, double* coef,
+                                    double* coefn, double* plk, const DrawGroups* gr = nullptr) {
+    long long maxcnt = 0;
+    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
+    const eftb_config& c = e->c;
+    const int ntr = e->ntr, nG = e->like_nG;
+    if (S < 1) return fail("%s: S = %d samples per draw, at least 1", who, S);
+    if (coefn && !c.with_nnlo) return fail("%s: coefn needs an engine built with with_nnlo", who);
+    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta, f)) return rc;
+    for (long long q = 0; q < N * S * nG; ++q)
+        if (!std::isfinite(z[q])) return fail("%s: z[%lld][%d][%d] is not finite", who, q / ((long long)S * nG), (int)(q / nG % S), (int)(q % nG));
+    // (plk: draws_logp_check has held the block to the likelihood's [nl][24][nx] and to its walkers x tracers entries, all eftb_draws_reduce asks)
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int P = rcp.P, nnzp = (rcp.nnz + 1) & ~1;
+    DrawShape sh;  // beside W_c: fp, col and erow [nnzp]; per wave: th [34], val [nnzp] and b of ADJ_KB samples
+    if (int rc = draws_logp_shape(e, who, RECIPE_MAXTR * RECIPE_FPOW * sizeof(double) + 2 * nnzp * sizeof(int), (34 + (size_t)nnzp + (size_t)ADJ_KB * nG) * sizeof(double),
+                                  &sh)) {
+        const int J1w = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
+        if (J1w > DRAW_MAXJ1) return rc;
+        return fail("%s: the samples of nG = %d parameters with J + 1 = %d columns do not fit the LDS (S = %d, %d samples at a time)", who, nG, J1w, S, ADJ_KB);
+    }
+    if (N == 0) return 0;
+    const bool want_coef = coef || coefn || plk, nn = c.with_nnlo;
+    const int nl = e->cur_nl, nx = e->cur_nx;
+    const size_t ns = (size_t)N * S;
+    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets, gr ? gr->nwalk : -1)) return rc;
+    if (!e->smp_lds) {
+        for (const void* k : {reinterpret_cast<const void*>(&draws_sample_params_kernel<false>), reinterpret_cast<const void*>(&draws_sample_params_kernel<true>)})
+            HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->smp_lds = true;
+    }
+    if (gr)
+        if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
+    const double* W = gr ? e->drw_Wg : e->drw_W;
+    if (int rc = sample_grow(who, &e->smp_z, &e->smp_z_cap, std::max<size_t>(1, ns * nG), sizeof(double), "z", N, S, nG)) return rc;
+    if (int rc = sample_grow(who, &e->smp_b, &e->smp_b_cap, std::max<size_t>(1, ns * nG), sizeof(double), "the samples", N, S, nG)) return rc;
+    if (int rc = sample_grow(who, &e->smp_chi2, &e->smp_chi2_cap, ns, sizeof(double), "chi2 of the samples", N, S, nG)) return rc;
+    if (want_coef) {
+        if (int rc = sample_grow(who, &e->smp_coef, &e->smp_coef_cap, ns * ntr * NROW, sizeof(double), "the coefficient rows", N, S, nG)) return rc;
+        if (nn)
+            if (int rc = sample_grow(who, &e->smp_coefn, &e->smp_coefn_cap, ns * ntr * 3, sizeof(double), "the NNLO coefficient rows", N, S, nG)) return rc;
+    }
+    if (plk) {
+        if (int rc = sample_grow(who, &e->smp_plk, &e->smp_plk_cap, ns * ntr * nl * nx, sizeof(double), "P_l of the samples", N, S, nG)) return rc;
+        if (int rc = sample_grow(who, &e->smp_off, &e->smp_off_cap, (size_t)C + 1, sizeof(long long), "the offsets", N, S, nG)) return rc;
+    }
+    const double *dtheta = nullptr, *df = nullptr;
+    if (int rc = draws_params_upload(e, P, C, N, theta, f, &dtheta, &df)) return rc;
+    hipStream_t st = e->stream;
+    if (nG) HIPCHK(hipMemcpyAsync(e->smp_z, z, ns * nG * sizeof(double), hipMemcpyHostToDevice, st));
+    const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
+    const int J1 = sh.J1;
+    const RecipeTab rt = recipe_tab(rcp);
+    const int* erow = rcp.dtab + P + 1 + 2 * rcp.ndt;  // (RecipeGradTab: pstart | dent | dpack | erow)
+    double* dcoef = want_coef ? e->smp_coef : nullptr;
+    double* dcoefn = want_coef && nn ? e->smp_coefn : nullptr;
+    if (J1 > 64)
+        hipLaunchKernelGGL(draws_sample_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, S, rt, erow, e->drw_off, dtheta, df, W, e->like_mu,
+                           e->like_sinv, e->smp_z, e->drw_out, e->smp_b, e->smp_chi2, dcoef, dcoefn);
+    else
+        hipLaunchKernelGGL(draws_sample_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, S, rt, erow, e->drw_off, dtheta, df, W, e->like_mu,
+                           e->like_sinv, e->smp_z, e->drw_out, e->smp_b, e->smp_chi2, dcoef, dcoefn);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    if (plk) {  // the launch of eftb_draws_reduce on N S draws with offsets S
+        e->smp_off_host.resize((size_t)C + 1);
+        for (int w = 0; w <= C; ++w) e->smp_off_host[w] = (long long)offsets[w] * S;
+        HIPCHK(hipMemcpyAsync(e->smp_off, e->smp_off_host.data(), ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+        const int xtiles = (nx + 63) / 64, shares = draw_shares(maxcnt * S, 4, (long long)C * ntr * nl * xtiles);
+        hipLaunchKernelGGL(draws_reduce_kernel, dim3(xtiles * shares, ntr * nl, C), dim3(256), 0, st, nx, nl, ntr, reduce_msplit(c), xtiles, e->smp_off, e->smp_coef,
+                           e->buf[EFTB_B_TEMPL], nn ? e->smp_coefn : nullptr, nn ? e->buf[EFTB_B_TEMPLN] : nullptr, e->smp_plk);
+        le = hipGetLastError();
+        if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+        HIPCHK(hipMemcpyAsync(plk, e->smp_plk, ns * ntr * nl * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (nG) HIPCHK(hipMemcpyAsync(bsamp, e->smp_b, ns * nG * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(chi2samp, e->smp_chi2, ns * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (coef) HIPCHK(hipMemcpyAsync(coef, e->smp_coef, ns * ntr * NROW * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (coefn) HIPCHK(hipMemcpyAsync(coefn, e->smp_coefn, ns * ntr * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    return draws_records(e, N, logp, fullchi2, best);
+}
+
+int eftb_draws_sample_params(eftb_engine* e, int C, long long N, int S, const int64_t* offsets, const double* theta, const double* f, const double* z,
+                             double* logp, double* fullchi2, double* best, double* bsamp, double* chi2samp, double* coef, double* coefn, double* plk) {
+    static const char* who = "eftb_draws_sample_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta || !z || !logp || !bsamp || !chi2samp))) return fail("%s: null argument", who);
+    return draws_sample_params_impl(e, who, C, N, S, offsets, theta, f, z, logp, fullchi2, best, bsamp, chi2samp, coef, coefn, plk);
+}
+
+int eftb_draws_sample_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int S, const int64_t* offsets,
+                                      const double* theta, const double* f, const double* z, double* logp, double* fullchi2, double* best, double* bsamp,
+                                      double* chi2samp, double* coef, double* coefn) {
+    static const char* who = "eftb_draws_sample_params_datasets";
+    if (e) sub_drain(e);
+    if (!e || !walker || !dataset || !offsets || !f || (N > 0 && (!theta || !z || !logp || !bsamp || !chi2samp))) return fail("%s: null argument", who);
+    DrawGroups gr{0, walker, dataset};
+    if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
+    return draws_sample_params_impl(e, who, G, N, S, offsets, theta, e->grp_f.data(), z, logp, fullchi2, best, bsamp, chi2samp, coef, coefn, nullptr, &gr);
 }

@@ -7,6 +7,7 @@ Gaussian parameters) cross PCIe instead of 0.3 MB of templates per walker.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -15,6 +16,9 @@ from . import _lib as L
 from .parambasis import _ndraws, gaussian_params, gaussian_rows, gaussian_rows_many
 
 MAXG = 24
+
+# what MarginalLikelihood.sample_gaussian_params returns; fields that were not asked for are None
+GaussianSamples = collections.namedtuple("GaussianSamples", "logp fullchi2 best b chi2 coef coef_nnlo plk")
 
 
 def data_index(ls, masks, nx, tracer=0, nl=None):
@@ -273,6 +277,72 @@ class MarginalLikelihood:
                                                              off.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(theta), L.dptr(f), L.dptr(logp), L.dptr(dlogp),
                                                              L.dptr(d2logp), L.dptr(full), L.dptr(best)))
         return logp, dlogp, d2logp, full, best
+
+    def sample_gaussian_params(self, theta, offsets, f, z, groups=None, predict=False, return_coef=False):
+        """Samples of the marginalised parameters of params draws (``eftb_draws_sample_params``).  Given theta they are exactly Gaussian,
+        b | theta, data ~ N(best, F2^-1), with and without Jeffreys; the device takes the Cholesky factor F2 = U^T U per draw and returns
+        b = best + U^-1 z for the caller's standard normals z [N, S, nG] ([N, nG]: one sample per draw) -- the posterior of the
+        counter-terms, stochastic terms and b3 behind a marginalised chain or the best fits of ``maximize_draws_params``.
+        theta, offsets, f and ``groups`` as ``logp_draws_params``.  -> ``GaussianSamples(logp, fullchi2, best, b, chi2, coef, coef_nnlo,
+        plk)``: logp [N], fullchi2 [N] and best [N, nG] are the bits of ``logp_draws_params(return_best=True)``; b [N, S, nG]; chi2
+        [N, S] the full chi2 at each sample (z = 0 gives best and fullchi2 bit for bit); with ``return_coef`` coef [N, S, ntr, 24]
+        ([N, S, 24] with one tracer) and, on with_NNLO engines, coef_nnlo [N, S, ntr, 3]: the rows ``Engine.reduce_draws`` takes; with
+        ``predict`` plk [N, S, ntr, nl, nx] ([N, S, nl, nx]), the posterior-predictive P_l of every sample, the bits of
+        ``reduce_draws(coef, offsets * S, bias_nnlo=coef_nnlo)``.  Fields not asked for are None.  A sample's bits depend neither on S
+        nor on how the draws are split into calls.
+        Raises RuntimeError("det of F2ij <= 0") where ln P is NaN, like its siblings, and RuntimeError("F2ij is not positive definite")
+        where only the samples are (det F2 > 0 with an even number of negative eigenvalues); ValueError for ``predict`` with
+        ``groups`` (the P_l kernel addresses templates by walker: feed coef to ``reduce_draws``)."""
+        out = self._sample_raw(theta, offsets, f, z, groups, predict, return_coef)
+        if np.any(np.isnan(out.logp)):
+            raise RuntimeError("det of F2ij <= 0")
+        if np.any(np.isnan(out.b)) or np.any(np.isnan(out.chi2)):
+            raise RuntimeError("F2ij is not positive definite")
+        return out
+
+    def _sample_raw(self, theta, offsets, f, z, groups=None, predict=False, return_coef=False):
+        """``sample_gaussian_params`` without the two RuntimeErrors: NaN where det F2 <= 0 or F2 is not positive definite"""
+        from .engine import _params_args
+
+        ntr, nG = self.eng.ntracers, self.nG
+        if predict and groups is not None:
+            raise ValueError("predict=True does not go with groups: P_l is reduced against a walker's templates (reduce_draws takes coef)")
+        rec = getattr(self, "_recipe", None)
+        wk = ds = None
+        if groups is not None:
+            theta, off, f, wk, ds = _groups_args(rec, theta, offsets, f, ntr, groups)
+        else:
+            theta, off, f = _params_args(rec, theta, offsets, f, ntr)
+        N = theta.shape[0]
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.shape == (N, nG):
+            z = z.reshape(N, 1, nG)
+        if z.ndim != 3 or z.shape[0] != N or z.shape[2] != nG:
+            raise ValueError(f"z must be [{N}, S, {nG}] standard normals ([{N}, {nG}] for one sample per draw)")
+        S = z.shape[1]
+        if S < 1:
+            raise ValueError("z must be [N, S, nG] with S >= 1 samples per draw")
+        nn = self.eng.cfg.with_NNLO
+        logp, full, best = np.empty(N), np.empty(N), np.empty((N, nG))
+        b, chi2 = np.empty((N, S, nG)), np.empty((N, S))
+        coef = np.empty((N, S, ntr, 24)) if return_coef else None
+        coefn = np.empty((N, S, ntr, 3)) if return_coef and nn else None
+        i64p = C.POINTER(C.c_int64)
+        if groups is not None:
+            i32p = C.POINTER(C.c_int32)
+            L.check(self.eng.lib.eftb_draws_sample_params_datasets(self.eng._h, f.shape[0], wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p), N, S,
+                                                                   off.ctypes.data_as(i64p), L.dptr(theta), L.dptr(f), L.dptr(z), L.dptr(logp), L.dptr(full),
+                                                                   L.dptr(best), L.dptr(b), L.dptr(chi2), L.dptr(coef), L.dptr(coefn)))
+            plk = None
+        else:
+            nl, nx = self.eng.dims
+            plk = np.empty((N, S, ntr, nl, nx)) if predict else None
+            L.check(self.eng.lib.eftb_draws_sample_params(self.eng._h, off.size - 1, N, S, off.ctypes.data_as(i64p), L.dptr(theta), L.dptr(f), L.dptr(z),
+                                                          L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(b), L.dptr(chi2), L.dptr(coef), L.dptr(coefn),
+                                                          L.dptr(plk)))
+        if ntr == 1:  # (as reduce_draws: no tracer axis)
+            coef, coefn, plk = (None if a is None else a.reshape(a.shape[:2] + a.shape[3:]) for a in (coef, coefn, plk))
+        return GaussianSamples(logp, full, best, b, chi2, coef, coefn, plk)
 
     def maximize_draws_params(self, theta0, offsets, f, groups=None, **kw):
         """Best fits over the recipe's parameters at fixed cosmology: ``newton_maximize`` fed with the Hessian call, all starts of all

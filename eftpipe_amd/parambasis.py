@@ -657,6 +657,28 @@ class DrawRecipe:
         """-> the NNLO columns [N, ntr, ng1, 3]"""
         return self._eval(theta, f, 24, 27)
 
+    def _coefficients(self, rows, b):
+        b = np.asarray(b, dtype=np.float64)
+        N = rows.shape[0]
+        if b.shape == (N, self.ng1 - 1):
+            b = b[:, None]
+        if b.ndim != 3 or b.shape[0] != N or b.shape[2] != self.ng1 - 1:
+            raise ValueError(f"b must be [{N}, S, {self.ng1 - 1}]: S sets of the linear parameters per draw")
+        out = np.repeat(rows[:, None, :, 0], b.shape[1], axis=1)  # row 0, then the rows g >= 1 in their order
+        for g in range(1, self.ng1):
+            out = out + b[:, :, None, g - 1, None] * rows[:, None, :, g]
+        return out
+
+    def coefficients(self, theta, f, b):
+        """theta [N, P], f as ``rows``, b [N, S, ng1 - 1] ([N, ng1 - 1]: S = 1) values of the linear parameters -> the coefficient rows
+        rows[0] + sum_g b[g - 1] rows[g] [N, S, ntr, 24] that ``Engine.reduce_draws`` contracts with the templates: the host counterpart of
+        the coefficients ``MarginalLikelihood.sample_gaussian_params`` builds on the device"""
+        return self._coefficients(self.rows(theta, f), b)
+
+    def coefficients_nnlo(self, theta, f, b):
+        """-> the NNLO columns of ``coefficients`` [N, S, ntr, 3]"""
+        return self._coefficients(self.rows_nnlo(theta, f), b)
+
     def derivative(self):
         """The terms of d rows / d theta: for each term and each distinct theta index p in it one record (p, tracer, row, col, coef *
         multiplicity of p in the term, fpow, idx [2]: the two remaining indices, -1 last), sorted by (p, row, tracer, col) and, inside an

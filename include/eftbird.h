@@ -369,6 +369,32 @@ int  eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data);
 int  eftb_draws_logp_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, const int64_t* offsets,
                                      const double* theta, const double* f, double* logp, double* grad, double* hess, double* fullchi2, double* best);
 
+/* Samples of the marginalised parameters of params draws, and what follows from them.  Given theta the marginalised parameters are exactly
+ * Gaussian, b | theta, data ~ N(b^ = F2^-1 F1, F2^-1), with and without Jeffreys (which only drops ln det F2 from the marginal).  Per draw
+ * the kernel runs the forward pass and solve of eftb_draws_logp_params (the same functions: logp, fullchi2 and best are that call's bits),
+ * takes the upper Cholesky factor F2 = U^T U wave-synchronously without pivoting, and for each of the S standard-normal vectors
+ * z [N][S][nG] of the caller returns
+ *     bsamp [N][S][nG]      b = b^ + U^-1 z            (cov = U^-1 U^-T = F2^-1; z = 0 gives best bit for bit)
+ *     chi2samp [N][S]       the full chi2 at b, by the formula and in the order of fullchi2 (z = 0: its bits)
+ *     coef [N][S][ntr][24]  (or NULL) the coefficient rows R^[0] + sum_g b[g - 1] R^[g] of eftb_draws_reduce, from the entries of the kind-0
+ *                           recipe in table order; coefn [N][S][ntr][3] (or NULL; with_nnlo engines only) their NNLO columns
+ *     plk [N][S][ntr][nl][nx] (or NULL) P_l of every sample: draws_reduce_kernel launched as eftb_draws_reduce launches it on the N S
+ *                           coefficient rows with offsets S -- the bits of eftb_draws_reduce fed with coef (and coefn); the rows then
+ *                           stay on the device unless coef is given too
+ * z comes from the caller: as many bytes as b going back, reproducible under any seed and stream discipline; there is no generator on
+ * the device.  A sample's bits depend neither on S, nor on its place among the S, nor on how the draws are split into calls.
+ * A draw whose F2 is not positive definite (a Cholesky pivot <= 0 or NaN) or has det F2 <= 0 gets NaN in all its samples, their chi2 and
+ * coefficient rows (P_l follows); its record is what eftb_draws_logp_params returns for it.
+ * Refused before anything is copied: what eftb_draws_logp_params refuses, S < 1, a non-finite z (naming draw, sample and parameter), coefn
+ * on an engine without with_nnlo, a working set that does not fit the LDS (as eftb_draws_logp_params, plus 4 nG doubles per wave). */
+int  eftb_draws_sample_params(eftb_engine* e, int C, long long N, int S, const int64_t* offsets, const double* theta, const double* f, const double* z,
+                              double* logp, double* fullchi2, double* best, double* bsamp, double* chi2samp, double* coef, double* coefn, double* plk);
+/* eftb_draws_sample_params per group (walker[g], dataset[g]) of eftb_draws_logp_params_datasets: the same kernel on the groups' Gram matrices.
+ * No plk: draws_reduce_kernel addresses templates by walker; feed coef to eftb_draws_reduce walker by walker. */
+int  eftb_draws_sample_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int S,
+                                       const int64_t* offsets, const double* theta, const double* f, const double* z, double* logp, double* fullchi2,
+                                       double* best, double* bsamp, double* chi2samp, double* coef, double* coefn);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

@@ -29,6 +29,17 @@ shapes, 1 walker x M data sets x --draws draws per group (default 1024 in this m
 On a tree without set_datasets (a) is skipped, so that the same file times (b) and (c) on the parent commit.
 
     python tools/draws_probe.py --datasets M [--draws N]
+
+--samples [S,S,...]: samples of the marginalised parameters (MarginalLikelihood.sample_gaussian_params) instead, for both
+shapes, 1 walker x --draws draws (default 4096), medians of 9 cached calls with [min, max]:
+
+    (a) samples  the sample call at each S (default 1, 8, 64), with and without predict
+    (b) floor    logp_draws_params(return_best=True) on the same draws, the S = 0 floor; and the gradient and Hessian calls
+    (c) numpy    the NumPy route of tests/sample_util.data_space_samples on templates fetched to the host (timed on 32 draws, scaled)
+
+On a tree without sample_gaussian_params only (b) runs, so that the same file times the existing calls on the parent commit.
+
+    python tools/draws_probe.py --samples [--draws N]
 """
 import argparse
 import json
@@ -266,13 +277,63 @@ def probe_datasets(name, setup, M, n, repeats=9):
     return out
 
 
+def probe_samples(name, setup, S_list, N=4096, repeats=9, host_draws=32):
+    """(a), (b), (c) of --samples for one shape: one walker x N draws, medians of `repeats` cached calls with [min, max]"""
+    rng = np.random.default_rng(1)
+    eng, like, templ, _, ndata, nG, (rec, theta_build, fC), (data, invcov, loc, scale, jeff) = setup(1, N, rng)
+    eng.put("TEMPL", templ)
+    theta = theta_build()
+    off = [0, N]
+    like.set_draw_recipe(rec)
+    stat = lambda ts: {"ms": 1e3 * float(np.median(ts)), "ms_spread": [1e3 * min(ts), 1e3 * max(ts)]}
+    out = {"shape": name, "draws": N, "ndata": ndata, "nG": nG, "P": theta.shape[1]}
+    for key, kw in (("floor", dict(return_best=True)), ("grad", dict(grad=True)), ("hess", dict(grad=True, hess=True))):
+        call = lambda: like.logp_draws_params(theta, off, fC, **kw)
+        call()
+        out[key] = stat(times(call, repeats))
+    if hasattr(like, "sample_gaussian_params"):
+        import grad_util as GU
+        import sample_util as SU
+
+        for S in S_list:
+            z = np.random.default_rng(S).standard_normal((N, S, nG))
+            for predict in (False, True):
+                call = lambda: like.sample_gaussian_params(theta, off, fC, z, predict=predict)
+                call()
+                r = stat(times(call, repeats))
+                r["over_floor"] = r["ms"] / out["floor"]["ms"]
+                out["samples_S%d%s" % (S, "_predict" if predict else "")] = r
+        # what a user has today: the templates on the host, and per draw V, F2, a Cholesky factor and the samples in NumPy
+        ntr = eng.ntracers
+        nl, nx = eng.dims
+        th = eng.get("TEMPL", (ntr, nl, 24, nx))
+        S = S_list[-1] if len(S_list) < 2 else S_list[1]
+        z = np.random.default_rng(S).standard_normal((host_draws, S, nG))
+        ff = np.reshape(fC, (1, ntr))[0]
+        t0 = time.perf_counter()
+        for d in range(host_draws):
+            SU.data_space_samples(GU.model_vectors(rec.rows(theta[d : d + 1], ff[None])[0], th, like.index), data, invcov, loc, scale, z[d], jeffreys=jeff)
+        t = (time.perf_counter() - t0) / host_draws * N
+        out["numpy_S%d" % S] = {"ms": 1e3 * t, "timed_draws": host_draws, "device_call_speedup": 1e3 * t / out["samples_S%d" % S]["ms"]}
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", nargs="?", const="1,8,64", default=None,
+                    help="S[,S...] samples of the marginalised parameters per draw (default 1,8,64): time sample_gaussian_params with and without predict, the "
+                         "logp / gradient / Hessian calls on the same draws and the NumPy route on fetched templates")
     ap.add_argument("--draws", type=int, default=None)
     ap.add_argument("--walkers", type=int, default=32)
     ap.add_argument("--datasets", type=int, default=0, help="M data vectors sharing the covariance: time the groups call, the per-vector loop and the plain call")
     a = ap.parse_args()
-    if a.datasets:
+    if a.samples:
+        S_list = [int(s) for s in a.samples.split(",")]
+        probe_samples("marg", marg_setup, S_list, a.draws or 4096)
+        probe_samples("cfg3", cfg3_setup, S_list, a.draws or 4096)
+    elif a.datasets:
         probe_datasets("marg", marg_setup, a.datasets, a.draws or 1024)
         probe_datasets("cfg3", cfg3_setup, a.datasets, a.draws or 1024)
     else:
