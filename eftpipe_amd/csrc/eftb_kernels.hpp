@@ -4494,4 +4494,142 @@ __global__ __launch_bounds__(256) void draws_sample_params_kernel(int ntr, int n
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Metropolis chains over theta at fixed templates (eftb_draws_chain_params): one wave per chain, all steps of a launch in the kernel.
+// Target ln pi(theta) = ln P_marg(theta) + pri(theta), pri = -1/2 sum_p ((theta_p - loc_p) sinv_p)^2 inside the box [lower, upper].
+// Nothing random happens here: the caller supplies the increments step [N][Tc][P] and lnu [N][Tc] = ln of its uniforms.
+// draws_logp_params_kernel's outer shape and staging, then per chain
+//   start          the record of the starting theta (draws_recipe_forward + draws_solve<false>: the bits of eftb_draws_logp_params), its pri;
+//                  ln P not finite there (det F2 <= 0 gives NaN), or an accept count of -1 from an earlier launch: the chain has failed,
+//                  NaN in its slots and in theta, accept count -1
+//   step i         theta' = theta + step[i]; outside the box: rejected without an evaluation.  Otherwise the forward pass and solve at
+//                  theta' into the record slot that is not the current one, then
+//                      accept iff ln P' is finite and lnu[i] < (ln P' + pri') - (ln P + pri)
+//                  taken from lane 0 and broadcast: the branch around the forward pass and the flip of the slot index are wave-uniform
+//   store          after every thin-th step of the whole chain (t0 steps came before this launch): theta to chain [N][kstride][P], the
+//                  current record to rec [N][kstride][MARG_OUT], the launch's slots 0 ... kc - 1 in turn
+//   end            theta [N][P] and nacc [N] are overwritten with the state after the launch's last step: all that the next launch needs
+// pri and the accept expression are evaluated with every operation rounded on its own (no contraction), in parameter order, so that
+// NumPy reproduces them bit for bit; sinv_p = 0 skips parameter p.  Every loop's trip count is fixed at launch.
+// LDS: as draws_logp_params_kernel, with pr [4][RECIPE_MAXP] (lower | upper | loc | sinv) after col and, per wave after G, the current
+// theta [RECIPE_MAXP], the trial theta [RECIPE_MAXP] and two records [2][MARG_OUT].
+// ------------------------------------------------------------------------------------------------
+constexpr int CHAIN_PRI = 4 * RECIPE_MAXP, CHAIN_WAVE = 2 * RECIPE_MAXP + 2 * MARG_OUT;
+
+__device__ __forceinline__ double chain_prior(int P, const double* t, const double* pr) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int p = 0; p < P; ++p) {
+        const double s = pr[3 * RECIPE_MAXP + p];
+        if (s != 0.0) {
+            const double q = (t[p] - pr[2 * RECIPE_MAXP + p]) * s;
+            acc = acc + q * q;
+        }
+    }
+    return -0.5 * acc;
+}
+
+__device__ __forceinline__ bool chain_accept(double lnu, double lp1, double pri1, double lp0, double pri0) {
+#pragma clang fp contract(off)
+    return __builtin_isfinite(lp1) && lnu < (lp1 + pri1) - (lp0 + pri0);
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(256) void draws_chain_params_kernel(int ntr, int nG, int J1, int jeffreys, int Tc, int t0, int thin, int kc, int kstride,
+                                                                 RecipeTab rt, const long long* __restrict__ offsets, double* __restrict__ theta,
+                                                                 long long* __restrict__ nacc, const double* __restrict__ f, const double* __restrict__ W,
+                                                                 const double* __restrict__ mu, const double* __restrict__ sinv,
+                                                                 const double* __restrict__ prior, const double* __restrict__ step,
+                                                                 const double* __restrict__ lnu, double* __restrict__ chain, double* __restrict__ rec) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1, P = rt.P;
+    const long long d0 = offsets[c], d1 = offsets[c + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no chain for this share)
+    double* Ws = sm;
+    double* fp = Ws + J1 * J1;
+    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
+    double* pr = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp / 2;
+    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
+    for (int n = threadIdx.x; n < nnz; n += blockDim.x) col[n] = recipe_col(rt.ent[n], ntr);
+    for (int e = threadIdx.x; e < CHAIN_PRI; e += blockDim.x) pr[e] = prior[e];
+    recipe_fpow(f, c, ntr, threadIdx.x, fp);
+    __syncthreads();
+    double* th = pr + CHAIN_PRI + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1 + CHAIN_WAVE);
+    double* val = th + 34;
+    double* Hs = val + nnzp;
+    double* Gs = Hs + ng1 * J1;
+    double* tc = Gs + ng1 * ng1;
+    double* tp = tc + RECIPE_MAXP;
+    double* rs = tp + RECIPE_MAXP;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        long long na = nacc[d];
+        double* oc = chain + (size_t)d * kstride * P;
+        double* orec = rec + (size_t)d * kstride * MARG_OUT;
+        if (lane < P) tc[lane] = tp[lane] = theta[(size_t)d * P + lane];
+        wave_lds_sync();
+        int cur = 0;
+        double lp0 = nan, pri0 = 0.0;
+        if (na >= 0) {  // (wave-uniform)
+            draws_recipe_forward<TWO>(rt, tp, 0, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+            draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, rs);
+            wave_lds_sync();
+            lp0 = rs[0];
+            pri0 = chain_prior(P, tp, pr);
+        }
+        if (!__builtin_amdgcn_readfirstlane((int)__builtin_isfinite(lp0))) {  // a failed chain
+            for (int k = 0; k < kc; ++k) {
+                if (lane < P) oc[(size_t)k * P + lane] = nan;
+                if (lane < MARG_OUT) orec[(size_t)k * MARG_OUT + lane] = nan;
+            }
+            if (lane < P) theta[(size_t)d * P + lane] = nan;
+            if (lane == 0) nacc[d] = -1;
+            wave_lds_sync();
+            continue;
+        }
+        int left = thin - t0 % thin, k = 0;
+        for (int i = 0; i < Tc; ++i) {
+            if (lane < P) tp[lane] = tc[lane] + step[((size_t)d * Tc + i) * P + lane];
+            wave_lds_sync();
+            bool in = true;
+            for (int p = 0; p < P; ++p) {
+                const double v = tp[p];
+                in = in && v >= pr[p] && v <= pr[RECIPE_MAXP + p];
+            }
+            int acc = 0;
+            double lp1 = nan, pri1 = 0.0;
+            if (__builtin_amdgcn_readfirstlane((int)in)) {  // (wave-uniform: the forward pass and the solve are wave-synchronous)
+                double* ot = rs + (cur ^ 1) * MARG_OUT;
+                draws_recipe_forward<TWO>(rt, tp, 0, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+                draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, ot);
+                wave_lds_sync();
+                lp1 = ot[0];
+                pri1 = chain_prior(P, tp, pr);
+                acc = __builtin_amdgcn_readfirstlane((int)chain_accept(lnu[(size_t)d * Tc + i], lp1, pri1, lp0, pri0));
+            }
+            if (acc) {
+                cur ^= 1;
+                lp0 = lp1;
+                pri0 = pri1;
+                ++na;
+                if (lane < P) tc[lane] = tp[lane];
+            }
+            if (--left == 0) {
+                left = thin;
+                if (k < kc) {  // (always: the host counts the slots of the launch the same way)
+                    if (lane < P) oc[(size_t)k * P + lane] = tc[lane];
+                    if (lane < MARG_OUT) orec[(size_t)k * MARG_OUT + lane] = rs[cur * MARG_OUT + lane];
+                }
+                ++k;
+            }
+            wave_lds_sync();  // (the next step overwrites the trial theta, th, val, H, G and the other record)
+        }
+        if (lane < P) theta[(size_t)d * P + lane] = tc[lane];
+        if (lane == 0) nacc[d] = na;
+        wave_lds_sync();
+    }
+}
+
 }  // namespace eftb

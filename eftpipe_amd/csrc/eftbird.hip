@@ -7,6 +7,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -183,6 +184,13 @@ struct eftb_engine {
     long long* smp_off = nullptr;
     std::vector<long long> smp_off_host;
     bool smp_lds = false;           // the draws_sample_params_kernel instantiations opted in to the large dynamic LDS
+    // eftb_draws_chain_params: one launch's slice of step [N][Tc][P] and lnu [N][Tc], the prior table [4][RECIPE_MAXP], the accept counts
+    // [N], and the launch's stored states [N][kstride][P] and records [N][kstride][MARG_OUT] with their D2H landing blocks; grown on demand
+    double *chn_step = nullptr, *chn_lnu = nullptr, *chn_pri = nullptr, *chn_chain = nullptr, *chn_rec = nullptr;
+    size_t chn_step_cap = 0, chn_lnu_cap = 0, chn_pri_cap = 0, chn_chain_cap = 0, chn_rec_cap = 0, chn_nacc_cap = 0;
+    long long* chn_nacc = nullptr;
+    std::vector<double> chn_host_chain, chn_host_rec;
+    std::vector<long long> chn_host_nacc;
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -2170,6 +2178,7 @@ void eftb_destroy(eftb_engine* e) {
                     (void*)e->recipe[0].dtab, (void*)e->drw_grad, (void*)e->recipe[0].hcoef, (void*)e->recipe[0].htab, (void*)e->drw_hess}) if (p) (void)hipFree(p);
     for (void* p : {(void*)e->dset_D, (void*)e->dset_Ud, (void*)e->drw_Wg, (void*)e->drw_gtab}) if (p) (void)hipFree(p);
     for (void* p : {(void*)e->smp_z, (void*)e->smp_b, (void*)e->smp_chi2, (void*)e->smp_coef, (void*)e->smp_coefn, (void*)e->smp_plk, (void*)e->smp_off}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)e->chn_step, (void*)e->chn_lnu, (void*)e->chn_pri, (void*)e->chn_chain, (void*)e->chn_rec, (void*)e->chn_nacc}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
@@ -2485,9 +2494,12 @@ static int draws_logp_shape(eftb_engine* e, const char* who, size_t extra_w, siz
     return 0;
 }
 
-// the large dynamic LDS for every logp draw kernel, once per engine
+static std::array<const void*, 2> draws_chain_kernels();  // (defined behind the last kernel instantiation of the draw calls)
+
+// the large dynamic LDS for every logp draw kernel and the chain kernels, once per engine
 static int draws_lds_optin(eftb_engine* e) {
     if (e->drw_lds) return 0;
+    for (const void* k : draws_chain_kernels()) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     for (const void* k : {reinterpret_cast<const void*>(&draws_logp_kernel<false>), reinterpret_cast<const void*>(&draws_logp_kernel<true>),
                           reinterpret_cast<const void*>(&draws_logp_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_params_kernel<true>),
                           reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<true>),
@@ -4075,4 +4087,160 @@ int eftb_draws_sample_params_datasets(eftb_engine* e, int C, int G, const int32_
     DrawGroups gr{0, walker, dataset};
     if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
     return draws_sample_params_impl(e, who, G, N, S, offsets, theta, e->grp_f.data(), z, logp, fullchi2, best, bsamp, chi2samp, coef, coefn, nullptr, &gr);
+}
+
+// ------------------------------------------------------------------------------------------------ Metropolis chains over the draw parameters
+// steps of a chain per launch: no launch's duration grows with the caller's T, and one slice of step and lnu is resident at a time.  An
+// evaluation costs tens of microseconds per wave, so 256 steps keep a launch in the milliseconds and spend one evaluation in 256 on the
+// record of the launch's starting theta
+constexpr int CHAIN_STEPS = 256;
+
+static std::array<const void*, 2> draws_chain_kernels() {
+    return {reinterpret_cast<const void*>(&draws_chain_params_kernel<false>), reinterpret_cast<const void*>(&draws_chain_params_kernel<true>)};
+}
+
+// device buffer of at least n elements for eftb_draws_chain_params (as grow_dev; a failed allocation names the shape that asked for it)
+static int chain_grow(const char* who, void* pp, size_t* cap, size_t n, size_t elem, const char* what, long long N, int T, int P) {
+    void** p = static_cast<void**>(pp);
+    if (n <= *cap) return 0;
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    hipError_t me = hipMalloc(p, n * elem);
+    if (me != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail("%s: no device memory for %s of N = %lld chains x T = %d steps with P = %d parameters (%zu bytes): %s", who, what, N, T, P, n * elem,
+                    hipGetErrorString(me));
+    }
+    *cap = n;
+    return 0;
+}
+
+// eftb_draws_chain_params and eftb_draws_chain_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group): the checks, W_c
+// and uploads of draws_logp_params_impl, then draws_chain_params_kernel once per CHAIN_STEPS steps.  Between the launches theta and the accept
+// counts stay on the device; every launch's stored states and records come back behind it
+static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0,
+                                   const double* f, const double* step, const double* lnu, const double* lower, const double* upper, const double* ploc,
+                                   const double* pscale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept,
+                                   const DrawGroups* gr = nullptr) {
+    long long maxcnt = 0;
+    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
+    const int ntr = e->ntr, nG = e->like_nG;
+    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int P = rcp.P, nnzp = (rcp.nnz + 1) & ~1;
+    if (P < 1) return fail("%s: the draw recipe has no parameters to move", who);
+    if (T < 1) return fail("%s: T = %d steps, at least 1", who, T);
+    if (thin < 1 || thin > T) return fail("%s: thin = %d outside [1, T = %d]", who, thin, T);
+    const long long TP = (long long)T * P;
+    for (long long q = 0; q < N * TP; ++q)
+        if (!std::isfinite(step[q])) return fail("%s: step[%lld][%lld][%d] is not finite", who, q / TP, q / P % T, (int)(q % P));
+    for (long long q = 0; q < N * T; ++q)
+        if (!(lnu[q] <= 0.0)) return fail("%s: lnu[%lld][%lld] = %g is not the logarithm of a uniform in [0, 1]", who, q / T, q % T, lnu[q]);
+    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
+    for (int p = 0; p < P; ++p) {
+        const double lo = lower ? lower[p] : -INFINITY, hi = upper ? upper[p] : INFINITY, sc = pscale ? pscale[p] : INFINITY;
+        const double mu = ploc ? ploc[p] : 0.0;
+        if (lo != lo || hi != hi) return fail("%s: a bound of parameter %d is NaN", who, p);
+        if (lo > hi) return fail("%s: lower[%d] = %g > upper[%d] = %g", who, p, lo, p, hi);
+        if (!(sc > 0.0)) return fail("%s: prior_scale[%d] = %g, not > 0", who, p, sc);
+        if (std::isfinite(sc) && !std::isfinite(mu)) return fail("%s: prior_loc[%d] is not finite", who, p);
+        pri[p] = lo;
+        pri[RECIPE_MAXP + p] = hi;
+        pri[2 * RECIPE_MAXP + p] = std::isfinite(sc) ? mu : 0.0;
+        pri[3 * RECIPE_MAXP + p] = 1.0 / sc;  // (inf: 0, the parameter is skipped)
+    }
+    for (int p = P; p < RECIPE_MAXP; ++p) pri[p] = pri[RECIPE_MAXP + p] = pri[2 * RECIPE_MAXP + p] = pri[3 * RECIPE_MAXP + p] = 0.0;
+    for (long long q = 0; q < N * P; ++q)
+        if (!(theta0[q] >= pri[q % P] && theta0[q] <= pri[RECIPE_MAXP + q % P]))
+            return fail("%s: theta0[%lld][%d] = %g outside [%g, %g]", who, q / P, (int)(q % P), theta0[q], pri[q % P], pri[RECIPE_MAXP + q % P]);
+    DrawShape sh;  // beside W_c: fp, col [nnzp] and the prior table; per wave: th [34], val [nnzp], two theta and two records
+    if (int rc = draws_logp_shape(e, who, (RECIPE_MAXTR * RECIPE_FPOW + CHAIN_PRI) * sizeof(double) + nnzp * sizeof(int),
+                                  (34 + (size_t)nnzp + CHAIN_WAVE) * sizeof(double), &sh)) {
+        const int J1w = (e->c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
+        if (J1w > DRAW_MAXJ1) return rc;
+        return fail("%s: the chains of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS", who, P, nG, J1w);
+    }
+    if (N == 0) return 0;
+    const int K = T / thin, kstride = std::max(1, std::min(K, CHAIN_STEPS / thin + 1)), Tmax = std::min(T, CHAIN_STEPS);
+    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets, gr ? gr->nwalk : -1)) return rc;
+    if (gr)
+        if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
+    const double* W = gr ? e->drw_Wg : e->drw_W;
+    if (int rc = chain_grow(who, &e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, sizeof(double), "the steps", N, T, P)) return rc;
+    if (int rc = chain_grow(who, &e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, sizeof(double), "lnu", N, T, P)) return rc;
+    if (int rc = chain_grow(who, &e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, sizeof(double), "the prior table", N, T, P)) return rc;
+    if (int rc = chain_grow(who, &e->chn_nacc, &e->chn_nacc_cap, (size_t)N, sizeof(long long), "the accept counts", N, T, P)) return rc;
+    if (int rc = chain_grow(who, &e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, sizeof(double), "the stored states", N, T, P)) return rc;
+    if (int rc = chain_grow(who, &e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * MARG_OUT, sizeof(double), "the stored records", N, T, P)) return rc;
+    const double *dtheta = nullptr, *df = nullptr;
+    if (int rc = draws_params_upload(e, P, C, N, theta0, f, &dtheta, &df)) return rc;
+    hipStream_t st = e->stream;
+    HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
+    const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
+    const int J1 = sh.J1;
+    const RecipeTab rt = recipe_tab(rcp);
+    e->chn_host_chain.resize((size_t)N * kstride * P);
+    e->chn_host_rec.resize((size_t)N * kstride * MARG_OUT);
+    for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) {
+        const int Tc = std::min(CHAIN_STEPS, T - t0), k0 = t0 / thin, kc = (t0 + Tc) / thin - k0;
+        // this launch's steps of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
+        HIPCHK(hipMemcpy2DAsync(e->chn_step, (size_t)Tc * P * sizeof(double), step + (size_t)t0 * P, (size_t)T * P * sizeof(double), (size_t)Tc * P * sizeof(double),
+                                (size_t)N, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
+                                hipMemcpyHostToDevice, st));
+        if (J1 > 64)
+            hipLaunchKernelGGL(draws_chain_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, Tc, t0, thin, kc, kstride, rt, e->drw_off,
+                               e->drw_theta, e->chn_nacc, df, W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu, e->chn_chain, e->chn_rec);
+        else
+            hipLaunchKernelGGL(draws_chain_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, Tc, t0, thin, kc, kstride, rt, e->drw_off,
+                               e->drw_theta, e->chn_nacc, df, W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu, e->chn_chain, e->chn_rec);
+        hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+        if (!kc) continue;
+        HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, (size_t)N * kstride * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (long long n = 0; n < N; ++n)
+            for (int k = 0; k < kc; ++k) {
+                const size_t to = (size_t)n * K + k0 + k, from = (size_t)n * kstride + k;
+                std::copy_n(e->chn_host_chain.data() + from * P, P, chain + to * P);
+                const double* o = e->chn_host_rec.data() + from * MARG_OUT;
+                if (logp) logp[to] = o[0];
+                if (fullchi2) fullchi2[to] = o[1];
+                if (best) std::copy_n(o + 2, nG, best + to * nG);
+            }
+    }
+    e->chn_host_nacc.resize((size_t)N);
+    HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (long long n = 0; n < N; ++n) naccept[n] = e->chn_host_nacc[n];
+    return 0;
+}
+
+int eftb_draws_chain_params(eftb_engine* e, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0, const double* f,
+                            const double* step, const double* lnu, const double* lower, const double* upper, const double* prior_loc,
+                            const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept) {
+    static const char* who = "eftb_draws_chain_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta0 || !step || !lnu || !chain || !last || !naccept))) return fail("%s: null argument", who);
+    return draws_chain_params_impl(e, who, C, N, T, thin, offsets, theta0, f, step, lnu, lower, upper, prior_loc, prior_scale, chain, logp, fullchi2, best,
+                                   last, naccept);
+}
+
+int eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int T, int thin,
+                                     const int64_t* offsets, const double* theta0, const double* f, const double* step, const double* lnu,
+                                     const double* lower, const double* upper, const double* prior_loc, const double* prior_scale, double* chain,
+                                     double* logp, double* fullchi2, double* best, double* last, int64_t* naccept) {
+    static const char* who = "eftb_draws_chain_params_datasets";
+    if (e) sub_drain(e);
+    if (!e || !walker || !dataset || !offsets || !f || (N > 0 && (!theta0 || !step || !lnu || !chain || !last || !naccept)))
+        return fail("%s: null argument", who);
+    DrawGroups gr{0, walker, dataset};
+    if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
+    return draws_chain_params_impl(e, who, G, N, T, thin, offsets, theta0, e->grp_f.data(), step, lnu, lower, upper, prior_loc,
+                                   prior_scale, chain, logp, fullchi2, best, last, naccept, &gr);
 }

@@ -20,6 +20,9 @@ MAXG = 24
 # what MarginalLikelihood.sample_gaussian_params returns; fields that were not asked for are None
 GaussianSamples = collections.namedtuple("GaussianSamples", "logp fullchi2 best b chi2 coef coef_nnlo plk")
 
+# what MarginalLikelihood.metropolis_draws_params returns; fullchi2 and best are None unless return_best is set
+DrawChains = collections.namedtuple("DrawChains", "theta logp naccept last fullchi2 best")
+
 
 def data_index(ls, masks, nx, tracer=0, nl=None):
     """Flat indices l * nx + x of the data vector in the order of reference likelihood.py:167-195 (``flatten``):
@@ -344,6 +347,70 @@ class MarginalLikelihood:
             coef, coefn, plk = (None if a is None else a.reshape(a.shape[:2] + a.shape[3:]) for a in (coef, coefn, plk))
         return GaussianSamples(logp, full, best, b, chi2, coef, coefn, plk)
 
+    def metropolis_draws_params(self, theta0, offsets, f, step, lnu, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None, groups=None,
+                                return_best=False):
+        """Metropolis chains over theta at fixed templates, all T steps of all N chains in one device call (``eftb_draws_chain_params``): the
+        fast steps of a dragging or oversampling sampler behind one slow step.  theta0 [N, P], offsets, f and ``groups`` as
+        ``logp_draws_params``: chain n starts at theta0[n] and belongs to the walker (group) that owns draw n.  The target is
+        ln P_marg(theta) + ln prior(theta) with the prior on theta given by box bounds ``lower`` / ``upper`` [P] (None or -inf / inf: none)
+        and independent Gaussians ``prior_loc`` / ``prior_scale`` [P] (None or scale inf: none).  The caller supplies the randomness
+        (``metropolis_proposals``): step [N, T, P], the proposal increments, and lnu [N, T], the logarithms of its uniforms; step t
+        proposes theta + step[n, t], rejects it without an evaluation outside the box, and accepts iff ln P' is finite and
+        lnu[n, t] < (ln P' + pri') - (ln P + pri).  A proposal with det F2 <= 0 is rejected, not an error.
+        -> ``DrawChains(theta [N, K, P], logp [N, K], naccept [N], last [N, P], fullchi2, best)`` with K = T // thin: the state after steps
+        thin, 2 thin, ..., its ln P_marg (the bits of ``logp_draws_params`` there) and, with ``return_best``, full chi2 [N, K] and best
+        [N, K, nG]; ``last`` is the state after step T, the theta0 that continues the chains: a T-step call equals a T1-step call and a
+        T2-step call from ``last`` bit for bit.  A chain's bits depend neither on the other chains nor on the split into calls.
+        Raises RuntimeError("det of F2ij <= 0") where a chain's starting point has no finite ln P."""
+        out = self._chains_raw(theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, groups, return_best)
+        if np.any(out.naccept < 0):
+            raise RuntimeError("det of F2ij <= 0")
+        return out
+
+    def _chains_raw(self, theta0, offsets, f, step, lnu, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None, groups=None, return_best=False):
+        """``metropolis_draws_params`` without the RuntimeError: a chain that failed at its start has NaN states and naccept = -1"""
+        from .engine import _params_args
+
+        ntr, nG = self.eng.ntracers, self.nG
+        rec = getattr(self, "_recipe", None)
+        wk = ds = None
+        if groups is not None:
+            theta0, off, f, wk, ds = _groups_args(rec, theta0, offsets, f, ntr, groups)
+        else:
+            theta0, off, f = _params_args(rec, theta0, offsets, f, ntr)
+        N, P = theta0.shape
+        step = np.ascontiguousarray(step, dtype=np.float64)
+        if step.ndim != 3 or step.shape[0] != N or step.shape[2] != P or step.shape[1] < 1:
+            raise ValueError(f"step must be [{N}, T, {P}] proposal increments with T >= 1 steps")
+        T = step.shape[1]
+        lnu = np.ascontiguousarray(lnu, dtype=np.float64)
+        if lnu.shape != (N, T):
+            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and step")
+        if thin != int(thin) or not 1 <= thin <= T:
+            raise ValueError(f"thin must be an integer in [1, T = {T}]")
+        thin = int(thin)
+        pri = []
+        for name, a in (("lower", lower), ("upper", upper), ("prior_loc", prior_loc), ("prior_scale", prior_scale)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (P,):
+                    raise ValueError(f"{name} must be [{P}], one value per parameter")
+            pri.append(a)
+        K = T // thin
+        theta, logp, last, nacc = np.empty((N, K, P)), np.empty((N, K)), np.empty((N, P)), np.empty(N, dtype=np.int64)
+        full = np.empty((N, K)) if return_best else None
+        best = np.empty((N, K, nG)) if return_best else None
+        i64p = C.POINTER(C.c_int64)
+        tail = (off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(step), L.dptr(lnu)) + tuple(L.dptr(a) for a in pri) + (
+            L.dptr(theta), L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(last), nacc.ctypes.data_as(i64p))
+        if groups is not None:
+            i32p = C.POINTER(C.c_int32)
+            L.check(self.eng.lib.eftb_draws_chain_params_datasets(self.eng._h, f.shape[0], wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p), N, T,
+                                                                  thin, *tail))
+        else:
+            L.check(self.eng.lib.eftb_draws_chain_params(self.eng._h, off.size - 1, N, T, thin, *tail))
+        return DrawChains(theta, logp, nacc, last, full, best)
+
     def maximize_draws_params(self, theta0, offsets, f, groups=None, **kw):
         """Best fits over the recipe's parameters at fixed cosmology: ``newton_maximize`` fed with the Hessian call, all starts of all
         walkers at once (theta0 [N, P], offsets and f as ``logp_draws_params``; kw: max_iter, tol) -> theta, logp, grad, hess, n_iter,
@@ -471,4 +538,40 @@ def newton_maximize(fun, theta0, max_iter=50, tol=1e-8):
     return theta, logp, grad, hess, n_iter, converged
 
 
-__all__ = ["MarginalLikelihood", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]
+def proposal_factor(hess, scale=None):
+    """Lower Cholesky factor L of the Gaussian proposal covariance scale^2 (-H)^-1 at a maximum: hess [P, P] or [N, P, P], the Hessian of
+    ln P from ``logp_draws_params(..., hess=True)`` or ``maximize_draws_params`` -> L [P, P] or [N, P, P] with L L^T (-H) = scale^2 I.
+    scale defaults to 2.38 / sqrt(P), the optimal random-walk scaling of a Gaussian target.  ValueError where -H is not positive definite
+    (no maximum: a proposal cannot be taken from the curvature there)."""
+    H = np.asarray(hess, dtype=np.float64)
+    if H.ndim not in (2, 3) or H.shape[-1] != H.shape[-2] or H.shape[-1] < 1:
+        raise ValueError("hess must be [P, P] or [N, P, P]")
+    P = H.shape[-1]
+    scale = 2.38 / np.sqrt(P) if scale is None else float(scale)
+    A = -0.5 * (H + np.swapaxes(H, -1, -2))
+    if not np.all(np.isfinite(A)):
+        raise ValueError("-H is not positive definite (not finite)")
+    try:
+        np.linalg.cholesky(A)  # (raises where -H is not positive definite)
+        cov = np.linalg.inv(A)
+        return scale * np.linalg.cholesky(0.5 * (cov + np.swapaxes(cov, -1, -2)))
+    except np.linalg.LinAlgError:
+        raise ValueError("-H is not positive definite") from None
+
+
+def metropolis_proposals(rng, N, T, factor):
+    """The randomness of ``MarginalLikelihood.metropolis_draws_params`` from a ``numpy.random.Generator``: -> (step [N, T, P], lnu [N, T]) with
+    step = z @ factor^T for standard normals z [N, T, P] and lnu = log(rng.random((N, T))).  factor is [P, P] (``proposal_factor``), one
+    for all chains, or [N, P, P], one per chain."""
+    F = np.asarray(factor, dtype=np.float64)
+    if F.ndim not in (2, 3) or F.shape[-1] != F.shape[-2] or (F.ndim == 3 and F.shape[0] != N):
+        raise ValueError(f"factor must be [P, P] or [{N}, P, P]")
+    P = F.shape[-1]
+    z = rng.standard_normal((N, T, P))
+    step = np.einsum("ntq,pq->ntp", z, F) if F.ndim == 2 else np.einsum("ntq,npq->ntp", z, F)
+    with np.errstate(divide="ignore"):
+        lnu = np.log(rng.random((N, T)))
+    return np.ascontiguousarray(step), lnu
+
+
+__all__ = ["MarginalLikelihood", "DrawChains", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]

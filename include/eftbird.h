@@ -395,6 +395,40 @@ int  eftb_draws_sample_params_datasets(eftb_engine* e, int C, int G, const int32
                                        const int64_t* offsets, const double* theta, const double* f, const double* z, double* logp, double* fullchi2,
                                        double* best, double* bsamp, double* chi2samp, double* coef, double* coefn);
 
+/* Metropolis chains over the parameters theta of the kind-0 recipe at fixed templates: all T steps of all N chains in the kernel, one wave per
+ * chain, so that a dragging or oversampling run pays one call instead of T.  Chain n belongs to the walker (or group) that owns draw n in
+ * offsets, starts at theta0[n] and targets
+ *     ln pi(theta) = ln P_marg(theta) + pri(theta),      pri = -1/2 sum_p ((theta_p - prior_loc_p) / prior_scale_p)^2 inside [lower, upper],
+ * ln P_marg being the record of eftb_draws_logp_params (the same functions: every ln P, full chi2 and best fit of a chain are that call's
+ * bits at that theta).  lower / upper [P] (NULL or -inf / inf: no bound) and prior_loc / prior_scale [P] (NULL or scale = inf: none) are
+ * the sampler's prior on theta.  Nothing random happens on the device: the caller supplies step [N][T][P], the proposal increments
+ * already multiplied by its proposal factor, and lnu [N][T], the logarithms of its uniforms (-inf allowed).  Step t of chain n:
+ *     theta' = theta + step[n][t]; outside the box: rejected without an evaluation; otherwise the forward pass and solve at theta', and
+ *     accepted iff ln P' is finite and lnu[n][t] < (ln P' + pri') - (ln P + pri)         (det F2 <= 0 at theta': rejected, no error)
+ * pri is summed in parameter order as q = (theta_p - loc_p) sinv_p, acc = acc + q q, pri = -acc / 2 with sinv_p = 1 / scale_p (sinv_p = 0
+ * skipped), every operation rounded on its own, and the accept expression is evaluated as written: NumPy reproduces both bit for bit.
+ * After every thin-th step the state is stored: with K = T / thin,
+ *     chain [N][K][P]       theta after steps thin, 2 thin, ...
+ *     logp [N][K], fullchi2 [N][K], best [N][K][nG]   (each or NULL) the record at the stored theta
+ *     last [N][P]           theta after step T (whether or not thin divides T): theta0 of the call that continues the chain
+ *     naccept [N]           accepted steps
+ * The host splits T into launches of at most 256 steps; between them only theta and the accept counts persist on the device and every
+ * launch first recomputes the record of its starting theta, so a T-step call equals a T1-step call followed by a T2-step call from
+ * `last` bit for bit, the accept counts summed (and the stored states too where thin divides T1).  A chain's bits do not depend on the
+ * other chains of the call or on how the chains are split into calls.
+ * A chain whose theta0 has no finite ln P (det F2 <= 0) fails alone: NaN in its chain, logp, fullchi2, best and last, naccept = -1.
+ * Refused before anything is copied, naming chain, step and parameter where they apply: what eftb_draws_logp_params refuses, T < 1, thin
+ * outside [1, T], a non-finite step, lnu NaN or > 0, lower > upper, a NaN bound, prior_scale <= 0 or NaN, theta0 outside the box, a working
+ * set that does not fit the LDS (as eftb_draws_logp_params, plus 128 doubles per workgroup and 116 per wave). */
+int  eftb_draws_chain_params(eftb_engine* e, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0, const double* f,
+                             const double* step, const double* lnu, const double* lower, const double* upper, const double* prior_loc,
+                             const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept);
+/* eftb_draws_chain_params per group (walker[g], dataset[g]) of eftb_draws_logp_params_datasets: the same kernel on the groups' Gram matrices. */
+int  eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int T, int thin,
+                                      const int64_t* offsets, const double* theta0, const double* f, const double* step, const double* lnu,
+                                      const double* lower, const double* upper, const double* prior_loc, const double* prior_scale, double* chain,
+                                      double* logp, double* fullchi2, double* best, double* last, int64_t* naccept);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

@@ -40,6 +40,18 @@ shapes, 1 walker x --draws draws (default 4096), medians of 9 cached calls with 
 On a tree without sample_gaussian_params only (b) runs, so that the same file times the existing calls on the parent commit.
 
     python tools/draws_probe.py --samples [--draws N]
+
+--chains [n,n,...]: Metropolis chains over theta (MarginalLikelihood.metropolis_draws_params) instead, for both shapes,
+--walkers walkers (default 128 in this mode) x n chains each (default 1 and 8), --steps T steps (default 256), medians of 9 cached calls
+with [min, max], on the same proposals:
+
+    (a) chains   one metropolis_draws_params call: all T steps of all chains in the kernel
+    (b) loop     the host loop: per step the proposals formed in NumPy, one logp_draws_params call, the acceptance rule in NumPy
+    (c) ceiling  one logp_draws_params call on N T independent draws: the throughput a Markov chain cannot reach
+
+On a tree without metropolis_draws_params (a) is skipped, so that the same file times (b) and (c) on the parent commit.
+
+    python tools/draws_probe.py --chains [--walkers C] [--steps T]
 """
 import argparse
 import json
@@ -320,16 +332,74 @@ def probe_samples(name, setup, S_list, N=4096, repeats=9, host_draws=32):
     return out
 
 
+def probe_chains(name, setup, C, n, T, repeats=9):
+    """(a), (b), (c) of --chains for one shape: C walkers x n chains x T steps, medians of `repeats` cached calls with [min, max]"""
+    rng = np.random.default_rng(1)
+    N = C * n
+    eng, like, templ, _, ndata, nG, (rec, theta_build, fC), _ = setup(C, N, rng)
+    eng.put("TEMPL", templ)
+    theta0 = theta_build()
+    P = theta0.shape[1]
+    off = np.arange(C + 1) * n
+    like.set_draw_recipe(rec)
+    step = 0.3 * (theta_build() - np.median(theta0, axis=0))[:, None, :] * rng.standard_normal((N, T, 1)) + 0.01 * rng.standard_normal((N, T, P))
+    lnu = np.log(rng.random((N, T)))
+    stat = lambda ts: {"ms": 1e3 * float(np.median(ts)), "ms_spread": [1e3 * min(ts), 1e3 * max(ts)]}
+    out = {"shape": name, "walkers": C, "chains": N, "steps": T, "ndata": ndata, "nG": nG, "P": P}
+
+    def loop():
+        cur = theta0.copy()
+        lp = like.logp_draws_params(cur, off, fC)
+        nacc = np.zeros(N, dtype=np.int64)
+        for t in range(T):
+            trial = cur + step[:, t]
+            try:
+                lp1 = like.logp_draws_params(trial, off, fC)
+            except RuntimeError:  # det F2 <= 0 at a proposal: the public call has no NaN to give, the step is lost for all chains
+                lp1, out["loop_hit_nan"] = np.full(N, np.nan), True
+            acc = np.isfinite(lp1) & (lnu[:, t] < lp1 - lp)
+            cur[acc], lp[acc] = trial[acc], lp1[acc]
+            nacc += acc
+        return cur, nacc
+
+    last, nacc = loop()
+    out["accept_rate"] = float(np.mean(nacc)) / T
+    out["loop"] = stat(times(loop, repeats))
+    many = np.ascontiguousarray((theta0[:, None, :] + step).reshape(N * T, P))
+    ceiling = lambda: like.logp_draws_params(many, off * T, fC)
+    ceiling()
+    out["ceiling"] = stat(times(ceiling, repeats))
+    if hasattr(like, "metropolis_draws_params"):
+        call = lambda: like.metropolis_draws_params(theta0, off, fC, step, lnu)
+        r = call()
+        assert "loop_hit_nan" in out or (np.array_equal(r.last, last) and np.array_equal(r.naccept, nacc))  # the same chains as the loop
+        out["chains"] = stat(times(call, repeats))
+        out["loop_over_chains"] = out["loop"]["ms"] / out["chains"]["ms"]
+        out["chains_over_ceiling"] = out["chains"]["ms"] / out["ceiling"]["ms"]
+        out["steps_per_s"] = N * T / (1e-3 * out["chains"]["ms"])
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", nargs="?", const="1,8", default=None,
+                    help="n[,n...] chains per walker (default 1,8): time metropolis_draws_params, the host loop of logp_draws_params calls on the same "
+                         "proposals and one logp_draws_params call on as many independent draws")
+    ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--samples", nargs="?", const="1,8,64", default=None,
                     help="S[,S...] samples of the marginalised parameters per draw (default 1,8,64): time sample_gaussian_params with and without predict, the "
                          "logp / gradient / Hessian calls on the same draws and the NumPy route on fetched templates")
     ap.add_argument("--draws", type=int, default=None)
-    ap.add_argument("--walkers", type=int, default=32)
+    ap.add_argument("--walkers", type=int, default=None)
     ap.add_argument("--datasets", type=int, default=0, help="M data vectors sharing the covariance: time the groups call, the per-vector loop and the plain call")
     a = ap.parse_args()
-    if a.samples:
+    if a.chains:
+        for n in (int(x) for x in a.chains.split(",")):
+            probe_chains("marg", marg_setup, a.walkers or 128, n, a.steps)
+            probe_chains("cfg3", cfg3_setup, a.walkers or 128, n, a.steps)
+    elif a.samples:
         S_list = [int(s) for s in a.samples.split(",")]
         probe_samples("marg", marg_setup, S_list, a.draws or 4096)
         probe_samples("cfg3", cfg3_setup, S_list, a.draws or 4096)
@@ -337,5 +407,5 @@ if __name__ == "__main__":
         probe_datasets("marg", marg_setup, a.datasets, a.draws or 1024)
         probe_datasets("cfg3", cfg3_setup, a.datasets, a.draws or 1024)
     else:
-        probe("marg", marg_setup, a.walkers, a.draws or 32768, 1)
-        probe("cfg3", cfg3_setup, a.walkers, a.draws or 32768, 3)
+        probe("marg", marg_setup, a.walkers or 32, a.draws or 32768, 1)
+        probe("cfg3", cfg3_setup, a.walkers or 32, a.draws or 32768, 3)
