@@ -2489,6 +2489,9 @@ static int draws_logp_shape(eftb_engine* e, const char* who, size_t extra_w, siz
     const size_t lds_w = (size_t)J1 * J1 * sizeof(double) + extra_w, lds_wave = ((size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double) + extra_wave;
     int nw = 4;
     while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
+    // Reachable from the sample call alone (which words it anew): J + 1 <= 121 (five tracers; with NNLO four, 109), nG <= 24 and at most
+    // 1024 recipe entries leave the rows, params, gradient and chain calls at most 146328, 159336, 163432 and 161288 of the 163840 bytes at
+    // one wave, so this message is never seen.
     if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
     *sh = DrawShape{J1, nw, lds_w + nw * lds_wave};
     return 0;
@@ -4007,6 +4010,8 @@ static int draws_sample_params_impl(eftb_engine* e, const char* who, int C, long
                                   &sh)) {
         const int J1w = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
         if (J1w > DRAW_MAXJ1) return rc;
+        // Reachable at one shape only: five tracers (J + 1 = 121), nG = 24 and a recipe of at least 1001 entries (147816 + 16 nnzp bytes
+        // at one wave, nnzp the entry count rounded up to even, against 163840); tests/test_gpu_draw_synthetic.py goes there.
         return fail("%s: the samples of nG = %d parameters with J + 1 = %d columns do not fit the LDS (S = %d, %d samples at a time)", who, nG, J1w, S, ADJ_KB);
     }
     if (N == 0) return 0;
@@ -4160,6 +4165,7 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
                                   (34 + (size_t)nnzp + CHAIN_WAVE) * sizeof(double), &sh)) {
         const int J1w = (e->c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
         if (J1w > DRAW_MAXJ1) return rc;
+        // Unreachable: the largest shape there is (J + 1 = 121, nG = 24, 1024 recipe entries) takes 161288 of the 163840 bytes at one wave.
         return fail("%s: the chains of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS", who, P, nG, J1w);
     }
     if (N == 0) return 0;
