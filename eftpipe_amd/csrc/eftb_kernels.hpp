@@ -3642,11 +3642,103 @@ __device__ __forceinline__ bool draws_solve(int lane, int nG, int jeffreys, doub
     return ok;
 }
 
+constexpr int RECIPE_MAXP = 32, RECIPE_MAXTERMS = 1024, RECIPE_FPOW = 7, RECIPE_MAXTR = 8;  // (draw recipes: see RecipeTab)
+constexpr int CHAIN_PRI = 4 * RECIPE_MAXP;                                                 // the prior table of the chain kernel
+
+// The dynamic LDS of a draw kernel, in doubles: what the host sizes the launch from and what the kernel takes its pointers from.
+//   per workgroup  W_c [J1][J1] at 0, then (all but rows) fp [RECIPE_MAXTR][RECIPE_FPOW] and the int tables, two ints to a double:
+//                  col [nnzp]; erow [nnzp] (gradient, Hessian, sample); drow | dcol [ndtp] (Hessian); then pr [CHAIN_PRI] (chain)
+//   per wave       (all but rows) th [P + 1 -> 34], val [nnzp]; H [ng1][J1], G [ng1][ng1]; then the kind's tail:
+//                  Hessian K [nG][nG] | dval [ndtp] | hv [J1] | u [P][nG] | w [P][nG] | G_p | M_p [P][nG][nG] (the last two empty under Jeffreys)
+//                  sample  bs [ADJ_KB][nG]
+//                  chain   tc | tp [RECIPE_MAXP] (the current and the trial theta) | rs [2][MARG_OUT] (two records)
+// nnzp and ndtp: the entries of the recipe and its derivative records, rounded up to even.  A region a kind does not have is empty.
+enum DrawKind { DRAW_ROWS, DRAW_PARAMS, DRAW_GRAD, DRAW_HESS, DRAW_SAMPLE, DRAW_CHAIN };
+
+struct DrawLds {
+    int fp = 0, col = 0, erow = 0, drow = 0, dcol = 0, pr = 0, wg = 0;  // offsets from the start of the LDS; wg: doubles per workgroup
+    int th = 0, val = 0, H = 0, G = 0, K = 0, dval = 0, hv = 0, u = 0, w = 0, Gp = 0, Mp = 0, bs = 0, tc = 0, tp = 0, rs = 0,
+        wave = 0;  // offsets from the start of the wave's part; wave: doubles per wave
+
+    DrawLds() = default;
+    static constexpr bool has_erow(DrawKind kind) { return kind == DRAW_GRAD || kind == DRAW_HESS || kind == DRAW_SAMPLE; }
+    __host__ __device__ constexpr DrawLds(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) {
+        const bool recipe = kind != DRAW_ROWS, adj = has_erow(kind), hess = kind == DRAW_HESS;
+        const int ng1 = nG + 1, nnzp = (nnz + 1) & ~1, ndtp = (ndt + 1) & ~1, gpn = hess && !jeffreys ? P * nG * nG : 0;
+        int o = J1 * J1;
+        fp = o, o += recipe ? RECIPE_MAXTR * RECIPE_FPOW : 0;
+        col = o, o += recipe ? nnzp / 2 : 0;
+        erow = o, o += adj ? nnzp / 2 : 0;
+        drow = o, o += hess ? ndtp / 2 : 0;
+        dcol = o, o += hess ? ndtp / 2 : 0;
+        pr = o, o += kind == DRAW_CHAIN ? CHAIN_PRI : 0;
+        wg = o;
+        o = 0;
+        th = o, o += recipe ? 34 : 0;
+        val = o, o += recipe ? nnzp : 0;
+        H = o, o += ng1 * J1;
+        G = o, o += ng1 * ng1;
+        K = o, o += hess ? nG * nG : 0;
+        dval = o, o += hess ? ndtp : 0;
+        hv = o, o += hess ? J1 : 0;
+        u = o, o += hess ? P * nG : 0;
+        w = o, o += hess ? P * nG : 0;
+        Gp = o, o += gpn;
+        Mp = o, o += gpn;
+        bs = o, o += kind == DRAW_SAMPLE ? ADJ_KB * nG : 0;
+        tc = o, o += kind == DRAW_CHAIN ? RECIPE_MAXP : 0;
+        tp = o, o += kind == DRAW_CHAIN ? RECIPE_MAXP : 0;
+        rs = o, o += kind == DRAW_CHAIN ? 2 * MARG_OUT : 0;
+        wave = o;
+    }
+    __host__ __device__ constexpr size_t bytes_wg() const { return (size_t)wg * sizeof(double); }
+    __host__ __device__ constexpr size_t bytes_wave() const { return (size_t)wave * sizeof(double); }
+    __host__ __device__ constexpr size_t bytes(int nw) const { return bytes_wg() + nw * bytes_wave(); }
+    // the waves of a workgroup: 4, 2 or 1, as many as fit beside W_c; 0 if one does not
+    __host__ __device__ constexpr int fit(size_t limit) const { return bytes(4) <= limit ? 4 : bytes(2) <= limit ? 2 : bytes(1) <= limit ? 1 : 0; }
+    // every region holds what its kernel keeps there and ends where the next begins or before (the int tables in whole doubles, so every
+    // region starts on an 8-byte boundary), whatever the arithmetic above becomes
+    __host__ __device__ constexpr bool sound(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) const {
+        const bool recipe = kind != DRAW_ROWS, adj = has_erow(kind), hess = kind == DRAW_HESS;
+        const bool chain = kind == DRAW_CHAIN;
+        const int ng1 = nG + 1, gpn = hess && !jeffreys ? P * nG * nG : 0;
+        const int at[] = {0, fp, col, erow, drow, dcol, pr, wg}, atw[] = {th, val, H, G, K, dval, hv, u, w, Gp, Mp, bs, tc, tp, rs, wave};
+        const int len[] = {J1 * J1, recipe ? RECIPE_MAXTR * RECIPE_FPOW : 0, recipe ? (nnz + 1) / 2 : 0, adj ? (nnz + 1) / 2 : 0, hess ? (ndt + 1) / 2 : 0,
+                           hess ? (ndt + 1) / 2 : 0, chain ? CHAIN_PRI : 0};
+        const int lenw[] = {recipe ? P + 1 : 0, recipe ? nnz : 0, ng1 * J1, ng1 * ng1, hess ? nG * nG : 0, hess ? ndt : 0, hess ? J1 : 0, hess ? P * nG : 0,
+                            hess ? P * nG : 0, gpn, gpn, kind == DRAW_SAMPLE ? ADJ_KB * nG : 0, chain ? P : 0, chain ? P : 0, chain ? 2 * MARG_OUT : 0};
+        for (int i = 0; i < 7; ++i)
+            if (at[i] + len[i] > at[i + 1]) return false;
+        for (int i = 0; i < 15; ++i)
+            if (atw[i] + lenw[i] > atw[i + 1]) return false;
+        return true;
+    }
+};
+
+// The layout is pinned on the published figures of the largest shape there is (J + 1 = 121, nG = 24, 1024 recipe entries, one wave)
+// and on `sound` at that shape and at an odd one, with Jeffreys off and on
+constexpr size_t draw_lds_pin(DrawKind kind, int nnz) { return DrawLds(kind, 121, 24, nnz, 0, RECIPE_MAXP, 0).bytes(1); }
+static_assert(MARG_OUT == 26 && ADJ_KB == 4, "the figures below are for these");
+static_assert(draw_lds_pin(DRAW_ROWS, 1024) == 146328 && draw_lds_pin(DRAW_PARAMS, 1024) == 159336 && draw_lds_pin(DRAW_GRAD, 1024) == 163432 &&
+                  draw_lds_pin(DRAW_CHAIN, 1024) == 161288,
+              "DrawLds: rows, params, gradient, chain at the largest shape");
+static_assert(draw_lds_pin(DRAW_SAMPLE, 1024) == 147816 + 16 * 1024 && draw_lds_pin(DRAW_SAMPLE, 999) == 147816 + 16 * 1000 &&
+                  draw_lds_pin(DRAW_SAMPLE, 1000) == 163816,
+              "DrawLds: sample, 147816 + 16 nnzp bytes");
+constexpr bool draw_lds_sound(int J1, int nG, int nnz, int ndt, int P) {
+    for (int kind = DRAW_ROWS; kind <= DRAW_CHAIN; ++kind)
+        for (int jeffreys = 0; jeffreys < 2; ++jeffreys)
+            if (!DrawLds((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys).sound((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys)) return false;
+    return true;
+}
+static_assert(draw_lds_sound(121, 24, 1024, 2048, RECIPE_MAXP) && draw_lds_sound(25, 3, 37, 51, 5) && draw_lds_sound(2, 0, 0, 0, 0),
+              "DrawLds: a region overlaps the next");
+
 // One workgroup per (walker, share of its draws): W_c is staged in LDS once, then every wave takes one draw at a time.
 //   H = R^ W_c    lanes over the columns j (j = lane and lane + 64 with TWO), nG + 1 accumulators each; R^[g][k] wave-uniform (scalar loads)
 //   G = H R^^T    lane h (lanes 32-63: the second half of the j sum, added with one shuffle), H from the wave's LDS scratch, G back to it
 //   then draws_solve on G
-// Output: the [MARG_OUT] record of the LOGP stage per draw.  LDS: W_c [J1][J1], then per wave H [nG + 1][J1] and G [nG + 1][nG + 1].
+// Output: the [MARG_OUT] record of the LOGP stage per draw.  LDS: DrawLds, DRAW_ROWS.
 template <bool TWO>
 __global__ __launch_bounds__(256) void draws_logp_kernel(int ntr, int nG, int J1, int jeffreys, const long long* __restrict__ offsets,
                                                          const double* __restrict__ rows, const double* __restrict__ rowsn,
@@ -3658,11 +3750,12 @@ __global__ __launch_bounds__(256) void draws_logp_kernel(int ntr, int nG, int J1
     const int ng1 = nG + 1, J = J1 - 1;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
+    const DrawLds L(DRAW_ROWS, J1, nG, 0, 0, 0, jeffreys);
     double* Ws = sm;
     for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
     __syncthreads();
-    double* Hs = sm + J1 * J1 + wv * (ng1 * J1 + ng1 * ng1);
-    double* Gs = Hs + ng1 * J1;
+    double* Hs = sm + L.wg + wv * L.wave + L.H;
+    double* Gs = sm + L.wg + wv * L.wave + L.G;
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
         const double* Rd = rows + (size_t)d * ntr * ng1 * NROW;
         const double* Rn = rowsn ? rowsn + (size_t)d * ntr * ng1 * 3 : nullptr;
@@ -3866,8 +3959,6 @@ __global__ __launch_bounds__(256) void stream_read_kernel(const double* __restri
 //         | slot [ntr * 27] (the entry of (tau, r) in row 0, or -1: draws_recipe_rows_kernel)
 //   pack = i | j << 6 | k << 12 | (tau * 7 + e) << 18, with the factor 1 at theta index P
 // ------------------------------------------------------------------------------------------------
-constexpr int RECIPE_MAXP = 32, RECIPE_MAXTERMS = 1024, RECIPE_FPOW = 7, RECIPE_MAXTR = 8;
-
 struct RecipeTab {
     const double* coef;  // [nterms]
     const int *rowstart, *ent, *tstart, *pack, *slot;
@@ -3953,13 +4044,43 @@ __device__ __forceinline__ void draws_recipe_forward(const RecipeTab& rt, const 
     wave_lds_sync();
 }
 
+// What a params draw kernel of one kind does between its early exit and its first draw: W_c of walker c, col[n] (the column of entry n) and,
+// where the kind has them, erow[n] (its row), drow | dcol (row and column of every derivative record) and the prior table, then the powers
+// of f, go to the workgroup's LDS at the places of L.  Behind the barrier: the start of wave wv's part.  (The pointers themselves are the
+// kernel's, sm + L.x and the wave's start + L.x: handed back in a struct they cost every kernel some twenty registers.)
+template <DrawKind KIND>
+__device__ __forceinline__ double* draws_stage(const DrawLds& L, double* sm, int wv, int c, int ntr, int J1, const RecipeTab& rt,
+                                               const double* __restrict__ f, const double* __restrict__ W,
+                                               const int* __restrict__ erow_tab = nullptr, const int* __restrict__ dent = nullptr, int ndt = 0,
+                                               const double* __restrict__ prior = nullptr) {
+    int *col = reinterpret_cast<int*>(sm + L.col), *erow = reinterpret_cast<int*>(sm + L.erow);
+    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) sm[e] = W[(size_t)c * J1 * J1 + e];
+    for (int n = threadIdx.x; n < rt.nnz; n += blockDim.x) {
+        col[n] = recipe_col(rt.ent[n], ntr);
+        if (DrawLds::has_erow(KIND)) erow[n] = erow_tab[n];
+    }
+    if (KIND == DRAW_HESS) {
+        int *drow = reinterpret_cast<int*>(sm + L.drow), *dcol = reinterpret_cast<int*>(sm + L.dcol);
+        for (int t = threadIdx.x; t < ndt; t += blockDim.x) {
+            const int n = dent[t];
+            drow[t] = erow_tab[n];
+            dcol[t] = recipe_col(rt.ent[n], ntr);
+        }
+    }
+    if (KIND == DRAW_CHAIN)
+        for (int e = threadIdx.x; e < CHAIN_PRI; e += blockDim.x) sm[L.pr + e] = prior[e];
+    recipe_fpow(f, c, ntr, threadIdx.x, sm + L.fp);
+    __syncthreads();
+    return sm + L.wg + wv * L.wave;
+}
+
 // draws_logp_kernel for draws given as theta [N][P] and f [C][ntr]: the same workgroup shape (W_c in LDS once, one wave per draw at a
 // time) and the same algebra after G (draws_solve), but R^ only exists as the values of its nnz non-zero entries in the wave's LDS:
 //   val[n]        lanes over the entries of the recipe
 //   H = R^ W_c    row g at a time: lanes over the columns j (j = lane and lane + 64 with TWO), one FMA per non-zero of row g, the value a
 //                 broadcast LDS read; R^[0][J] = 1 stays implicit (the data row of W_c is added to row 0)
 //   G = H R^^T    lane g + 32 half holds row g of H and takes every second non-zero of row h; the halves are added with one shuffle
-// LDS: W_c [J1][J1], fp [RECIPE_MAXTR * 7], col [nnz] (ints), then per wave th [P + 1 -> 34], val [nnz], H [ng1][J1], G [ng1][ng1].
+// LDS: DrawLds, DRAW_PARAMS.
 template <bool TWO>
 __global__ __launch_bounds__(256) void draws_logp_params_kernel(int ntr, int nG, int J1, int jeffreys, RecipeTab rt, const long long* __restrict__ offsets,
                                                                 const double* __restrict__ theta, const double* __restrict__ f,
@@ -3968,20 +4089,13 @@ __global__ __launch_bounds__(256) void draws_logp_params_kernel(int ntr, int nG,
     extern __shared__ double sm[];
     const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1;
+    const int ng1 = nG + 1;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
-    double* Ws = sm;
-    double* fp = Ws + J1 * J1;
-    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
-    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
-    for (int n = threadIdx.x; n < nnz; n += blockDim.x) col[n] = recipe_col(rt.ent[n], ntr);
-    recipe_fpow(f, c, ntr, threadIdx.x, fp);
-    __syncthreads();
-    double* th = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp / 2 + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1);
-    double* val = th + 34;
-    double* Hs = val + nnzp;
-    double* Gs = Hs + ng1 * J1;
+    const DrawLds L(DRAW_PARAMS, J1, nG, rt.nnz, 0, rt.P, jeffreys);
+    double* wave = draws_stage<DRAW_PARAMS>(L, sm, wv, c, ntr, J1, rt, f, W);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    const int* col = reinterpret_cast<int*>(sm + L.col);
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
         draws_recipe_forward<TWO>(rt, theta, d, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
         draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
@@ -4038,7 +4152,7 @@ struct RecipeGradTab {
 //                  symmetric up to rounding only: both halves of dG get their own factor)
 //   grad[p]        lane = share << lgP2 | p: share s of the 64 >> lgP2 takes every (64 >> lgP2)-th record of parameter p in table order,
 //                  the shares are added by an xor butterfly over the share bits (a fixed tree: the same bits however the grid is split)
-// A draw with det F2 <= 0 gets NaN in all P slots.  LDS: as draws_logp_params_kernel, and erow [nnz] (ints) after col.
+// A draw with det F2 <= 0 gets NaN in all P slots.  LDS: DrawLds, DRAW_GRAD.
 template <bool TWO>
 __global__ __launch_bounds__(256) void draws_logp_grad_params_kernel(int ntr, int nG, int J1, int jeffreys, RecipeTab rt, RecipeGradTab gt,
                                                                      const long long* __restrict__ offsets, const double* __restrict__ theta,
@@ -4048,24 +4162,13 @@ __global__ __launch_bounds__(256) void draws_logp_grad_params_kernel(int ntr, in
     extern __shared__ double sm[];
     const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1, P = rt.P;
+    const int ng1 = nG + 1, nnz = rt.nnz, P = rt.P;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
-    double* Ws = sm;
-    double* fp = Ws + J1 * J1;
-    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
-    int* erow = col + nnzp;
-    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
-    for (int n = threadIdx.x; n < nnz; n += blockDim.x) {
-        col[n] = recipe_col(rt.ent[n], ntr);
-        erow[n] = gt.erow[n];
-    }
-    recipe_fpow(f, c, ntr, threadIdx.x, fp);
-    __syncthreads();
-    double* th = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1);
-    double* val = th + 34;
-    double* Hs = val + nnzp;
-    double* Gs = Hs + ng1 * J1;
+    const DrawLds L(DRAW_GRAD, J1, nG, nnz, 0, P, jeffreys);
+    double* wave = draws_stage<DRAW_GRAD>(L, sm, wv, c, ntr, J1, rt, f, W, gt.erow);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    const int *col = reinterpret_cast<int*>(sm + L.col), *erow = reinterpret_cast<int*>(sm + L.erow);
     const int pmask = (1 << gt.lgP2) - 1, gp = lane & pmask, share = lane >> gt.lgP2, nshare = 64 >> gt.lgP2;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
@@ -4124,8 +4227,7 @@ struct RecipeHessTab {
 //                  derivative record of p (t2, against every record of q), i (t3) and (i, j) (t4) of its pair; the shares are added by
 //                  an xor butterfly over the share bits.  Assignment and tree depend on the recipe alone.
 // Entry (q, p) is a copy of (p, q).  A draw with det F2 <= 0 gets NaN in all P^2 slots, as in grad and ln P.  Every loop is bounded by a
-// table size.  LDS: as the gradient kernel, then drow | dcol [ndt] (ints: row and column of every derivative record) per workgroup and
-// K [nG][nG], dval [ndt], hv [J1], u [P][nG], w [P][nG] and, unless Jeffreys, G_p and M_p [P][nG][nG] per wave.
+// table size.  LDS: DrawLds, DRAW_HESS.
 template <bool TWO>
 __global__ __launch_bounds__(256) void draws_logp_hess_params_kernel(int ntr, int nG, int J1, int jeffreys, RecipeTab rt, RecipeGradTab gt, RecipeHessTab ht,
                                                                      const long long* __restrict__ offsets, const double* __restrict__ theta,
@@ -4135,39 +4237,16 @@ __global__ __launch_bounds__(256) void draws_logp_hess_params_kernel(int ntr, in
     extern __shared__ double sm[];
     const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1, P = rt.P, ndt = ht.ndt, ndtp = (ndt + 1) & ~1, nG2 = nG * nG;
+    const int ng1 = nG + 1, nnz = rt.nnz, P = rt.P, ndt = ht.ndt, nG2 = nG * nG;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
-    double* Ws = sm;
-    double* fp = Ws + J1 * J1;
-    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
-    int* erow = col + nnzp;
-    int* drow = erow + nnzp;
-    int* dcol = drow + ndtp;
-    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
-    for (int n = threadIdx.x; n < nnz; n += blockDim.x) {
-        col[n] = recipe_col(rt.ent[n], ntr);
-        erow[n] = gt.erow[n];
-    }
-    for (int t = threadIdx.x; t < ndt; t += blockDim.x) {
-        const int n = gt.dent[t];
-        drow[t] = gt.erow[n];
-        dcol[t] = recipe_col(rt.ent[n], ntr);
-    }
-    recipe_fpow(f, c, ntr, threadIdx.x, fp);
-    __syncthreads();
+    const DrawLds L(DRAW_HESS, J1, nG, nnz, ndt, P, jeffreys);
+    double* wave = draws_stage<DRAW_HESS>(L, sm, wv, c, ntr, J1, rt, f, W, gt.erow, gt.dent, ndt);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    double *Ks = wave + L.K, *dval = wave + L.dval, *hv = wave + L.hv, *us = wave + L.u, *ws = wave + L.w, *Gp = wave + L.Gp, *Mp = wave + L.Mp;
+    const int *col = reinterpret_cast<int*>(sm + L.col), *erow = reinterpret_cast<int*>(sm + L.erow);
+    const int *drow = reinterpret_cast<int*>(sm + L.drow), *dcol = reinterpret_cast<int*>(sm + L.dcol);
     const int gpn = jeffreys ? 0 : P * nG2;
-    double* th = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp + ndtp + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1 + nG2 + ndtp + J1 + 2 * P * nG + 2 * gpn);
-    double* val = th + 34;
-    double* Hs = val + nnzp;
-    double* Gs = Hs + ng1 * J1;
-    double* Ks = Gs + ng1 * ng1;
-    double* dval = Ks + nG2;
-    double* hv = dval + ndtp;
-    double* us = hv + J1;
-    double* ws = us + P * nG;
-    double* Gp = ws + P * nG;
-    double* Mp = Gp + gpn;
     const int pmask = (1 << gt.lgP2) - 1, gp = lane & pmask, share = lane >> gt.lgP2, nshare = 64 >> gt.lgP2;
     const int qmask = (1 << ht.lgPP) - 1, hshare = lane >> ht.lgPP, nhshare = 64 >> ht.lgPP;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
@@ -4356,7 +4435,7 @@ __global__ __launch_bounds__(NT) void draws_gram_groups_kernel(int ndata, int J1
 //                  in table order: lanes over the 27 ntr slots, zero where the recipe has no entry, every coefficient written once (as
 //                  draws_recipe_rows_kernel); the 24 template coefficients to coef [N S][ntr][24], the NNLO ones to coefn [N S][ntr][3]
 // A failed draw (det F2 <= 0 of draws_solve, or a pivot <= 0) gets NaN in all S samples, their chi2 and its coefficient rows; its record is
-// what draws_solve wrote.  LDS: as draws_logp_grad_params_kernel (erow after col), and per wave bs [ADJ_KB][nG] after G.
+// what draws_solve wrote.  LDS: DrawLds, DRAW_SAMPLE.
 // ------------------------------------------------------------------------------------------------
 template <bool TWO>
 __global__ __launch_bounds__(256) void draws_sample_params_kernel(int ntr, int nG, int J1, int jeffreys, int S, RecipeTab rt, const int* __restrict__ erow_tab,
@@ -4368,25 +4447,13 @@ __global__ __launch_bounds__(256) void draws_sample_params_kernel(int ntr, int n
     extern __shared__ double sm[];
     const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1;
+    const int ng1 = nG + 1, nnz = rt.nnz;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no draw for this share)
-    double* Ws = sm;
-    double* fp = Ws + J1 * J1;
-    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
-    int* erow = col + nnzp;
-    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
-    for (int n = threadIdx.x; n < nnz; n += blockDim.x) {
-        col[n] = recipe_col(rt.ent[n], ntr);
-        erow[n] = erow_tab[n];
-    }
-    recipe_fpow(f, c, ntr, threadIdx.x, fp);
-    __syncthreads();
-    double* th = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1 + ADJ_KB * nG);
-    double* val = th + 34;
-    double* Hs = val + nnzp;
-    double* Gs = Hs + ng1 * J1;
-    double* bs = Gs + ng1 * ng1;
+    const DrawLds L(DRAW_SAMPLE, J1, nG, nnz, 0, rt.P, jeffreys);
+    double* wave = draws_stage<DRAW_SAMPLE>(L, sm, wv, c, ntr, J1, rt, f, W, erow_tab);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G, *bs = wave + L.bs;
+    const int *col = reinterpret_cast<int*>(sm + L.col), *erow = reinterpret_cast<int*>(sm + L.erow);
     const bool own = lane < nG;
     const int nslot = ntr * (NROW + 3);
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
@@ -4511,11 +4578,8 @@ __global__ __launch_bounds__(256) void draws_sample_params_kernel(int ntr, int n
 //   end            theta [N][P] and nacc [N] are overwritten with the state after the launch's last step: all that the next launch needs
 // pri and the accept expression are evaluated with every operation rounded on its own (no contraction), in parameter order, so that
 // NumPy reproduces them bit for bit; sinv_p = 0 skips parameter p.  Every loop's trip count is fixed at launch.
-// LDS: as draws_logp_params_kernel, with pr [4][RECIPE_MAXP] (lower | upper | loc | sinv) after col and, per wave after G, the current
-// theta [RECIPE_MAXP], the trial theta [RECIPE_MAXP] and two records [2][MARG_OUT].
+// LDS: DrawLds, DRAW_CHAIN; pr [4][RECIPE_MAXP] = lower | upper | loc | sinv.
 // ------------------------------------------------------------------------------------------------
-constexpr int CHAIN_PRI = 4 * RECIPE_MAXP, CHAIN_WAVE = 2 * RECIPE_MAXP + 2 * MARG_OUT;
-
 __device__ __forceinline__ double chain_prior(int P, const double* t, const double* pr) {
 #pragma clang fp contract(off)
     double acc = 0.0;
@@ -4544,25 +4608,15 @@ __global__ __launch_bounds__(256) void draws_chain_params_kernel(int ntr, int nG
     extern __shared__ double sm[];
     const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ng1 = nG + 1, nnz = rt.nnz, nnzp = (nnz + 1) & ~1, P = rt.P;
+    const int ng1 = nG + 1, P = rt.P;
     const long long d0 = offsets[c], d1 = offsets[c + 1];
     if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no chain for this share)
-    double* Ws = sm;
-    double* fp = Ws + J1 * J1;
-    int* col = reinterpret_cast<int*>(fp + RECIPE_MAXTR * RECIPE_FPOW);
-    double* pr = fp + RECIPE_MAXTR * RECIPE_FPOW + nnzp / 2;
-    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) Ws[e] = W[(size_t)c * J1 * J1 + e];
-    for (int n = threadIdx.x; n < nnz; n += blockDim.x) col[n] = recipe_col(rt.ent[n], ntr);
-    for (int e = threadIdx.x; e < CHAIN_PRI; e += blockDim.x) pr[e] = prior[e];
-    recipe_fpow(f, c, ntr, threadIdx.x, fp);
-    __syncthreads();
-    double* th = pr + CHAIN_PRI + wv * (34 + nnzp + ng1 * J1 + ng1 * ng1 + CHAIN_WAVE);
-    double* val = th + 34;
-    double* Hs = val + nnzp;
-    double* Gs = Hs + ng1 * J1;
-    double* tc = Gs + ng1 * ng1;
-    double* tp = tc + RECIPE_MAXP;
-    double* rs = tp + RECIPE_MAXP;
+    const DrawLds L(DRAW_CHAIN, J1, nG, rt.nnz, 0, P, jeffreys);
+    double* wave = draws_stage<DRAW_CHAIN>(L, sm, wv, c, ntr, J1, rt, f, W, nullptr, nullptr, 0, prior);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    double *tc = wave + L.tc, *tp = wave + L.tp, *rs = wave + L.rs;
+    const int* col = reinterpret_cast<int*>(sm + L.col);
+    const double* pr = sm + L.pr;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
         long long na = nacc[d];

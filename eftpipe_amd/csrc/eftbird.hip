@@ -144,7 +144,7 @@ struct eftb_engine {
     size_t drw_A_cap = 0, drw_U_cap = 0, drw_W_cap = 0, drw_in_cap = 0, drw_inn_cap = 0, drw_out_cap = 0, drw_off_cap = 0;
     long long* drw_off = nullptr;
     std::vector<double> drw_host;   // eftb_draws_logp: D2H landing block [N][MARG_OUT]
-    bool drw_lds = false;           // the draws_logp*_kernel instantiations opted in to the large dynamic LDS
+    bool drw_lds = false;           // every draw kernel instantiation has opted in to the large dynamic LDS (draws_lds_optin)
     // draw recipes (eftb_set_draw_recipe): [0] of eftb_draws_logp_params, [1] of eftb_draws_reduce_params.  coef [nterms] and the int table
     // rowstart | ent | tstart | pack | slot (RecipeTab) live on the device; set = false: none (never set, withdrawn, or dropped)
     struct Recipe {
@@ -183,7 +183,6 @@ struct eftb_engine {
     size_t smp_z_cap = 0, smp_b_cap = 0, smp_chi2_cap = 0, smp_coef_cap = 0, smp_coefn_cap = 0, smp_plk_cap = 0, smp_off_cap = 0;
     long long* smp_off = nullptr;
     std::vector<long long> smp_off_host;
-    bool smp_lds = false;           // the draws_sample_params_kernel instantiations opted in to the large dynamic LDS
     // eftb_draws_chain_params: one launch's slice of step [N][Tc][P] and lnu [N][Tc], the prior table [4][RECIPE_MAXP], the accept counts
     // [N], and the launch's stored states [N][kstride][P] and records [N][kstride][MARG_OUT] with their D2H landing blocks; grown on demand
     double *chn_step = nullptr, *chn_lnu = nullptr, *chn_pri = nullptr, *chn_chain = nullptr, *chn_rec = nullptr;
@@ -526,6 +525,13 @@ template <typename... P, typename... A>
 static void launch_nh(void (*fixed)(P...), void (*any)(P..., int), int nh, dim3 grid, dim3 block, hipStream_t st, A... args) {
     if (nh == NHALF) hipLaunchKernelGGL(fixed, grid, block, 0, st, args...);
     else hipLaunchKernelGGL(any, grid, block, 0, st, args..., nh);
+}
+
+// a draw kernel's pair of instantiations: TWO where a walker has more than 64 columns (J1 of them, the data row included)
+template <typename... P, typename... A>
+static void launch_two(void (*one)(P...), void (*two)(P...), int J1, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    if (J1 > 64) hipLaunchKernelGGL(two, grid, block, lds, st, args...);
+    else hipLaunchKernelGGL(one, grid, block, lds, st, args...);
 }
 
 // anti-diagonal sums of every loop matrix for the batch (shared by the k-space and the xi-space pieces), then the
@@ -2382,16 +2388,28 @@ int eftb_eval_logp_batch(eftb_engine* e, int B, const double* Pin, const double*
 }
 
 // ------------------------------------------------------------------------------------------------ parameter draws (fast / slow split)
-// device buffer of at least n elements: grows, never shrinks (freed by eftb_destroy); separate from every buffer of the runs
-static int grow_dev(void* pp, size_t* cap, size_t n, size_t elem = sizeof(double)) {
+// device buffer of at least n elements: grows, never shrinks (freed by eftb_destroy); separate from every buffer of the runs.  With who, a
+// failed allocation is that call's refusal and names what, of which shape, asked for it; without, it fails as every HIP call does
+static int grow_dev(void* pp, size_t* cap, size_t n, size_t elem = sizeof(double), const char* who = nullptr, const char* what = nullptr,
+                    const char* shape = nullptr) {
     void** p = static_cast<void**>(pp);
     if (n <= *cap) return 0;
     if (*p) HIPCHK(hipFree(*p));
     *p = nullptr;
     *cap = 0;
-    HIPCHK(hipMalloc(p, n * elem));
+    if (!who) HIPCHK(hipMalloc(p, n * elem));
+    else if (hipError_t me = hipMalloc(p, n * elem); me != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail("%s: no device memory for %s of %s (%zu bytes): %s", who, what, shape, n * elem, hipGetErrorString(me));
+    }
     *cap = n;
     return 0;
+}
+
+static int launched(const char* who) {
+    const hipError_t le = hipGetLastError();
+    return le == hipSuccess ? 0 : fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
 }
 
 // offsets (walker c owns draws [offsets[c], offsets[c + 1])) and the state of the template block; *maxcnt: the most draws one walker owns.
@@ -2441,28 +2459,27 @@ static int draws_gram(eftb_engine* e, const char* who, int C, int J1) {
         launch_times_invcov(e, st, e->drw_A, C * J1, e->drw_U);  // U = A C^-1 for all walkers, exactly as the LOGP stage multiplies V
         const int gy = std::min(1024, (J1 * J1 + 63) / 64);
         hipLaunchKernelGGL(draws_gram_kernel, dim3(C, gy), dim3(256), 0, st, nd, J1, e->drw_A, e->drw_U, e->drw_W);
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+        if (int rc = launched(who)) return rc;
         e->gram_gen = e->draw_gen;
         e->gram_C = C;
     }
     return 0;
 }
 
+// a [MARG_OUT] record of a logp draw kernel -> slot `to` of logp, fullchi2 and best [..][nG], where the caller asks for them
+static void draws_unpack(const double* o, int nG, size_t to, double* logp, double* fullchi2, double* best) {
+    if (logp) logp[to] = o[0];
+    if (fullchi2) fullchi2[to] = o[1];
+    if (best) std::copy_n(o + 2, nG, best + to * nG);
+}
+
 // the [N][MARG_OUT] records of a logp draw kernel -> logp [N], fullchi2 [N], best [N][nG] (synchronises the stream)
 static int draws_records(eftb_engine* e, long long N, double* logp, double* fullchi2, double* best) {
-    const int nG = e->like_nG;
     hipStream_t st = e->stream;
     e->drw_host.resize((size_t)N * MARG_OUT);
     HIPCHK(hipMemcpyAsync(e->drw_host.data(), e->drw_out, (size_t)N * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (long long d = 0; d < N; ++d) {
-        const double* o = e->drw_host.data() + (size_t)d * MARG_OUT;
-        logp[d] = o[0];
-        if (fullchi2) fullchi2[d] = o[1];
-        if (best)
-            for (int i = 0; i < nG; ++i) best[(size_t)d * nG + i] = o[2 + i];
-    }
+    for (long long d = 0; d < N; ++d) draws_unpack(e->drw_host.data() + (size_t)d * MARG_OUT, e->like_nG, (size_t)d, logp, fullchi2, best);
     return 0;
 }
 
@@ -2477,37 +2494,35 @@ static int draws_logp_check(eftb_engine* e, const char* who, int C, long long N,
     return 0;
 }
 
-// workgroup of a logp draw kernel: J1 columns of W_c, nw waves (as many as the LDS holds beside W_c), lds bytes.  The kernel keeps
-// W_c [J1][J1] and extra_w bytes per workgroup, H [ng1][J1], G [ng1][ng1] and extra_wave bytes per wave.
+// workgroup of a logp draw kernel of one kind (with the recipe rcp, unless rows): J1 columns of W_c, its LDS layout, nw waves (as many as the
+// LDS holds beside W_c; 0: not even one, which the caller words) and the launch's lds bytes
 struct DrawShape {
     int J1, nw;
+    DrawLds L;
     size_t lds;
 };
-static int draws_logp_shape(eftb_engine* e, const char* who, size_t extra_w, size_t extra_wave, DrawShape* sh) {
-    const int ng1 = e->like_nG + 1, J1 = (e->c.with_nnlo ? NROW + 3 : NROW) * e->ntr + 1;
+static int draws_logp_shape(eftb_engine* e, const char* who, DrawKind kind, const eftb_engine::Recipe* rcp, DrawShape* sh) {
+    const int J1 = (e->c.with_nnlo ? NROW + 3 : NROW) * e->ntr + 1;
     if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
-    const size_t lds_w = (size_t)J1 * J1 * sizeof(double) + extra_w, lds_wave = ((size_t)ng1 * J1 + (size_t)ng1 * ng1) * sizeof(double) + extra_wave;
-    int nw = 4;
-    while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
-    // Reachable from the sample call alone (which words it anew): J + 1 <= 121 (five tracers; with NNLO four, 109), nG <= 24 and at most
-    // 1024 recipe entries leave the rows, params, gradient and chain calls at most 146328, 159336, 163432 and 161288 of the 163840 bytes at
-    // one wave, so this message is never seen.
-    if (lds_w + nw * lds_wave > 160 * 1024) return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1);
-    *sh = DrawShape{J1, nw, lds_w + nw * lds_wave};
+    const DrawLds L(kind, J1, e->like_nG, rcp ? rcp->nnz : 0, rcp ? rcp->ndt : 0, rcp ? rcp->P : 0, e->jeffreys);
+    const int nw = L.fit(160 * 1024);
+    *sh = DrawShape{J1, nw, L, L.bytes(nw)};
     return 0;
 }
 
-static std::array<const void*, 2> draws_chain_kernels();  // (defined behind the last kernel instantiation of the draw calls)
+// Reachable from the sample call alone (which words it anew): J + 1 <= 121 (five tracers; with NNLO four, 109), nG <= 24 and at most
+// 1024 recipe entries leave the rows, params, gradient and chain calls at most 146328, 159336, 163432 and 161288 of the 163840 bytes at
+// one wave, so this message is never seen.
+static int draws_no_fit(const char* who, int J1) { return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1); }
 
-// the large dynamic LDS for every logp draw kernel and the chain kernels, once per engine
+// the large dynamic LDS for every logp draw kernel, once per engine
 static int draws_lds_optin(eftb_engine* e) {
     if (e->drw_lds) return 0;
-    for (const void* k : draws_chain_kernels()) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    for (const void* k : {reinterpret_cast<const void*>(&draws_logp_kernel<false>), reinterpret_cast<const void*>(&draws_logp_kernel<true>),
-                          reinterpret_cast<const void*>(&draws_logp_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_params_kernel<true>),
-                          reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_grad_params_kernel<true>),
-                          reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<false>), reinterpret_cast<const void*>(&draws_logp_hess_params_kernel<true>)})
+#define DRAW_PAIR(k) reinterpret_cast<const void*>(&k<false>), reinterpret_cast<const void*>(&k<true>)
+    for (const void* k : {DRAW_PAIR(draws_logp_kernel), DRAW_PAIR(draws_logp_params_kernel), DRAW_PAIR(draws_logp_grad_params_kernel),
+                          DRAW_PAIR(draws_logp_hess_params_kernel), DRAW_PAIR(draws_sample_params_kernel), DRAW_PAIR(draws_chain_params_kernel)})
         HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#undef DRAW_PAIR
     e->drw_lds = true;
     return 0;
 }
@@ -2534,7 +2549,8 @@ int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, 
     if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt)) return rc;
     if (rows_nnlo && !e->c.with_nnlo) return fail("%s: rows_nnlo needs an engine built with with_nnlo", who);
     DrawShape sh;
-    if (int rc = draws_logp_shape(e, who, 0, 0, &sh)) return rc;
+    if (int rc = draws_logp_shape(e, who, DRAW_ROWS, nullptr, &sh)) return rc;
+    if (!sh.nw) return draws_no_fit(who, sh.J1);
     if (N == 0) return 0;
     if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets)) return rc;
     const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1, J1 = sh.J1;
@@ -2546,50 +2562,10 @@ int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, 
     HIPCHK(hipMemcpyAsync(e->drw_in, rows, rn * sizeof(double), hipMemcpyHostToDevice, st));
     if (rows_nnlo) HIPCHK(hipMemcpyAsync(e->drw_inn, rows_nnlo, rnn * sizeof(double), hipMemcpyHostToDevice, st));
     const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
-    if (J1 > 64)
-        hipLaunchKernelGGL(draws_logp_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
-                           e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
-    else
-        hipLaunchKernelGGL(draws_logp_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in, rows_nnlo ? e->drw_inn : nullptr,
-                           e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    launch_two(draws_logp_kernel<false>, draws_logp_kernel<true>, sh.J1, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, e->drw_off, e->drw_in,
+               rows_nnlo ? e->drw_inn : nullptr, e->drw_W, e->like_mu, e->like_sinv, e->drw_out);
+    if (int rc = launched(who)) return rc;
     return draws_records(e, N, logp, fullchi2, best);
-}
-
-int eftb_draws_reduce(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* bias, const double* bias_nnlo, double* plk) {
-    static const char* who = "eftb_draws_reduce";
-    if (e) sub_drain(e);
-    if (!e || !offsets || (N > 0 && (!bias || !plk))) return fail("%s: null argument", who);
-    long long maxcnt = 0;
-    if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
-    const eftb_config& c = e->c;
-    if (bias_nnlo && !c.with_nnlo) return fail("%s: bias_nnlo needs an engine built with with_nnlo", who);
-    if (N == 0) return 0;
-    const int ntr = e->ntr, nl = e->cur_nl, nx = e->cur_nx, xtiles = (nx + 63) / 64;
-    HIPCHK(hipSetDevice(c.device));
-    hipStream_t st = e->stream;
-    join_back(e);
-    const size_t bn = (size_t)N * ntr * NROW, bnn = (size_t)N * ntr * 3, pn = (size_t)N * ntr * nl * nx;
-    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
-    if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, bn)) return rc;
-    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, pn)) return rc;
-    if (c.with_nnlo)
-        if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, bnn)) return rc;
-    HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->drw_in, bias, bn * sizeof(double), hipMemcpyHostToDevice, st));
-    if (c.with_nnlo) {  // (no bias_nnlo: zeros, as the REDUCE stage of eftb_eval_batch)
-        if (bias_nnlo) HIPCHK(hipMemcpyAsync(e->drw_inn, bias_nnlo, bnn * sizeof(double), hipMemcpyHostToDevice, st));
-        else HIPCHK(hipMemsetAsync(e->drw_inn, 0, bnn * sizeof(double), st));
-    }
-    const int shares = draw_shares(maxcnt, 4, (long long)C * ntr * nl * xtiles);
-    hipLaunchKernelGGL(draws_reduce_kernel, dim3(xtiles * shares, ntr * nl, C), dim3(256), 0, st, nx, nl, ntr, reduce_msplit(c), xtiles, e->drw_off, e->drw_in,
-                       e->buf[EFTB_B_TEMPL], c.with_nnlo ? e->drw_inn : nullptr, c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, e->drw_out);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
-    HIPCHK(hipMemcpyAsync(plk, e->drw_out, pn * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
 }
 
 void* eftb_host_alloc(size_t bytes) {
@@ -3713,7 +3689,47 @@ struct DrawGroups {
     const int32_t *walker, *dataset;
 };
 
-static int draws_gram_groups(eftb_engine* e, const char* who, int G, int J1, const DrawGroups& gr);  // (defined behind the last kernel instantiation of the params calls)
+// Wg [G][J1][J1] of a groups call, after draws_gram: kept while the template block, the likelihood, the tracers (draw_gen), the data sets
+// (dset_gen) and the group table are those it was built from
+static int draws_gram_groups(eftb_engine* e, const char* who, int G, int J1, const DrawGroups& gr) {
+    if (e->grp_draw_gen == e->draw_gen && e->grp_dset_gen == e->dset_gen && e->grp_tab.size() == 2 * (size_t)G &&
+        std::equal(gr.walker, gr.walker + G, e->grp_tab.begin()) && std::equal(gr.dataset, gr.dataset + G, e->grp_tab.begin() + G))
+        return 0;
+    e->grp_draw_gen = 0;
+    char shape[64];
+    snprintf(shape, sizeof shape, "G = %d groups with J + 1 = %d columns", G, J1);
+    if (int rc = grow_dev(&e->drw_Wg, &e->drw_Wg_cap, (size_t)G * J1 * J1, sizeof(double), who, "the Gram matrices", shape)) return rc;
+    if (int rc = grow_dev(&e->drw_gtab, &e->drw_gtab_cap, 2 * (size_t)G, sizeof(int))) return rc;
+    e->grp_tab.assign(gr.walker, gr.walker + G);
+    e->grp_tab.insert(e->grp_tab.end(), gr.dataset, gr.dataset + G);
+    HIPCHK(hipMemcpyAsync(e->drw_gtab, e->grp_tab.data(), 2 * (size_t)G * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(draws_gram_groups_kernel<256>, dim3(G), dim3(256), 0, e->stream, e->like_ndata, J1, e->drw_gtab, e->drw_gtab + G, e->drw_A, e->drw_U,
+                       e->drw_W, e->dset_D, e->dset_Ud, e->drw_Wg);
+    if (int rc = launched(who)) return rc;
+    e->grp_draw_gen = e->draw_gen;
+    e->grp_dset_gen = e->dset_gen;
+    return 0;
+}
+
+// What the params calls do between "the shape is known" and their launch: draws_logp_begin, Wg of a groups call (the kernels read it where they
+// read W_c), theta and f on the device, the launch geometry and the recipe's table
+struct DrawRun {
+    const double *W, *theta, *f;
+    dim3 grid, block;
+    RecipeTab rt;
+};
+static int draws_params_begin(eftb_engine* e, const char* who, int C, long long N, long long maxcnt, const DrawShape& sh, const int64_t* offsets,
+                              const double* theta, const double* f, const DrawGroups* gr, DrawRun* run) {
+    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets, gr ? gr->nwalk : -1)) return rc;
+    if (gr)
+        if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
+    run->W = gr ? e->drw_Wg : e->drw_W;
+    if (int rc = draws_params_upload(e, e->recipe[0].P, C, N, theta, f, &run->theta, &run->f)) return rc;
+    run->grid = dim3(C, draw_shares(maxcnt, sh.nw, C));
+    run->block = dim3(64 * sh.nw);
+    run->rt = recipe_tab(e->recipe[0]);
+    return 0;
+}
 
 // eftb_draws_logp_params (grad == nullptr: the forward kernel and its LDS layout), eftb_draws_logp_grad_params and eftb_draws_logp_hess_params
 // (hess != nullptr, with grad: the Hessian kernel and its LDS layout).  gr (eftb_draws_logp_params_datasets): C counts the groups, offsets and
@@ -3725,75 +3741,48 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
     const int ntr = e->ntr, nG = e->like_nG;
     if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta, f)) return rc;
     const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int P = rcp.P, nnzp = (rcp.nnz + 1) & ~1;
-    DrawShape sh;  // beside W_c: fp, col [nnzp] and, with the gradient, erow [nnzp]; per wave: th [34] and val [nnzp]
-    if (int rc = draws_logp_shape(e, who, RECIPE_MAXTR * RECIPE_FPOW * sizeof(double) + (grad ? 2 : 1) * nnzp * sizeof(int), (34 + (size_t)nnzp) * sizeof(double), &sh))
-        return rc;
-    const int ndtp = (rcp.ndt + 1) & ~1;
-    if (hess) {  // beside the gradient's: drow and dcol [ndtp] per workgroup; K, dval, hv, u, w and, unless Jeffreys, G_p and M_p per wave
-        const size_t n = (size_t)nG, J1 = (size_t)sh.J1, ng1 = n + 1;
-        const size_t lds_w = (J1 * J1 + RECIPE_MAXTR * RECIPE_FPOW + nnzp + ndtp) * sizeof(double);
-        const size_t lds_wave = (34 + nnzp + ng1 * J1 + ng1 * ng1 + n * n + ndtp + J1 + 2 * P * n + (e->jeffreys ? 0 : 2 * P * n * n)) * sizeof(double);
-        int nw = 4;
-        while (nw > 1 && lds_w + nw * lds_wave > 160 * 1024) nw /= 2;
-        if (lds_w + nw * lds_wave > 160 * 1024)
-            return fail("%s: the Hessian of P = %d parameters with nG = %d and J + 1 = %d columns does not fit the LDS (%zu bytes per workgroup and %zu per wave)",
-                        who, P, nG, sh.J1, lds_w, lds_wave);
-        sh.nw = nw;
-        sh.lds = lds_w + nw * lds_wave;
+    const int P = rcp.P;
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, hess ? DRAW_HESS : grad ? DRAW_GRAD : DRAW_PARAMS, &rcp, &sh)) return rc;
+    if (!sh.nw) {
+        if (!hess) return draws_no_fit(who, sh.J1);
+        return fail("%s: the Hessian of P = %d parameters with nG = %d and J + 1 = %d columns does not fit the LDS (%zu bytes per workgroup and %zu per wave)",
+                    who, P, nG, sh.J1, sh.L.bytes_wg(), sh.L.bytes_wave());
     }
     if (N == 0) return 0;
-    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets, gr ? gr->nwalk : -1)) return rc;
-    if (gr)
-        if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
-    const double* W = gr ? e->drw_Wg : e->drw_W;
+    DrawRun run;
+    if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta, f, gr, &run)) return rc;
     if (grad)
         if (int rc = grow_dev(&e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
     if (hess)
         if (int rc = grow_dev(&e->drw_hess, &e->drw_hess_cap, std::max<size_t>(1, (size_t)N * P * P))) return rc;
-    const double *dtheta = nullptr, *df = nullptr;
-    if (int rc = draws_params_upload(e, P, C, N, theta, f, &dtheta, &df)) return rc;
     hipStream_t st = e->stream;
-    const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
     const int J1 = sh.J1;
-    const RecipeTab rt = recipe_tab(rcp);
-    if (grad) {
-        RecipeGradTab gt{};
-        gt.dcoef = rcp.dcoef;
-        gt.pstart = rcp.dtab;
-        gt.dent = gt.pstart + P + 1;
-        gt.dpack = gt.dent + rcp.ndt;
-        gt.erow = gt.dpack + rcp.ndt;
-        while ((1 << gt.lgP2) < P) ++gt.lgP2;
-        if (hess) {
-            RecipeHessTab ht{};
-            ht.npair = P * (P + 1) / 2;
-            ht.ndt = rcp.ndt;
-            ht.hcoef = rcp.hcoef;
-            ht.hstart = rcp.htab;
-            ht.hent = ht.hstart + ht.npair + 1;
-            ht.hpack = ht.hent + rcp.nh;
-            while ((1 << ht.lgPP) < std::min(ht.npair, 64)) ++ht.lgPP;
-            if (J1 > 64)
-                hipLaunchKernelGGL(draws_logp_hess_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, W,
-                                   e->like_mu, e->like_sinv, e->drw_out, e->drw_grad, e->drw_hess);
-            else
-                hipLaunchKernelGGL(draws_logp_hess_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, ht, e->drw_off, dtheta, df, W,
-                                   e->like_mu, e->like_sinv, e->drw_out, e->drw_grad, e->drw_hess);
-        } else if (J1 > 64)
-            hipLaunchKernelGGL(draws_logp_grad_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, W,
-                               e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
-        else
-            hipLaunchKernelGGL(draws_logp_grad_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, gt, e->drw_off, dtheta, df, W,
-                               e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
-    } else if (J1 > 64)
-        hipLaunchKernelGGL(draws_logp_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, W, e->like_mu,
-                           e->like_sinv, e->drw_out);
+    RecipeGradTab gt{};
+    gt.dcoef = rcp.dcoef;
+    gt.pstart = rcp.dtab;
+    gt.dent = gt.pstart + P + 1;
+    gt.dpack = gt.dent + rcp.ndt;
+    gt.erow = gt.dpack + rcp.ndt;
+    while ((1 << gt.lgP2) < P) ++gt.lgP2;
+    if (hess) {
+        RecipeHessTab ht{};
+        ht.npair = P * (P + 1) / 2;
+        ht.ndt = rcp.ndt;
+        ht.hcoef = rcp.hcoef;
+        ht.hstart = rcp.htab;
+        ht.hent = ht.hstart + ht.npair + 1;
+        ht.hpack = ht.hent + rcp.nh;
+        while ((1 << ht.lgPP) < std::min(ht.npair, 64)) ++ht.lgPP;
+        launch_two(draws_logp_hess_params_kernel<false>, draws_logp_hess_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, J1, e->jeffreys, run.rt, gt,
+                   ht, e->drw_off, run.theta, run.f, run.W, e->like_mu, e->like_sinv, e->drw_out, e->drw_grad, e->drw_hess);
+    } else if (grad)
+        launch_two(draws_logp_grad_params_kernel<false>, draws_logp_grad_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, J1, e->jeffreys, run.rt, gt,
+                   e->drw_off, run.theta, run.f, run.W, e->like_mu, e->like_sinv, e->drw_out, e->drw_grad);
     else
-        hipLaunchKernelGGL(draws_logp_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, rt, e->drw_off, dtheta, df, W, e->like_mu,
-                           e->like_sinv, e->drw_out);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+        launch_two(draws_logp_params_kernel<false>, draws_logp_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, J1, e->jeffreys, run.rt, e->drw_off,
+                   run.theta, run.f, run.W, e->like_mu, e->like_sinv, e->drw_out);
+    if (int rc = launched(who)) return rc;
     if (grad && P) HIPCHK(hipMemcpyAsync(grad, e->drw_grad, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
     if (hess && P) HIPCHK(hipMemcpyAsync(hess, e->drw_hess, (size_t)N * P * P * sizeof(double), hipMemcpyDeviceToHost, st));
     return draws_records(e, N, logp, fullchi2, best);
@@ -3807,40 +3796,69 @@ int eftb_draws_logp_params(eftb_engine* e, int C, long long N, const int64_t* of
     return draws_logp_params_impl(e, who, C, N, offsets, theta, f, logp, nullptr, fullchi2, best);
 }
 
-int eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* plk) {
-    static const char* who = "eftb_draws_reduce_params";
-    if (e) sub_drain(e);
-    if (!e || !offsets || !f || (N > 0 && (!theta || !plk))) return fail("%s: null argument", who);
+// draws_reduce_kernel on the coefficient rows bias [n][ntr][24] (with NNLO, biasn [n][ntr][3]) of the draws that off [C + 1] deals to the walkers
+static int launch_draws_reduce(eftb_engine* e, const char* who, int C, long long maxcnt, const long long* off, const double* bias, const double* biasn,
+                               double* plk) {
+    const eftb_config& c = e->c;
+    const int ntr = e->ntr, nl = e->cur_nl, nx = e->cur_nx, xtiles = (nx + 63) / 64, shares = draw_shares(maxcnt, 4, (long long)C * ntr * nl * xtiles);
+    hipLaunchKernelGGL(draws_reduce_kernel, dim3(xtiles * shares, ntr * nl, C), dim3(256), 0, e->stream, nx, nl, ntr, reduce_msplit(c), xtiles, off, bias,
+                       e->buf[EFTB_B_TEMPL], c.with_nnlo ? biasn : nullptr, c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, plk);
+    return launched(who);
+}
+
+// eftb_draws_reduce (the caller's bias and bias_nnlo) and eftb_draws_reduce_params (f != nullptr: the rows of recipe 1 at theta and f)
+static int draws_reduce_impl(eftb_engine* e, const char* who, int C, long long N, const int64_t* offsets, const double* bias, const double* bias_nnlo,
+                             const double* theta, const double* f, double* plk) {
     long long maxcnt = 0;
     if (int rc = draws_check(e, who, C, N, offsets, &maxcnt)) return rc;
-    if (int rc = draws_params_check(e, who, 1, 1, C, N, theta, f)) return rc;
-    if (N == 0) return 0;
     const eftb_config& c = e->c;
-    const eftb_engine::Recipe& rcp = e->recipe[1];
-    const int ntr = e->ntr, nl = e->cur_nl, nx = e->cur_nx, xtiles = (nx + 63) / 64;
+    if (f) {
+        if (int rc = draws_params_check(e, who, 1, 1, C, N, theta, f)) return rc;
+    } else if (bias_nnlo && !c.with_nnlo) return fail("%s: bias_nnlo needs an engine built with with_nnlo", who);
+    if (N == 0) return 0;
+    const int ntr = e->ntr;
     HIPCHK(hipSetDevice(c.device));
     hipStream_t st = e->stream;
     join_back(e);
-    const size_t bn = (size_t)N * ntr * NROW, bnn = (size_t)N * ntr * 3, pn = (size_t)N * ntr * nl * nx;
+    const size_t bn = (size_t)N * ntr * NROW, bnn = (size_t)N * ntr * 3, pn = (size_t)N * ntr * e->cur_nl * e->cur_nx;
     if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
     if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, bn)) return rc;
     if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, pn)) return rc;
     if (c.with_nnlo)
         if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, bnn)) return rc;
     HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    const double *dtheta = nullptr, *df = nullptr;
-    if (int rc = draws_params_upload(e, rcp.P, C, N, theta, f, &dtheta, &df)) return rc;
-    const dim3 rgrid(C, draw_shares(maxcnt, 4, C));
-    if (c.with_nnlo) hipLaunchKernelGGL(draws_recipe_rows_kernel<true>, rgrid, dim3(256), 0, st, ntr, recipe_tab(rcp), e->drw_off, dtheta, df, e->drw_in, e->drw_inn);
-    else hipLaunchKernelGGL(draws_recipe_rows_kernel<false>, rgrid, dim3(256), 0, st, ntr, recipe_tab(rcp), e->drw_off, dtheta, df, e->drw_in, nullptr);
-    const int shares = draw_shares(maxcnt, 4, (long long)C * ntr * nl * xtiles);
-    hipLaunchKernelGGL(draws_reduce_kernel, dim3(xtiles * shares, ntr * nl, C), dim3(256), 0, st, nx, nl, ntr, reduce_msplit(c), xtiles, e->drw_off, e->drw_in,
-                       e->buf[EFTB_B_TEMPL], c.with_nnlo ? e->drw_inn : nullptr, c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, e->drw_out);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    if (f) {
+        const eftb_engine::Recipe& rcp = e->recipe[1];
+        const double *dtheta = nullptr, *df = nullptr;
+        if (int rc = draws_params_upload(e, rcp.P, C, N, theta, f, &dtheta, &df)) return rc;
+        const dim3 rgrid(C, draw_shares(maxcnt, 4, C));
+        if (c.with_nnlo) hipLaunchKernelGGL(draws_recipe_rows_kernel<true>, rgrid, dim3(256), 0, st, ntr, recipe_tab(rcp), e->drw_off, dtheta, df, e->drw_in, e->drw_inn);
+        else hipLaunchKernelGGL(draws_recipe_rows_kernel<false>, rgrid, dim3(256), 0, st, ntr, recipe_tab(rcp), e->drw_off, dtheta, df, e->drw_in, nullptr);
+    } else {
+        HIPCHK(hipMemcpyAsync(e->drw_in, bias, bn * sizeof(double), hipMemcpyHostToDevice, st));
+        if (c.with_nnlo) {  // (no bias_nnlo: zeros, as the REDUCE stage of eftb_eval_batch)
+            if (bias_nnlo) HIPCHK(hipMemcpyAsync(e->drw_inn, bias_nnlo, bnn * sizeof(double), hipMemcpyHostToDevice, st));
+            else HIPCHK(hipMemsetAsync(e->drw_inn, 0, bnn * sizeof(double), st));
+        }
+    }
+    if (int rc = launch_draws_reduce(e, who, C, maxcnt, e->drw_off, e->drw_in, e->drw_inn, e->drw_out)) return rc;
     HIPCHK(hipMemcpyAsync(plk, e->drw_out, pn * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return 0;
+}
+
+int eftb_draws_reduce(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* bias, const double* bias_nnlo, double* plk) {
+    static const char* who = "eftb_draws_reduce";
+    if (e) sub_drain(e);
+    if (!e || !offsets || (N > 0 && (!bias || !plk))) return fail("%s: null argument", who);
+    return draws_reduce_impl(e, who, C, N, offsets, bias, bias_nnlo, nullptr, nullptr, plk);
+}
+
+int eftb_draws_reduce_params(eftb_engine* e, int C, long long N, const int64_t* offsets, const double* theta, const double* f, double* plk) {
+    static const char* who = "eftb_draws_reduce_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta || !plk))) return fail("%s: null argument", who);
+    return draws_reduce_impl(e, who, C, N, offsets, nullptr, nullptr, theta, f, plk);
 }
 
 // ------------------------------------------------------------------------------------------------ d ln P / d theta of params draws
@@ -3862,42 +3880,6 @@ int eftb_draws_logp_hess_params(eftb_engine* e, int C, long long N, const int64_
     if (!grad) return fail("%s: grad == NULL (the Hessian call returns the gradient too)", who);
     if (!hess) return fail("%s: hess == NULL (eftb_draws_logp_grad_params is the call without the Hessian)", who);
     return draws_logp_params_impl(e, who, C, N, offsets, theta, f, logp, grad, fullchi2, best, hess);
-}
-
-// ------------------------------------------------------------------------------------------------ draws against many data vectors, one covariance
-// Wg [G][J1][J1] of a groups call, after draws_gram: kept while the template block, the likelihood, the tracers (draw_gen), the data sets
-// (dset_gen) and the group table are those it was built from.  The kernel is a template instantiated here, behind every other one, so that the
-// existing kernels keep their code and labels
-static int draws_gram_groups(eftb_engine* e, const char* who, int G, int J1, const DrawGroups& gr) {
-    if (e->grp_draw_gen == e->draw_gen && e->grp_dset_gen == e->dset_gen && e->grp_tab.size() == 2 * (size_t)G &&
-        std::equal(gr.walker, gr.walker + G, e->grp_tab.begin()) && std::equal(gr.dataset, gr.dataset + G, e->grp_tab.begin() + G))
-        return 0;
-    e->grp_draw_gen = 0;
-    const size_t need = (size_t)G * J1 * J1;
-    if (need > e->drw_Wg_cap) {
-        if (e->drw_Wg) HIPCHK(hipFree(e->drw_Wg));
-        e->drw_Wg = nullptr;
-        e->drw_Wg_cap = 0;
-        hipError_t me = hipMalloc(&e->drw_Wg, need * sizeof(double));
-        if (me != hipSuccess) {
-            (void)hipGetLastError();
-            e->drw_Wg = nullptr;
-            return fail("%s: no device memory for the Gram matrices of G = %d groups with J + 1 = %d columns (%zu bytes): %s", who, G, J1,
-                        need * sizeof(double), hipGetErrorString(me));
-        }
-        e->drw_Wg_cap = need;
-    }
-    if (int rc = grow_dev(&e->drw_gtab, &e->drw_gtab_cap, 2 * (size_t)G, sizeof(int))) return rc;
-    e->grp_tab.assign(gr.walker, gr.walker + G);
-    e->grp_tab.insert(e->grp_tab.end(), gr.dataset, gr.dataset + G);
-    HIPCHK(hipMemcpyAsync(e->drw_gtab, e->grp_tab.data(), 2 * (size_t)G * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(draws_gram_groups_kernel<256>, dim3(G), dim3(256), 0, e->stream, e->like_ndata, J1, e->drw_gtab, e->drw_gtab + G, e->drw_A, e->drw_U,
-                       e->drw_W, e->dset_D, e->dset_Ud, e->drw_Wg);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
-    e->grp_draw_gen = e->draw_gen;
-    e->grp_dset_gen = e->dset_gen;
-    return 0;
 }
 
 int eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data) {
@@ -3924,8 +3906,7 @@ int eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data) {
     hipStream_t st = e->stream;
     HIPCHK(hipMemcpyAsync(e->dset_D, data, (size_t)M * nd * sizeof(double), hipMemcpyHostToDevice, st));
     launch_times_invcov(e, st, e->dset_D, M, e->dset_Ud);  // Ud = D C^-1, as draws_gram multiplies A: a row of -D there is the exact negation of its row here
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    if (int rc = launched(who)) return rc;
     HIPCHK(hipStreamSynchronize(st));  // (the caller's array is free again)
     e->dset_M = M;
     return 0;
@@ -3968,28 +3949,9 @@ int eftb_draws_logp_params_datasets(eftb_engine* e, int C, int G, const int32_t*
 }
 
 // ------------------------------------------------------------------------------------------------ samples of the marginalised parameters
-// device buffer of at least n elements for eftb_draws_sample_params (as grow_dev; a failed allocation names the shape that asked for it)
-static int sample_grow(const char* who, void* pp, size_t* cap, size_t n, size_t elem, const char* what, long long N, int S, int nG) {
-    void** p = static_cast<void**>(pp);
-    if (n <= *cap) return 0;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    hipError_t me = hipMalloc(p, n * elem);
-    if (me != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return fail("%s: no device memory for %s of N = %lld draws x S = %d samples with nG = %d (%zu bytes): %s", who, what, N, S, nG, n * elem,
-                    hipGetErrorString(me));
-    }
-    *cap = n;
-    return 0;
-}
-
 // eftb_draws_sample_params and eftb_draws_sample_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group, no plk): the
 // checks, W_c, uploads and records of draws_logp_params_impl around draws_sample_params_kernel, then draws_reduce_kernel on the [N S]
-// coefficient rows where plk is asked for.  The kernel is a template instantiated here, behind every other one, so that the existing kernels
-// keep their code and labels
+// coefficient rows where plk is asked for
 static int draws_sample_params_impl(eftb_engine* e, const char* who, int C, long long N, int S, const int64_t* offsets, const double* theta, const double* f,
                                     const double* z, double* logp, double* fullchi2, double* best, double* bsamp, double* chi2samp, double* coef,
                                     double* coefn, double* plk, const DrawGroups* gr = nullptr) {
@@ -4004,68 +3966,46 @@ static int draws_sample_params_impl(eftb_engine* e, const char* who, int C, long
         if (!std::isfinite(z[q])) return fail("%s: z[%lld][%d][%d] is not finite", who, q / ((long long)S * nG), (int)(q / nG % S), (int)(q % nG));
     // (plk: draws_logp_check has held the block to the likelihood's [nl][24][nx] and to its walkers x tracers entries, all eftb_draws_reduce asks)
     const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int P = rcp.P, nnzp = (rcp.nnz + 1) & ~1;
-    DrawShape sh;  // beside W_c: fp, col and erow [nnzp]; per wave: th [34], val [nnzp] and b of ADJ_KB samples
-    if (int rc = draws_logp_shape(e, who, RECIPE_MAXTR * RECIPE_FPOW * sizeof(double) + 2 * nnzp * sizeof(int), (34 + (size_t)nnzp + (size_t)ADJ_KB * nG) * sizeof(double),
-                                  &sh)) {
-        const int J1w = (c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
-        if (J1w > DRAW_MAXJ1) return rc;
-        // Reachable at one shape only: five tracers (J + 1 = 121), nG = 24 and a recipe of at least 1001 entries (147816 + 16 nnzp bytes
-        // at one wave, nnzp the entry count rounded up to even, against 163840); tests/test_gpu_draw_synthetic.py goes there.
-        return fail("%s: the samples of nG = %d parameters with J + 1 = %d columns do not fit the LDS (S = %d, %d samples at a time)", who, nG, J1w, S, ADJ_KB);
-    }
+    const int P = rcp.P;
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, DRAW_SAMPLE, &rcp, &sh)) return rc;
+    // Reachable at one shape only: five tracers (J + 1 = 121), nG = 24 and a recipe of at least 1001 entries (147816 + 16 nnzp bytes
+    // at one wave, nnzp the entry count rounded up to even, against 163840); tests/test_gpu_draw_synthetic.py goes there.
+    if (!sh.nw) return fail("%s: the samples of nG = %d parameters with J + 1 = %d columns do not fit the LDS (S = %d, %d samples at a time)", who, nG, sh.J1, S, ADJ_KB);
     if (N == 0) return 0;
     const bool want_coef = coef || coefn || plk, nn = c.with_nnlo;
     const int nl = e->cur_nl, nx = e->cur_nx;
     const size_t ns = (size_t)N * S;
-    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets, gr ? gr->nwalk : -1)) return rc;
-    if (!e->smp_lds) {
-        for (const void* k : {reinterpret_cast<const void*>(&draws_sample_params_kernel<false>), reinterpret_cast<const void*>(&draws_sample_params_kernel<true>)})
-            HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        e->smp_lds = true;
-    }
-    if (gr)
-        if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
-    const double* W = gr ? e->drw_Wg : e->drw_W;
-    if (int rc = sample_grow(who, &e->smp_z, &e->smp_z_cap, std::max<size_t>(1, ns * nG), sizeof(double), "z", N, S, nG)) return rc;
-    if (int rc = sample_grow(who, &e->smp_b, &e->smp_b_cap, std::max<size_t>(1, ns * nG), sizeof(double), "the samples", N, S, nG)) return rc;
-    if (int rc = sample_grow(who, &e->smp_chi2, &e->smp_chi2_cap, ns, sizeof(double), "chi2 of the samples", N, S, nG)) return rc;
+    DrawRun run;
+    if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta, f, gr, &run)) return rc;
+    char shape[96];
+    snprintf(shape, sizeof shape, "N = %lld draws x S = %d samples with nG = %d", N, S, nG);
+    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(pp, cap, n, elem, who, what, shape); };
+    if (int rc = grow(&e->smp_z, &e->smp_z_cap, std::max<size_t>(1, ns * nG), "z")) return rc;
+    if (int rc = grow(&e->smp_b, &e->smp_b_cap, std::max<size_t>(1, ns * nG), "the samples")) return rc;
+    if (int rc = grow(&e->smp_chi2, &e->smp_chi2_cap, ns, "chi2 of the samples")) return rc;
     if (want_coef) {
-        if (int rc = sample_grow(who, &e->smp_coef, &e->smp_coef_cap, ns * ntr * NROW, sizeof(double), "the coefficient rows", N, S, nG)) return rc;
+        if (int rc = grow(&e->smp_coef, &e->smp_coef_cap, ns * ntr * NROW, "the coefficient rows")) return rc;
         if (nn)
-            if (int rc = sample_grow(who, &e->smp_coefn, &e->smp_coefn_cap, ns * ntr * 3, sizeof(double), "the NNLO coefficient rows", N, S, nG)) return rc;
+            if (int rc = grow(&e->smp_coefn, &e->smp_coefn_cap, ns * ntr * 3, "the NNLO coefficient rows")) return rc;
     }
     if (plk) {
-        if (int rc = sample_grow(who, &e->smp_plk, &e->smp_plk_cap, ns * ntr * nl * nx, sizeof(double), "P_l of the samples", N, S, nG)) return rc;
-        if (int rc = sample_grow(who, &e->smp_off, &e->smp_off_cap, (size_t)C + 1, sizeof(long long), "the offsets", N, S, nG)) return rc;
+        if (int rc = grow(&e->smp_plk, &e->smp_plk_cap, ns * ntr * nl * nx, "P_l of the samples")) return rc;
+        if (int rc = grow(&e->smp_off, &e->smp_off_cap, (size_t)C + 1, "the offsets", sizeof(long long))) return rc;
     }
-    const double *dtheta = nullptr, *df = nullptr;
-    if (int rc = draws_params_upload(e, P, C, N, theta, f, &dtheta, &df)) return rc;
     hipStream_t st = e->stream;
     if (nG) HIPCHK(hipMemcpyAsync(e->smp_z, z, ns * nG * sizeof(double), hipMemcpyHostToDevice, st));
-    const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
-    const int J1 = sh.J1;
-    const RecipeTab rt = recipe_tab(rcp);
     const int* erow = rcp.dtab + P + 1 + 2 * rcp.ndt;  // (RecipeGradTab: pstart | dent | dpack | erow)
     double* dcoef = want_coef ? e->smp_coef : nullptr;
     double* dcoefn = want_coef && nn ? e->smp_coefn : nullptr;
-    if (J1 > 64)
-        hipLaunchKernelGGL(draws_sample_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, S, rt, erow, e->drw_off, dtheta, df, W, e->like_mu,
-                           e->like_sinv, e->smp_z, e->drw_out, e->smp_b, e->smp_chi2, dcoef, dcoefn);
-    else
-        hipLaunchKernelGGL(draws_sample_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, S, rt, erow, e->drw_off, dtheta, df, W, e->like_mu,
-                           e->like_sinv, e->smp_z, e->drw_out, e->smp_b, e->smp_chi2, dcoef, dcoefn);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+    launch_two(draws_sample_params_kernel<false>, draws_sample_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, S, run.rt, erow,
+               e->drw_off, run.theta, run.f, run.W, e->like_mu, e->like_sinv, e->smp_z, e->drw_out, e->smp_b, e->smp_chi2, dcoef, dcoefn);
+    if (int rc = launched(who)) return rc;
     if (plk) {  // the launch of eftb_draws_reduce on N S draws with offsets S
         e->smp_off_host.resize((size_t)C + 1);
         for (int w = 0; w <= C; ++w) e->smp_off_host[w] = (long long)offsets[w] * S;
         HIPCHK(hipMemcpyAsync(e->smp_off, e->smp_off_host.data(), ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-        const int xtiles = (nx + 63) / 64, shares = draw_shares(maxcnt * S, 4, (long long)C * ntr * nl * xtiles);
-        hipLaunchKernelGGL(draws_reduce_kernel, dim3(xtiles * shares, ntr * nl, C), dim3(256), 0, st, nx, nl, ntr, reduce_msplit(c), xtiles, e->smp_off, e->smp_coef,
-                           e->buf[EFTB_B_TEMPL], nn ? e->smp_coefn : nullptr, nn ? e->buf[EFTB_B_TEMPLN] : nullptr, e->smp_plk);
-        le = hipGetLastError();
-        if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+        if (int rc = launch_draws_reduce(e, who, C, maxcnt * S, e->smp_off, e->smp_coef, e->smp_coefn, e->smp_plk)) return rc;
         HIPCHK(hipMemcpyAsync(plk, e->smp_plk, ns * ntr * nl * nx * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     if (nG) HIPCHK(hipMemcpyAsync(bsamp, e->smp_b, ns * nG * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4100,28 +4040,6 @@ int eftb_draws_sample_params_datasets(eftb_engine* e, int C, int G, const int32_
 // record of the launch's starting theta
 constexpr int CHAIN_STEPS = 256;
 
-static std::array<const void*, 2> draws_chain_kernels() {
-    return {reinterpret_cast<const void*>(&draws_chain_params_kernel<false>), reinterpret_cast<const void*>(&draws_chain_params_kernel<true>)};
-}
-
-// device buffer of at least n elements for eftb_draws_chain_params (as grow_dev; a failed allocation names the shape that asked for it)
-static int chain_grow(const char* who, void* pp, size_t* cap, size_t n, size_t elem, const char* what, long long N, int T, int P) {
-    void** p = static_cast<void**>(pp);
-    if (n <= *cap) return 0;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    hipError_t me = hipMalloc(p, n * elem);
-    if (me != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return fail("%s: no device memory for %s of N = %lld chains x T = %d steps with P = %d parameters (%zu bytes): %s", who, what, N, T, P, n * elem,
-                    hipGetErrorString(me));
-    }
-    *cap = n;
-    return 0;
-}
-
 // eftb_draws_chain_params and eftb_draws_chain_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group): the checks, W_c
 // and uploads of draws_logp_params_impl, then draws_chain_params_kernel once per CHAIN_STEPS steps.  Between the launches theta and the accept
 // counts stay on the device; every launch's stored states and records come back behind it
@@ -4134,7 +4052,7 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     const int ntr = e->ntr, nG = e->like_nG;
     if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
     const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int P = rcp.P, nnzp = (rcp.nnz + 1) & ~1;
+    const int P = rcp.P;
     if (P < 1) return fail("%s: the draw recipe has no parameters to move", who);
     if (T < 1) return fail("%s: T = %d steps, at least 1", who, T);
     if (thin < 1 || thin > T) return fail("%s: thin = %d outside [1, T = %d]", who, thin, T);
@@ -4160,34 +4078,26 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     for (long long q = 0; q < N * P; ++q)
         if (!(theta0[q] >= pri[q % P] && theta0[q] <= pri[RECIPE_MAXP + q % P]))
             return fail("%s: theta0[%lld][%d] = %g outside [%g, %g]", who, q / P, (int)(q % P), theta0[q], pri[q % P], pri[RECIPE_MAXP + q % P]);
-    DrawShape sh;  // beside W_c: fp, col [nnzp] and the prior table; per wave: th [34], val [nnzp], two theta and two records
-    if (int rc = draws_logp_shape(e, who, (RECIPE_MAXTR * RECIPE_FPOW + CHAIN_PRI) * sizeof(double) + nnzp * sizeof(int),
-                                  (34 + (size_t)nnzp + CHAIN_WAVE) * sizeof(double), &sh)) {
-        const int J1w = (e->c.with_nnlo ? NROW + 3 : NROW) * ntr + 1;
-        if (J1w > DRAW_MAXJ1) return rc;
-        // Unreachable: the largest shape there is (J + 1 = 121, nG = 24, 1024 recipe entries) takes 161288 of the 163840 bytes at one wave.
-        return fail("%s: the chains of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS", who, P, nG, J1w);
-    }
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, DRAW_CHAIN, &rcp, &sh)) return rc;
+    // Unreachable: the largest shape there is (J + 1 = 121, nG = 24, 1024 recipe entries) takes 161288 of the 163840 bytes at one wave.
+    if (!sh.nw) return fail("%s: the chains of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS", who, P, nG, sh.J1);
     if (N == 0) return 0;
     const int K = T / thin, kstride = std::max(1, std::min(K, CHAIN_STEPS / thin + 1)), Tmax = std::min(T, CHAIN_STEPS);
-    if (int rc = draws_logp_begin(e, who, C, N, sh.J1, offsets, gr ? gr->nwalk : -1)) return rc;
-    if (gr)
-        if (int rc = draws_gram_groups(e, who, C, sh.J1, *gr)) return rc;
-    const double* W = gr ? e->drw_Wg : e->drw_W;
-    if (int rc = chain_grow(who, &e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, sizeof(double), "the steps", N, T, P)) return rc;
-    if (int rc = chain_grow(who, &e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, sizeof(double), "lnu", N, T, P)) return rc;
-    if (int rc = chain_grow(who, &e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, sizeof(double), "the prior table", N, T, P)) return rc;
-    if (int rc = chain_grow(who, &e->chn_nacc, &e->chn_nacc_cap, (size_t)N, sizeof(long long), "the accept counts", N, T, P)) return rc;
-    if (int rc = chain_grow(who, &e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, sizeof(double), "the stored states", N, T, P)) return rc;
-    if (int rc = chain_grow(who, &e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * MARG_OUT, sizeof(double), "the stored records", N, T, P)) return rc;
-    const double *dtheta = nullptr, *df = nullptr;
-    if (int rc = draws_params_upload(e, P, C, N, theta0, f, &dtheta, &df)) return rc;
+    DrawRun run;
+    if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
+    char shape[96];
+    snprintf(shape, sizeof shape, "N = %lld chains x T = %d steps with P = %d parameters", N, T, P);
+    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(pp, cap, n, elem, who, what, shape); };
+    if (int rc = grow(&e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, "the steps")) return rc;
+    if (int rc = grow(&e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, "lnu")) return rc;
+    if (int rc = grow(&e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
+    if (int rc = grow(&e->chn_nacc, &e->chn_nacc_cap, (size_t)N, "the accept counts", sizeof(long long))) return rc;
+    if (int rc = grow(&e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, "the stored states")) return rc;
+    if (int rc = grow(&e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * MARG_OUT, "the stored records")) return rc;
     hipStream_t st = e->stream;
     HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
-    const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
-    const int J1 = sh.J1;
-    const RecipeTab rt = recipe_tab(rcp);
     e->chn_host_chain.resize((size_t)N * kstride * P);
     e->chn_host_rec.resize((size_t)N * kstride * MARG_OUT);
     for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) {
@@ -4197,14 +4107,10 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
                                 (size_t)N, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
                                 hipMemcpyHostToDevice, st));
-        if (J1 > 64)
-            hipLaunchKernelGGL(draws_chain_params_kernel<true>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, Tc, t0, thin, kc, kstride, rt, e->drw_off,
-                               e->drw_theta, e->chn_nacc, df, W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu, e->chn_chain, e->chn_rec);
-        else
-            hipLaunchKernelGGL(draws_chain_params_kernel<false>, grid, block, sh.lds, st, ntr, nG, J1, e->jeffreys, Tc, t0, thin, kc, kstride, rt, e->drw_off,
-                               e->drw_theta, e->chn_nacc, df, W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu, e->chn_chain, e->chn_rec);
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail("%s: kernel launch failed: %s", who, hipGetErrorString(le));
+        launch_two(draws_chain_params_kernel<false>, draws_chain_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin, kc,
+                   kstride, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu, e->chn_chain,
+                   e->chn_rec);
+        if (int rc = launched(who)) return rc;
         if (!kc) continue;
         HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, (size_t)N * kstride * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4213,10 +4119,7 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
             for (int k = 0; k < kc; ++k) {
                 const size_t to = (size_t)n * K + k0 + k, from = (size_t)n * kstride + k;
                 std::copy_n(e->chn_host_chain.data() + from * P, P, chain + to * P);
-                const double* o = e->chn_host_rec.data() + from * MARG_OUT;
-                if (logp) logp[to] = o[0];
-                if (fullchi2) fullchi2[to] = o[1];
-                if (best) std::copy_n(o + 2, nG, best + to * nG);
+                draws_unpack(e->chn_host_rec.data() + from * MARG_OUT, nG, to, logp, fullchi2, best);
             }
     }
     e->chn_host_nacc.resize((size_t)N);
