@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "eftb_kernels.hpp"
+#include "eftb_staged.hpp"
 
 using namespace eftb;
 
@@ -219,6 +220,31 @@ struct eftb_engine {
     bool ap_overlap = true, back_pending = false, allow_back = false;  // EFTB_AP_OVERLAP=0 disables
     unsigned back_step = 0;
     hipStream_t opstream = nullptr;  // where the operator launchers put their kernels (null: the main stream)
+    // direct-P_l runs in the three-stream layout keep their FRONT (operand rows, first-stage products, anti-diagonal sums, synthesis rows, Q(f):
+    // functions of the inputs alone) on the side stream, one run ahead of the rest of the look-ahead chain (syntheses, contraction, operand
+    // build): two sets of everything the front writes, swapped per run
+    struct FrontSet {
+        double *PA1 = nullptr, *PA2 = nullptr, *PA2T = nullptr, *PA3 = nullptr, *coefT = nullptr, *A22 = nullptr, *A13 = nullptr, *ACF = nullptr, *ALC = nullptr;
+        double *P11 = nullptr, *COEF = nullptr, *XY = nullptr, *Q = nullptr;
+        double2* SAD = nullptr;
+    } alt;
+    hipEvent_t evFront = nullptr, evFrontFree[2] = {nullptr, nullptr};  // this run's front is done (side stream); the readers of front set [slot] are done
+    unsigned front_step = 0;
+    bool prev_front_side = false;
+    bool ap_plk_fused = false;          // the AP stage of direct-P_l runs as ap_plk_fused_kernel (k grids whose tables fit the LDS; EFTB_AP_PLK_FUSED=0: ap_prefix + ap_plk_mom)
+    bool ap_plk_nodes = false;          // EFTB_AP_PLK_NODES=1: the AP stage of direct-P_l runs as the node quadrature (ap_plk_kernel, round 3) instead of the moment form
+    double* PLK0 = nullptr;             // direct-P_l runs with a PROJECT stage: P_l [B][Nl][Nk] as the AP stage leaves it (the operator then takes ONE row per cosmology)
+    bool plk_direct = false;            // EFTB_O_PLK_DIRECT: whole-pipeline runs that end in REDUCE contract with the bias first (regroup_plk_kernel)
+    int cur_nl = 0, cur_nx = 0;  // shape of the template block
+    int resum_splits = 1;
+    int Nn = 0;
+    double* sm2 = nullptr;  // s^-2 row scale of Cct
+    double* sm4 = nullptr;  // s^-4 row scale of CctNNLO
+    double* XB = nullptr;  // optiresum: BAO-extracted copies of C11 [B][Nl][80], Cct [B][Nl][80], Cloopl [B][Nl][12][80], in this order
+    double *coef2 = nullptr, *coefT2 = nullptr;  // dual_coef: FFTLog coefficients of the xi-space pieces (layouts of EFTB_B_COEF / coefT)
+    double *ZC = nullptr, *ZC2 = nullptr;  // with_nnlo: zeros standing in for C11 [B][Nl][80] / Cloopl [B][Nl][12][80] in the NNLO pass of Resum.Ps
+
+    // ---- staged-step state (everything above: state of an evaluation, whoever launches it) ----
     // Pipelined sampler steps (eftb_stage_inputs / eftb_run_staged / eftb_fetch_back): four sets of the per-step inputs (PIN, F, DA,
     // H, BIAS, GROWS) and outputs (PLK, LOGP) -- up to three launched and not yet fetched, one whose results are being fetched / refilled
     static constexpr int NSETS = 16; // rotating sets of per-launch inputs / outputs: the host may run fifteen steps ahead of the step it fetches (round 3: 8; a step's way from
@@ -233,7 +259,7 @@ struct eftb_engine {
     double* stage_host[NSLOT] = {};
     size_t stage_elems = 0;
     hipStream_t cpy = nullptr;
-    static constexpr int NLRING = 64;       // ring of the upload events, by launch number (a staging block is refilled 16 steps <= 16 launches later)
+    static constexpr int NLRING = 64;       // ring of the upload events, by launch number (a staging block is refilled NSLOT steps <= NSLOT launches later)
     hipEvent_t evStagedR[NLRING] = {}, evStagedAllR[NLRING] = {};
     hipEvent_t evSetDone[NSETS] = {};
     // Latency mode (a sampler whose next step depends on this step's P_l: nothing is queued behind the step being staged).  eftb_stage_inputs
@@ -242,40 +268,17 @@ struct eftb_engine {
     // follows off the critical path; only the few KB of f / DA / H / bias are waited for, copied on the compute queue itself), and P_l is
     // written to mapped host memory by the kernel that forms it (no DMA phase).  (Measured and dropped: the AP tables beside the resummation
     // instead of beside the loop chain -- the chain gained 20 us, the resummation lost 39.)
-    // direct-P_l runs in the three-stream layout keep their FRONT (operand rows, first-stage products, anti-diagonal sums, synthesis rows, Q(f):
-    // functions of the inputs alone) on the side stream, one run ahead of the rest of the look-ahead chain (syntheses, contraction, operand
-    // build): two sets of everything the front writes, swapped per run
-    struct FrontSet {
-        double *PA1 = nullptr, *PA2 = nullptr, *PA2T = nullptr, *PA3 = nullptr, *coefT = nullptr, *A22 = nullptr, *A13 = nullptr, *ACF = nullptr, *ALC = nullptr;
-        double *P11 = nullptr, *COEF = nullptr, *XY = nullptr, *Q = nullptr;
-        double2* SAD = nullptr;
-    } alt;
-    hipEvent_t evFront = nullptr, evFrontFree[2] = {nullptr, nullptr};  // this run's front is done (side stream); the readers of front set [slot] are done
-    unsigned front_step = 0;
-    bool prev_front_side = false;
-    bool upload_on_side = true;         // EFTB_UPLOAD_ON_SIDE=0: staged uploads always on the copy stream
-    bool ap_plk_fused = false;          // the AP stage of direct-P_l runs as ap_plk_fused_kernel (k grids whose tables fit the LDS; EFTB_AP_PLK_FUSED=0: ap_prefix + ap_plk_mom)
-    bool ap_plk_nodes = false;          // EFTB_AP_PLK_NODES=1: the AP stage of direct-P_l runs as the node quadrature (ap_plk_kernel, round 3) instead of the moment form
-    double* PLK0 = nullptr;             // direct-P_l runs with a PROJECT stage: P_l [B][Nl][Nk] as the AP stage leaves it (the operator then takes ONE row per cosmology)
-    bool plk_host_written = false;      // the kernel that formed the final P_l of the last launch also stored it to plk_host_out
-    bool plk_direct = false;            // EFTB_O_PLK_DIRECT: whole-pipeline runs that end in REDUCE contract with the bias first (regroup_plk_kernel)
     bool latency_auto = true;           // EFTB_LATENCY_MODE=0 disables
     bool set_latency[NSETS] = {};        // the launch on this set is a latency-mode step (evStagedAllR: the whole staging block has been uploaded; evStagedR: the part its first kernels wait for)
     bool lat_run = false;                // the run being launched is a latency-mode step
-    double* plk_host_out = nullptr;      // latency mode: where P_l goes besides the device buffer
-    int cur_set = 0;
+    double* plk_host_out = nullptr;      // where the kernel that forms P_l stores it besides the device buffer (PlkExit::stored; null: nowhere)
+    bool plk_host_written = false;      // the kernel that formed the final P_l of the last launch also stored it to plk_host_out
+    bool upload_on_side = true;         // EFTB_UPLOAD_ON_SIDE=0: staged uploads always on the copy stream
+    int cur_set = 0;                    // set of the launch issued last (NSETS - 1 before the first)
     // staged sets keep P_l in device memory: with a communicator RCCL sends from it; without one the step's last stream copies it to page-locked
     // host memory with the DMA engine (plk_host) -- measured 0.447 ms per step against 0.455 ms with REDUCE writing mapped host memory over PCIe
     // from its waves
     double* plk_host[NSETS] = {};
-    int cur_nl = 0, cur_nx = 0;  // shape of the template block
-    int resum_splits = 1;
-    int Nn = 0;
-    double* sm2 = nullptr;  // s^-2 row scale of Cct
-    double* sm4 = nullptr;  // s^-4 row scale of CctNNLO
-    double* XB = nullptr;  // optiresum: BAO-extracted copies of C11 [B][Nl][80], Cct [B][Nl][80], Cloopl [B][Nl][12][80], in this order
-    double *coef2 = nullptr, *coefT2 = nullptr;  // dual_coef: FFTLog coefficients of the xi-space pieces (layouts of EFTB_B_COEF / coefT)
-    double *ZC = nullptr, *ZC2 = nullptr;  // with_nnlo: zeros standing in for C11 [B][Nl][80] / Cloopl [B][Nl][12][80] in the NNLO pass of Resum.Ps
     // RCCL gather (multi-GPU batches)
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
@@ -317,6 +320,18 @@ struct eftb_engine {
     struct StepRec { int set, row, B, rc, nl, nx; unsigned long long launch; double* out; };
     StepRec rec[SUBREC] = {};
     char sub_err[SUBREC][256] = {};
+    // what the rings rely on:
+    // eftb_stage_inputs reads rec[] of the step that used the staging block last, NSLOT steps back, and a fetch that of a step < NSETS back
+    static_assert(NSLOT <= SUBREC && NSETS <= SUBREC, "rec[] / sub_err[] must still hold the record of a staging block's last step");
+    // every queued step owns a staging block, so at most NSLOT - 1 are pending in sub_ring[]
+    static_assert(NSLOT - 1 < SUBQ, "sub_ring[] must hold every pending step");
+    // launch_finished reads lring_set[] of the launches in flight: fewer than NSETS (sub_inflight's clamp; a set is reused behind its event)
+    static_assert(NSETS <= NLRING, "lring_set[] must hold the set of every launch in flight");
+    // eftb_stage_inputs waits on evStagedR / evStagedAllR [launch % NLRING] of that step's launch: every launch carries a step, so it is at
+    // most NSLOT launches back and its ring slot has not been recorded again
+    static_assert(NSLOT < NLRING, "the upload events of a staging block's last launch must not have been reused");
+    // sub_main's group, launch_upload's and copy_out's per-step arrays, and the argument of stage_gather_kernel
+    static_assert(MAX_UPLOAD_SEGS <= (int)(sizeof(StageSegs::s) / sizeof(StageSeg)), "a launch of MAX_COALESCE steps must fit the upload kernel's segment list");
     int coalesce_max = 1;                    // steps per launch at most (EFTB_COALESCE; 1 unless step_batch < max_batch)
     int sub_low = 2;                         // ... and below which it launches whatever is queued at once (EFTB_SUB_LOW); between the two it waits for a full group
     int sub_inflight = 4;                    // launches the submission thread keeps in flight before it lets the queue grow (EFTB_SUB_INFLIGHT)
@@ -795,17 +810,32 @@ static int check_status(eftb_engine* e, const char* who, int slot = -1) {
     return fail("%s: non-finite P_l(k) for cosmology %d (EFTB_O_CHECK_FINITE)", who, bad_out - 1);
 }
 
+static inline void cpu_pause() { __builtin_ia32_pause(); }
+
+// bound of every spin below, in seconds
+static double fetch_timeout_s() {
+    static const double limit_s = getenv("EFTB_FETCH_TIMEOUT_S") ? atof(getenv("EFTB_FETCH_TIMEOUT_S")) : 60.0;
+    return limit_s;
+}
+
+// The one bounded spin: polls done() with `pauses` pause instructions between polls and looks at the clock every period_mask + 1 polls (a
+// poll of plain memory is a few ns, an event query a microsecond: each site brings its own period).  false: the bound ran out first, counted
+// from t0.  What a time-out means is the caller's business.
+template <typename Done>
+static bool spin_until(Done done, unsigned period_mask, int pauses = 1, std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now()) {
+    for (unsigned spins = 0; !done(); ++spins) {
+        for (int i = 0; i < pauses; ++i) cpu_pause();
+        if ((spins & period_mask) == period_mask && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > fetch_timeout_s()) return false;
+    }
+    return true;
+}
+
 // bounded spin on an event (the sampler thread is about to enqueue the next step: the wake-up latency of a blocking wait would be paid once per step)
 static int spin_event(hipEvent_t ev, const char* who, const char* what) {
-    static const double limit_s = getenv("EFTB_FETCH_TIMEOUT_S") ? atof(getenv("EFTB_FETCH_TIMEOUT_S")) : 60.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        const hipError_t q = hipEventQuery(ev);
-        if (q == hipSuccess) return 0;
-        if (q != hipErrorNotReady) return fail("%s: %s", who, hipGetErrorString(q));
-        if ((spins & 0xfff) == 0xfff && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s)
-            return fail("%s: %s did not finish within %.0f s (EFTB_FETCH_TIMEOUT_S)", who, what, limit_s);
-    }
+    hipError_t q = hipSuccess;
+    if (!spin_until([&] { return (q = hipEventQuery(ev)) != hipErrorNotReady; }, 0xfff, 0))
+        return fail("%s: %s did not finish within %.0f s (EFTB_FETCH_TIMEOUT_S)", who, what, fetch_timeout_s());
+    return q == hipSuccess ? 0 : fail("%s: %s", who, hipGetErrorString(q));
 }
 
 // host inputs of one batch, before anything is copied: finite everywhere, P_lin positive where its logarithm is taken, distances positive
@@ -2586,6 +2616,19 @@ static const int kStagedIds[] = {EFTB_B_PIN, EFTB_B_F, EFTB_B_DA, EFTB_B_H, EFTB
 static const int kStagedIn[] = {EFTB_B_PIN, EFTB_B_F, EFTB_B_DA, EFTB_B_H, EFTB_B_BIAS, EFTB_B_GROWS};  // order inside a set's input block
 static const int kStagedOut[] = {EFTB_B_PLK, EFTB_B_LOGP};
 
+// the environment switches of the staged path, read once, when the first step is staged; sb: cosmologies a step brings at most
+static void read_staged_switches(eftb_engine* e, size_t sb) {
+    if (const char* f = getenv("EFTB_LATENCY_MODE")) e->latency_auto = atoi(f) != 0;
+    if (const char* f = getenv("EFTB_DONE_WORDS")) e->done_words = atoi(f) != 0;
+    if (const char* f = getenv("EFTB_PLK_DMA")) e->plk_dma = atoi(f) != 0;
+    if (const char* f = getenv("EFTB_SUB_STATS")) e->sub_stats = atoi(f) != 0;
+    if (const char* f = getenv("EFTB_SUB_INFLIGHT")) e->sub_inflight = std::max(1, std::min(eftb_engine::NSETS - 1, atoi(f)));
+    if (const char* f = getenv("EFTB_SUB_LOW")) e->sub_low = std::max(1, atoi(f));
+    e->sub_low = std::min(e->sub_low, e->sub_inflight);
+    e->coalesce_max = e->comm ? 1 : (int)std::min<size_t>(MAX_COALESCE, (size_t)e->c.max_batch / sb);   // (with a communicator every step is exchanged by itself)
+    if (const char* f = getenv("EFTB_COALESCE")) e->coalesce_max = std::max(1, std::min(e->coalesce_max, atoi(f)));
+}
+
 // Every set keeps its inputs in ONE device block with the layout of the page-locked staging blocks, so that staging is one upload
 // kernel (small separate copies are carried out by the host thread once the stream's dependencies have resolved,
 // which would stall the sampler loop for a whole step).
@@ -2644,15 +2687,7 @@ static int staged_setup(eftb_engine* e) {
         HIPCHK(hipEventRecord(e->evStagedR[r], e->cpy));
         HIPCHK(hipEventRecord(e->evStagedAllR[r], e->cpy));
     }
-    if (const char* f = getenv("EFTB_LATENCY_MODE")) e->latency_auto = atoi(f) != 0;
-    if (const char* f = getenv("EFTB_DONE_WORDS")) e->done_words = atoi(f) != 0;
-    if (const char* f = getenv("EFTB_PLK_DMA")) e->plk_dma = atoi(f) != 0;
-    if (const char* f = getenv("EFTB_SUB_STATS")) e->sub_stats = atoi(f) != 0;
-    if (const char* f = getenv("EFTB_SUB_INFLIGHT")) e->sub_inflight = std::max(1, std::min(eftb_engine::NSETS - 1, atoi(f)));
-    if (const char* f = getenv("EFTB_SUB_LOW")) e->sub_low = std::max(1, atoi(f));
-    e->sub_low = std::min(e->sub_low, e->sub_inflight);
-    e->coalesce_max = e->comm ? 1 : (int)std::min<size_t>(8, (size_t)e->c.max_batch / sb);   // (with a communicator every step is exchanged by itself)
-    if (const char* f = getenv("EFTB_COALESCE")) e->coalesce_max = std::max(1, std::min(e->coalesce_max, atoi(f)));
+    read_staged_switches(e, sb);
     {
         void* p = nullptr;
         HIPCHK(hipHostMalloc(&p, 2 * eftb_engine::NSETS * sizeof(unsigned long long), hipHostMallocMapped));
@@ -2684,173 +2719,243 @@ static void stage_fill(eftb_engine* e, int slot, int B, const double* Pin, const
 }
 
 // ... and the device part (issued by the caller's thread or by the submission thread): n queued steps become ONE launch on the next device set --
-// their staging blocks are gathered into the set's input block row after row by one upload kernel, then every stage runs on the joint batch
-static int issue_group(eftb_engine* e, const eftb_engine::SubCmd* cmds, int n, bool lat) {
-    const eftb_config& c = e->c;
-    const int q = (e->cur_set + 1) % eftb_engine::NSETS;
-    const unsigned long long L = e->launch_seq;
-    const int lr = (int)(L % eftb_engine::NLRING);
-    const int mask = cmds[0].mask;
-    const bool has_rows = cmds[0].has_rows != 0;
-    int Bt = 0;
-    for (int j = 0; j < n; ++j) Bt += cmds[j].B;
+// their staging blocks are gathered into the set's input block row after row by one upload kernel, then every stage runs on the joint batch.
+// plan_launch decides, one function per phase acts; what only the run knows (back_pending, plk_host_written, cur_nl /
+// cur_nx) is read behind run_stages, never in the plan.
+
+// how the P_l of a staged launch reaches host memory
+enum class PlkExit {
+    none,         // it does not: no REDUCE in the mask, or a communicator (P_l stays in device memory for the exchange)
+    stored,       // the kernel that forms it also stores it to the set's mapped host block: latency mode (one kernel less on the dependent sampler's
+                  // chain) and the node quadrature (round 3 stored from ap_plk_kernel: 1.6 MB of 8-byte PCIe stores kept every SIMD's waves
+                  // resident for ~25 us, which is why pipelined steps do not).  A run whose last kernel could not (plk_host_written) leaves by copy_by
+    copy_kernel,  // copy16_kernel / copy8_kernel behind the launch (EFTB_PLK_DMA=0)
+    dma,          // the DMA engine, in line behind the launch's last kernel (same-box A/B over 200 steps: 0.091-0.096 ms per step against 0.102-0.104
+                  // with copy16_kernel -- the what-if runs priced the kernel's PCIe stores at a fifth of the step)
+};
+
+struct LaunchPlan {
+    int q = 0, lr = 0;              // device set of the launch; slot of its upload events and of lring_set
+    unsigned long long L = 0;       // launch number
+    int mask = 0, Bt = 0;           // Bt: cosmologies of all steps together
+    bool has_rows = false, lat = false;
     // the upload goes where the launch's first kernels go: direct-P_l launches start on the side stream (their front), so the upload in front of
     // them on the same queue needs no cross-queue hand-over (20-35 us each on this runtime, and the chain of a launch has four more)
-    hipStream_t cs = (e->plk_direct && !lat && e->upload_on_side) ? e->side : e->cpy;
-    HIPCHK(hipStreamWaitEvent(cs, e->evSetDone[q], 0));  // the last launch on this set (and the fetch of its results) is over
-    // (an upload kernel reading the mapped staging blocks, not a DMA transfer: 0.4 MB is latency, and the DMA form measured the same or worse)
-    // only what was staged travels: P_lin, f, DA, H, the bias rows -- and the likelihood rows (0.6 MB at 128 walkers) when there are any.  Reads
-    // of host memory from a kernel run at ~16 GB/s: the whole 0.85 MB block took 48-53 us, on the critical path of a dependent sampler
-    const size_t width[6] = {(size_t)c.Nkin, 1, 1, 1, (size_t)NROW, (size_t)MARG_NG1 * NROW};
-    auto gather = [&](int id_lo, int id_hi, hipStream_t st) {  // arrays kStagedIn[id_lo .. id_hi) of every step of the group
+    hipStream_t up = nullptr;
+    PlkExit leave = PlkExit::none;
+    PlkExit copy_by = PlkExit::dma;  // dma or copy_kernel: how a copy behind the launch travels
+    bool own_dst = false;            // a step names its own destination (eftb_set_step_output): always a copy behind the launch, one transfer per destination
+    bool back_joins_copy = false;    // templates-first launches: whoever joins the back half also waits for the copy
+    bool compute_word = false, done_word = false;  // the completion words to write (hipStreamWriteValue64; EFTB_DONE_WORDS)
+};
+
+static void plan_launch(const eftb_engine* e, const eftb_engine::SubCmd* cmds, int n, bool lat, LaunchPlan* p) {
+    p->q = (e->cur_set + 1) % eftb_engine::NSETS;
+    p->L = e->launch_seq;
+    p->lr = (int)(p->L % eftb_engine::NLRING);
+    p->mask = cmds[0].mask;
+    p->has_rows = cmds[0].has_rows != 0;
+    p->lat = lat;
+    for (int j = 0; j < n; ++j) {
+        p->Bt += cmds[j].B;
+        p->own_dst = p->own_dst || cmds[j].out != nullptr;
+    }
+    p->up = (e->plk_direct && !lat && e->upload_on_side) ? e->side : e->cpy;
+    // latency mode: one queue for the whole step; P_l goes to mapped host memory from the kernel that forms it (REDUCE, or the AP epilogue)
+    // unless the NNLO pass adds to it afterwards
+    const bool has_plk = e->plk_host[p->q] && (p->mask & EFTB_S_REDUCE);
+    const bool direct = has_plk && (lat || (e->plk_direct && !e->comm)) && !e->c.with_nnlo;
+    if (direct) {
+        p->copy_by = e->plk_dma ? PlkExit::dma : PlkExit::copy_kernel;
+        p->leave = (lat || e->ap_plk_nodes) && !p->own_dst ? PlkExit::stored : p->copy_by;
+    } else if (has_plk) {
+        p->leave = PlkExit::dma;
+        p->back_joins_copy = true;
+    }
+    p->compute_word = e->done_words && !lat;   // compute finished: what the submission thread's flow control counts (the copy-out is not part of it)
+    p->done_word = e->done_words;
+}
+
+static UploadLayout upload_layout(const eftb_engine* e, bool has_rows) {
+    UploadLayout lay{};
+    const size_t width[STAGED_ARRAYS] = {(size_t)e->c.Nkin, 1, 1, 1, (size_t)NROW, (size_t)MARG_NG1 * NROW};
+    for (int a = 0; a < STAGED_ARRAYS; ++a) {
+        const int id = kStagedIn[a];
+        lay.width[a] = width[a];
+        lay.slot_off[a] = e->slot_off[id];
+        lay.stage_off[a] = e->stage_off[id];
+        lay.present[a] = e->buf_elems[id] && (id != EFTB_B_GROWS || has_rows);
+    }
+    return lay;
+}
+
+// the staging blocks of the group -> the set's input block, and the events that say so
+// (an upload kernel reading the mapped staging blocks, not a DMA transfer: 0.4 MB is latency, and the DMA form measured the same or worse)
+// only what was staged travels: P_lin, f, DA, H, the bias rows -- and the likelihood rows (0.6 MB at 128 walkers) when there are any.  Reads
+// of host memory from a kernel run at ~16 GB/s: the whole 0.85 MB block took 48-53 us, on the critical path of a dependent sampler
+static int launch_upload(eftb_engine* e, const LaunchPlan& p, const eftb_engine::SubCmd* cmds, int n) {
+    HIPCHK(hipStreamWaitEvent(p.up, e->evSetDone[p.q], 0));  // the last launch on this set (and the fetch of its results) is over
+    const UploadLayout lay = upload_layout(e, p.has_rows);
+    int B[MAX_COALESCE];
+    for (int j = 0; j < n; ++j) B[j] = cmds[j].B;
+    auto gather = [&](int lo, int hi, hipStream_t st) {  // arrays kStagedIn[lo .. hi) of every step of the group
+        const UploadSegs us = upload_segments(lay, B, n, lo, hi);
         StageSegs sg{};
-        unsigned total = 0;
-        int row = 0;
-        for (int j = 0; j < n; ++j) {
-            for (int a = id_lo; a < id_hi; ++a) {
-                const int id = kStagedIn[a];
-                if (!e->buf_elems[id] || (id == EFTB_B_GROWS && !has_rows)) continue;
-                StageSeg& g = sg.s[sg.n++];
-                g.src = e->stage_host[cmds[j].slot] + e->slot_off[id];
-                g.dst = e->setblock[q] + e->stage_off[id] + (size_t)row * width[a];
-                g.n = (unsigned)((size_t)cmds[j].B * width[a]);
-                g.first = total;
-                total += (g.n + 63u) & ~63u;
-            }
-            row += cmds[j].B;
+        for (; sg.n < us.n; ++sg.n) {
+            const UploadSeg& u = us.s[sg.n];
+            sg.s[sg.n] = StageSeg{e->stage_host[cmds[u.step].slot] + u.src_off, e->setblock[p.q] + u.dst_off, u.n, u.first};
         }
-        if (sg.n && !WHATIF_SKIP(1024)) hipLaunchKernelGGL(stage_gather_kernel, dim3((total + 255) / 256), dim3(256), 0, st, sg);
+        if (sg.n && !WHATIF_SKIP(1024)) hipLaunchKernelGGL(stage_gather_kernel, dim3((us.total + 255) / 256), dim3(256), 0, st, sg);
     };
     e->trace_slot = -1;
-    if (e->trace_on && !lat && e->evTraceBase) {
+    if (e->trace_on && !p.lat && e->evTraceBase) {
         e->trace_slot = (int)(e->trace_n++ % eftb_engine::NTRACE);
-        e->trace_B[e->trace_slot] = Bt;
-        e->trace_launch[e->trace_slot] = L;
-        trace_point(e, 0, cs);
+        e->trace_B[e->trace_slot] = p.Bt;
+        e->trace_launch[e->trace_slot] = p.L;
+        trace_point(e, 0, p.up);
     }
-    e->set_latency[q] = lat;
-    if (lat) {
+    e->set_latency[p.q] = p.lat;
+    if (p.lat) {
         // the small arrays go first and on the compute queue itself (in line in front of the step's kernels: no cross-queue hand-over; the
         // GPU is idle, nothing of an earlier step can still be reading the set): they are all the step's first kernels wait for -- its first
         // kernel reads P_lin from the staging block itself, whose device copy follows on the copy queue
-        gather(1, 6, e->stream);
-        HIPCHK(hipEventRecord(e->evStagedR[lr], e->stream));
-        gather(0, 1, cs);
-        HIPCHK(hipEventRecord(e->evStagedAllR[lr], cs));
+        gather(1, STAGED_ARRAYS, e->stream);
+        HIPCHK(hipEventRecord(e->evStagedR[p.lr], e->stream));
+        gather(0, 1, p.up);
+        HIPCHK(hipEventRecord(e->evStagedAllR[p.lr], p.up));
     } else {
-        gather(0, 6, cs);
-        trace_point(e, 9, cs);
-        HIPCHK(hipEventRecord(e->evStagedR[lr], cs));
+        gather(0, STAGED_ARRAYS, p.up);
+        trace_point(e, 9, p.up);
+        HIPCHK(hipEventRecord(e->evStagedR[p.lr], p.up));
     }
-    // the set becomes current and the launch goes out
-    e->cur_set = q;
-    e->lring_set[lr] = q;
+    return 0;
+}
+
+// the set becomes current: the steps' records, the engine's buffer pointers, the set's flags, and the streams behind the upload
+static int bind_set(eftb_engine* e, const LaunchPlan& p, const eftb_engine::SubCmd* cmds, int n) {
+    e->cur_set = p.q;
+    e->lring_set[p.lr] = p.q;
     ++e->launch_seq;
     int row = 0;
     for (int j = 0; j < n; ++j) {  // where each step's rows will be (the fetch needs it even when the launch fails below: to say so)
         eftb_engine::StepRec& r = e->rec[cmds[j].step % eftb_engine::SUBREC];
-        r.set = q; r.row = row; r.B = cmds[j].B; r.launch = L; r.rc = 0; r.out = cmds[j].out;
+        r.set = p.q; r.row = row; r.B = cmds[j].B; r.launch = p.L; r.rc = 0; r.out = cmds[j].out;
         row += cmds[j].B;
     }
     for (int id : kStagedIds)
-        if (e->setbuf[q][id]) e->buf[id] = e->setbuf[q][id];
-    e->status_slot = q;  // this launch's kernels raise this set's flags (cleared here: whatever an abandoned step left is void)
-    e->status[2 * q] = e->status[2 * q + 1] = 0;
+        if (e->setbuf[p.q][id]) e->buf[id] = e->setbuf[p.q][id];
+    e->status[2 * p.q] = e->status[2 * p.q + 1] = 0;  // (whatever an abandoned step left in this set's flags is void)
     ++e->epoch;  // (captured graphs hold the other set's pointers)
-    const hipStream_t staged_on = lat ? e->stream : cs;   // (where evStagedR was recorded: that stream is behind it already -- a call saved per launch)
-    if (staged_on != e->stream) HIPCHK(hipStreamWaitEvent(e->stream, e->evStagedR[lr], 0));  // the side stream forks from here, so it inherits the wait
-    if (staged_on != e->pre) HIPCHK(hipStreamWaitEvent(e->pre, e->evStagedR[lr], 0));
-    if (staged_on != e->side) HIPCHK(hipStreamWaitEvent(e->side, e->evStagedR[lr], 0));
-    // latency mode: one queue for the whole step; P_lin is read from the page-locked staging block (its device copy arrives behind evStagedAllR);
-    // P_l goes to mapped host memory from the kernel that forms it (REDUCE, or the AP epilogue) unless the NNLO pass adds to it afterwards
-    const bool plk_direct = (lat || (e->plk_direct && !e->comm)) && e->plk_host[q] && (mask & EFTB_S_REDUCE) && !c.with_nnlo;
-    // ... from the kernel that forms it in latency mode (one kernel less on the dependent sampler's chain); in pipelined steps by a small copy
-    // kernel behind the step (round 3 stored from ap_plk_kernel: 1.6 MB of 8-byte PCIe stores kept every SIMD's waves resident for ~25 us)
-    const bool plk_tail = plk_direct && !lat && !e->ap_plk_nodes;
-    double* pin_dev = e->buf[EFTB_B_PIN];
-    if (lat) e->buf[EFTB_B_PIN] = e->stage_host[cmds[0].slot] + e->slot_off[EFTB_B_PIN];
-    e->lat_run = lat;
-    // steps with a destination of their own (eftb_set_step_output): P_l always leaves through the copy-out below, one transfer per destination
-    bool any_out = false;
-    for (int j = 0; j < n; ++j) any_out = any_out || cmds[j].out != nullptr;
-    e->plk_host_out = plk_direct && !plk_tail && !any_out ? e->plk_host[q] : nullptr;
-    e->inputs_settled = e->allow_back = !lat;
-    const int rc = run_stages(e, mask, Bt);
-    e->inputs_settled = e->allow_back = false;
-    e->lat_run = false;
-    e->plk_host_out = nullptr;
-    e->buf[EFTB_B_PIN] = pin_dev;
-    e->status_slot = eftb_engine::NSETS;
-    if (rc) { e->trace_slot = -1; return rc; }
-    for (int j = 0; j < n; ++j) {  // shape of the output rows (after the pipeline operator, if the mask has one)
-        eftb_engine::StepRec& r = e->rec[cmds[j].step % eftb_engine::SUBREC];
-        r.nl = e->cur_nl; r.nx = e->cur_nx;
+    const hipStream_t staged_on = p.lat ? e->stream : p.up;   // (where evStagedR was recorded: that stream is behind it already -- a call saved per launch)
+    if (staged_on != e->stream) HIPCHK(hipStreamWaitEvent(e->stream, e->evStagedR[p.lr], 0));  // the side stream forks from here, so it inherits the wait
+    if (staged_on != e->pre) HIPCHK(hipStreamWaitEvent(e->pre, e->evStagedR[p.lr], 0));
+    if (staged_on != e->side) HIPCHK(hipStreamWaitEvent(e->side, e->evStagedR[p.lr], 0));
+    return 0;
+}
+
+// what run_stages reads from the engine about the staged launch around it, set here and put back on every way out: this launch's kernels
+// raise this set's flags; a latency-mode step reads P_lin from the page-locked staging block (its device copy arrives behind evStagedAllR),
+// a pipelined one has settled inputs and may use the back stream; plk_host_out is where a storing kernel puts P_l
+struct StagedRunScope {
+    eftb_engine* e;
+    double* pin_dev;
+    StagedRunScope(eftb_engine* e_, const LaunchPlan& p, double* pin_host) : e(e_), pin_dev(e_->buf[EFTB_B_PIN]) {
+        e->status_slot = p.q;
+        if (p.lat) e->buf[EFTB_B_PIN] = pin_host;
+        e->lat_run = p.lat;
+        e->plk_host_out = p.leave == PlkExit::stored ? e->plk_host[p.q] : nullptr;
+        e->inputs_settled = e->allow_back = !p.lat;
     }
-    hipStream_t last = e->back_pending ? e->back : e->stream;  // the launch ends where its back half ran
-    if (lat) HIPCHK(hipStreamWaitEvent(last, e->evStagedAllR[lr], 0));  // (the set is not "done" before its own upload is)
+    ~StagedRunScope() {
+        e->inputs_settled = e->allow_back = false;
+        e->lat_run = false;
+        e->plk_host_out = nullptr;
+        e->buf[EFTB_B_PIN] = pin_dev;
+        e->status_slot = eftb_engine::NSETS;
+    }
+    StagedRunScope(const StagedRunScope&) = delete;
+    StagedRunScope& operator=(const StagedRunScope&) = delete;
+};
+
+// P_l [rows of the launch][nl][nx] to host memory on stream st: the set's own page-locked block, or -- per step -- the caller's page-locked array
+// (merge_out_spans: which steps share a transfer)
+static int copy_out(eftb_engine* e, const LaunchPlan& p, const eftb_engine::SubCmd* cmds, int n, PlkExit by, hipStream_t st) {
     constexpr int copy_wgs = 48;   // (8 ... 512 workgroups measured the same: the kernel's time is the PCIe transfer)
-    hipStream_t done_on = last;  // where the launch's LAST work runs: what the set's event and completion word follow
-    if (e->done_words && !lat) {   // compute finished: what the submission thread's flow control counts (the copy-out below is not part of it)
-        if (hipStreamWriteValue64(last, const_cast<unsigned long long*>(e->set_done) + eftb_engine::NSETS + q, L + 1, 0) == hipSuccess) e->set_cword[q] = L + 1;
-        else (void)hipGetLastError();
-    }
-    // P_l [rows of the launch][nl][nx] to host memory: the set's own page-locked block, or -- per step -- the caller's page-locked array; steps next to
-    // each other that go to the set's block travel as one transfer
-    auto copy_out = [&](hipStream_t st) -> int {
-        const size_t per = (size_t)e->cur_nl * e->cur_nx;
-        // the DMA engine, in line behind the launch's last kernel (same-box A/B over 200 steps: 0.091-0.096 ms per step against 0.102-0.104 with
-        // copy16_kernel -- the what-if runs priced the kernel's PCIe stores at a fifth of the step; EFTB_PLK_DMA=0 brings the kernel back)
-        const bool dma = e->plk_dma || !plk_direct;
-        // (16 bytes per lane only where both ends are 16-byte aligned: with an odd row length the later steps of a launch start at odd offsets)
-        auto launch_copy = [&](const double* src, double* dst, size_t count) {
-            if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0)
-                hipLaunchKernelGGL(copy16_kernel, dim3(copy_wgs), dim3(256), 0, st, src, dst, count);
-            else hipLaunchKernelGGL(copy8_kernel, dim3(copy_wgs), dim3(256), 0, st, src, dst, count);
-        };
-        if (WHATIF_SKIP(512)) return 0;   // (what-if: P_l stays on the device)
-        if (WHATIF_SKIP(2048) && e->PLK0) {   // (what-if: the copy kernel with a device destination -- the stream holds it, PCIe does not)
-            launch_copy(e->buf[EFTB_B_PLK], e->PLK0, (size_t)Bt * per);
-            return 0;
-        }
-        for (int j = 0; j < n; ++j)
-            if (cmds[j].out && cmds[j].out_count < (size_t)cmds[j].B * per)
-                return fail("eftb_run_staged: the step's P_l has %zu elements, the destination of eftb_set_step_output holds %zu", (size_t)cmds[j].B * per, cmds[j].out_count);
-        int row = 0;
-        for (int j = 0; j < n;) {
-            int j1 = j + 1, rows = cmds[j].B;
-            if (!cmds[j].out)
-                for (; j1 < n && !cmds[j1].out; ++j1) rows += cmds[j1].B;
-            else   // destinations that follow each other in memory (the slices of one results array) travel as one transfer too
-                for (; j1 < n && cmds[j1].out == cmds[j].out + (size_t)rows * per; ++j1) rows += cmds[j1].B;
-            const double* src = e->buf[EFTB_B_PLK] + (size_t)row * per;
-            double* dst = cmds[j].out ? cmds[j].out : e->plk_host[q] + (size_t)row * per;
-            if (dma) HIPCHK(hipMemcpyAsync(dst, src, (size_t)rows * per * sizeof(double), hipMemcpyDeviceToHost, st));
-            else launch_copy(src, dst, (size_t)rows * per);
-            row += rows;
-            j = j1;
-        }
-        return 0;
+    const size_t per = (size_t)e->cur_nl * e->cur_nx;
+    // (16 bytes per lane only where both ends are 16-byte aligned: with an odd row length the later steps of a launch start at odd offsets)
+    auto launch_copy = [&](const double* src, double* dst, size_t count) {
+        if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0)
+            hipLaunchKernelGGL(copy16_kernel, dim3(copy_wgs), dim3(256), 0, st, src, dst, count);
+        else hipLaunchKernelGGL(copy8_kernel, dim3(copy_wgs), dim3(256), 0, st, src, dst, count);
     };
-    const bool kernel_stored = plk_direct && !plk_tail && !any_out && e->plk_host_written;  // the kernel that formed P_l wrote it to the set's host block too
-    if (plk_direct && !kernel_stored) {
-        if (int crc = copy_out(done_on)) return crc;
+    if (WHATIF_SKIP(512)) return 0;   // (what-if: P_l stays on the device)
+    if (WHATIF_SKIP(2048) && e->PLK0) {   // (what-if: the copy kernel with a device destination -- the stream holds it, PCIe does not)
+        launch_copy(e->buf[EFTB_B_PLK], e->PLK0, (size_t)p.Bt * per);
+        return 0;
     }
-    if (e->plk_host[q] && (mask & EFTB_S_REDUCE) && !plk_direct) {
-        if (int crc = copy_out(last)) return crc;
+    const double* out[MAX_COALESCE];
+    int B[MAX_COALESCE];
+    for (int j = 0; j < n; ++j) {
+        if (cmds[j].out && cmds[j].out_count < (size_t)cmds[j].B * per)
+            return fail("eftb_run_staged: the step's P_l has %zu elements, the destination of eftb_set_step_output holds %zu", (size_t)cmds[j].B * per, cmds[j].out_count);
+        out[j] = cmds[j].out;
+        B[j] = cmds[j].B;
     }
-    trace_point(e, 8, done_on);
+    OutSpan spans[MAX_COALESCE];
+    const int ns = merge_out_spans(out, B, n, per, spans);
+    for (int i = 0; i < ns; ++i) {
+        const OutSpan& s = spans[i];
+        const double* src = e->buf[EFTB_B_PLK] + (size_t)s.row * per;
+        double* dst = s.own ? cmds[s.step].out : e->plk_host[p.q] + (size_t)s.row * per;
+        if (by == PlkExit::dma) HIPCHK(hipMemcpyAsync(dst, src, (size_t)s.rows * per * sizeof(double), hipMemcpyDeviceToHost, st));
+        else launch_copy(src, dst, (size_t)s.rows * per);
+    }
+    return 0;
+}
+
+// compute finished: written behind the launch's last kernel, in front of the copy-out
+static void signal_compute_done(eftb_engine* e, const LaunchPlan& p, hipStream_t last) {
+    if (!p.compute_word) return;
+    if (hipStreamWriteValue64(last, const_cast<unsigned long long*>(e->set_done) + eftb_engine::NSETS + p.q, p.L + 1, 0) == hipSuccess) e->set_cword[p.q] = p.L + 1;
+    else (void)hipGetLastError();
+}
+
+// everything finished: the set's event and, behind it, the set's completion word
+static int signal_done(eftb_engine* e, const LaunchPlan& p, hipStream_t last) {
+    trace_point(e, 8, last);
     e->trace_slot = -1;
-    HIPCHK(hipEventRecord(e->evSetDone[q], done_on));
-    if (e->back_pending && e->plk_host[q] && (mask & EFTB_S_REDUCE) && !plk_direct)
-        HIPCHK(hipEventRecord(e->evBack[(e->back_step + 1) & 1], last));  // whoever joins the back half also waits for the copy
-    if (e->done_words) {
-        if (hipStreamWriteValue64(done_on, const_cast<unsigned long long*>(e->set_done) + q, L + 1, 0) == hipSuccess) e->set_word[q] = L + 1;
+    HIPCHK(hipEventRecord(e->evSetDone[p.q], last));
+    if (e->back_pending && p.back_joins_copy) HIPCHK(hipEventRecord(e->evBack[(e->back_step + 1) & 1], last));
+    if (p.done_word) {
+        if (hipStreamWriteValue64(last, const_cast<unsigned long long*>(e->set_done) + p.q, p.L + 1, 0) == hipSuccess) e->set_word[p.q] = p.L + 1;
         else {
             (void)hipGetLastError();
             e->done_words = false;  // this runtime refuses the command: event queries from here on (the words of the earlier launches stay valid)
         }
     }
     return 0;
+}
+
+static int issue_group(eftb_engine* e, const eftb_engine::SubCmd* cmds, int n, bool lat) {
+    LaunchPlan p;
+    plan_launch(e, cmds, n, lat, &p);
+    if (int rc = launch_upload(e, p, cmds, n)) return rc;
+    if (int rc = bind_set(e, p, cmds, n)) return rc;
+    {
+        StagedRunScope scope(e, p, e->stage_host[cmds[0].slot] + e->slot_off[EFTB_B_PIN]);
+        if (int rc = run_stages(e, p.mask, p.Bt)) { e->trace_slot = -1; return rc; }
+    }
+    for (int j = 0; j < n; ++j) {  // shape of the output rows (after the pipeline operator, if the mask has one)
+        eftb_engine::StepRec& r = e->rec[cmds[j].step % eftb_engine::SUBREC];
+        r.nl = e->cur_nl; r.nx = e->cur_nx;
+    }
+    const hipStream_t last = e->back_pending ? e->back : e->stream;  // the launch ends where its back half ran: the copy-out, the set's event and its word follow there
+    if (lat) HIPCHK(hipStreamWaitEvent(last, e->evStagedAllR[p.lr], 0));  // (the set is not "done" before its own upload is)
+    signal_compute_done(e, p, last);
+    const PlkExit by = p.leave == PlkExit::stored ? (e->plk_host_written ? PlkExit::none : p.copy_by) : p.leave;
+    if (by != PlkExit::none)
+        if (int rc = copy_out(e, p, cmds, n, by, last)) return rc;
+    return signal_done(e, p, last);
 }
 
 // issue_group + bookkeeping shared by both issuing threads: the steps' records, the clocks, the publication of "issued"
@@ -2880,15 +2985,22 @@ static int issue_and_publish(eftb_engine* e, const eftb_engine::SubCmd* cmds, in
     return rc;
 }
 
-static inline void cpu_pause() { __builtin_ia32_pause(); }
-
-// has staged launch L finished?  (issuing thread; its completion word if one was enqueued, else its set's event)
-static bool launch_finished(eftb_engine* e, unsigned long long L) {
-    const int q = e->lring_set[L % eftb_engine::NLRING];
-    if (e->set_cword[q] >= L + 1) return e->set_done[eftb_engine::NSETS + q] >= L + 1;   // its compute has finished (the copy-out of P_l may still run)
-    if (e->set_word[q] >= L + 1) return e->set_done[q] >= L + 1;   // (words grow with the launch number: a later launch on the set says it too)
-    return hipEventQuery(e->evSetDone[q]) == hipSuccess;
+// The one completion rule.  What says that launch L on set q has finished: its compute-done word if one was enqueued and the compute is all that
+// is asked about (the copy-out of P_l may still run), else its done word if one was enqueued, else the set's event (EFTB_DONE_WORDS=0, or the
+// runtime refused the write).  Words grow with the launch number: a later launch on the set says it too.
+// done_word_of: the word in mapped memory that says so once it has reached L + 1, or null: ask the event.  (A caller that spins takes the pointer
+// once and polls that word alone -- set_word / set_cword share cache lines with what the issuing thread writes at every launch.)
+static inline const volatile unsigned long long* done_word_of(const eftb_engine* e, int q, unsigned long long L, bool compute_only) {
+    if (compute_only && e->set_cword[q] >= L + 1) return e->set_done + eftb_engine::NSETS + q;
+    return e->set_word[q] >= L + 1 ? e->set_done + q : nullptr;
 }
+static bool launch_over(eftb_engine* e, int q, unsigned long long L, bool compute_only) {
+    const volatile unsigned long long* w = done_word_of(e, q, L, compute_only);
+    return w ? *w >= L + 1 : hipEventQuery(e->evSetDone[q]) == hipSuccess;
+}
+
+// has the compute of staged launch L finished?  (issuing thread: what its flow control counts)
+static bool launch_finished(eftb_engine* e, unsigned long long L) { return launch_over(e, e->lring_set[L % eftb_engine::NLRING], L, true); }
 
 // ---- submission thread (see eftb_engine::SubCmd)
 static void sub_main(eftb_engine* e) {
@@ -2910,24 +3022,20 @@ static void sub_main(eftb_engine* e) {
         // flow control: with sub_inflight launches still running the queue is left to grow -- what has piled up by the time one of them finishes
         // leaves as one launch (coalesce_max steps at most)
         while (e->launch_done < e->launch_seq && launch_finished(e, e->launch_done)) ++e->launch_done;
-        {
-            static const double limit_s = getenv("EFTB_FETCH_TIMEOUT_S") ? atof(getenv("EFTB_FETCH_TIMEOUT_S")) : 60.0;
-            const auto tw0 = std::chrono::steady_clock::now();
-            for (unsigned wspins = 0;;) {
+        auto go = [&] {
+            for (;; ++e->launch_done) {
                 const long long inflight = (long long)(e->launch_seq - e->launch_done);
                 // go: below the in-flight limit AND (a full group is waiting, or the GPU is about to run dry: fewer than sub_low launches left)
                 if (inflight < e->sub_inflight &&
                     (inflight < e->sub_low || (long long)(e->sub_tail.load(std::memory_order_acquire) - head) >= e->coalesce_max ||
-                     e->sub_flush.load(std::memory_order_acquire))) break;
-                if (inflight > 0 && launch_finished(e, e->launch_done)) { ++e->launch_done; continue; }
-                for (int i = 0; i < 16; ++i) cpu_pause();
-                // (a launch that never finishes must not hold the queue -- and with it every entry point that drains it -- for ever: the steps go
-                // out anyway and their fetches report the time-out)
-                if ((++wspins & 0xffff) == 0 && (e->sub_stop.load(std::memory_order_acquire) ||
-                                                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count() > limit_s)) break;
+                     e->sub_flush.load(std::memory_order_acquire))) return true;
+                if (inflight <= 0 || !launch_finished(e, e->launch_done)) return false;
             }
-        }
-        eftb_engine::SubCmd grp[8];
+        };
+        // (a launch that never finishes must not hold the queue -- and with it every entry point that drains it -- for ever: on a time-out the
+        // steps go out anyway and their fetches report it)
+        (void)spin_until([&] { return go() || e->sub_stop.load(std::memory_order_acquire); }, 0xffff, 16);
+        eftb_engine::SubCmd grp[MAX_COALESCE];
         int n = 0, Bt = 0;
         const unsigned long long tail = e->sub_tail.load(std::memory_order_acquire);
         while (head + n < tail && n < e->coalesce_max) {
@@ -2968,15 +3076,9 @@ static void sub_stop_thread(eftb_engine* e) {
 
 // waits until the launch of staged step `step` has been issued, and reports its launch error (if any) as this call's
 static int sub_wait_launched(eftb_engine* e, unsigned long long step, const char* who) {
-    static const double limit_s = getenv("EFTB_FETCH_TIMEOUT_S") ? atof(getenv("EFTB_FETCH_TIMEOUT_S")) : 60.0;
-    if (e->steps_launched.load(std::memory_order_acquire) <= step) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0; e->steps_launched.load(std::memory_order_acquire) <= step; ++spins) {
-            cpu_pause();
-            if ((spins & 0xffff) == 0xffff && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s)
-                return fail("%s: the submission thread did not issue the step within %.0f s (EFTB_FETCH_TIMEOUT_S)", who, limit_s);
-        }
-    }
+    auto issued = [&] { return e->steps_launched.load(std::memory_order_acquire) > step; };
+    if (!issued() && !spin_until(issued, 0xffff))   // (the usual case takes no clock reading)
+        return fail("%s: the submission thread did not issue the step within %.0f s (EFTB_FETCH_TIMEOUT_S)", who, fetch_timeout_s());
     const int r = (int)(step % eftb_engine::SUBREC);
     if (e->rec[r].rc) return fail("%s: the launch of this step failed: %s", who, e->sub_err[r]);
     return 0;
@@ -3011,8 +3113,7 @@ int eftb_stage_inputs(eftb_engine* e, int B, const double* Pin, const double* f,
         (void)sub_wait_launched(e, e->slot_step[slot] - 1, "eftb_stage_inputs");  // (a failed launch left nothing to wait for; its fetch reports it)
         const eftb_engine::StepRec& r = e->rec[(e->slot_step[slot] - 1) % eftb_engine::SUBREC];
         // (a launch whose completion word has been written is over, its upload with it: no runtime call -- hipEventSynchronize costs this thread 6 us per step)
-        const bool over = r.launch != ~0ull && e->set_word[r.set] >= r.launch + 1 && e->set_done[r.set] >= r.launch + 1;
-        if (r.launch != ~0ull && !over) {
+        if (r.launch != ~0ull && !launch_over(e, r.set, r.launch, false)) {
             const int lr = (int)(r.launch % eftb_engine::NLRING);
             // ... and the block is free again (the upload from it has finished; a latency-mode step's first kernel read P_lin from the block itself:
             // that step must be over too -- it almost always is)
@@ -3082,6 +3183,7 @@ int eftb_run_staged(eftb_engine* e, int mask, int B) {
         if (!e->plk_host[0]) return fail("eftb_run_staged: eftb_set_step_output needs an engine whose P_l leaves through the copy-out (no communicator)");
     }
     const eftb_engine::SubCmd cmd{e->stg_slot, mask, B, e->stg_rows, step, out, e->stg_out_count};
+    int rc = 0;
     if (!e->stg_inline) {  // queued: the submission thread uploads the staging block and launches the step (with whatever else is queued by then)
         if (!e->sub_started) {
             e->sub_stop.store(false);
@@ -3096,15 +3198,12 @@ int eftb_run_staged(eftb_engine* e, int mask, int B) {
             std::lock_guard<std::mutex> lk(e->sub_mx);
             e->sub_cv.notify_one();
         }
-        e->slot_step[e->stg_slot] = step + 1;
-        e->stg_slot = -1;
-        ++e->steps_submitted;
-        return 0;
+    } else {
+        sub_drain(e);
+        // (launch bookkeeping of the issuing thread: bring "finished" up to date, as the submission thread does before its launches)
+        while (e->launch_done < e->launch_seq && launch_finished(e, e->launch_done)) ++e->launch_done;
+        rc = issue_and_publish(e, &cmd, 1, e->stg_lat, true);
     }
-    sub_drain(e);
-    // (launch bookkeeping of the issuing thread: bring "finished" up to date, as the submission thread does before its launches)
-    while (e->launch_done < e->launch_seq && launch_finished(e, e->launch_done)) ++e->launch_done;
-    const int rc = issue_and_publish(e, &cmd, 1, e->stg_lat, true);
     e->slot_step[e->stg_slot] = step + 1;
     e->stg_slot = -1;
     ++e->steps_submitted;
@@ -3116,15 +3215,10 @@ static int wait_step_done(eftb_engine* e, const eftb_engine::StepRec& r, const c
     const auto tw0 = std::chrono::steady_clock::now();
     int rc = 0;
     const int t = r.set;
-    if (e->set_word[t] >= r.launch + 1) {   // (else: no completion write was enqueued for this launch -- EFTB_DONE_WORDS=0, or the runtime refused it)
-        static const double limit_s = getenv("EFTB_FETCH_TIMEOUT_S") ? atof(getenv("EFTB_FETCH_TIMEOUT_S")) : 60.0;
-        for (unsigned spins = 0; e->set_done[t] < r.launch + 1; ++spins) {
-            cpu_pause();
-            if ((spins & 0xfffff) == 0xfffff && std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count() > limit_s) {
-                rc = fail("%s: the step did not finish within %.0f s (EFTB_FETCH_TIMEOUT_S)", who, limit_s);
-                break;
-            }
-        }
+    if (const volatile unsigned long long* w = done_word_of(e, t, r.launch, false)) {   // (else: no completion write was enqueued for this launch)
+        const unsigned long long want = r.launch + 1;
+        if (!spin_until([w, want] { return *w >= want; }, 0xfffff, 1, tw0))
+            rc = fail("%s: the step did not finish within %.0f s (EFTB_FETCH_TIMEOUT_S)", who, fetch_timeout_s());
         std::atomic_thread_fence(std::memory_order_acquire);
     } else {
         rc = spin_event(e->evSetDone[t], who, "the step");
@@ -3150,20 +3244,36 @@ static inline size_t step_offset(const eftb_engine* e, const eftb_engine::StepRe
     return id == EFTB_B_PLK ? (size_t)r.row * r.nl * r.nx : (size_t)(r.row / e->ntr) * MARG_OUT;
 }
 
+// front half of both fetches: the step's record once its launch has finished, and where its rows start in the set's block.  count: elements the
+// caller wants copied (a view: 0); view: the block itself is handed out, so it has to be in host memory
+static int fetch_front(eftb_engine* e, const char* who, int back, int id, size_t count, bool view, const eftb_engine::StepRec** rec, size_t* off) {
+    if (id != EFTB_B_PLK && id != EFTB_B_LOGP) return fail("%s: only EFTB_B_PLK and EFTB_B_LOGP are per-set outputs", who);
+    if (count > e->buf_elems[id]) return fail("%s: buffer %d holds %zu elements, asked %zu", who, id, e->buf_elems[id], count);
+    if (int rc = staged_step(e, who, back, rec)) return rc;
+    HIPCHK(hipSetDevice(e->c.device));
+    if (view && id == EFTB_B_PLK && !e->plk_host[(*rec)->set])
+        return fail("%s: P_l of this engine stays in device memory for the RCCL exchange (eftb_gathered_view hands out the gathered block)", who);
+    if (int rc = wait_step_done(e, **rec, who)) return rc;
+    *off = step_offset(e, **rec, id);
+    return 0;
+}
+
+// the step's P_l went to the caller's own array (eftb_set_step_output), this many doubles of it
+static inline bool step_own_plk(const eftb_engine::StepRec& r, int id, size_t* elems) {
+    *elems = (size_t)r.B * r.nl * r.nx;
+    return id == EFTB_B_PLK && r.out;
+}
+
 int eftb_fetch_back(eftb_engine* e, int back, int id, double* host, size_t count) {
     if (!e || !host) return fail("eftb_fetch_back: null argument");
-    if (id != EFTB_B_PLK && id != EFTB_B_LOGP) return fail("eftb_fetch_back: only EFTB_B_PLK and EFTB_B_LOGP are per-set outputs");
-    if (count > e->buf_elems[id]) return fail("eftb_fetch_back: buffer %d holds %zu elements, asked %zu", id, e->buf_elems[id], count);
     const eftb_engine::StepRec* r = nullptr;
-    if (int rc = staged_step(e, "eftb_fetch_back", back, &r)) return rc;
-    HIPCHK(hipSetDevice(e->c.device));
+    size_t off = 0, own = 0;
+    if (int rc = fetch_front(e, "eftb_fetch_back", back, id, count, false, &r, &off)) return rc;
     const int t = r->set;
-    if (int rc = wait_step_done(e, *r, "eftb_fetch_back")) return rc;
-    const size_t off = step_offset(e, *r, id);
     if (off + count > e->buf_elems[id]) return fail("eftb_fetch_back: the step's rows start at element %zu of %zu, asked %zu", off, e->buf_elems[id], count);
-    if (id == EFTB_B_PLK && r->out) {
-        if (count > (size_t)r->B * r->nl * r->nx) return fail("eftb_fetch_back: the step's P_l has %zu elements, asked %zu", (size_t)r->B * r->nl * r->nx, count);
-        if (host != r->out) memcpy(host, r->out, count * sizeof(double));  // (it went to the caller's own array: eftb_set_step_output)
+    if (step_own_plk(*r, id, &own)) {
+        if (count > own) return fail("eftb_fetch_back: the step's P_l has %zu elements, asked %zu", own, count);
+        if (host != r->out) memcpy(host, r->out, count * sizeof(double));
     } else if (id == EFTB_B_PLK && e->plk_host[t])
         memcpy(host, e->plk_host[t] + off, count * sizeof(double));  // copied out behind the step
     else if (id == EFTB_B_PLK)  // multi-GPU runs keep P_l on the device for the RCCL exchange
@@ -3177,22 +3287,13 @@ int eftb_fetch_previous(eftb_engine* e, int id, double* host, size_t count) { re
 
 int eftb_fetch_view(eftb_engine* e, int back, int id, const double** block, size_t* count) {
     if (!e || !block) return fail("eftb_fetch_view: null argument");
-    if (id != EFTB_B_PLK && id != EFTB_B_LOGP) return fail("eftb_fetch_view: only EFTB_B_PLK and EFTB_B_LOGP are per-set outputs");
     const eftb_engine::StepRec* r = nullptr;
-    if (int rc = staged_step(e, "eftb_fetch_view", back, &r)) return rc;
-    HIPCHK(hipSetDevice(e->c.device));
+    size_t off = 0, own = 0;
+    if (int rc = fetch_front(e, "eftb_fetch_view", back, id, 0, true, &r, &off)) return rc;
     const int t = r->set;
-    const double* p = id == EFTB_B_PLK ? e->plk_host[t] : e->setbuf[t][id];
-    if (!p) return fail("eftb_fetch_view: P_l of this engine stays in device memory for the RCCL exchange (eftb_gathered_view hands out the gathered block)");
-    if (int rc = wait_step_done(e, *r, "eftb_fetch_view")) return rc;
-    const size_t off = step_offset(e, *r, id);
-    if (id == EFTB_B_PLK && r->out) {   // the step's P_l went to the caller's own array (eftb_set_step_output): that is the block
-        *block = r->out;
-        if (count) *count = (size_t)r->B * r->nl * r->nx;
-        return check_status(e, "eftb_fetch_view", t);
-    }
-    *block = p + off;
-    if (count) *count = e->buf_elems[id] - off;
+    const bool own_plk = step_own_plk(*r, id, &own);   // (then the caller's array is the block)
+    *block = own_plk ? r->out : (id == EFTB_B_PLK ? e->plk_host[t] : e->setbuf[t][id]) + off;
+    if (count) *count = own_plk ? own : e->buf_elems[id] - off;
     return check_status(e, "eftb_fetch_view", t);
 }
 

@@ -4,8 +4,10 @@
     python3 tools/ab_bits.py cmp A.npz B.npz                   exit status 1 unless both hold the same arrays, array_equal each
 
 One dump per process: _lib.py reads EFTB_LIB once, when it is loaded.  The kernels use integer atomics only (status flags, a min / max in
-ap_weights_kernel), so a build must reproduce itself, and a host-side refactor its parent, in every case.  Each case names the arm of the stage
-launcher (launch_stages_impl) it is there for; shapes are the smallest that reach the arm."""
+ap_weights_kernel), so a build must reproduce itself, and a host-side refactor its parent, in every case.  Each case names the arm it is there
+for -- of the stage launcher (launch_stages_impl) or of the staged launch around it (issue_group: every value of PlkExit,
+both completion rules, both issuing threads, both upload streams, per-step destinations, the GROWS upload); shapes are the
+smallest that reach the arm."""
 import os
 import sys
 
@@ -105,6 +107,114 @@ def staged_direct():
     return got
 
 
+def staged_engine(B, nk=None, direct=True):
+    import bench
+    eng = Engine(cfg(k=synth.survey_kgrid(nk or bench.NK)), max_batch=B, coalesce=3)
+    eng.set_plk_direct(direct)
+    eng.set_latency_mode(False)
+    return eng, eng.full_mask(reduce=True), (B, bench.NL, nk or bench.NK)
+
+
+def held_launch(eng, mask, steps, outs):
+    """the steps leave as ONE launch (the submission thread is held while they are queued), step i into outs[i] (None: the set's own block)"""
+    eng.set_submit_thread(2)
+    eng.hold_submissions(True)
+    for s, out in zip(steps, outs):
+        eng.step(mask, s["Pin"], s["f"], s["DA"], s["H"], bias=s["bias"], out=out)
+    eng.hold_submissions(False)
+
+
+def staged_outputs():
+    """eftb_set_step_output: launches of three steps whose destinations follow each other in memory (one transfer), leave a gap (one each),
+    have a step without a destination between them; then a free-running loop, every step into its own slice"""
+    B, K, depth = 16, 12, 4
+    eng, mask, shape = staged_engine(B)
+    sets, dest, got = [draws(B, 830 + i) for i in range(3)], eng.pinned_empty((K,) + shape), []
+    for slots in ((0, 1, 2), (3, 5, 7), (8, None, 9)):
+        dest.fill(-1.0)
+        held_launch(eng, mask, sets, [None if j is None else dest[j] for j in slots])
+        got += [eng.fetch_previous("PLK", shape, back=2 - i) for i in range(3)] + [dest.copy()]
+    dest.fill(-1.0)
+    eng.set_submit_thread(1)
+    for i in range(K):
+        s = sets[i % 3]
+        eng.step(mask, s["Pin"], s["f"], s["DA"], s["H"], bias=s["bias"], back=depth if i >= depth else -1, shape=shape, out=dest[i])
+    for back in range(depth - 1, -1, -1):
+        eng.fetch_previous("PLK", shape, back=back, copy=False)
+    got.append(dest.copy())
+    eng.close()
+    return got
+
+
+def staged_odd():
+    """odd nx and an odd batch: the later steps of a launch start at addresses that are only 8-byte aligned (EFTB_PLK_DMA=0: copy8_kernel)"""
+    import bench
+    B, K, depth = 5, 12, 4
+    eng, mask, shape = staged_engine(B, nk=bench.NK - 1)
+    sets, dest, got = [draws(B, 840 + i) for i in range(3)], eng.pinned_empty((3,) + shape), []
+    held_launch(eng, mask, sets, [None] * 3)
+    got += [eng.fetch_previous("PLK", shape, back=2 - i) for i in range(3)]
+    dest.fill(-1.0)
+    held_launch(eng, mask, sets, [dest[2], dest[0], dest[1]])
+    got += [eng.fetch_previous("PLK", shape, back=2 - i) for i in range(3)] + [dest.copy()]
+    eng.set_submit_thread(1)
+    for i in range(K):
+        s = sets[i % 3]
+        view = eng.step(mask, s["Pin"], s["f"], s["DA"], s["H"], bias=s["bias"], back=depth if i >= depth else -1, shape=shape)
+        if i >= depth:
+            got.append(view.copy())
+    got += [eng.fetch_previous("PLK", shape, back=back) for back in range(depth - 1, -1, -1)]
+    eng.close()
+    return got
+
+
+def staged_templates_first():
+    """the staged loop with set_plk_direct(False): P_l leaves through the copy behind the back half, which the next join waits for"""
+    B, K, depth = 16, 12, 4
+    eng, mask, shape = staged_engine(B, direct=False)
+    sets, got = [draws(B, 850 + i) for i in range(3)], []
+    for i in range(K):
+        s = sets[i % 3]
+        view = eng.step(mask, s["Pin"], s["f"], s["DA"], s["H"], bias=s["bias"], back=depth if i >= depth else -1, shape=shape)
+        if i >= depth:
+            got.append(view.copy())
+    got += [eng.fetch_previous("PLK", shape, back=back) for back in range(depth - 1, -1, -1)]
+    eng.close()
+    return got
+
+
+def staged_logp():
+    """a staged LOGP loop: every step brings its likelihood rows (the GROWS segment of the upload), ln P fetched from the set's mapped block"""
+    from eftpipe_amd.marginal import MarginalLikelihood
+    B, K, depth, nG = 4, 12, 3, 5
+    eng, rng = Engine(cfg(), max_batch=B, coalesce=3), np.random.default_rng(23)
+    eng.set_pipeline_operator(eng.add_operator(thin(eng, 2)))
+    index = np.arange(0, 3 * eng.out_dims()[1], 4)
+    A = 0.03 * rng.standard_normal((index.size, index.size))
+    MarginalLikelihood(eng, index, 1e3 * rng.standard_normal(index.size), 1e-6 * (np.eye(index.size) + A @ A.T), np.zeros(nG), np.full(nG, 2.0))
+    sets = [draws(n, 860 + n) for n in (4, 3, 1)]
+    for s in sets:
+        s["rows"] = np.concatenate([s["bias"][:, None, :], 0.1 * rng.standard_normal((s["bias"].shape[0], nG, 24))], axis=1)
+    mask, got = eng.full_mask() | L.S_LOGP, []
+    eng.set_latency_mode(False)
+    eng.set_submit_thread(2)
+    eng.hold_submissions(True)
+    for s in sets:
+        eng.step(mask, s["Pin"], s["f"], s["DA"], s["H"], rows=s["rows"])
+    eng.hold_submissions(False)
+    got += [eng.fetch_previous("LOGP", (sets[i]["f"].size, 26), back=2 - i) for i in range(3)]
+    eng.set_submit_thread(1)
+    size = lambda i: sets[i % 3]["f"].size
+    for i in range(K):
+        s = sets[i % 3]
+        view = eng.step(mask, s["Pin"], s["f"], s["DA"], s["H"], rows=s["rows"], back=depth if i >= depth else -1, fetch="LOGP", shape=(size(i - depth), 26))
+        if i >= depth:
+            got.append(view.copy())
+    got += [eng.fetch_previous("LOGP", (size(K - 1 - back), 26), back=back) for back in range(depth - 1, -1, -1)]
+    eng.close()
+    return got
+
+
 def logp_tracers():
     """eval_logp with two tracers per walker (marg_build, U = V C^-1, marg_solve)"""
     from eftpipe_amd.marginal import MarginalLikelihood
@@ -163,6 +273,15 @@ CASES = {
     "staged_direct": ("front_side, coalesced launches, host-written P_l; AP form ap_plk_fused", {}, staged_direct),
     "staged_direct_mom": ("... AP form ap_prefix + ap_plk_mom", {"EFTB_AP_PLK_FUSED": "0"}, staged_direct),
     "staged_direct_nodes": ("... AP form ap_plk (node quadrature)", {"EFTB_AP_PLK_NODES": "1"}, staged_direct),
+    # the arms of the staged launch (issue_group)
+    "staged_copy_kernel": ("P_l leaves through copy16_kernel", {"EFTB_PLK_DMA": "0"}, staged_direct),
+    "staged_event_completion": ("no completion words: the set's event answers 'finished?'", {"EFTB_DONE_WORDS": "0"}, staged_direct),
+    "staged_by_caller": ("every launch issued by the calling thread", {"EFTB_SUBMIT_THREAD": "0"}, staged_direct),
+    "staged_upload_on_copy": ("uploads on the copy stream: three streams wait for them", {"EFTB_UPLOAD_ON_SIDE": "0"}, staged_direct),
+    "staged_outputs": ("per-step destinations: contiguous (merged), with a gap, around a step without one", {}, staged_outputs),
+    "staged_odd_copy8": ("odd nx, odd batch: copy8_kernel for the later steps of a launch", {"EFTB_PLK_DMA": "0"}, staged_odd),
+    "staged_templates_first": ("templates-first launches: the DMA copy behind the back half, evBack recorded again", {}, staged_templates_first),
+    "staged_logp": ("LOGP steps with likelihood rows: the GROWS segments of the upload, ln P from the mapped block", {}, staged_logp),
     "direct_project": ("direct_proj, one operator", {}, sync_eval(4, 4, direct=True, ops=[lambda e: thin(e, 2)])),
     "direct_project_tracers": ("direct_proj, per-tracer operators", {}, sync_eval(4, 4, direct=True, tracers=2, ops=[lambda e: thin(e, 2), lambda e: 0.9 * thin(e, 2)])),
     "project_st_op": ("templates-first PROJECT, stochastic companion (st_op)", {}, sync_eval(3, 3, APst=True, ops=[(lambda e: thin(e, 2), lambda e: 0.5 * thin(e, 2))])),
