@@ -20,12 +20,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <tuple>
 #include <algorithm>
 #include <vector>
 
 #include "eftb_kernels.hpp"
+#include "eftb_own.hpp"
 #include "eftb_staged.hpp"
 
 using namespace eftb;
@@ -53,14 +55,61 @@ static int fail(const char* fmt, ...) {
     return 1;
 }
 
+// (a failed call's error is reported here: the runtime would otherwise keep it for the next hipGetLastError, some other call's launch check)
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+        if (_e != hipSuccess) {                                                               \
+            (void)hipGetLastError();                                                          \
+            return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+        }                                                                                     \
     } while (0)
+
+// Everything that is acquired -- device memory (zero: filled with zeros on the null stream), page-locked memory, events (flags 0: a timing
+// event), streams -- is acquired here and held by a ledger (eftb_own.hpp) from then on: the engine's, or a probe's local one.  The ledger
+// alone releases; the pointers the callers keep only view.  (eftb_host_alloc / eftb_host_free: the caller's memory, not held anywhere.)
+static void drop_dev(void* p) { (void)hipFree(p); }
+static void drop_host(void* p) { (void)hipHostFree(p); }
+static void drop_event(void* p) { (void)hipEventDestroy(static_cast<hipEvent_t>(p)); }
+static void drop_stream(void* p) { (void)hipStreamDestroy(static_cast<hipStream_t>(p)); }
+
+template <class T>
+static hipError_t own_dev(Ledger& own, T** p, size_t bytes, bool zero = false) {
+    void* q = nullptr;
+    *p = nullptr;
+    if (hipError_t st = hipMalloc(&q, bytes); st != hipSuccess) return st;
+    own.hold(q, drop_dev);
+    *p = static_cast<T*>(q);
+    return zero ? hipMemset(q, 0, bytes) : hipSuccess;
+}
+
+template <class T>
+static hipError_t own_host(Ledger& own, T** p, size_t bytes, unsigned flags) {
+    void* q = nullptr;
+    *p = nullptr;
+    if (hipError_t st = hipHostMalloc(&q, bytes, flags); st != hipSuccess) return st;
+    own.hold(q, drop_host);
+    *p = static_cast<T*>(q);
+    return hipSuccess;
+}
+
+static hipError_t own_event(Ledger& own, hipEvent_t* ev, unsigned flags = 0) {
+    *ev = nullptr;
+    if (hipError_t st = flags ? hipEventCreateWithFlags(ev, flags) : hipEventCreate(ev); st != hipSuccess) return st;
+    own.hold(*ev, drop_event);
+    return hipSuccess;
+}
+
+static hipError_t own_stream(Ledger& own, hipStream_t* s, int prio) {
+    *s = nullptr;
+    if (hipError_t st = hipStreamCreateWithPriority(s, hipStreamNonBlocking, prio); st != hipSuccess) return st;
+    own.hold(*s, drop_stream);
+    return hipSuccess;
+}
 
 struct eftb_engine {
     eftb_config c;
+    Ledger own;  // everything below that came from the device runtime; released newest first when the engine is deleted (eftb_destroy)
     hipStream_t stream = nullptr, side = nullptr;   // side: the small input-only kernels (IR filters, AP prefix sums) run beside the loop path
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evFork = nullptr, evJoin = nullptr, evJoinAP = nullptr;  // evJoin: X, Y, Q(f) ready; evJoinAP: AP prefix sums + knot weights ready
     bool finalized = false;
@@ -1619,10 +1668,12 @@ static int launch_stages(eftb_engine* e, int mask, int B) {
     return tail ? launch_stages_impl(e, tail, B, false) : 0;
 }
 
-// the likelihood's device arrays (eftb_set_likelihood replaces them, eftb_destroy drops them)
-static void free_likelihood(eftb_engine* e) {
-    for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) if (p) (void)hipFree(p);
+// the likelihood's device arrays go (eftb_set_likelihood replaces them), and with them the likelihood: until the next one is complete every
+// call that needs one refuses, as after eftb_set_tracers
+static void drop_likelihood(eftb_engine* e) {
+    for (void* p : {(void*)e->like_index, (void*)e->like_data, (void*)e->like_invcov, (void*)e->like_mu, (void*)e->like_sinv, (void*)e->like_V, (void*)e->like_U}) e->own.release(p);
     e->like_index = nullptr; e->like_data = e->like_invcov = e->like_mu = e->like_sinv = e->like_V = e->like_U = nullptr;
+    e->like_ndata = e->like_nG = 0;
 }
 
 static void drop_graphs(eftb_engine* e) {
@@ -1693,14 +1744,14 @@ static int run_stages(eftb_engine* e, int mask, int B) {
 // back / copy stream, each touched once so that its hardware queue exists.  Which hardware queue a stream lands on decides which other streams'
 // barrier packets its kernels wait behind (round 4: the copy-out of P_l on a stream of its own ran at 0.16 or 0.103 ms per step depending on how
 // many streams were created before it) -- a sweep of the placement of the engine's own five streams, tools/pad_sweep.sh.
-static int pad_streams(int which, int prio) {
+static int pad_streams(eftb_engine* e, int which, int prio) {
     const char* f = getenv("EFTB_STREAM_PAD");
     if (!f) return 0;
     int v[5] = {0, 0, 0, 0, 0};
     sscanf(f, "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]);
     for (int i = 0; i < v[which]; ++i) {
         hipStream_t dummy = nullptr;
-        HIPCHK(hipStreamCreateWithPriority(&dummy, hipStreamNonBlocking, prio));
+        HIPCHK(own_stream(e->own, &dummy, prio));
         hipLaunchKernelGGL(wake_kernel, dim3(1), dim3(64), 0, dummy);
     }
     return 0;
@@ -1736,7 +1787,9 @@ int eftb_create(const eftb_config* cfg, eftb_engine** out) {
         return fail("eftb_create: no HIP device visible -- libeftbird has no CPU fallback");
     if (c.device < 0 || c.device >= ndev) return fail("eftb_create: device %d out of range (%d visible)", c.device, ndev);
     HIPCHK(hipSetDevice(c.device));
-    eftb_engine* e = new eftb_engine();
+    struct Destroy { void operator()(eftb_engine* p) const { eftb_destroy(p); } };
+    std::unique_ptr<eftb_engine, Destroy> guard(new eftb_engine());  // every failing exit below destroys what the engine holds so far
+    eftb_engine* e = guard.get();
     e->c = c;
     for (int& g : e->gath_set) g = eftb_engine::NSETS;
     e->Nn = 2 * c.NIR * c.Na;
@@ -1755,101 +1808,97 @@ int eftb_create(const eftb_config* cfg, eftb_engine** out) {
         const char* f = getenv(name);
         return !f ? dflt : (atoi(f) > 0 ? prio_lo : (atoi(f) < 0 ? prio_hi : 0));
     };
-    if (int rc = pad_streams(0, prio_of("EFTB_MAIN_PRIO", prio_lo))) return rc;
-    HIPCHK(hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, prio_of("EFTB_MAIN_PRIO", prio_lo)));
-    if (int rc = pad_streams(1, prio_of("EFTB_SIDE_PRIO", 0))) return rc;
-    HIPCHK(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, prio_of("EFTB_SIDE_PRIO", 0)));
-    if (int rc = pad_streams(2, prio_of("EFTB_PRE_PRIO", prio_hi))) return rc;
-    HIPCHK(hipStreamCreateWithPriority(&e->pre, hipStreamNonBlocking, prio_of("EFTB_PRE_PRIO", prio_hi)));
-    HIPCHK(hipEventCreateWithFlags(&e->evPrep, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evFront, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evFrontFree[0], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evFrontFree[1], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evXY, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evAS, hipEventDisableTiming));
+    if (int rc = pad_streams(e, 0, prio_of("EFTB_MAIN_PRIO", prio_lo))) return rc;
+    HIPCHK(own_stream(e->own, &e->stream, prio_of("EFTB_MAIN_PRIO", prio_lo)));
+    if (int rc = pad_streams(e, 1, prio_of("EFTB_SIDE_PRIO", 0))) return rc;
+    HIPCHK(own_stream(e->own, &e->side, prio_of("EFTB_SIDE_PRIO", 0)));
+    if (int rc = pad_streams(e, 2, prio_of("EFTB_PRE_PRIO", prio_hi))) return rc;
+    HIPCHK(own_stream(e->own, &e->pre, prio_of("EFTB_PRE_PRIO", prio_hi)));
+    HIPCHK(own_event(e->own, &e->evPrep, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evFront, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evFrontFree[0], hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evFrontFree[1], hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evXY, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evAS, hipEventDisableTiming));
     if (const char* f = getenv("EFTB_AP_OVERLAP")) e->ap_overlap = atoi(f) != 0;
     {
         int bp = prio_lo;  // measured: 290 k evaluations/s with the back half at low priority, 286 k at high, 278 k without the stream
         if (const char* f = getenv("EFTB_BACK_PRIO")) bp = atoi(f) > 0 ? prio_lo : (atoi(f) < 0 ? prio_hi : 0);
-        if (int rc = pad_streams(3, bp)) return rc;
-        HIPCHK(hipStreamCreateWithPriority(&e->back, hipStreamNonBlocking, bp));
+        if (int rc = pad_streams(e, 3, bp)) return rc;
+        HIPCHK(own_stream(e->own, &e->back, bp));
     }
-    HIPCHK(hipEventCreateWithFlags(&e->evResum, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evBack[0], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evBack[1], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evInFree, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evResum, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evBack[0], hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evBack[1], hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evInFree, hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->evInFree, e->pre));
-    HIPCHK(hipEventCreateWithFlags(&e->evFork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evJoin, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->evJoinAP, hipEventDisableTiming));
-    for (hipEvent_t& ev : e->evRsDone) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (hipEvent_t& ev : e->evRun) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evFork, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evJoin, hipEventDisableTiming));
+    HIPCHK(own_event(e->own, &e->evJoinAP, hipEventDisableTiming));
+    for (hipEvent_t& ev : e->evRsDone) HIPCHK(own_event(e->own, &ev, hipEventDisableTiming));
+    for (hipEvent_t& ev : e->evRun) HIPCHK(own_event(e->own, &ev, hipEventDisableTiming));
     for (int t = 0; t < eftb_engine::NTIMER; ++t) {
-        HIPCHK(hipEventCreate(&e->evT0[t]));
-        HIPCHK(hipEventCreate(&e->evT1[t]));
+        HIPCHK(own_event(e->own, &e->evT0[t]));
+        HIPCHK(own_event(e->own, &e->evT1[t]));
     }
-    HIPCHK(hipEventCreate(&e->ev0));
-    HIPCHK(hipEventCreate(&e->ev1));
+    HIPCHK(own_event(e->own, &e->ev0));
+    HIPCHK(own_event(e->own, &e->ev1));
     for (int id = 0; id < EFTB_B_COUNT; ++id) {
         const size_t n = need_buffer_elems(c, id);
         e->buf_elems[id] = n;
-        if (n) {
-            HIPCHK(hipMalloc(&e->buf[id], (n + 2) * sizeof(double)));  // (+2: ap_rows_kernel's 16-byte window loads may end one element past a row)
-            HIPCHK(hipMemset(e->buf[id], 0, (n + 2) * sizeof(double)));
-        }
+        if (n) HIPCHK(own_dev(e->own, &e->buf[id], (n + 2) * sizeof(double), true));  // (+2: ap_rows_kernel's 16-byte window loads may end one element past a row)
     }
     const size_t B = c.max_batch;
-    HIPCHK(hipMalloc(&e->sm2, NS * sizeof(double)));
-    HIPCHK(hipMalloc(&e->sm4, NS * sizeof(double)));
+    HIPCHK(own_dev(e->own, &e->sm2, NS * sizeof(double)));
+    HIPCHK(own_dev(e->own, &e->sm4, NS * sizeof(double)));
     // scratch of the anti-diagonal pipeline; padded rows / coefficients of the synthesis rows stay zero
     {
         const size_t nc = c.nbasis + (c.with_resum ? c.nbasis13 : 0);
         // sizes of this NFFT: NCH coefficients, NPOW anti-diagonals, synthesis rows of 1 + 4 nh / 1 + 2 nh (padded)
         const size_t nch = cfg_nch(c), npow = cfg_npow(c), ksyn = ksyn_of(cfg_nh(c)), klin = klin_of(cfg_nh(c));
-        auto zalloc = [](double** p, size_t n) {
-            if (hipMalloc(p, n * sizeof(double)) != hipSuccess) return 1;
-            return hipMemset(*p, 0, n * sizeof(double)) != hipSuccess ? 1 : 0;
+        struct Zeroed { double** p; size_t n; };  // (p null: not in this configuration)
+        auto zeroed = [&](std::initializer_list<Zeroed> list) {
+            for (const Zeroed& z : list)
+                if (z.p && own_dev(e->own, z.p, z.n * sizeof(double), true) != hipSuccess) return false;
+            return true;
         };
-        int bad = zalloc(&e->coefT, 2 * nch * B);
-        bad |= zalloc(&e->PA1, B * kpad(c.Nkin)) | zalloc(&e->PA2, B * kpad(c.Nkin + c.ntail)) | zalloc(&e->PA2T, B * kpad(c.Nkin + c.ntail));
-        if (c.with_resum) bad |= zalloc(&e->PA3, B * kpad(c.Nkin + c.nxtail));
-        if (c.dual_coef) bad |= zalloc(&e->coef2, 2 * nch * B) | zalloc(&e->coefT2, 2 * nch * B);
-        bad |= zalloc(reinterpret_cast<double**>(&e->SAD), 2 * (size_t)AD_CH * B * nc * npow);
-        bad |= zalloc(&e->A22, B * BAS22 * ksyn) | zalloc(&e->A13, B * 10 * klin) | zalloc(&e->Y22, B * BAS22 * c.Nk);
-        if (c.with_resum) bad |= zalloc(&e->ACF, B * BASC * ksyn) | zalloc(&e->ALC, B * (c.with_nnlo ? 3 : 2) * c.Nl * klin) | zalloc(&e->YCF, B * BASC * NS);
-        if (bad) return fail("eftb_create: out of device memory for the loop scratch");
+        const size_t nalc = B * (c.with_nnlo ? 3 : 2) * c.Nl * klin, nsad = 2 * (size_t)AD_CH * B * nc * npow;
+        const bool rs = c.with_resum, dual = c.dual_coef;
+        if (!zeroed({{&e->coefT, 2 * nch * B}, {&e->PA1, B * kpad(c.Nkin)}, {&e->PA2, B * kpad(c.Nkin + c.ntail)}, {&e->PA2T, B * kpad(c.Nkin + c.ntail)},
+                     {rs ? &e->PA3 : nullptr, B * kpad(c.Nkin + c.nxtail)}, {dual ? &e->coef2 : nullptr, 2 * nch * B}, {dual ? &e->coefT2 : nullptr, 2 * nch * B},
+                     {reinterpret_cast<double**>(&e->SAD), nsad}, {&e->A22, B * BAS22 * ksyn}, {&e->A13, B * 10 * klin}, {&e->Y22, B * BAS22 * c.Nk},
+                     {rs ? &e->ACF : nullptr, B * BASC * ksyn}, {rs ? &e->ALC : nullptr, nalc}, {rs ? &e->YCF : nullptr, B * BASC * NS}}))
+            return fail("eftb_create: out of device memory for the loop scratch");
         if (c.with_resum && c.Nl == 3 && !c.dual_coef) {  // second set of the front's outputs (direct-P_l runs, see FrontSet)
             eftb_engine::FrontSet& a = e->alt;
-            bad = zalloc(&a.coefT, 2 * nch * B) | zalloc(&a.PA1, B * kpad(c.Nkin)) | zalloc(&a.PA2, B * kpad(c.Nkin + c.ntail)) | zalloc(&a.PA2T, B * kpad(c.Nkin + c.ntail)) |
-                  zalloc(&a.PA3, B * kpad(c.Nkin + c.nxtail)) | zalloc(reinterpret_cast<double**>(&a.SAD), 2 * (size_t)AD_CH * B * nc * npow) |
-                  zalloc(&a.A22, B * BAS22 * ksyn) | zalloc(&a.A13, B * 10 * klin) | zalloc(&a.ACF, B * BASC * ksyn) | zalloc(&a.ALC, B * (c.with_nnlo ? 3 : 2) * c.Nl * klin) |
-                  zalloc(&a.P11, e->buf_elems[EFTB_B_P11]) | zalloc(&a.COEF, e->buf_elems[EFTB_B_COEF]) | zalloc(&a.XY, e->buf_elems[EFTB_B_XY]) |
-                  zalloc(&a.Q, e->buf_elems[EFTB_B_Q]);
-            if (bad) return fail("eftb_create: out of device memory for the second front set");
+            if (!zeroed({{&a.coefT, 2 * nch * B}, {&a.PA1, B * kpad(c.Nkin)}, {&a.PA2, B * kpad(c.Nkin + c.ntail)}, {&a.PA2T, B * kpad(c.Nkin + c.ntail)},
+                         {&a.PA3, B * kpad(c.Nkin + c.nxtail)}, {reinterpret_cast<double**>(&a.SAD), nsad}, {&a.A22, B * BAS22 * ksyn}, {&a.A13, B * 10 * klin},
+                         {&a.ACF, B * BASC * ksyn}, {&a.ALC, nalc}, {&a.P11, e->buf_elems[EFTB_B_P11]}, {&a.COEF, e->buf_elems[EFTB_B_COEF]},
+                         {&a.XY, e->buf_elems[EFTB_B_XY]}, {&a.Q, e->buf_elems[EFTB_B_Q]}}))
+                return fail("eftb_create: out of device memory for the second front set");
         }
     }
-    HIPCHK(hipMalloc(&e->Talt, (e->buf_elems[EFTB_B_TEMPL] + 2) * sizeof(double)));
+    HIPCHK(own_dev(e->own, &e->Talt, (e->buf_elems[EFTB_B_TEMPL] + 2) * sizeof(double)));
     if (c.with_ap) {
-        HIPCHK(hipMalloc(&e->SD, (e->buf_elems[EFTB_B_TEMPL] + 2) * sizeof(double)));  // knot slopes of the splines, laid out like the template block
-        HIPCHK(hipMemset(e->SD, 0, (e->buf_elems[EFTB_B_TEMPL] + 2) * sizeof(double)));
-        HIPCHK(hipMalloc(&e->APP, (size_t)c.max_batch * (c.nmu + 1) * c.Nl * c.Nl * 4 * sizeof(double)));
-        HIPCHK(hipMalloc(&e->APR, (size_t)c.max_batch * c.nmu * sizeof(double)));
-        HIPCHK(hipMalloc(&e->APP2, (size_t)c.max_batch * (c.nmu + 1) * c.Nl * c.Nl * 4 * sizeof(double)));
-        HIPCHK(hipMalloc(&e->APR2, (size_t)c.max_batch * c.nmu * sizeof(double)));
+        HIPCHK(own_dev(e->own, &e->SD, (e->buf_elems[EFTB_B_TEMPL] + 2) * sizeof(double), true));  // knot slopes of the splines, laid out like the template block
+        HIPCHK(own_dev(e->own, &e->APP, (size_t)c.max_batch * (c.nmu + 1) * c.Nl * c.Nl * 4 * sizeof(double)));
+        HIPCHK(own_dev(e->own, &e->APR, (size_t)c.max_batch * c.nmu * sizeof(double)));
+        HIPCHK(own_dev(e->own, &e->APP2, (size_t)c.max_batch * (c.nmu + 1) * c.Nl * c.Nl * 4 * sizeof(double)));
+        HIPCHK(own_dev(e->own, &e->APR2, (size_t)c.max_batch * c.nmu * sizeof(double)));
         const size_t kt = (c.Nk + 63) / 64;
         for (int q = 0; q < 2; ++q) {
-            HIPCHK(hipMalloc(q ? &e->APW2 : &e->APW, (size_t)c.max_batch * kt * APW_DCAP * c.Nl * c.Nl * 64 * sizeof(double)));
-            HIPCHK(hipMalloc(q ? &e->API2 : &e->API, (size_t)c.max_batch * kt * 64 * sizeof(int)));
-            HIPCHK(hipMalloc(q ? &e->APM2 : &e->APM, (size_t)c.max_batch * 2 * kt * sizeof(int4)));  // one window record per tile of 32 k
+            HIPCHK(own_dev(e->own, q ? &e->APW2 : &e->APW, (size_t)c.max_batch * kt * APW_DCAP * c.Nl * c.Nl * 64 * sizeof(double)));
+            HIPCHK(own_dev(e->own, q ? &e->API2 : &e->API, (size_t)c.max_batch * kt * 64 * sizeof(int)));
+            HIPCHK(own_dev(e->own, q ? &e->APM2 : &e->APM, (size_t)c.max_batch * 2 * kt * sizeof(int4)));  // one window record per tile of 32 k
         }
     }
     if (const char* f = getenv("EFTB_AP_PLK_NODES")) e->ap_plk_nodes = atoi(f) != 0;
     if (const char* f = getenv("EFTB_UPLOAD_ON_SIDE")) e->upload_on_side = atoi(f) != 0;
     if (const char* f = getenv("EFTB_SUBMIT_THREAD")) e->sub_mode = std::max(0, std::min(2, atoi(f)));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->status), 2 * (eftb_engine::NSETS + 1) * sizeof(int), hipHostMallocMapped));
+    HIPCHK(own_host(e->own, &e->status, 2 * (eftb_engine::NSETS + 1) * sizeof(int), hipHostMallocMapped));
     memset(e->status, 0, 2 * (eftb_engine::NSETS + 1) * sizeof(int));
     HIPCHK(hipDeviceSynchronize());  // the zero fills above ran on the null stream, which the engine's non-blocking streams do not wait for
-    *out = e;
+    *out = guard.release();
     return 0;
 }
 
@@ -1862,7 +1911,7 @@ int eftb_set_table(eftb_engine* e, int id, const void* host, size_t nbytes) {
     if (need == 0) return fail("eftb_set_table: table %d is not used by this configuration", id);
     if (need != nbytes) return fail("eftb_set_table: table %d expects %zu bytes, got %zu", id, need, nbytes);
     HIPCHK(hipSetDevice(e->c.device));
-    if (!e->tab[id]) HIPCHK(hipMalloc(&e->tab[id], nbytes));
+    if (!e->tab[id]) HIPCHK(own_dev(e->own, &e->tab[id], nbytes));
     else if (e->finalized) HIPCHK(sync_all(e));  // replacing a resident table (e.g. the AP fiducial): no run may still be reading it
     HIPCHK(hipMemcpy(e->tab[id], host, nbytes, hipMemcpyHostToDevice));
     e->tab_bytes[id] = nbytes;
@@ -1889,26 +1938,25 @@ int eftb_finalize(eftb_engine* e) {
         e->resum_splits = c.max_batch >= 16 ? 1 : 8;
         {
             const size_t pbytes = (size_t)c.max_batch * e->resum_splits * 2 * c.Nl * c.Nl * 21 * c.Nk * sizeof(double);
-            HIPCHK(hipMalloc(&e->part, pbytes));
-            HIPCHK(hipMemset(e->part, 0, pbytes));  // the matrix-core kernel never touches k < Nklow
+            HIPCHK(own_dev(e->own, &e->part, pbytes, true));  // (zero: the matrix-core kernel never touches k < Nklow)
         }
-        if (c.optiresum) HIPCHK(hipMalloc(&e->XB, (size_t)c.max_batch * c.Nl * 14 * NS * sizeof(double)));
+        if (c.optiresum) HIPCHK(own_dev(e->own, &e->XB, (size_t)c.max_batch * c.Nl * 14 * NS * sizeof(double)));
         if (c.with_nnlo) {
-            HIPCHK(hipMalloc(&e->ZC, e->buf_elems[EFTB_B_C11] * sizeof(double)));
-            HIPCHK(hipMalloc(&e->ZC2, e->buf_elems[EFTB_B_CLOOPL] * sizeof(double)));
+            HIPCHK(own_dev(e->own, &e->ZC, e->buf_elems[EFTB_B_C11] * sizeof(double)));
+            HIPCHK(own_dev(e->own, &e->ZC2, e->buf_elems[EFTB_B_CLOOPL] * sizeof(double)));
             HIPCHK(hipMemset(e->ZC, 0, e->buf_elems[EFTB_B_C11] * sizeof(double)));
             HIPCHK(hipMemset(e->ZC2, 0, e->buf_elems[EFTB_B_CLOOPL] * sizeof(double)));
         }
         {
             const size_t abytes = (size_t)c.max_batch * RS_ROWS * RS_NB * sizeof(double);
-            HIPCHK(hipMalloc(&e->RSA, abytes));
-            HIPCHK(hipMalloc(&e->RSC, ((size_t)c.max_batch * NS + RS_PF) * RS_REC * sizeof(double)));
-            HIPCHK(hipMalloc(&e->RSA2, abytes));
+            HIPCHK(own_dev(e->own, &e->RSA, abytes));
+            HIPCHK(own_dev(e->own, &e->RSC, ((size_t)c.max_batch * NS + RS_PF) * RS_REC * sizeof(double)));
+            HIPCHK(own_dev(e->own, &e->RSA2, abytes));
             if (c.Nl == 3) {  // one operand per s
-                HIPCHK(hipMalloc(&e->RSAS, ((size_t)c.max_batch * NS + RS_PF) * RS3_AS * sizeof(double)));
-                HIPCHK(hipMalloc(&e->RSAS2, ((size_t)c.max_batch * NS + RS_PF) * RS3_AS * sizeof(double)));
+                HIPCHK(own_dev(e->own, &e->RSAS, ((size_t)c.max_batch * NS + RS_PF) * RS3_AS * sizeof(double)));
+                HIPCHK(own_dev(e->own, &e->RSAS2, ((size_t)c.max_batch * NS + RS_PF) * RS3_AS * sizeof(double)));
             }
-            HIPCHK(hipMalloc(&e->RSC2, ((size_t)c.max_batch * NS + RS_PF) * RS_REC * sizeof(double)));
+            HIPCHK(own_dev(e->own, &e->RSC2, ((size_t)c.max_batch * NS + RS_PF) * RS_REC * sizeof(double)));
         }
     }
     // opt in to the large dynamic LDS tiles
@@ -1934,14 +1982,12 @@ int eftb_finalize(eftb_engine* e) {
 #undef APM_LDS
         }
     }
-    if (c.with_ap && c.Nl == 3 && !e->PLK0) {
-        HIPCHK(hipMalloc(&e->PLK0, e->buf_elems[EFTB_B_PLK] * sizeof(double)));
-        HIPCHK(hipMemset(e->PLK0, 0, e->buf_elems[EFTB_B_PLK] * sizeof(double)));
-    }
-    if (e->ap_overlap && !e->T3) HIPCHK(hipMalloc(&e->T3, (e->buf_elems[EFTB_B_TEMPL] + 2) * sizeof(double)));  // third template block (engine.back)
+    if (c.with_ap && c.Nl == 3 && !e->PLK0)
+        HIPCHK(own_dev(e->own, &e->PLK0, e->buf_elems[EFTB_B_PLK] * sizeof(double), true));
+    if (e->ap_overlap && !e->T3) HIPCHK(own_dev(e->own, &e->T3, (e->buf_elems[EFTB_B_TEMPL] + 2) * sizeof(double)));  // third template block (engine.back)
     if (e->ap_overlap && e->c.with_nnlo && e->c.with_ap && !e->T3N) {
-        HIPCHK(hipMalloc(&e->T3N, (e->buf_elems[EFTB_B_TEMPLN] + 2) * sizeof(double)));
-        HIPCHK(hipMalloc(&e->TaltN, (e->buf_elems[EFTB_B_TEMPLN] + 2) * sizeof(double)));
+        HIPCHK(own_dev(e->own, &e->T3N, (e->buf_elems[EFTB_B_TEMPLN] + 2) * sizeof(double)));
+        HIPCHK(own_dev(e->own, &e->TaltN, (e->buf_elems[EFTB_B_TEMPLN] + 2) * sizeof(double)));
         HIPCHK(hipMemset(e->T3N, 0, e->buf_elems[EFTB_B_TEMPLN] * sizeof(double)));
         HIPCHK(hipMemset(e->TaltN, 0, e->buf_elems[EFTB_B_TEMPLN] * sizeof(double)));
     }
@@ -1967,8 +2013,11 @@ int eftb_add_operator(eftb_engine* e, int nl_out, int nx_out, int nl_in, int nx_
                 const double* src = op + (((size_t)a * nl_in + l) * nx_out + x) * nx_in;
                 for (int k = 0; k < nx_in; ++k) t[((size_t)l * nx_in + k) * o.ld + (size_t)a * nx_out + x] = src[k];
             }
-    HIPCHK(hipMalloc(&o.dev, t.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(o.dev, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(own_dev(e->own, &o.dev, t.size() * sizeof(double)));
+    if (int rc = [&] { HIPCHK(hipMemcpy(o.dev, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice)); return 0; }()) {
+        e->own.release(o.dev);  // (the operator is not registered: nobody would use the matrix)
+        return rc;
+    }
     e->ops.push_back(o);
     *op_id = (int)e->ops.size() - 1;
     return 0;
@@ -2071,9 +2120,9 @@ int eftb_set_option(eftb_engine* e, int option, int value) {
         case EFTB_O_STEP_TRACE:
             if (value && !e->evTraceBase) {
                 HIPCHK(hipSetDevice(e->c.device));
-                HIPCHK(hipEventCreate(&e->evTraceBase));
+                HIPCHK(own_event(e->own, &e->evTraceBase));
                 for (auto& row : e->evTrace)
-                    for (hipEvent_t& ev : row) HIPCHK(hipEventCreate(&ev));
+                    for (hipEvent_t& ev : row) HIPCHK(own_event(e->own, &ev));
             }
             if (value) {
                 HIPCHK(hipEventRecord(e->evTraceBase, e->stream));
@@ -2157,17 +2206,17 @@ int eftb_set_likelihood(eftb_engine* e, int ndata, const int32_t* index, const d
         }
     HIPCHK(hipSetDevice(e->c.device));
     HIPCHK(sync_all(e));  // a likelihood stage of an overlapped run may still be reading the old tables on the back-half stream
-    free_likelihood(e);
+    drop_likelihood(e);
     {
         const size_t vb = (size_t)(e->c.max_batch / e->ntr + 1) * (nG + 1) * ndata * sizeof(double);
-        HIPCHK(hipMalloc(&e->like_V, vb));
-        HIPCHK(hipMalloc(&e->like_U, vb));
+        HIPCHK(own_dev(e->own, &e->like_V, vb));
+        HIPCHK(own_dev(e->own, &e->like_U, vb));
     }
-    HIPCHK(hipMalloc(&e->like_index, ndata * sizeof(int)));
-    HIPCHK(hipMalloc(&e->like_data, ndata * sizeof(double)));
-    HIPCHK(hipMalloc(&e->like_invcov, (size_t)ndata * ndata * sizeof(double)));
-    HIPCHK(hipMalloc(&e->like_mu, MARG_MAXG * sizeof(double)));
-    HIPCHK(hipMalloc(&e->like_sinv, MARG_MAXG * sizeof(double)));
+    HIPCHK(own_dev(e->own, &e->like_index, ndata * sizeof(int)));
+    HIPCHK(own_dev(e->own, &e->like_data, ndata * sizeof(double)));
+    HIPCHK(own_dev(e->own, &e->like_invcov, (size_t)ndata * ndata * sizeof(double)));
+    HIPCHK(own_dev(e->own, &e->like_mu, MARG_MAXG * sizeof(double)));
+    HIPCHK(own_dev(e->own, &e->like_sinv, MARG_MAXG * sizeof(double)));
     HIPCHK(hipMemcpy(e->like_index, index, ndata * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->like_data, data, ndata * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->like_invcov, invcov, (size_t)ndata * ndata * sizeof(double), hipMemcpyHostToDevice));
@@ -2193,67 +2242,11 @@ void eftb_destroy(eftb_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (hipStream_t q : {e->pre, e->side, e->cpy, e->back}) if (q) (void)hipStreamSynchronize(q);  // look-ahead work and staged uploads still in flight
     drop_graphs(e);
-    if (e->cpy)
-        for (int id = 0; id < EFTB_B_COUNT; ++id)
-            if (e->orig[id]) e->buf[id] = e->orig[id];  // the staged sets are freed below, the engine's own buffers with e->buf
-    for (auto& p : e->tab) if (p) (void)hipFree(p);
-    for (auto& p : e->buf) if (p) (void)hipFree(p);
-    for (double* p : {e->alt.PA1, e->alt.PA2, e->alt.PA2T, e->alt.PA3, e->alt.coefT, e->alt.A22, e->alt.A13, e->alt.ACF, e->alt.ALC, e->alt.P11, e->alt.COEF, e->alt.XY, e->alt.Q, reinterpret_cast<double*>(e->alt.SAD), e->PLK0, e->RSA, e->RSC, e->RSA2, e->RSC2, e->RSAS, e->RSAS2, e->APP, e->APR, e->APP2, e->APR2, e->SD, e->Talt, e->T3, e->TaltN, e->T3N, e->part, e->PA1, e->PA2, e->PA2T, e->PA3, e->A22, e->A13, e->ACF, e->ALC, e->Y22, e->YCF, e->coefT, e->sm2, e->sm4, e->ZC, e->ZC2, e->coef2, e->coefT2, e->XB, reinterpret_cast<double*>(e->SAD)}) if (p) (void)hipFree(p);
-    for (int q = 0; q < eftb_engine::NSETS; ++q) {
-        if (e->gathered2[q]) (void)hipFree(e->gathered2[q]);
-        if (e->evGath2[q]) (void)hipEventDestroy(e->evGath2[q]);
-        if (e->gath_host[q]) (void)hipHostFree(e->gath_host[q]);
-        if (e->evGathHost[q]) (void)hipEventDestroy(e->evGathHost[q]);
-    }
-    e->gathered = nullptr;  // (one of gathered2)
-    for (void* p : {(void*)e->APW, (void*)e->APW2, (void*)e->API, (void*)e->API2, (void*)e->APM, (void*)e->APM2}) if (p) (void)hipFree(p);
-    for (auto& o : e->ops) if (o.dev) (void)hipFree(o.dev);
-    free_likelihood(e);
-    for (void* p : {(void*)e->drw_A, (void*)e->drw_U, (void*)e->drw_W, (void*)e->drw_in, (void*)e->drw_inn, (void*)e->drw_out, (void*)e->drw_off, (void*)e->drw_theta,
-                    (void*)e->recipe[0].coef, (void*)e->recipe[0].tab, (void*)e->recipe[1].coef, (void*)e->recipe[1].tab, (void*)e->recipe[0].dcoef,
-                    (void*)e->recipe[0].dtab, (void*)e->drw_grad, (void*)e->recipe[0].hcoef, (void*)e->recipe[0].htab, (void*)e->drw_hess}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)e->dset_D, (void*)e->dset_Ud, (void*)e->drw_Wg, (void*)e->drw_gtab}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)e->smp_z, (void*)e->smp_b, (void*)e->smp_chi2, (void*)e->smp_coef, (void*)e->smp_coefn, (void*)e->smp_plk, (void*)e->smp_off}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)e->chn_step, (void*)e->chn_lnu, (void*)e->chn_pri, (void*)e->chn_chain, (void*)e->chn_rec, (void*)e->chn_nacc}) if (p) (void)hipFree(p);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
-    for (hipEvent_t ev : {e->ev0, e->ev1, e->evFork, e->evJoin, e->evJoinAP, e->evXY, e->evAS, e->evFront, e->evFrontFree[0], e->evFrontFree[1], e->evPrep, e->evInFree, e->evResum, e->evBack[0], e->evBack[1], e->evRsDone[0], e->evRsDone[1]}) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->evRun) if (ev) (void)hipEventDestroy(ev);
-    for (int t = 0; t < eftb_engine::NTIMER; ++t) {
-        if (e->evT0[t]) (void)hipEventDestroy(e->evT0[t]);
-        if (e->evT1[t]) (void)hipEventDestroy(e->evT1[t]);
-    }
-    if (e->pre) (void)hipStreamDestroy(e->pre);
-    if (e->back) (void)hipStreamDestroy(e->back);
-    if (e->cpy) (void)hipStreamDestroy(e->cpy);
-    for (int h = 0; h < eftb_engine::NSLOT; ++h)
-        if (e->stage_host[h]) (void)hipHostFree(e->stage_host[h]);
-    for (int r = 0; r < eftb_engine::NLRING; ++r) {
-        if (e->evStagedR[r]) (void)hipEventDestroy(e->evStagedR[r]);
-        if (e->evStagedAllR[r]) (void)hipEventDestroy(e->evStagedAllR[r]);
-    }
-    for (int q = 0; q < eftb_engine::NSETS; ++q) {
-        if (e->evSetDone[q]) (void)hipEventDestroy(e->evSetDone[q]);
-        if (e->setblock[q]) (void)hipFree(e->setblock[q]);
-        for (int id : {EFTB_B_PLK, EFTB_B_LOGP})
-            if (e->setbuf[q][id]) {
-                if (id == EFTB_B_PLK && e->plk_host[q]) (void)hipHostFree(e->plk_host[q]);
-                if (id == EFTB_B_PLK) (void)hipFree(e->setbuf[q][id]);
-                else (void)hipHostFree(e->setbuf[q][id]);
-            }
-    }
-    if (e->evTraceBase) {
-        (void)hipEventDestroy(e->evTraceBase);
-        for (auto& row : e->evTrace)
-            for (hipEvent_t ev : row) if (ev) (void)hipEventDestroy(ev);
-    }
-    if (e->set_done) (void)hipHostFree(const_cast<unsigned long long*>(e->set_done));
     if (e->sub_stats && e->issue_n)
         fprintf(stderr, "[eftbird] staged steps: %llu issued (%llu by the caller's thread), %.1f us per step in the issuing thread, %.1f us filling the staging block, "
                         "%.1f us waiting for results\n", e->issue_n, e->inline_n, e->issue_ns / e->issue_n * 1e-3, e->fill_ns / e->issue_n * 1e-3, e->wait_ns / e->issue_n * 1e-3);
-    if (e->status) (void)hipHostFree(e->status);
-    if (e->side) (void)hipStreamDestroy(e->side);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;  // the ledger releases what the engine holds, newest first: memory and events before the streams they were used on
 }
 
 size_t eftb_buffer_size(const eftb_engine* e, int id) {
@@ -2418,19 +2411,17 @@ int eftb_eval_logp_batch(eftb_engine* e, int B, const double* Pin, const double*
 }
 
 // ------------------------------------------------------------------------------------------------ parameter draws (fast / slow split)
-// device buffer of at least n elements: grows, never shrinks (freed by eftb_destroy); separate from every buffer of the runs.  With who, a
-// failed allocation is that call's refusal and names what, of which shape, asked for it; without, it fails as every HIP call does
-static int grow_dev(void* pp, size_t* cap, size_t n, size_t elem = sizeof(double), const char* who = nullptr, const char* what = nullptr,
+// device buffer of at least n elements: grows, never shrinks (held by the engine's ledger); separate from every buffer of the runs.  With
+// who, a failed allocation is that call's refusal and names what, of which shape, asked for it; without, it fails as every HIP call does
+static int grow_dev(eftb_engine* e, void* pp, size_t* cap, size_t n, size_t elem = sizeof(double), const char* who = nullptr, const char* what = nullptr,
                     const char* shape = nullptr) {
     void** p = static_cast<void**>(pp);
     if (n <= *cap) return 0;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
+    e->own.release(*p);
     *cap = 0;
-    if (!who) HIPCHK(hipMalloc(p, n * elem));
-    else if (hipError_t me = hipMalloc(p, n * elem); me != hipSuccess) {
+    if (!who) HIPCHK(own_dev(e->own, p, n * elem));
+    else if (hipError_t me = own_dev(e->own, p, n * elem); me != hipSuccess) {
         (void)hipGetLastError();
-        *p = nullptr;
         return fail("%s: no device memory for %s of %s (%zu bytes): %s", who, what, shape, n * elem, hipGetErrorString(me));
     }
     *cap = n;
@@ -2481,9 +2472,9 @@ static int draws_gram(eftb_engine* e, const char* who, int C, int J1) {
     if (e->gram_gen != e->draw_gen || e->gram_C < C) {
         e->gram_gen = 0;
         const size_t ae = (size_t)C * J1 * nd;
-        if (int rc = grow_dev(&e->drw_A, &e->drw_A_cap, ae)) return rc;
-        if (int rc = grow_dev(&e->drw_U, &e->drw_U_cap, ae)) return rc;
-        if (int rc = grow_dev(&e->drw_W, &e->drw_W_cap, (size_t)C * J1 * J1)) return rc;
+        if (int rc = grow_dev(e, &e->drw_A, &e->drw_A_cap, ae)) return rc;
+        if (int rc = grow_dev(e, &e->drw_U, &e->drw_U_cap, ae)) return rc;
+        if (int rc = grow_dev(e, &e->drw_W, &e->drw_W_cap, (size_t)C * J1 * J1)) return rc;
         hipLaunchKernelGGL(draws_gather_kernel, dim3(C), dim3(256), 0, st, e->cur_nl, e->cur_nx, ntr, nd, J1, e->like_index, e->like_data,
                            e->buf[EFTB_B_TEMPL], c.with_nnlo ? e->buf[EFTB_B_TEMPLN] : nullptr, e->drw_A);
         launch_times_invcov(e, st, e->drw_A, C * J1, e->drw_U);  // U = A C^-1 for all walkers, exactly as the LOGP stage multiplies V
@@ -2564,8 +2555,8 @@ static int draws_logp_begin(eftb_engine* e, const char* who, int C, long long N,
     join_back(e);
     if (int rc = draws_lds_optin(e)) return rc;
     if (int rc = draws_gram(e, who, nwalk < 0 ? C : nwalk, J1)) return rc;
-    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
-    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
+    if (int rc = grow_dev(e, &e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(e, &e->drw_out, &e->drw_out_cap, (size_t)N * MARG_OUT)) return rc;
     HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, e->stream));
     return 0;
 }
@@ -2586,9 +2577,9 @@ int eftb_draws_logp(eftb_engine* e, int C, long long N, const int64_t* offsets, 
     const int ntr = e->ntr, nG = e->like_nG, ng1 = nG + 1, J1 = sh.J1;
     hipStream_t st = e->stream;
     const size_t rn = (size_t)N * ntr * ng1 * NROW, rnn = (size_t)N * ntr * ng1 * 3;
-    if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, rn)) return rc;
+    if (int rc = grow_dev(e, &e->drw_in, &e->drw_in_cap, rn)) return rc;
     if (rows_nnlo)
-        if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, rnn)) return rc;
+        if (int rc = grow_dev(e, &e->drw_inn, &e->drw_inn_cap, rnn)) return rc;
     HIPCHK(hipMemcpyAsync(e->drw_in, rows, rn * sizeof(double), hipMemcpyHostToDevice, st));
     if (rows_nnlo) HIPCHK(hipMemcpyAsync(e->drw_inn, rows_nnlo, rnn * sizeof(double), hipMemcpyHostToDevice, st));
     const dim3 grid(C, draw_shares(maxcnt, sh.nw, C)), block(64 * sh.nw);
@@ -2632,13 +2623,12 @@ static void read_staged_switches(eftb_engine* e, size_t sb) {
 // Every set keeps its inputs in ONE device block with the layout of the page-locked staging blocks, so that staging is one upload
 // kernel (small separate copies are carried out by the host thread once the stream's dependencies have resolved,
 // which would stall the sampler loop for a whole step).
-static int staged_setup(eftb_engine* e) {
-    if (e->cpy) return 0;
+static int staged_acquire(eftb_engine* e) {
     HIPCHK(hipSetDevice(e->c.device));
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (int rc = pad_streams(4, prio_hi)) return rc;
-    HIPCHK(hipStreamCreateWithPriority(&e->cpy, hipStreamNonBlocking, prio_hi));
+    if (int rc = pad_streams(e, 4, prio_hi)) return rc;
+    HIPCHK(own_stream(e->own, &e->cpy, prio_hi));
     size_t off = 0;
     for (int id : kStagedIn) {
         e->stage_off[id] = off;
@@ -2647,26 +2637,24 @@ static int staged_setup(eftb_engine* e) {
     e->stage_elems = (off + 1) & ~(size_t)1;  // whole double2s for the copy kernel
     for (int id : kStagedIds) e->orig[id] = e->buf[id];
     for (int q = 0; q < eftb_engine::NSETS; ++q) {
-        HIPCHK(hipMalloc(&e->setblock[q], e->stage_elems * sizeof(double)));
-        HIPCHK(hipMemset(e->setblock[q], 0, e->stage_elems * sizeof(double)));
+        HIPCHK(own_dev(e->own, &e->setblock[q], e->stage_elems * sizeof(double), true));
         for (int id : kStagedIn) e->setbuf[q][id] = e->buf_elems[id] ? e->setblock[q] + e->stage_off[id] : nullptr;
         // per-step outputs: ln P (a few KB) lives in page-locked host memory mapped into the device and is written by the kernel itself;
         // P_l stays in device memory and is copied to page-locked host memory by the DMA engine on the stream the step ends on (the back-half
         // stream in pipelined steps: round 1 measured ~70 us of stalled compute queue per step for such a transfer on the COMPUTE stream)
         for (int id : kStagedOut) {
             if (id == EFTB_B_PLK) {
-                HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->setbuf[q][id]), e->buf_elems[id] * sizeof(double)));
-                HIPCHK(hipMemset(e->setbuf[q][id], 0, e->buf_elems[id] * sizeof(double)));
+                HIPCHK(own_dev(e->own, &e->setbuf[q][id], e->buf_elems[id] * sizeof(double), true));
                 if (!e->comm) {
-                    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->plk_host[q]), e->buf_elems[id] * sizeof(double), hipHostMallocMapped));  // (mapped: latency-mode steps write it from the kernel)
+                    HIPCHK(own_host(e->own, &e->plk_host[q], e->buf_elems[id] * sizeof(double), hipHostMallocMapped));  // (mapped: latency-mode steps write it from the kernel)
                     memset(e->plk_host[q], 0, e->buf_elems[id] * sizeof(double));
                 }
                 continue;
             }
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->setbuf[q][id]), e->buf_elems[id] * sizeof(double), hipHostMallocMapped));
+            HIPCHK(own_host(e->own, &e->setbuf[q][id], e->buf_elems[id] * sizeof(double), hipHostMallocMapped));
             memset(e->setbuf[q][id], 0, e->buf_elems[id] * sizeof(double));
         }
-        HIPCHK(hipEventCreateWithFlags(&e->evSetDone[q], hipEventDisableTiming));
+        HIPCHK(own_event(e->own, &e->evSetDone[q], hipEventDisableTiming));
         HIPCHK(hipEventRecord(e->evSetDone[q], e->cpy));
     }
     // a staging block is sized for one step (step_batch cosmologies), laid out like the device block of a set that holds only that step
@@ -2678,25 +2666,38 @@ static int staged_setup(eftb_engine* e) {
     }
     e->slot_elems = (hoff + 1) & ~(size_t)1;
     for (int h = 0; h < eftb_engine::NSLOT; ++h) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->stage_host[h]), e->slot_elems * sizeof(double), hipHostMallocMapped));
+        HIPCHK(own_host(e->own, &e->stage_host[h], e->slot_elems * sizeof(double), hipHostMallocMapped));
         memset(e->stage_host[h], 0, e->slot_elems * sizeof(double));
     }
     for (int r = 0; r < eftb_engine::NLRING; ++r) {
-        HIPCHK(hipEventCreateWithFlags(&e->evStagedR[r], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&e->evStagedAllR[r], hipEventDisableTiming));
+        HIPCHK(own_event(e->own, &e->evStagedR[r], hipEventDisableTiming));
+        HIPCHK(own_event(e->own, &e->evStagedAllR[r], hipEventDisableTiming));
         HIPCHK(hipEventRecord(e->evStagedR[r], e->cpy));
         HIPCHK(hipEventRecord(e->evStagedAllR[r], e->cpy));
     }
     read_staged_switches(e, sb);
     {
         void* p = nullptr;
-        HIPCHK(hipHostMalloc(&p, 2 * eftb_engine::NSETS * sizeof(unsigned long long), hipHostMallocMapped));
+        HIPCHK(own_host(e->own, &p, 2 * eftb_engine::NSETS * sizeof(unsigned long long), hipHostMallocMapped));
         memset(p, 0, 2 * eftb_engine::NSETS * sizeof(unsigned long long));
         e->set_done = static_cast<volatile unsigned long long*>(p);
     }
     e->cur_set = eftb_engine::NSETS - 1;  // the engine's own buffers are current until the first staged launch; sets 0, 1, 2, 3 follow in turn
     HIPCHK(hipDeviceSynchronize());  // the zero fills ran on the null stream; the copy stream is about to write into these blocks
     return 0;
+}
+
+// all of it or none: a set-up that failed half way gives back what it got and leaves no copy stream, which every staged entry point looks at --
+// the next eftb_stage_inputs starts over, and assigns every field again
+static int staged_setup(eftb_engine* e) {
+    if (e->cpy) return 0;
+    const Ledger::Mark before = e->own.mark();
+    const int rc = staged_acquire(e);
+    if (rc) {
+        e->own.release_to(before);  // (releasing device memory waits for the zero fills in flight, releasing the stream for what was recorded on it)
+        e->cpy = nullptr;
+    }
+    return rc;
 }
 
 // ---- staged steps: the host part (inputs -> page-locked block `slot`) ...
@@ -3156,7 +3157,7 @@ int eftb_set_step_output(eftb_engine* e, double* dst, size_t count) {
     if (!dst) { e->stg_out = nullptr; e->stg_out_count = 0; return 0; }
     if (e->comm) return fail("eftb_set_step_output: P_l of an engine with a communicator stays in device memory for the exchange (eftb_gathered_view)");
     HIPCHK(hipSetDevice(e->c.device));
-    // the DMA engine writes the array behind the step: it must be page-locked (eftb_host_alloc, hipHostMalloc, hipHostRegister) -- pageable memory would
+    // the DMA engine writes the array behind the step: it must be page-locked (eftb_host_alloc or the runtime's own page-locked allocation or registration) -- pageable memory would
     // turn every transfer into a synchronous staged copy on the issuing thread
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, dst) != hipSuccess || at.type != hipMemoryTypeHost) {
@@ -3381,10 +3382,10 @@ int eftb_gather_plk(eftb_engine* e, int B, int root, double* host_out) {
         const int q = e->gather_slot;
         if (!e->gathered2[q]) {
             const size_t bytes = (size_t)e->nranks * e->c.max_batch * e->c.Nl * e->c.Nk * sizeof(double);
-            HIPCHK(hipMalloc(&e->gathered2[q], bytes));
-            HIPCHK(hipEventCreateWithFlags(&e->evGath2[q], hipEventDisableTiming));
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->gath_host[q]), bytes, hipHostMallocDefault));
-            HIPCHK(hipEventCreateWithFlags(&e->evGathHost[q], hipEventDisableTiming));
+            HIPCHK(own_dev(e->own, &e->gathered2[q], bytes));
+            HIPCHK(own_event(e->own, &e->evGath2[q], hipEventDisableTiming));
+            HIPCHK(own_host(e->own, &e->gath_host[q], bytes, hipHostMallocDefault));
+            HIPCHK(own_event(e->own, &e->evGathHost[q], hipEventDisableTiming));
         }
         e->gathered = e->gathered2[q];
     }
@@ -3459,11 +3460,12 @@ int eftb_mfma_f64_peak(int device, double* tflops) {
     HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
+    Ledger own;  // (released when the probe returns, however it returns)
     double* sink = nullptr;
-    HIPCHK(hipMalloc(&sink, sizeof(double)));
+    HIPCHK(own_dev(own, &sink, sizeof(double)));
     hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
+    HIPCHK(own_event(own, &a));
+    HIPCHK(own_event(own, &b));
     const int iters = 40000, blocks = prop.multiProcessorCount;  // 8 waves per CU = 2 waves per SIMD
     hipLaunchKernelGGL(mfma_peak_kernel, dim3(blocks), dim3(512), 0, 0, 100, sink);
     HIPCHK(hipDeviceSynchronize());
@@ -3475,9 +3477,6 @@ int eftb_mfma_f64_peak(int device, double* tflops) {
     HIPCHK(hipEventElapsedTime(&ms, a, b));
     const double flops = (double)blocks * 8 * iters * 4 * (2.0 * 16 * 16 * 4);
     *tflops = flops / (ms * 1e-3) / 1e12;
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    (void)hipFree(sink);
     return 0;
 }
 
@@ -3488,13 +3487,14 @@ int eftb_stream_read_probe(int device, size_t bytes, int bytes_per_lane, double*
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("eftb_stream_read_probe: no HIP device visible");
     HIPCHK(hipSetDevice(device));
     const size_t n = bytes / sizeof(double) / 2 * 2;
+    Ledger own;
     double *src = nullptr, *sink = nullptr;
-    HIPCHK(hipMalloc(&src, n * sizeof(double)));
-    HIPCHK(hipMalloc(&sink, sizeof(double)));
+    HIPCHK(own_dev(own, &src, n * sizeof(double)));
+    HIPCHK(own_dev(own, &sink, sizeof(double)));
     HIPCHK(hipMemset(src, 0, n * sizeof(double)));
     hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
+    HIPCHK(own_event(own, &a));
+    HIPCHK(own_event(own, &b));
     float ms = 0.f;
     for (int rep = 0; rep < 2; ++rep) {  // the second launch is the timed one
         HIPCHK(hipEventRecord(a, 0));
@@ -3505,10 +3505,6 @@ int eftb_stream_read_probe(int device, size_t bytes, int bytes_per_lane, double*
         HIPCHK(hipEventElapsedTime(&ms, a, b));
     }
     if (gbps) *gbps = (double)n * sizeof(double) / (ms * 1e-3) / 1e9;
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    (void)hipFree(src);
-    (void)hipFree(sink);
     return 0;
 }
 
@@ -3525,15 +3521,8 @@ int eftb_window_precompute(int device, int Na, int Nl, int Nk, int nx, int Np, c
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("eftb_window_precompute: no HIP device visible");
     HIPCHK(hipSetDevice(device));
     const size_t R = (size_t)Na * Nl, nW = R * Nk * Np;
-    struct Pool {
-        std::vector<void*> v;
-        ~Pool() { for (void* q : v) (void)hipFree(q); }
-    } pool;
-    auto dalloc = [&](size_t n, double** out) -> hipError_t {
-        hipError_t st = hipMalloc((void**)out, n * sizeof(double));
-        if (st == hipSuccess) pool.v.push_back(*out);
-        return st;
-    };
+    Ledger own;
+    auto dalloc = [&](size_t n, double** out) { return own_dev(own, out, n * sizeof(double)); };
     double *dk, *dx, *dQ, *dT, *dp, *dA, *dW, *dWd = nullptr, *dS = nullptr, *dF = nullptr;
     HIPCHK(dalloc(Nk, &dk)); HIPCHK(dalloc(nx, &dx)); HIPCHK(dalloc(R * nx, &dQ)); HIPCHK(dalloc((size_t)Nl * nx * Np, &dT));
     HIPCHK(dalloc(Np, &dp)); HIPCHK(dalloc(R * Nk * nx, &dA)); HIPCHK(dalloc(nW, &dW));
@@ -3547,8 +3536,8 @@ int eftb_window_precompute(int device, int Na, int Nl, int Nk, int nx, int Np, c
     if (Wfold) HIPCHK(hipMemcpy(dS, S, (size_t)Np * Nk * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipEvent_t ev0, ev1;
-    HIPCHK(hipEventCreate(&ev0));
-    HIPCHK(hipEventCreate(&ev1));
+    HIPCHK(own_event(own, &ev0));
+    HIPCHK(own_event(own, &ev1));
     HIPCHK(hipEventRecord(ev0, 0));
     hipLaunchKernelGGL(window_bessel_kernel, dim3((nx + 255) / 256, Nk), dim3(256), 0, 0, Na, Nl, Nk, nx, dk, dx, dQ, dA);
     for (int l = 0; l < Nl; ++l) {  // rows = (a, k), A_al [Nk][nx] @ T_l [nx][Np]
@@ -3574,8 +3563,6 @@ int eftb_window_precompute(int device, int Na, int Nl, int Nk, int nx, int Np, c
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
     if (device_ms) *device_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
     HIPCHK(hipMemcpy(Wal, dW, nW * sizeof(double), hipMemcpyDeviceToHost));
     if (Waldk) HIPCHK(hipMemcpy(Waldk, dWd, nW * sizeof(double), hipMemcpyDeviceToHost));
     if (Wfold) HIPCHK(hipMemcpy(Wfold, dF, R * Nk * Nk * sizeof(double), hipMemcpyDeviceToHost));
@@ -3718,24 +3705,24 @@ int eftb_set_draw_recipe(eftb_engine* e, int kind, int P, int ng1, int nterms, c
     HIPCHK(hipSetDevice(e->c.device));
     HIPCHK(sync_all(e));  // (a params call is synchronous: nothing reads the old tables any more; as eftb_set_likelihood)
     rc.set = false;
-    for (void* p : {(void*)rc.coef, (void*)rc.tab, (void*)rc.dcoef, (void*)rc.dtab, (void*)rc.hcoef, (void*)rc.htab}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)rc.coef, (void*)rc.tab, (void*)rc.dcoef, (void*)rc.dtab, (void*)rc.hcoef, (void*)rc.htab}) e->own.release(p);
     rc.coef = nullptr;
     rc.tab = nullptr;
     rc.dcoef = nullptr;
     rc.dtab = nullptr;
     rc.hcoef = nullptr;
     rc.htab = nullptr;
-    HIPCHK(hipMalloc(&rc.coef, coef.size() * sizeof(double)));
-    HIPCHK(hipMalloc(&rc.tab, tab.size() * sizeof(int)));
+    HIPCHK(own_dev(e->own, &rc.coef, coef.size() * sizeof(double)));
+    HIPCHK(own_dev(e->own, &rc.tab, tab.size() * sizeof(int)));
     HIPCHK(hipMemcpy(rc.coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(rc.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
     if (kind == 0) {  // (a table without records still holds pstart and erow)
-        HIPCHK(hipMalloc(&rc.dcoef, std::max<size_t>(1, dcoef.size()) * sizeof(double)));
-        HIPCHK(hipMalloc(&rc.dtab, dtab.size() * sizeof(int)));
+        HIPCHK(own_dev(e->own, &rc.dcoef, std::max<size_t>(1, dcoef.size()) * sizeof(double)));
+        HIPCHK(own_dev(e->own, &rc.dtab, dtab.size() * sizeof(int)));
         if (!dcoef.empty()) HIPCHK(hipMemcpy(rc.dcoef, dcoef.data(), dcoef.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(rc.dtab, dtab.data(), dtab.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&rc.hcoef, std::max<size_t>(1, hcoef.size()) * sizeof(double)));
-        HIPCHK(hipMalloc(&rc.htab, htab.size() * sizeof(int)));
+        HIPCHK(own_dev(e->own, &rc.hcoef, std::max<size_t>(1, hcoef.size()) * sizeof(double)));
+        HIPCHK(own_dev(e->own, &rc.htab, htab.size() * sizeof(int)));
         if (!hcoef.empty()) HIPCHK(hipMemcpy(rc.hcoef, hcoef.data(), hcoef.size() * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(rc.htab, htab.data(), htab.size() * sizeof(int), hipMemcpyHostToDevice));
     }
@@ -3776,7 +3763,7 @@ static int draws_params_check(eftb_engine* e, const char* who, int kind, int ng1
 // theta [N][P] and f [C][ntr] to the device (one buffer: theta, then f)
 static int draws_params_upload(eftb_engine* e, int P, int C, long long N, const double* theta, const double* f, const double** dtheta, const double** df) {
     const size_t nt = (size_t)N * P, nf = (size_t)C * e->ntr;
-    if (int rc = grow_dev(&e->drw_theta, &e->drw_theta_cap, nt + nf)) return rc;
+    if (int rc = grow_dev(e, &e->drw_theta, &e->drw_theta_cap, nt + nf)) return rc;
     if (nt) HIPCHK(hipMemcpyAsync(e->drw_theta, theta, nt * sizeof(double), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->drw_theta + nt, f, nf * sizeof(double), hipMemcpyHostToDevice, e->stream));
     *dtheta = e->drw_theta;
@@ -3799,8 +3786,8 @@ static int draws_gram_groups(eftb_engine* e, const char* who, int G, int J1, con
     e->grp_draw_gen = 0;
     char shape[64];
     snprintf(shape, sizeof shape, "G = %d groups with J + 1 = %d columns", G, J1);
-    if (int rc = grow_dev(&e->drw_Wg, &e->drw_Wg_cap, (size_t)G * J1 * J1, sizeof(double), who, "the Gram matrices", shape)) return rc;
-    if (int rc = grow_dev(&e->drw_gtab, &e->drw_gtab_cap, 2 * (size_t)G, sizeof(int))) return rc;
+    if (int rc = grow_dev(e, &e->drw_Wg, &e->drw_Wg_cap, (size_t)G * J1 * J1, sizeof(double), who, "the Gram matrices", shape)) return rc;
+    if (int rc = grow_dev(e, &e->drw_gtab, &e->drw_gtab_cap, 2 * (size_t)G, sizeof(int))) return rc;
     e->grp_tab.assign(gr.walker, gr.walker + G);
     e->grp_tab.insert(e->grp_tab.end(), gr.dataset, gr.dataset + G);
     HIPCHK(hipMemcpyAsync(e->drw_gtab, e->grp_tab.data(), 2 * (size_t)G * sizeof(int), hipMemcpyHostToDevice, e->stream));
@@ -3854,9 +3841,9 @@ static int draws_logp_params_impl(eftb_engine* e, const char* who, int C, long l
     DrawRun run;
     if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta, f, gr, &run)) return rc;
     if (grad)
-        if (int rc = grow_dev(&e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
+        if (int rc = grow_dev(e, &e->drw_grad, &e->drw_grad_cap, std::max<size_t>(1, (size_t)N * P))) return rc;
     if (hess)
-        if (int rc = grow_dev(&e->drw_hess, &e->drw_hess_cap, std::max<size_t>(1, (size_t)N * P * P))) return rc;
+        if (int rc = grow_dev(e, &e->drw_hess, &e->drw_hess_cap, std::max<size_t>(1, (size_t)N * P * P))) return rc;
     hipStream_t st = e->stream;
     const int J1 = sh.J1;
     RecipeGradTab gt{};
@@ -3922,11 +3909,11 @@ static int draws_reduce_impl(eftb_engine* e, const char* who, int C, long long N
     hipStream_t st = e->stream;
     join_back(e);
     const size_t bn = (size_t)N * ntr * NROW, bnn = (size_t)N * ntr * 3, pn = (size_t)N * ntr * e->cur_nl * e->cur_nx;
-    if (int rc = grow_dev(&e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
-    if (int rc = grow_dev(&e->drw_in, &e->drw_in_cap, bn)) return rc;
-    if (int rc = grow_dev(&e->drw_out, &e->drw_out_cap, pn)) return rc;
+    if (int rc = grow_dev(e, &e->drw_off, &e->drw_off_cap, (size_t)C + 1, sizeof(long long))) return rc;
+    if (int rc = grow_dev(e, &e->drw_in, &e->drw_in_cap, bn)) return rc;
+    if (int rc = grow_dev(e, &e->drw_out, &e->drw_out_cap, pn)) return rc;
     if (c.with_nnlo)
-        if (int rc = grow_dev(&e->drw_inn, &e->drw_inn_cap, bnn)) return rc;
+        if (int rc = grow_dev(e, &e->drw_inn, &e->drw_inn_cap, bnn)) return rc;
     HIPCHK(hipMemcpyAsync(e->drw_off, offsets, ((size_t)C + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     if (f) {
         const eftb_engine::Recipe& rcp = e->recipe[1];
@@ -4002,8 +3989,8 @@ int eftb_set_likelihood_datasets(eftb_engine* e, int M, const double* data) {
     join_back(e);
     e->dset_M = 0;
     ++e->dset_gen;
-    if (int rc = grow_dev(&e->dset_D, &e->dset_D_cap, (size_t)M * nd)) return rc;
-    if (int rc = grow_dev(&e->dset_Ud, &e->dset_Ud_cap, (size_t)M * nd)) return rc;
+    if (int rc = grow_dev(e, &e->dset_D, &e->dset_D_cap, (size_t)M * nd)) return rc;
+    if (int rc = grow_dev(e, &e->dset_Ud, &e->dset_Ud_cap, (size_t)M * nd)) return rc;
     hipStream_t st = e->stream;
     HIPCHK(hipMemcpyAsync(e->dset_D, data, (size_t)M * nd * sizeof(double), hipMemcpyHostToDevice, st));
     launch_times_invcov(e, st, e->dset_D, M, e->dset_Ud);  // Ud = D C^-1, as draws_gram multiplies A: a row of -D there is the exact negation of its row here
@@ -4081,7 +4068,7 @@ static int draws_sample_params_impl(eftb_engine* e, const char* who, int C, long
     if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta, f, gr, &run)) return rc;
     char shape[96];
     snprintf(shape, sizeof shape, "N = %lld draws x S = %d samples with nG = %d", N, S, nG);
-    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(pp, cap, n, elem, who, what, shape); };
+    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(e, pp, cap, n, elem, who, what, shape); };
     if (int rc = grow(&e->smp_z, &e->smp_z_cap, std::max<size_t>(1, ns * nG), "z")) return rc;
     if (int rc = grow(&e->smp_b, &e->smp_b_cap, std::max<size_t>(1, ns * nG), "the samples")) return rc;
     if (int rc = grow(&e->smp_chi2, &e->smp_chi2_cap, ns, "chi2 of the samples")) return rc;
@@ -4189,7 +4176,7 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
     char shape[96];
     snprintf(shape, sizeof shape, "N = %lld chains x T = %d steps with P = %d parameters", N, T, P);
-    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(pp, cap, n, elem, who, what, shape); };
+    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(e, pp, cap, n, elem, who, what, shape); };
     if (int rc = grow(&e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, "the steps")) return rc;
     if (int rc = grow(&e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, "lnu")) return rc;
     if (int rc = grow(&e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;

@@ -6,8 +6,8 @@
 One dump per process: _lib.py reads EFTB_LIB once, when it is loaded.  The kernels use integer atomics only (status flags, a min / max in
 ap_weights_kernel), so a build must reproduce itself, and a host-side refactor its parent, in every case.  Each case names the arm it is there
 for -- of the stage launcher (launch_stages_impl) or of the staged launch around it (issue_group: every value of PlkExit,
-both completion rules, both issuing threads, both upload streams, per-step destinations, the GROWS upload); shapes are the
-smallest that reach the arm."""
+both completion rules, both issuing threads, both upload streams, per-step destinations, the GROWS upload), or the
+buffers an engine replaces while it lives; shapes are the smallest that reach the arm."""
 import os
 import sys
 
@@ -231,6 +231,97 @@ def logp_tracers():
     return out
 
 
+def draws_engine(B=4, nG=3, step=4, seed=31):
+    """templates of B seeded cosmologies in the block, and a likelihood over every step-th point of it with nG marginalised parameters"""
+    from eftpipe_amd.marginal import MarginalLikelihood
+    eng, d, rng = Engine(cfg(), max_batch=B), draws(B, seed), np.random.default_rng(seed)
+    eng.eval_batch(d["Pin"], d["f"], d["DA"], d["H"])
+
+    def likelihood(step):
+        index = np.arange(0, 3 * eng.Nk, step)
+        A = 0.03 * rng.standard_normal((index.size, index.size))
+        return MarginalLikelihood(eng, index, 1e3 * rng.standard_normal(index.size), 1e-6 * (np.eye(index.size) + A @ A.T), np.zeros(nG), np.full(nG, 2.0))
+    return eng, d, rng, likelihood, likelihood(step)
+
+
+def recipe(names=("cct", "cr1", "cr2"), kmA=0.7):
+    from eftpipe_amd.marginal import joint_draw_recipe
+    from eftpipe_amd.parambasis import WestCoastBasis
+    return joint_draw_recipe([WestCoastBasis(prefix="")], list(names), [dict(kmA=kmA, krA=0.25, ndA=4.5e-5)])
+
+
+def theta_of(rng, N):  # (b1, b2, b4) per draw
+    return np.array([2.0, 0.5, 0.3]) + rng.standard_normal((N, 3)) * [0.05, 0.3, 0.3]
+
+
+def even_offsets(N, C):
+    return np.arange(C + 1) * (N // C)
+
+
+def relike():
+    """eftb_set_likelihood twice on one engine (the second replaces the first's device arrays, of other sizes), a rows call after each"""
+    B, nG, N = 4, 3, 8
+    eng, d, rng, likelihood, like = draws_engine(B, nG)
+    rows = np.concatenate([np.repeat(d["bias"], N // B, axis=0)[:, None, :], 0.1 * rng.standard_normal((N, nG, 24))], axis=1)
+    out = list(like.logp_draws(rows, even_offsets(N, B), return_best=True))
+    like = likelihood(3)
+    out += list(like.logp_draws(rows, even_offsets(N, B), return_best=True))
+    eng.close()
+    return out
+
+
+def regrow():
+    """grow_dev: a params call of 8 draws, one of 4096 (every draw buffer is replaced by a larger one), 8 again (nothing grows)"""
+    B = 4
+    eng, d, rng, _, like = draws_engine(B)
+    like.set_draw_recipe(recipe())
+    out = []
+    for N in (8, 4096, 8):
+        out += list(like.logp_draws_params(theta_of(rng, N), even_offsets(N, B), d["f"], return_best=True, grad=True, hess=True))
+    eng.close()
+    return out
+
+
+def rerecipe():
+    """eftb_set_draw_recipe twice with recipes of other sizes (the second replaces the first's tables), a params call after each"""
+    B, N = 4, 8
+    eng, d, rng, _, like = draws_engine(B)
+    theta, out = theta_of(rng, N), []
+    for rec in (recipe(), recipe(("b3", "ce0", "cr1"), kmA=0.45)):
+        like.set_draw_recipe(rec)
+        out += list(like.logp_draws_params(theta, even_offsets(N, B), d["f"], return_best=True, grad=True, hess=True))
+    eng.close()
+    return out
+
+
+def redatasets():
+    """eftb_set_likelihood_datasets with 2 data sets, with 5 (the blocks grow), withdrawn; a groups call after each of the first two"""
+    B, N = 4, 12
+    eng, d, rng, _, like = draws_engine(B)
+    like.set_draw_recipe(recipe())
+    theta, out = theta_of(rng, N), []
+    for M in (2, 5):
+        like.set_datasets(1e3 * rng.standard_normal((M, like.index.size)))
+        groups = (np.arange(6) % B, np.arange(6) % M)
+        out += list(like.logp_draws_params(theta, even_offsets(N, 6), d["f"], return_best=True, grad=True, hess=True, groups=groups))
+    like.set_datasets(None)
+    out += list(like.logp_draws_params(theta, even_offsets(N, B), d["f"], return_best=True))
+    eng.close()
+    return out
+
+
+def gather_single():
+    """eftb_gather_plk on one rank without a communicator: the lazily created blocks and events of two exchange slots"""
+    B = 3
+    eng, d = Engine(cfg(), max_batch=B), draws(B, 37)
+    out = []
+    for scale in (1.0, 1.1):
+        eng.eval_batch(scale * d["Pin"], d["f"], d["DA"], d["H"], bias=d["bias"])
+        out.append(eng.gather_plk(B, to_host=True))
+    eng.close()
+    return out
+
+
 def partial_masks():
     """REGROUP without RESUM; EFTB_K_RESUM alone after a full run; EFTB_K_IRFILTER alone; a direct engine split in front of REGROUP"""
     B = 3
@@ -297,6 +388,12 @@ CASES = {
     "nfft512_lo": ("NFFT 512 with low-k tails: prep_rows_lo_kernel, the _nh entry points", {}, sync_eval(3, 3, **LO)),
     "nfft512_lo_direct": ("... on the front of three-stream direct runs: prep_rows_qf_lo_kernel", {}, async_runs(5, direct=True, **LO)),
     "graph": ("captured graph, replayed", {"EFTB_GRAPH": "1"}, graph_replay),
+    # what an engine replaces while it lives: the release-then-acquire paths
+    "relike": ("eftb_set_likelihood twice, a draws call after each", {}, relike),
+    "regrow": ("grow_dev: 8 draws, 4096, 8", {}, regrow),
+    "rerecipe": ("eftb_set_draw_recipe twice, a params call after each", {}, rerecipe),
+    "redatasets": ("eftb_set_likelihood_datasets: 2 data sets, 5, none; groups calls", {}, redatasets),
+    "gather_single": ("eftb_gather_plk without a communicator", {}, gather_single),
     "partial_masks": ("stand-alone REGROUP, EFTB_K_RESUM, EFTB_K_IRFILTER, a split direct run", {}, partial_masks),
 }
 

@@ -31,11 +31,11 @@ MFMA_FLOPS = {"v_mfma_f64_16x16x4_f64": 2 * 16 * 16 * 4, "v_mfma_f64_16x16x4f64"
 
 
 def source_hash():
-    """first 16 hex digits of sha256(eftbird.hip + eftb_kernels.hpp + eftb_staged.hpp): the same value csrc/Makefile compiles into the library"""
+    """first 16 hex digits of sha256(eftbird.hip + eftb_kernels.hpp + eftb_staged.hpp + eftb_own.hpp): the same value csrc/Makefile compiles into the library"""
     import hashlib
 
     h = hashlib.sha256()
-    for f in ("eftbird.hip", "eftb_kernels.hpp", "eftb_staged.hpp"):
+    for f in ("eftbird.hip", "eftb_kernels.hpp", "eftb_staged.hpp", "eftb_own.hpp"):
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
