@@ -115,7 +115,17 @@ def loop_basis(M22, tol=1e-11):
     resid = np.max(np.abs(X @ A[basis] - A)) / np.max(np.abs(A))
     if resid > 1e-13 or np.max(np.abs(X.imag)) > 1e-12 or rank > 16:
         raise ValueError(f"loop-matrix basis reduction failed: rank {rank}, residual {resid:.2e}")
-    return basis, np.ascontiguousarray(X.real)
+    # The fit leaves the combination good to 5e-15 only, and some matrices are small against the basis they are combined from (row 12 of M22: 3000
+    # times at the entries (n, m) near (0, N)), so that this error is 3e-11 of such a piece.  A step of refinement with the residual formed in
+    # extended precision removes it (a second one moves the result by 5e-17 and is left out); what remains, 2e-15 between fits over different subsets
+    # of the entries, is the rounding of the matrix entries themselves.
+    # (on every fourth entry: seven unknowns per row against tens of thousands of equations either way, at a quarter of the set-up time)
+    X = X.real
+    A = A[:, ::4]
+    R = A.astype(np.clongdouble) - X.astype(np.longdouble) @ A[basis].astype(np.clongdouble)
+    Ar = np.concatenate([A[basis].real, A[basis].imag], axis=1)
+    X = X + np.linalg.lstsq(Ar.T, np.concatenate([R.real, R.imag], axis=1).astype(np.float64).T, rcond=None)[0].T
+    return basis, np.ascontiguousarray(X)
 
 
 def antidiagonal_tables(M22b, M13b):

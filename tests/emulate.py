@@ -5,7 +5,9 @@ oracle before (and independently of) the HIP kernels, which implement exactly th
 """
 import numpy as np
 
-NH = 128
+def kpad(n, m=48):
+    """rows of a synthesis operand: n rounded up to the K chunk of synth_kernel (tables.synthesis_table)"""
+    return (n + m - 1) // m * m
 
 
 def tail_params(lnk, y):
@@ -14,49 +16,62 @@ def tail_params(lnk, y):
     return amp, slope
 
 
-def coef_half(t, Pin):
+def coef_half(t, Pin, xi=False):
+    """[Pin | high-k tail | low-k tail] . (Gc ; Ec) -> [2, NCH]; xi: the coefficient set of the xi-space pieces (Gc2 / Ec2 where the tables carry one)"""
     lnk = np.log(t["kin"])
+    lnx, nlo = t["lnx_tail"], int(t["ntail_lo"])
+    nhi = lnx.size - nlo
     amp, slope = tail_params(lnk, Pin)
-    tail = amp * np.exp(slope * t["lnx_tail"])
-    return t["Gc"] @ Pin + t["Ec"] @ tail  # [2,129]
+    tail = amp * np.exp(slope * lnx[:nhi])
+    if nlo:  # power law through the first two samples (reference fftlog.py:140-145)
+        amp, slope = tail_params(lnk[1::-1], Pin[1::-1])
+        tail = np.concatenate([tail, amp * np.exp(slope * lnx[nhi:])])
+    G, E = ("Gc2", "Ec2") if xi and "Gc2" in t else ("Gc", "Ec")
+    return t[G] @ Pin + t[E] @ tail  # [2,NCH]
 
 
 def antidiagonal_sums(t, c):
-    """c [2,129] -> S[nc, 257] complex: S[c, j'] = sum_{n+m=256+j'} c_n c_m M_c[n,m] (device: antidiag_kernel)."""
+    """c [2,NCH] -> S[nc, NPOW] complex: S[c, j'] = sum_{n+m=N+j'} c_n c_m M_c[n,m] (device: antidiag_kernel); N = 2 (NCH - 1), 256 by default."""
     ch = c[0] + 1j * c[1]
-    full = np.concatenate([ch, np.conj(ch[:NH][::-1])])  # c_{256-n} = conj(c_n)
+    nh = ch.size - 1
+    N = 2 * nh
+    full = np.concatenate([ch, np.conj(ch[:nh][::-1])])  # c_{N-n} = conj(c_n)
     AD = t["ad"]
     S = np.zeros(AD.shape[:2], dtype=complex)
     for jp in range(AD.shape[1]):
-        cnt = ((256 + jp) >> 1) - jp + 1
+        cnt = ((N + jp) >> 1) - jp + 1
         tt = np.arange(cnt)
-        S[:, jp] = AD[:, jp, :cnt] @ (full[jp + tt] * full[256 - tt])
+        S[:, jp] = AD[:, jp, :cnt] @ (full[jp + tt] * full[N - tt])
     return S
 
 
 def rows_from_sums(Z):
-    """complex [rows, 257] -> real synthesis rows [rows, 528]: (Re Z_0, Re Z_1, Im Z_1, ...) zero padded (build_rows_kernel)."""
-    out = np.zeros((Z.shape[0], 528))
+    """complex [rows, NPOW] -> real synthesis rows [rows, KSYN]: (Re Z_0, Re Z_1, Im Z_1, ...) zero padded (build_rows_kernel); KSYN = 528 at NPOW = 257."""
+    K = 2 * Z.shape[1] - 1
+    out = np.zeros((Z.shape[0], kpad(K)))
     out[:, 0] = Z[:, 0].real
-    out[:, 1:513:2] = Z[:, 1:].real
-    out[:, 2:513:2] = Z[:, 1:].imag
+    out[:, 1:K:2] = Z[:, 1:].real
+    out[:, 2:K:2] = Z[:, 1:].imag
     return out
 
 
 def rows_from_vectors(c, V):
-    """single sums: X_n = c_n V_n (n = 0..128) -> rows (Re X_128, Re X_127, Im X_127, ..., Re X_0, Im X_0, 0, 0, 0)"""
+    """single sums: X_n = c_n V_n (n = 0..nh) -> rows (Re X_nh, Re X_nh-1, Im X_nh-1, ..., Re X_0, Im X_0, 0, ...) [rows, KLIN]; KLIN = 288 at nh = 128"""
     X = (c[0] + 1j * c[1])[None, :] * V
-    out = np.zeros((V.shape[0], 288))
-    out[:, 0] = X[:, NH].real
-    out[:, 1:257:2] = X[:, NH - 1 :: -1].real
-    out[:, 2:257:2] = X[:, NH - 1 :: -1].imag
+    nh = V.shape[1] - 1
+    K = 2 * nh + 1
+    out = np.zeros((V.shape[0], kpad(K)))
+    out[:, 0] = X[:, nh].real
+    out[:, 1:K:2] = X[:, nh - 1 :: -1].real
+    out[:, 2:K:2] = X[:, nh - 1 :: -1].imag
     return out
 
 
-def pscf(t, Pin, with_cf):
+def pscf(t, Pin, with_cf, coef=None):
+    """coef: (k-space, xi-space) coefficient halves [2, NCH] to use in the place of the first-stage product (tests of the stages behind it)"""
     k, s = t["k"], t["s"]
     P11 = t["Sk"] @ Pin
-    c = coef_half(t, Pin)
+    c = coef_half(t, Pin) if coef is None else coef[0]
     S = antidiagonal_sums(t, c)
     nb = t["comb22"].shape[1]
     out = dict(P11=P11)
@@ -65,13 +80,18 @@ def pscf(t, Pin, with_cf):
     out["P13"] = P11[None, :] * (rows_from_vectors(c, L[:10]) @ t["lin_k"])
     if with_cf:
         Nl = t["l11"].shape[0]
+        if "Gc2" in t:  # IRcutoff "loop" / "resum": the xi-space pieces have a coefficient set of their own
+            c = coef_half(t, Pin, xi=True) if coef is None else coef[1]
+            S = antidiagonal_sums(t, c)
         # device order: synthesise the Nl*(nb + nb13) weighted basis rows, then expand (expand_kernel)
         basis = np.concatenate([rows_from_sums(t["mlj"][l][None, :] * S) @ t["syn_s"] for l in range(Nl)])
         full = t["expand_c"] @ basis
         out["C22"] = full[: Nl * 28].reshape(Nl, 28, -1)
         out["C13"] = full[Nl * 28 :].reshape(Nl, 10, -1)
         out["C11"] = rows_from_vectors(c, L[10 : 10 + Nl]) @ t["lin_s"]
-        out["Cct"] = s[None, :] ** -2 * (rows_from_vectors(c, L[10 + Nl :]) @ t["lin_s"])
+        out["Cct"] = s[None, :] ** -2 * (rows_from_vectors(c, L[10 + Nl : 10 + 2 * Nl]) @ t["lin_s"])
+        if L.shape[0] > 10 + 2 * Nl:  # with_NNLO: the third linear row set
+            out["CctNNLO"] = s[None, :] ** -4 * (rows_from_vectors(c, L[10 + 2 * Nl :]) @ t["lin_s"])
     return out
 
 
