@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace eftb {
 
@@ -3647,13 +3648,15 @@ constexpr int CHAIN_PRI = 4 * RECIPE_MAXP;                                      
 
 // The dynamic LDS of a draw kernel, in doubles: what the host sizes the launch from and what the kernel takes its pointers from.
 //   per workgroup  W_c [J1][J1] at 0, then (all but rows) fp [RECIPE_MAXTR][RECIPE_FPOW] and the int tables, two ints to a double:
-//                  col [nnzp]; erow [nnzp] (gradient, Hessian, sample); drow | dcol [ndtp] (Hessian); then pr [CHAIN_PRI] (chain)
+//                  col [nnzp]; erow [nnzp] (gradient, Hessian, sample); drow | dcol [ndtp] (Hessian); then pr [CHAIN_PRI] (chain, drag).
+//                  drag stages a pair of walkers: the end walker's W_c [J1][J1] behind the start walker's (at W2(J1)) and its fp behind fp (at fp2())
 //   per wave       (all but rows) th [P + 1 -> 34], val [nnzp]; H [ng1][J1], G [ng1][ng1]; then the kind's tail:
 //                  Hessian K [nG][nG] | dval [ndtp] | hv [J1] | u [P][nG] | w [P][nG] | G_p | M_p [P][nG][nG] (the last two empty under Jeffreys)
 //                  sample  bs [ADJ_KB][nG]
 //                  chain   tc | tp [RECIPE_MAXP] (the current and the trial theta) | rs [2][MARG_OUT] (two records)
+//                  drag    tc | tp as chain | rs [2][2][MARG_OUT] (two pairs of records, start | end walker in each)
 // nnzp and ndtp: the entries of the recipe and its derivative records, rounded up to even.  A region a kind does not have is empty.
-enum DrawKind { DRAW_ROWS, DRAW_PARAMS, DRAW_GRAD, DRAW_HESS, DRAW_SAMPLE, DRAW_CHAIN };
+enum DrawKind { DRAW_ROWS, DRAW_PARAMS, DRAW_GRAD, DRAW_HESS, DRAW_SAMPLE, DRAW_CHAIN, DRAW_DRAG };
 
 struct DrawLds {
     int fp = 0, col = 0, erow = 0, drow = 0, dcol = 0, pr = 0, wg = 0;  // offsets from the start of the LDS; wg: doubles per workgroup
@@ -3662,7 +3665,11 @@ struct DrawLds {
 
     DrawLds() = default;
     static constexpr bool has_erow(DrawKind kind) { return kind == DRAW_GRAD || kind == DRAW_HESS || kind == DRAW_SAMPLE; }
+    // (every kind but DRAW_DRAG, whose layout is drag() below: of() is the way in that knows all seven)
     __host__ __device__ constexpr DrawLds(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) {
+#ifndef __HIP_DEVICE_COMPILE__
+        if (kind == DRAW_DRAG) abort();  // a constant expression that gets here does not compile; the kernels name their kind and never do
+#endif
         const bool recipe = kind != DRAW_ROWS, adj = has_erow(kind), hess = kind == DRAW_HESS;
         const int ng1 = nG + 1, nnzp = (nnz + 1) & ~1, ndtp = (ndt + 1) & ~1, gpn = hess && !jeffreys ? P * nG * nG : 0;
         int o = J1 * J1;
@@ -3691,23 +3698,39 @@ struct DrawLds {
         rs = o, o += kind == DRAW_CHAIN ? 2 * MARG_OUT : 0;
         wave = o;
     }
+    // DRAW_DRAG: the chain kind's layout with room for the end walker -- its W_c behind the start walker's (at W2(J1)), its powers of f
+    // behind fp (at fp2()), and a second pair of records at the end of the wave's part.  Built beside the constructor, not in it: the
+    // other kinds' kernels compile from the same expressions as before
+    static __host__ __device__ constexpr DrawLds drag(int J1, int nG, int nnz, int P, int jeffreys) {
+        DrawLds L(DRAW_CHAIN, J1, nG, nnz, 0, P, jeffreys);
+        const int more = J1 * J1 + RECIPE_MAXTR * RECIPE_FPOW;
+        L.fp += J1 * J1;
+        L.col += more, L.erow += more, L.drow += more, L.dcol += more, L.pr += more, L.wg += more;
+        L.wave += 2 * MARG_OUT;
+        return L;
+    }
+    static __host__ __device__ constexpr DrawLds of(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) {
+        return kind == DRAW_DRAG ? drag(J1, nG, nnz, P, jeffreys) : DrawLds(kind, J1, nG, nnz, ndt, P, jeffreys);
+    }
+    static __host__ __device__ constexpr int W2(int J1) { return J1 * J1; }
+    __host__ __device__ constexpr int fp2() const { return fp + RECIPE_MAXTR * RECIPE_FPOW; }
     __host__ __device__ constexpr size_t bytes_wg() const { return (size_t)wg * sizeof(double); }
     __host__ __device__ constexpr size_t bytes_wave() const { return (size_t)wave * sizeof(double); }
     __host__ __device__ constexpr size_t bytes(int nw) const { return bytes_wg() + nw * bytes_wave(); }
-    // the waves of a workgroup: 4, 2 or 1, as many as fit beside W_c; 0 if one does not
+    // the waves of a workgroup: 4, 2 or 1, as many as fit beside W_c (drag: beside both); 0 if one does not
     __host__ __device__ constexpr int fit(size_t limit) const { return bytes(4) <= limit ? 4 : bytes(2) <= limit ? 2 : bytes(1) <= limit ? 1 : 0; }
     // every region holds what its kernel keeps there and ends where the next begins or before (the int tables in whole doubles, so every
     // region starts on an 8-byte boundary), whatever the arithmetic above becomes
     __host__ __device__ constexpr bool sound(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) const {
         const bool recipe = kind != DRAW_ROWS, adj = has_erow(kind), hess = kind == DRAW_HESS;
-        const bool chain = kind == DRAW_CHAIN;
+        const bool drag = kind == DRAW_DRAG, chain = kind == DRAW_CHAIN || drag;
         const int ng1 = nG + 1, gpn = hess && !jeffreys ? P * nG * nG : 0;
-        const int at[] = {0, fp, col, erow, drow, dcol, pr, wg}, atw[] = {th, val, H, G, K, dval, hv, u, w, Gp, Mp, bs, tc, tp, rs, wave};
-        const int len[] = {J1 * J1, recipe ? RECIPE_MAXTR * RECIPE_FPOW : 0, recipe ? (nnz + 1) / 2 : 0, adj ? (nnz + 1) / 2 : 0, hess ? (ndt + 1) / 2 : 0,
-                           hess ? (ndt + 1) / 2 : 0, chain ? CHAIN_PRI : 0};
+        const int at[] = {0, drag ? W2(J1) : fp, fp, drag ? fp2() : col, col, erow, drow, dcol, pr, wg}, atw[] = {th, val, H, G, K, dval, hv, u, w, Gp, Mp, bs, tc, tp, rs, wave};
+        const int len[] = {J1 * J1, drag ? J1 * J1 : 0, recipe ? RECIPE_MAXTR * RECIPE_FPOW : 0, drag ? RECIPE_MAXTR * RECIPE_FPOW : 0, recipe ? (nnz + 1) / 2 : 0,
+                           adj ? (nnz + 1) / 2 : 0, hess ? (ndt + 1) / 2 : 0, hess ? (ndt + 1) / 2 : 0, chain ? CHAIN_PRI : 0};
         const int lenw[] = {recipe ? P + 1 : 0, recipe ? nnz : 0, ng1 * J1, ng1 * ng1, hess ? nG * nG : 0, hess ? ndt : 0, hess ? J1 : 0, hess ? P * nG : 0,
-                            hess ? P * nG : 0, gpn, gpn, kind == DRAW_SAMPLE ? ADJ_KB * nG : 0, chain ? P : 0, chain ? P : 0, chain ? 2 * MARG_OUT : 0};
-        for (int i = 0; i < 7; ++i)
+                            hess ? P * nG : 0, gpn, gpn, kind == DRAW_SAMPLE ? ADJ_KB * nG : 0, chain ? P : 0, chain ? P : 0, drag ? 4 * MARG_OUT : chain ? 2 * MARG_OUT : 0};
+        for (int i = 0; i < 9; ++i)
             if (at[i] + len[i] > at[i + 1]) return false;
         for (int i = 0; i < 15; ++i)
             if (atw[i] + lenw[i] > atw[i + 1]) return false;
@@ -3725,10 +3748,15 @@ static_assert(draw_lds_pin(DRAW_ROWS, 1024) == 146328 && draw_lds_pin(DRAW_PARAM
 static_assert(draw_lds_pin(DRAW_SAMPLE, 1024) == 147816 + 16 * 1024 && draw_lds_pin(DRAW_SAMPLE, 999) == 147816 + 16 * 1000 &&
                   draw_lds_pin(DRAW_SAMPLE, 1000) == 163816,
               "DrawLds: sample, 147816 + 16 nnzp bytes");
+// drag, which holds two Gram matrices, at the largest shape that fits: three tracers with NNLO (J + 1 = 82), nG = 24, 1024 recipe entries, one
+// wave; four tracers at nG = 24 (J + 1 = 97) do not fit
+static_assert(DrawLds::drag(82, 24, 1024, RECIPE_MAXP, 0).bytes(1) == 144808 && DrawLds::drag(82, 24, 1024, RECIPE_MAXP, 0).fit(160 * 1024) == 1 &&
+                  DrawLds::drag(97, 24, 0, 1, 0).fit(160 * 1024) == 0,
+              "DrawLds: drag at J + 1 = 82 and 97");
 constexpr bool draw_lds_sound(int J1, int nG, int nnz, int ndt, int P) {
-    for (int kind = DRAW_ROWS; kind <= DRAW_CHAIN; ++kind)
+    for (int kind = DRAW_ROWS; kind <= DRAW_DRAG; ++kind)
         for (int jeffreys = 0; jeffreys < 2; ++jeffreys)
-            if (!DrawLds((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys).sound((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys)) return false;
+            if (!DrawLds::of((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys).sound((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys)) return false;
     return true;
 }
 static_assert(draw_lds_sound(121, 24, 1024, 2048, RECIPE_MAXP) && draw_lds_sound(25, 3, 37, 51, 5) && draw_lds_sound(2, 0, 0, 0, 0),
@@ -4000,7 +4028,9 @@ __device__ __forceinline__ int recipe_col(int ent, int ntr) {
 
 // The forward pass of a params draw up to G (one wave; th, val, Hs and Gs are the wave's LDS, Ws, fp and col the workgroup's): theta,
 // val[n], H = R^ W_c and G = H R^^T as described at draws_logp_params_kernel.  G is ordered for the wave's reads on return.
-template <bool TWO>
+// WHO changes nothing in the function: the drag kernel instantiates its own copy (WHO = 1), because a sixth caller of the copy that the
+// five params kernels share moved their compiled code by a register or two.
+template <bool TWO, int WHO = 0>
 __device__ __forceinline__ void draws_recipe_forward(const RecipeTab& rt, const double* __restrict__ theta, long long d, int lane, int ng1, int J1,
                                                      const double* Ws, const double* fp, const int* col, double* th, double* val, double* Hs, double* Gs) {
     const int J = J1 - 1, nnz = rt.nnz;
@@ -4681,6 +4711,158 @@ __global__ __launch_bounds__(256) void draws_chain_params_kernel(int ntr, int nG
             wave_lds_sync();  // (the next step overwrites the trial theta, th, val, H, G and the other record)
         }
         if (lane < P) theta[(size_t)d * P + lane] = tc[lane];
+        if (lane == 0) nacc[d] = na;
+        wave_lds_sync();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dragging chains between two walkers (eftb_draws_drag_params): the chain kernel against a target that slides from the start walker a of
+// the chain's pair to its end walker b,
+//     ln pi_t(theta) = (1 - lam_t) ln pi_a(theta) + lam_t ln pi_b(theta),     ln pi_x = ln P_x + pri,     lam_t = frac[t] from the caller.
+// One workgroup per (pair, share of its chains) with W_a, W_b and the powers of f_a, f_b staged once; one wave per chain at a time, the
+// chain kernel's loop with two evaluations per point: draws_recipe_forward + draws_solve<false> against a, then (where ln P_a is finite:
+// wave-uniform) against b, through the same th / val / H / G scratch -- every record is eftb_draws_logp_params' for that (walker, theta).
+//   start          both records of the starting theta and its pri; either ln P not finite, or an accept count of -1 from an earlier launch:
+//                  the chain has failed, NaN in its slots, theta, sums and final records, accept count -1.  The first launch (t0 = 0)
+//                  starts the sums at sa = ln P_a + pri, sb = ln P_b + pri; a later one takes them from sums [N][2]
+//   step i         as the chain kernel's, with drag_accept; the trial pair of records goes beside the current pair and the pair index
+//                  flips on acceptance.  After the decision sa = sa + (ln P_a + pri), sb = sb + (ln P_b + pri) of the current state
+//   store          after every thin-th step (thin = 0: never): theta and the current pair of records, rec [N][kstride][2][MARG_OUT]
+//   end            theta, nacc, sums and the current pair of records (fin [N][2][MARG_OUT]) are overwritten with the state after the launch
+// drag_accept and drag_sum round every operation on its own, as chain_prior and chain_accept.  Every loop's trip count is fixed at launch.
+// LDS: DrawLds, DRAW_DRAG.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool drag_accept(double lnu, double lam, double la1, double lb1, double pri1, double la0, double lb0, double pri0) {
+#pragma clang fp contract(off)
+    const double u = 1.0 - lam;
+    const double a1 = la1 + pri1, b1 = lb1 + pri1, a0 = la0 + pri0, b0 = lb0 + pri0;
+    const double w1 = u * a1 + lam * b1, w0 = u * a0 + lam * b0;
+    return __builtin_isfinite(la1) && __builtin_isfinite(lb1) && lnu < w1 - w0;
+}
+
+__device__ __forceinline__ double drag_sum(double s, double lp, double pri) {
+#pragma clang fp contract(off)
+    return s + (lp + pri);
+}
+
+// draws_stage for a pair of walkers: the end walker's W_c and powers of f go in first, then everything the chain kernel stages for the
+// start walker (draws_stage of the chain kind, unchanged, at the places of the drag layout), behind one barrier
+__device__ __forceinline__ double* draws_stage_pair(const DrawLds& L, double* sm, int wv, int a, int b, int ntr, int J1, const RecipeTab& rt,
+                                                    const double* __restrict__ f, const double* __restrict__ W, const double* __restrict__ prior) {
+    for (int e = threadIdx.x; e < J1 * J1; e += blockDim.x) sm[DrawLds::W2(J1) + e] = W[(size_t)b * J1 * J1 + e];
+    recipe_fpow(f, b, ntr, threadIdx.x, sm + L.fp2());
+    return draws_stage<DRAW_CHAIN>(L, sm, wv, a, ntr, J1, rt, f, W, nullptr, nullptr, 0, prior);
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(256) void draws_drag_params_kernel(int ntr, int nG, int J1, int jeffreys, int Tc, int t0, int thin, int kc, int kstride,
+                                                                RecipeTab rt, const long long* __restrict__ offsets, const int* __restrict__ wstart,
+                                                                const int* __restrict__ wend, double* __restrict__ theta, long long* __restrict__ nacc,
+                                                                double* __restrict__ sums, const double* __restrict__ f, const double* __restrict__ W,
+                                                                const double* __restrict__ mu, const double* __restrict__ sinv,
+                                                                const double* __restrict__ prior, const double* __restrict__ frac,
+                                                                const double* __restrict__ step, const double* __restrict__ lnu,
+                                                                double* __restrict__ chain, double* __restrict__ rec, double* __restrict__ fin) {
+    extern __shared__ double sm[];
+    const int g = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ng1 = nG + 1, P = rt.P;
+    const long long d0 = offsets[g], d1 = offsets[g + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no chain for this share)
+    const DrawLds L = DrawLds::drag(J1, nG, rt.nnz, P, jeffreys);
+    double* wave = draws_stage_pair(L, sm, wv, wstart[g], wend[g], ntr, J1, rt, f, W, prior);
+    double *Wa = sm, *Wb = sm + DrawLds::W2(J1), *fa = sm + L.fp, *fb = sm + L.fp2(), *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    double *tc = wave + L.tc, *tp = wave + L.tp, *rs = wave + L.rs;
+    const int* col = reinterpret_cast<int*>(sm + L.col);
+    const double* pr = sm + L.pr;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    constexpr int PAIR = 2 * MARG_OUT;  // a pair of records: the start walker's, then the end walker's
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        long long na = nacc[d];
+        double* oc = chain + (size_t)d * kstride * P;
+        double* orec = rec + (size_t)d * kstride * PAIR;
+        if (lane < P) tc[lane] = tp[lane] = theta[(size_t)d * P + lane];
+        wave_lds_sync();
+        int cur = 0;
+        double la0 = nan, lb0 = nan, pri0 = 0.0;
+        if (na >= 0) {  // (wave-uniform)
+            draws_recipe_forward<TWO, 1>(rt, tp, 0, lane, ng1, J1, Wa, fa, col, th, val, Hs, Gs);
+            draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, rs);
+            wave_lds_sync();
+            draws_recipe_forward<TWO, 1>(rt, tp, 0, lane, ng1, J1, Wb, fb, col, th, val, Hs, Gs);
+            draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, rs + MARG_OUT);
+            wave_lds_sync();
+            la0 = rs[0];
+            lb0 = rs[MARG_OUT];
+            pri0 = chain_prior(P, tp, pr);
+        }
+        if (!__builtin_amdgcn_readfirstlane((int)(__builtin_isfinite(la0) && __builtin_isfinite(lb0)))) {  // a failed chain
+            for (int k = 0; k < kc; ++k) {
+                if (lane < P) oc[(size_t)k * P + lane] = nan;
+                if (lane < PAIR) orec[(size_t)k * PAIR + lane] = nan;
+            }
+            if (lane < P) theta[(size_t)d * P + lane] = nan;
+            if (lane < PAIR) fin[(size_t)d * PAIR + lane] = nan;
+            if (lane < 2) sums[(size_t)d * 2 + lane] = nan;
+            if (lane == 0) nacc[d] = -1;
+            wave_lds_sync();
+            continue;
+        }
+        double sa = la0 + pri0, sb = lb0 + pri0;  // the first term of the sums
+        if (t0 > 0) {
+            sa = sums[(size_t)d * 2];
+            sb = sums[(size_t)d * 2 + 1];
+        }
+        int left = thin ? thin - t0 % thin : Tc + 1, k = 0;  // (thin = 0: left never reaches 0)
+        for (int i = 0; i < Tc; ++i) {
+            if (lane < P) tp[lane] = tc[lane] + step[((size_t)d * Tc + i) * P + lane];
+            wave_lds_sync();
+            bool in = true;
+            for (int p = 0; p < P; ++p) {
+                const double v = tp[p];
+                in = in && v >= pr[p] && v <= pr[RECIPE_MAXP + p];
+            }
+            int acc = 0;
+            double la1 = nan, lb1 = nan, pri1 = 0.0;
+            if (__builtin_amdgcn_readfirstlane((int)in)) {  // (wave-uniform: the forward pass and the solve are wave-synchronous)
+                double* ot = rs + (cur ^ 1) * PAIR;
+                draws_recipe_forward<TWO, 1>(rt, tp, 0, lane, ng1, J1, Wa, fa, col, th, val, Hs, Gs);
+                draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, ot);
+                wave_lds_sync();
+                la1 = ot[0];
+                if (__builtin_amdgcn_readfirstlane((int)__builtin_isfinite(la1))) {  // (wave-uniform; not finite: rejected whatever the end gives)
+                    draws_recipe_forward<TWO, 1>(rt, tp, 0, lane, ng1, J1, Wb, fb, col, th, val, Hs, Gs);
+                    draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, ot + MARG_OUT);
+                    wave_lds_sync();
+                    lb1 = ot[MARG_OUT];
+                }
+                pri1 = chain_prior(P, tp, pr);
+                acc = __builtin_amdgcn_readfirstlane((int)drag_accept(lnu[(size_t)d * Tc + i], frac[t0 + i], la1, lb1, pri1, la0, lb0, pri0));
+            }
+            if (acc) {
+                cur ^= 1;
+                la0 = la1;
+                lb0 = lb1;
+                pri0 = pri1;
+                ++na;
+                if (lane < P) tc[lane] = tp[lane];
+            }
+            sa = drag_sum(sa, la0, pri0);
+            sb = drag_sum(sb, lb0, pri0);
+            if (--left == 0) {
+                left = thin;
+                if (k < kc) {  // (always: the host counts the slots of the launch the same way)
+                    if (lane < P) oc[(size_t)k * P + lane] = tc[lane];
+                    if (lane < PAIR) orec[(size_t)k * PAIR + lane] = rs[cur * PAIR + lane];
+                }
+                ++k;
+            }
+            wave_lds_sync();  // (the next step overwrites the trial theta, th, val, H, G and the other pair of records)
+        }
+        if (lane < P) theta[(size_t)d * P + lane] = tc[lane];
+        if (lane < PAIR) fin[(size_t)d * PAIR + lane] = rs[cur * PAIR + lane];
+        if (lane < 2) sums[(size_t)d * 2 + lane] = lane ? sb : sa;
         if (lane == 0) nacc[d] = na;
         wave_lds_sync();
     }

@@ -421,6 +421,15 @@ struct eftb_engine {
     bool sub_stats = false;
     double issue_ns = 0.0, fill_ns = 0.0, wait_ns = 0.0;
     unsigned long long issue_n = 0, inline_n = 0;
+    // eftb_draws_drag_params, which shares the chain call's buffers (its records are pairs): the pairs' walkers [2][G], frac [T], the sums [N][2]
+    // and the final pairs of records [N][2][MARG_OUT]; grown on demand.  Behind
+    // everything else: the fields that the submission thread and the callers share keep the places, and the cache lines, they had
+    int* drg_pair = nullptr;
+    double *drg_frac = nullptr, *drg_sums = nullptr, *drg_fin = nullptr;
+    size_t drg_pair_cap = 0, drg_frac_cap = 0, drg_sums_cap = 0, drg_fin_cap = 0;
+    std::vector<int> drg_host_pair;
+    bool drg_lds = false;  // the LDS opt-in of its kernel is done
+    std::vector<double> drg_host_fin;
 };
 
 static void sub_stop_thread(eftb_engine* e);
@@ -2525,7 +2534,7 @@ struct DrawShape {
 static int draws_logp_shape(eftb_engine* e, const char* who, DrawKind kind, const eftb_engine::Recipe* rcp, DrawShape* sh) {
     const int J1 = (e->c.with_nnlo ? NROW + 3 : NROW) * e->ntr + 1;
     if (J1 > DRAW_MAXJ1) return fail("%s: %d template columns per walker, at most %d", who, J1 - 1, DRAW_MAXJ1 - 1);
-    const DrawLds L(kind, J1, e->like_nG, rcp ? rcp->nnz : 0, rcp ? rcp->ndt : 0, rcp ? rcp->P : 0, e->jeffreys);
+    const DrawLds L = DrawLds::of(kind, J1, e->like_nG, rcp ? rcp->nnz : 0, rcp ? rcp->ndt : 0, rcp ? rcp->P : 0, e->jeffreys);
     const int nw = L.fit(160 * 1024);
     *sh = DrawShape{J1, nw, L, L.bytes(nw)};
     return 0;
@@ -4128,28 +4137,18 @@ int eftb_draws_sample_params_datasets(eftb_engine* e, int C, int G, const int32_
 // record of the launch's starting theta
 constexpr int CHAIN_STEPS = 256;
 
-// eftb_draws_chain_params and eftb_draws_chain_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group): the checks, W_c
-// and uploads of draws_logp_params_impl, then draws_chain_params_kernel once per CHAIN_STEPS steps.  Between the launches theta and the accept
-// counts stay on the device; every launch's stored states and records come back behind it
-static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0,
-                                   const double* f, const double* step, const double* lnu, const double* lower, const double* upper, const double* ploc,
-                                   const double* pscale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept,
-                                   const DrawGroups* gr = nullptr) {
-    long long maxcnt = 0;
-    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
-    const int ntr = e->ntr, nG = e->like_nG;
-    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
-    const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int P = rcp.P;
+// what the chain calls refuse in their own arguments, after draws_params_check: no parameter, T, thin (at least thin_min), step, lnu, the prior
+// on theta and a theta0 outside the box; pri [CHAIN_PRI] = lower | upper | loc | sinv is the table their kernels read
+static int chain_args_check(const char* who, int P, long long N, int T, int thin, int thin_min, const double* theta0, const double* step, const double* lnu,
+                            const double* lower, const double* upper, const double* ploc, const double* pscale, double* pri) {
     if (P < 1) return fail("%s: the draw recipe has no parameters to move", who);
     if (T < 1) return fail("%s: T = %d steps, at least 1", who, T);
-    if (thin < 1 || thin > T) return fail("%s: thin = %d outside [1, T = %d]", who, thin, T);
+    if (thin < thin_min || thin > T) return fail("%s: thin = %d outside [%d, T = %d]", who, thin, thin_min, T);
     const long long TP = (long long)T * P;
     for (long long q = 0; q < N * TP; ++q)
         if (!std::isfinite(step[q])) return fail("%s: step[%lld][%lld][%d] is not finite", who, q / TP, q / P % T, (int)(q % P));
     for (long long q = 0; q < N * T; ++q)
         if (!(lnu[q] <= 0.0)) return fail("%s: lnu[%lld][%lld] = %g is not the logarithm of a uniform in [0, 1]", who, q / T, q % T, lnu[q]);
-    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
     for (int p = 0; p < P; ++p) {
         const double lo = lower ? lower[p] : -INFINITY, hi = upper ? upper[p] : INFINITY, sc = pscale ? pscale[p] : INFINITY;
         const double mu = ploc ? ploc[p] : 0.0;
@@ -4166,6 +4165,24 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     for (long long q = 0; q < N * P; ++q)
         if (!(theta0[q] >= pri[q % P] && theta0[q] <= pri[RECIPE_MAXP + q % P]))
             return fail("%s: theta0[%lld][%d] = %g outside [%g, %g]", who, q / P, (int)(q % P), theta0[q], pri[q % P], pri[RECIPE_MAXP + q % P]);
+    return 0;
+}
+
+// eftb_draws_chain_params and eftb_draws_chain_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group): the checks, W_c
+// and uploads of draws_logp_params_impl, then draws_chain_params_kernel once per CHAIN_STEPS steps.  Between the launches theta and the accept
+// counts stay on the device; every launch's stored states and records come back behind it
+static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0,
+                                   const double* f, const double* step, const double* lnu, const double* lower, const double* upper, const double* ploc,
+                                   const double* pscale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept,
+                                   const DrawGroups* gr = nullptr) {
+    long long maxcnt = 0;
+    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
+    const int ntr = e->ntr, nG = e->like_nG;
+    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int P = rcp.P;
+    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
+    if (int rc = chain_args_check(who, P, N, T, thin, 1, theta0, step, lnu, lower, upper, ploc, pscale, pri)) return rc;
     DrawShape sh;
     if (int rc = draws_logp_shape(e, who, DRAW_CHAIN, &rcp, &sh)) return rc;
     // Unreachable: the largest shape there is (J + 1 = 121, nG = 24, 1024 recipe entries) takes 161288 of the 163840 bytes at one wave.
@@ -4240,4 +4257,113 @@ int eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_t
     if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
     return draws_chain_params_impl(e, who, G, N, T, thin, offsets, theta0, e->grp_f.data(), step, lnu, lower, upper, prior_loc,
                                    prior_scale, chain, logp, fullchi2, best, last, naccept, &gr);
+}
+
+// ------------------------------------------------------------------------------------------------ dragging chains between two walkers
+// eftb_draws_drag_params: the chain call's checks (chain_args_check, thin = 0 allowed), Gram cache (W_c of the C walkers), prior table,
+// buffers and split into launches of CHAIN_STEPS steps around draws_drag_params_kernel.  C walkers are resident; pair g = (wstart[g], wend[g])
+// owns the chains offsets[g] ... offsets[g + 1] - 1.  Between the launches theta, the accept counts and the sums [N][2] stay on the device;
+// every launch recomputes both records of its starting theta, so a chain's bits do not depend on the split.  The record arrays have
+// K + 1 slots per chain: the K stored records, then the one of the state after step T
+int eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, const int32_t* wend, long long N, int T, int thin, const int64_t* offsets,
+                           const double* theta0, const double* f, const double* frac, const double* step, const double* lnu, const double* lower,
+                           const double* upper, const double* prior_loc, const double* prior_scale, double* chain, double* logp_start, double* logp_end,
+                           double* fullchi2_start, double* fullchi2_end, double* best_start, double* best_end, double* last, int64_t* naccept, double* sums) {
+    static const char* who = "eftb_draws_drag_params";
+    if (e) sub_drain(e);
+    if (!e || !wstart || !wend || !offsets || !f || !frac || (N > 0 && (!theta0 || !step || !lnu || !last || !naccept || !sums)))
+        return fail("%s: null argument", who);
+    if (C < 1) return fail("%s: %d walkers", who, C);
+    long long maxcnt = 0;
+    if (int rc = draws_logp_check(e, who, G, N, offsets, &maxcnt, "pair", C)) return rc;
+    const int ntr = e->ntr, nG = e->like_nG;
+    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int P = rcp.P;
+    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
+    if (int rc = chain_args_check(who, P, N, T, thin, 0, theta0, step, lnu, lower, upper, prior_loc, prior_scale, pri)) return rc;
+    if (thin > 0 && N > 0 && !chain) return fail("%s: null argument (chain, with thin = %d)", who, thin);
+    for (int g = 0; g < G; ++g) {
+        if (wstart[g] < 0 || wstart[g] >= C) return fail("%s: wstart[%d] = %d outside [0, %d): the start walker of pair %d", who, g, wstart[g], C, g);
+        if (wend[g] < 0 || wend[g] >= C) return fail("%s: wend[%d] = %d outside [0, %d): the end walker of pair %d", who, g, wend[g], C, g);
+    }
+    for (int t = 0; t < T; ++t)
+        if (!(frac[t] >= 0.0 && frac[t] <= 1.0)) return fail("%s: frac[%d] = %g outside [0, 1]", who, t, frac[t]);
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, DRAW_DRAG, &rcp, &sh)) return rc;
+    if (!sh.nw)
+        return fail("%s: the call stages two Gram matrices of J + 1 = %d columns per workgroup; with nG = %d they do not fit the LDS beside one wave (%zu bytes per "
+                    "workgroup and %zu per wave of %d)", who, sh.J1, nG, sh.L.bytes_wg(), sh.L.bytes_wave(), 160 * 1024);
+    if (N == 0) return 0;
+    const int K = thin ? T / thin : 0, kstride = thin ? std::max(1, std::min(K, CHAIN_STEPS / thin + 1)) : 1, Tmax = std::min(T, CHAIN_STEPS);
+    constexpr int PAIR = 2 * MARG_OUT;
+    if (int rc = draws_logp_begin(e, who, G, N, sh.J1, offsets, C)) return rc;
+    if (!e->drg_lds) {  // the large dynamic LDS for this call's kernel, once per engine (as draws_lds_optin for the others)
+        for (const void* k : {reinterpret_cast<const void*>(&draws_drag_params_kernel<false>), reinterpret_cast<const void*>(&draws_drag_params_kernel<true>)})
+            HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->drg_lds = true;
+    }
+    const double *dtheta = nullptr, *df = nullptr;
+    if (int rc = draws_params_upload(e, P, C, N, theta0, f, &dtheta, &df)) return rc;
+    const dim3 grid(G, draw_shares(maxcnt, sh.nw, G)), block(64 * sh.nw);
+    const RecipeTab rt = recipe_tab(rcp);
+    char shape[96];
+    snprintf(shape, sizeof shape, "N = %lld chains x T = %d steps with P = %d parameters", N, T, P);
+    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(e, pp, cap, n, elem, who, what, shape); };
+    if (int rc = grow(&e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, "the steps")) return rc;
+    if (int rc = grow(&e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, "lnu")) return rc;
+    if (int rc = grow(&e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
+    if (int rc = grow(&e->chn_nacc, &e->chn_nacc_cap, (size_t)N, "the accept counts", sizeof(long long))) return rc;
+    if (int rc = grow(&e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, "the stored states")) return rc;
+    if (int rc = grow(&e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * PAIR, "the stored records")) return rc;
+    if (int rc = grow(&e->drg_pair, &e->drg_pair_cap, 2 * (size_t)G, "the pairs", sizeof(int))) return rc;
+    if (int rc = grow(&e->drg_frac, &e->drg_frac_cap, (size_t)T, "frac")) return rc;
+    if (int rc = grow(&e->drg_sums, &e->drg_sums_cap, 2 * (size_t)N, "the sums")) return rc;
+    if (int rc = grow(&e->drg_fin, &e->drg_fin_cap, (size_t)N * PAIR, "the final records")) return rc;
+    hipStream_t st = e->stream;
+    e->drg_host_pair.assign(wstart, wstart + G);
+    e->drg_host_pair.insert(e->drg_host_pair.end(), wend, wend + G);
+    HIPCHK(hipMemcpyAsync(e->drg_pair, e->drg_host_pair.data(), 2 * (size_t)G * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->drg_frac, frac, (size_t)T * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
+    e->chn_host_chain.resize((size_t)N * kstride * P);
+    e->chn_host_rec.resize((size_t)N * kstride * PAIR);
+    for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) {
+        const int Tc = std::min(CHAIN_STEPS, T - t0), k0 = thin ? t0 / thin : 0, kc = thin ? (t0 + Tc) / thin - k0 : 0;
+        // this launch's steps of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
+        HIPCHK(hipMemcpy2DAsync(e->chn_step, (size_t)Tc * P * sizeof(double), step + (size_t)t0 * P, (size_t)T * P * sizeof(double), (size_t)Tc * P * sizeof(double),
+                                (size_t)N, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
+                                hipMemcpyHostToDevice, st));
+        launch_two(draws_drag_params_kernel<false>, draws_drag_params_kernel<true>, sh.J1, grid, block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin, kc, kstride, rt,
+                   e->drw_off, e->drg_pair, e->drg_pair + G, e->drw_theta, e->chn_nacc, e->drg_sums, df, e->drw_W, e->like_mu, e->like_sinv, e->chn_pri, e->drg_frac,
+                   e->chn_step, e->chn_lnu, e->chn_chain, e->chn_rec, e->drg_fin);
+        if (int rc = launched(who)) return rc;
+        if (!kc) continue;
+        HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, (size_t)N * kstride * PAIR * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (long long n = 0; n < N; ++n)
+            for (int k = 0; k < kc; ++k) {
+                const size_t to = (size_t)n * (K + 1) + k0 + k, from = (size_t)n * kstride + k;
+                std::copy_n(e->chn_host_chain.data() + from * P, P, chain + ((size_t)n * K + k0 + k) * P);
+                draws_unpack(e->chn_host_rec.data() + from * PAIR, nG, to, logp_start, fullchi2_start, best_start);
+                draws_unpack(e->chn_host_rec.data() + from * PAIR + MARG_OUT, nG, to, logp_end, fullchi2_end, best_end);
+            }
+    }
+    e->chn_host_nacc.resize((size_t)N);
+    e->drg_host_fin.resize((size_t)N * PAIR);
+    HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(sums, e->drg_sums, 2 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(e->drg_host_fin.data(), e->drg_fin, (size_t)N * PAIR * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (long long n = 0; n < N; ++n) {
+        naccept[n] = e->chn_host_nacc[n];
+        const size_t to = (size_t)n * (K + 1) + K;
+        draws_unpack(e->drg_host_fin.data() + (size_t)n * PAIR, nG, to, logp_start, fullchi2_start, best_start);
+        draws_unpack(e->drg_host_fin.data() + (size_t)n * PAIR + MARG_OUT, nG, to, logp_end, fullchi2_end, best_end);
+    }
+    return 0;
 }

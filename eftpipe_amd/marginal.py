@@ -22,6 +22,8 @@ GaussianSamples = collections.namedtuple("GaussianSamples", "logp fullchi2 best 
 
 # what MarginalLikelihood.metropolis_draws_params returns; fullchi2 and best are None unless return_best is set
 DrawChains = collections.namedtuple("DrawChains", "theta logp naccept last fullchi2 best")
+DragChains = collections.namedtuple("DragChains", "theta logp_start logp_end last naccept last_logp_start last_logp_end sum_start sum_end log_ratio "
+                                    "fullchi2_start fullchi2_end best_start best_end last_fullchi2_start last_fullchi2_end last_best_start last_best_end")
 
 
 def data_index(ls, masks, nx, tracer=0, nl=None):
@@ -411,6 +413,68 @@ class MarginalLikelihood:
             L.check(self.eng.lib.eftb_draws_chain_params(self.eng._h, off.size - 1, N, T, thin, *tail))
         return DrawChains(theta, logp, nacc, last, full, best)
 
+    def drag_draws_params(self, theta0, offsets, f, pairs, step, lnu, frac=None, thin=0, lower=None, upper=None, prior_loc=None, prior_scale=None,
+                          return_best=False):
+        """The fast steps of a dragging sampler (cobaya's ``drag: true``) between two slow points, all T steps of all N chains in one device
+        call (``eftb_draws_drag_params``).  The C walkers of the resident template block are the slow points, f [C, ntr] their growth
+        rates; pairs = (start [G], end [G]) names the walkers each pair drags between (repeats and start = end allowed) and pair g owns the
+        chains offsets[g] ... offsets[g + 1] - 1 (offsets [G + 1]).  theta0, step, lnu, the box and the Gaussian prior on theta are those of
+        ``metropolis_draws_params``.  Step t of a chain targets
+            (1 - frac[t]) ln pi_start(theta) + frac[t] ln pi_end(theta),      ln pi_x = ln P_marg of walker x + ln prior(theta),
+        with frac [T] in [0, 1]; ``None`` is ``drag_fractions(T)``, cobaya's schedule.  Along the way the call sums ln pi_start and ln pi_end
+        of the current state, the starting state included: T + 1 terms each.
+        -> ``DragChains``: theta [N, K, P], logp_start and logp_end [N, K] after steps thin, 2 thin, ... (K = T // thin; thin = 0, a
+        sampler's normal use, stores no trajectory); last [N, P], naccept [N], last_logp_start and last_logp_end [N] after step T; sum_start,
+        sum_end [N] and log_ratio = (sum_end - sum_start) / (T + 1), the logarithm of the acceptance ratio of the whole slow + fast move
+        (``drag_accept``).  With ``return_best`` the fields fullchi2_* and best_* [.., nG] of both walkers are filled too, else None.
+        Every ln P, chi2 and best fit is the bit pattern ``logp_draws_params`` returns for that walker at that theta, and a chain's bits
+        depend neither on the other chains nor on the order of the pairs.
+        Raises RuntimeError("det of F2ij <= 0") where a chain's starting point has no finite ln P at either walker."""
+        out = self._drag_raw(theta0, offsets, f, pairs, step, lnu, frac, thin, lower, upper, prior_loc, prior_scale, return_best)
+        if np.any(out.naccept < 0):
+            raise RuntimeError("det of F2ij <= 0")
+        return out
+
+    def _drag_raw(self, theta0, offsets, f, pairs, step, lnu, frac=None, thin=0, lower=None, upper=None, prior_loc=None, prior_scale=None, return_best=False):
+        """``drag_draws_params`` without the RuntimeError: a chain that failed at its start has NaN states, records and sums and naccept = -1"""
+        ntr, nG = self.eng.ntracers, self.nG
+        theta0, off, f, wa, wb = _groups_args(getattr(self, "_recipe", None), theta0, offsets, f, ntr, pairs, "pairs must be (start [G], end [G])", "pair")
+        N, P = theta0.shape
+        step = np.ascontiguousarray(step, dtype=np.float64)
+        if step.ndim != 3 or step.shape[0] != N or step.shape[2] != P or step.shape[1] < 1:
+            raise ValueError(f"step must be [{N}, T, {P}] proposal increments with T >= 1 steps")
+        T = step.shape[1]
+        lnu = np.ascontiguousarray(lnu, dtype=np.float64)
+        if lnu.shape != (N, T):
+            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and step")
+        frac = drag_fractions(T) if frac is None else np.ascontiguousarray(frac, dtype=np.float64)
+        if frac.shape != (T,):
+            raise ValueError(f"frac must be [{T}]: the weight of the end point at every step")
+        if thin != int(thin) or not 0 <= thin <= T:
+            raise ValueError(f"thin must be an integer in [0, T = {T}]")
+        thin = int(thin)
+        pri = []
+        for name, a in (("lower", lower), ("upper", upper), ("prior_loc", prior_loc), ("prior_scale", prior_scale)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (P,):
+                    raise ValueError(f"{name} must be [{P}], one value per parameter")
+            pri.append(a)
+        K = T // thin if thin else 0
+        theta, last, nacc, sums = np.empty((N, K, P)), np.empty((N, P)), np.empty(N, dtype=np.int64), np.empty((N, 2))
+        la, lb = np.empty((N, K + 1)), np.empty((N, K + 1))
+        fa, fb = (np.empty((N, K + 1)), np.empty((N, K + 1))) if return_best else (None, None)
+        ba, bb = (np.empty((N, K + 1, nG)), np.empty((N, K + 1, nG))) if return_best else (None, None)
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        L.check(self.eng.lib.eftb_draws_drag_params(self.eng._h, f.shape[0], wa.size, wa.ctypes.data_as(i32p), wb.ctypes.data_as(i32p), N, T, thin,
+                                                    off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(frac), L.dptr(step), L.dptr(lnu),
+                                                    *[L.dptr(a) for a in pri], L.dptr(theta), L.dptr(la), L.dptr(lb), L.dptr(fa), L.dptr(fb), L.dptr(ba),
+                                                    L.dptr(bb), L.dptr(last), nacc.ctypes.data_as(i64p), L.dptr(sums)))
+        sa, sb = sums[:, 0].copy(), sums[:, 1].copy()
+        cut = lambda a: (None, None) if a is None else (a[:, :K], a[:, K])
+        (fak, fal), (fbk, fbl), (bak, bal), (bbk, bbl) = cut(fa), cut(fb), cut(ba), cut(bb)
+        return DragChains(theta, la[:, :K], lb[:, :K], last, nacc, la[:, K], lb[:, K], sa, sb, (sb - sa) / (T + 1), fak, fbk, bak, bbk, fal, fbl, bal, bbl)
+
     def maximize_draws_params(self, theta0, offsets, f, groups=None, **kw):
         """Best fits over the recipe's parameters at fixed cosmology: ``newton_maximize`` fed with the Hessian call, all starts of all
         walkers at once (theta0 [N, P], offsets and f as ``logp_draws_params``; kw: max_iter, tol) -> theta, logp, grad, hess, n_iter,
@@ -452,25 +516,26 @@ def _offsets(offsets):
     return off
 
 
-def _groups_args(recipe, theta, offsets, f, ntr, groups):
+def _groups_args(recipe, theta, offsets, f, ntr, groups, what="groups must be (walker [G], dataset [G])", unit="group"):
     """theta [N, P], offsets [G + 1], f [C, ntr] and groups = (walker [G], dataset [G]) of a groups call as the library takes them; shape
-    errors are raised here, the values (a walker or data set out of range) are the library's to refuse"""
+    errors are raised here, the values (a walker or data set out of range) are the library's to refuse.  ``drag_draws_params`` passes its
+    pairs (start [G], end [G]) through here with its own wording."""
     try:
         wk, ds = groups
     except (TypeError, ValueError):
-        raise ValueError("groups must be (walker [G], dataset [G])") from None
+        raise ValueError(what) from None
     wk, ds = np.asarray(wk), np.asarray(ds)
     if wk.ndim != 1 or wk.shape != ds.shape or wk.size < 1:
-        raise ValueError("groups must be (walker [G], dataset [G]): two integer arrays of one length G >= 1")
+        raise ValueError(what + ": two integer arrays of one length G >= 1")
     for a in (wk, ds):
         if a.dtype.kind not in "iu" or np.any(a != a.astype(np.int32)):
-            raise ValueError("groups must be (walker [G], dataset [G]): integers")
+            raise ValueError(what + ": integers")
     from .engine import _theta_f_args
 
     theta, f = _theta_f_args(recipe, theta, f, ntr)
     off = np.ascontiguousarray(offsets, dtype=np.int64)
     if off.ndim != 1 or off.size != wk.size + 1:
-        raise ValueError(f"offsets must be [{wk.size + 1}]: group g owns draws offsets[g] ... offsets[g + 1] - 1")
+        raise ValueError(f"offsets must be [{wk.size + 1}]: {unit} g owns draws offsets[g] ... offsets[g + 1] - 1")
     return theta, off, f.reshape(-1, ntr), np.ascontiguousarray(wk, dtype=np.int32), np.ascontiguousarray(ds, dtype=np.int32)
 
 
@@ -574,4 +639,23 @@ def metropolis_proposals(rng, N, T, factor):
     return np.ascontiguousarray(step), lnu
 
 
-__all__ = ["MarginalLikelihood", "DrawChains", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]
+def drag_fractions(T):
+    """The schedule of a dragging step of T fast steps (cobaya's ``drag: true``; Neal 2005): the weight of the end point at fast step
+    t = 1 ... T is t / (T + 1) -> frac [T].  The default of ``drag_draws_params``."""
+    if T != int(T) or T < 1:
+        raise ValueError("T must be an integer >= 1")
+    return np.arange(1, int(T) + 1) / (int(T) + 1)
+
+
+def drag_accept(lnu_slow, result):
+    """The decision on the whole slow + fast move of every chain of a ``DragChains``: lnu_slow [N], the logarithms of the caller's uniforms
+    -> accepted [N] = lnu_slow < result.log_ratio.  An accepted chain goes on from (end walker, result.last), a rejected one returns to
+    (start walker, its theta0).  The ratio is that of ln pi alone: a prior on the slow parameters and an asymmetric slow proposal are the
+    caller's to add to lnu_slow's side."""
+    lnu_slow = np.asarray(lnu_slow, dtype=np.float64)
+    if lnu_slow.shape != np.shape(result.log_ratio):
+        raise ValueError(f"lnu_slow must be {list(np.shape(result.log_ratio))}: the logarithm of a uniform per chain")
+    return lnu_slow < result.log_ratio
+
+
+__all__ = ["MarginalLikelihood", "DrawChains", "DragChains", "drag_fractions", "drag_accept", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]

@@ -429,6 +429,39 @@ int  eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_
                                       const double* lower, const double* upper, const double* prior_loc, const double* prior_scale, double* chain,
                                       double* logp, double* fullchi2, double* best, double* last, int64_t* naccept);
 
+/* Dragging chains between two cosmologies in one device call (the fast steps of cobaya's `drag: true` behind one slow proposal): the
+ * chain call against a target that slides from a start walker to an end walker.  C walkers are resident, each with its own templates and
+ * f [C][ntr]; pair g = (a = wstart[g], b = wend[g]) of G pairs (walkers may repeat, a = b is allowed) owns the chains
+ * offsets[g] ... offsets[g + 1] - 1 (offsets [G + 1]).  With ln pi_x(theta) = ln P_x(theta) + pri(theta), ln P_x the record of
+ * eftb_draws_logp_params for walker x and pri the chain call's prior on theta, step t = 0 ... T - 1 of chain n targets
+ *     ln pi_t = (1 - frac[t]) ln pi_a + frac[t] ln pi_b          (frac [T], each in [0, 1]: the caller's schedule, t / (T + 1) for dragging)
+ * Start: the records of theta0 at a and b and pri0; either ln P not finite: the chain fails as in the chain call (NaN everywhere, the sums
+ * included, naccept = -1).  Otherwise sa = la0 + pri0, sb = lb0 + pri0.  Step t: theta' = theta + step[n][t]; outside the box: rejected
+ * without an evaluation; otherwise la1 at a, lb1 at b (skipped where la1 is not finite), pri1, and with every operation rounded on its own
+ *     u = 1 - frac[t];  a1 = la1 + pri1;  b1 = lb1 + pri1;  a0 = la0 + pri0;  b0 = lb0 + pri0;  w1 = u a1 + frac[t] b1;  w0 = u a0 + frac[t] b0
+ *     accepted iff la1 and lb1 are finite and lnu[n][t] < w1 - w0
+ * then, whatever the decision, sa = sa + (la0 + pri0) and sb = sb + (lb0 + pri0) with the current values.  NumPy reproduces all of it bit
+ * for bit.  After every thin-th step the state and both current records are stored (thin = 0: no trajectory); with K = thin ? T / thin : 0
+ *     chain [N][K][P]                 theta after steps thin, 2 thin, ... (may be NULL with thin = 0)
+ *     logp_start, logp_end [N][K + 1], fullchi2_start, fullchi2_end [N][K + 1], best_start, best_end [N][K + 1][nG]   (each or NULL)
+ *                                     the records at the stored theta for a and for b, and in slot K those of the state after step T
+ *     last [N][P], naccept [N]        as the chain call
+ *     sums [N][2]                     sa, sb: T + 1 terms each; (sb - sa) / (T + 1) is the logarithm of the acceptance ratio of the whole
+ *                                     slow + fast move when frac[t] = (t + 1) / (T + 1)
+ * Every ln P, full chi2 and best fit is the bit pattern of eftb_draws_logp_params for that (walker, theta).  The host splits T into launches
+ * of at most 256 steps; theta, the accept counts and the sums persist on the device between them and every launch recomputes both
+ * starting records, so a chain's bits depend neither on the split nor on the other chains, pairs or their order.
+ * Each workgroup stages both walkers' Gram matrices: 2 (J + 1)^2 doubles beside at least one wave's scratch in 160 KB, which holds up to
+ * three tracers with NNLO (J + 1 = 82) at nG = 24; four tracers at nG = 24 and five tracers at any nG are refused.
+ * Refused before anything is copied, naming pair, chain, step or parameter: what eftb_draws_chain_params refuses (thin outside [0, T]
+ * here), a pair's walker outside [0, C), NaN or a value outside [0, 1] in frac, and a shape that does not fit the LDS (the message names
+ * J + 1 and nG and says that the call stages two Gram matrices).  There is no data-set (groups) variant. */
+int  eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, const int32_t* wend, long long N, int T, int thin, const int64_t* offsets,
+                            const double* theta0, const double* f, const double* frac, const double* step, const double* lnu, const double* lower,
+                            const double* upper, const double* prior_loc, const double* prior_scale, double* chain, double* logp_start, double* logp_end,
+                            double* fullchi2_start, double* fullchi2_end, double* best_start, double* best_end, double* last, int64_t* naccept,
+                            double* sums);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

@@ -52,6 +52,19 @@ with [min, max], on the same proposals:
 On a tree without metropolis_draws_params (a) is skipped, so that the same file times (b) and (c) on the parent commit.
 
     python tools/draws_probe.py --chains [--walkers C] [--steps T]
+
+--drag [n,n,...]: dragging chains between two walkers (MarginalLikelihood.drag_draws_params) instead, for both shapes,
+--walkers pairs (default 128; pair g drags from walker g to walker pairs + g, twice as many walkers are resident) x n chains each (default
+1 and 8), --steps T steps (default 256) on drag_fractions(T), medians of 9 cached calls with [min, max], on the same proposals:
+
+    (a) drag     one drag_draws_params call (thin = 0): all T steps of all chains in the kernel, both walkers' ln P per step
+    (b) loop     the host loop: per step the proposals formed in NumPy, two logp_draws_params calls (the start and the end walkers), the
+                 interpolated acceptance rule and the two sums in NumPy
+
+(a) and (b) are asserted to return the same chains, accept counts and sums.  On a tree without drag_draws_params (a) is skipped, so that the
+same file times (b) on the parent commit.
+
+    python tools/draws_probe.py --drag [--walkers G] [--steps T]
 """
 import argparse
 import json
@@ -382,11 +395,72 @@ def probe_chains(name, setup, C, n, T, repeats=9):
     return out
 
 
+def probe_drag(name, setup, G, n, T, repeats=9):
+    """(a) and (b) of --drag for one shape: G pairs x n chains x T steps, medians of `repeats` cached calls with [min, max]"""
+    rng = np.random.default_rng(1)
+    N, C = G * n, 2 * G
+    eng, like, templ, _, ndata, nG, (rec, theta_build, fC), _ = setup(C, N, rng)
+    eng.put("TEMPL", templ)
+    theta0 = theta_build()
+    P = theta0.shape[1]
+    counts = np.repeat([n, 0], G)
+    off_a, off_b = np.concatenate([[0], np.cumsum(counts)]), np.concatenate([[0], np.cumsum(counts[::-1])])  # the chains at their start and at their end walkers
+    fC = np.ascontiguousarray(fC * (1.0 + 0.02 * (np.arange(C) >= G)).reshape((C,) + (1,) * (np.ndim(fC) - 1)))  # the end walkers have their own growth rates
+    like.set_draw_recipe(rec)
+    step = 0.3 * (theta_build() - np.median(theta0, axis=0))[:, None, :] * rng.standard_normal((N, T, 1)) + 0.01 * rng.standard_normal((N, T, P))
+    lnu = np.log(rng.random((N, T)))
+    frac = np.arange(1, T + 1) / (T + 1)
+    stat = lambda ts: {"ms": 1e3 * float(np.median(ts)), "ms_spread": [1e3 * min(ts), 1e3 * max(ts)]}
+    out = {"shape": name, "pairs": G, "chains": N, "steps": T, "ndata": ndata, "nG": nG, "P": P}
+
+    def both(theta):
+        try:
+            return like.logp_draws_params(theta, off_a, fC), like.logp_draws_params(theta, off_b, fC)
+        except RuntimeError:  # det F2 <= 0 at a proposal: the public call has no NaN to give, the step is lost for all chains
+            out["loop_hit_nan"] = True
+            return np.full(N, np.nan), np.full(N, np.nan)
+
+    def loop():
+        cur = theta0.copy()
+        la, lb = both(cur)
+        sa, sb = la + 0.0, lb + 0.0
+        nacc = np.zeros(N, dtype=np.int64)
+        for t in range(T):
+            trial = cur + step[:, t]
+            la1, lb1 = both(trial)
+            u = 1.0 - frac[t]
+            acc = np.isfinite(la1) & np.isfinite(lb1) & (lnu[:, t] < (u * la1 + frac[t] * lb1) - (u * la + frac[t] * lb))
+            cur[acc], la[acc], lb[acc] = trial[acc], la1[acc], lb1[acc]
+            nacc += acc
+            sa, sb = sa + la, sb + lb
+        return cur, nacc, sa, sb
+
+    last, nacc, sa, sb = loop()
+    out["accept_rate"] = float(np.mean(nacc)) / T
+    out["loop"] = stat(times(loop, repeats))
+    if hasattr(like, "drag_draws_params"):
+        pairs = (np.arange(G), G + np.arange(G))
+        call = lambda: like.drag_draws_params(theta0, np.arange(G + 1) * n, fC, pairs, step, lnu)
+        r = call()
+        if "loop_hit_nan" not in out:  # the same chains as the loop
+            assert np.array_equal(r.last, last) and np.array_equal(r.naccept, nacc) and np.array_equal(r.sum_start, sa) and np.array_equal(r.sum_end, sb)
+        out["drag"] = stat(times(call, repeats))
+        out["loop_over_drag"] = out["loop"]["ms"] / out["drag"]["ms"]
+        out["steps_per_s"] = N * T / (1e-3 * out["drag"]["ms"])
+        out["mean_log_ratio"] = float(np.mean(r.log_ratio))
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--chains", nargs="?", const="1,8", default=None,
                     help="n[,n...] chains per walker (default 1,8): time metropolis_draws_params, the host loop of logp_draws_params calls on the same "
                          "proposals and one logp_draws_params call on as many independent draws")
+    ap.add_argument("--drag", nargs="?", const="1,8", default=None,
+                    help="n[,n...] chains per pair of walkers (default 1,8): time drag_draws_params and the host loop of two logp_draws_params calls per step "
+                         "on the same proposals")
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--samples", nargs="?", const="1,8,64", default=None,
                     help="S[,S...] samples of the marginalised parameters per draw (default 1,8,64): time sample_gaussian_params with and without predict, the "
@@ -395,7 +469,11 @@ if __name__ == "__main__":
     ap.add_argument("--walkers", type=int, default=None)
     ap.add_argument("--datasets", type=int, default=0, help="M data vectors sharing the covariance: time the groups call, the per-vector loop and the plain call")
     a = ap.parse_args()
-    if a.chains:
+    if a.drag:
+        for n in (int(x) for x in a.drag.split(",")):
+            probe_drag("marg", marg_setup, a.walkers or 128, n, a.steps)
+            probe_drag("cfg3", cfg3_setup, a.walkers or 128, n, a.steps)
+    elif a.chains:
         for n in (int(x) for x in a.chains.split(",")):
             probe_chains("marg", marg_setup, a.walkers or 128, n, a.steps)
             probe_chains("cfg3", cfg3_setup, a.walkers or 128, n, a.steps)
