@@ -3655,22 +3655,25 @@ constexpr int CHAIN_PRI = 4 * RECIPE_MAXP;                                      
 //                  sample  bs [ADJ_KB][nG]
 //                  chain   tc | tp [RECIPE_MAXP] (the current and the trial theta) | rs [2][MARG_OUT] (two records)
 //                  drag    tc | tp as chain | rs [2][2][MARG_OUT] (two pairs of records, start | end walker in each)
+//                  hmc     tc | tp | rs as chain | gs [2][RECIPE_MAXP] (the gradients of the two records) | mo [RECIPE_MAXP] (the momentum)
+//                          | F [P][P] (the chain's factor); erow is staged as for the gradient
 // nnzp and ndtp: the entries of the recipe and its derivative records, rounded up to even.  A region a kind does not have is empty.
-enum DrawKind { DRAW_ROWS, DRAW_PARAMS, DRAW_GRAD, DRAW_HESS, DRAW_SAMPLE, DRAW_CHAIN, DRAW_DRAG };
+enum DrawKind { DRAW_ROWS, DRAW_PARAMS, DRAW_GRAD, DRAW_HESS, DRAW_SAMPLE, DRAW_CHAIN, DRAW_DRAG, DRAW_HMC };
 
 struct DrawLds {
     int fp = 0, col = 0, erow = 0, drow = 0, dcol = 0, pr = 0, wg = 0;  // offsets from the start of the LDS; wg: doubles per workgroup
     int th = 0, val = 0, H = 0, G = 0, K = 0, dval = 0, hv = 0, u = 0, w = 0, Gp = 0, Mp = 0, bs = 0, tc = 0, tp = 0, rs = 0,
         wave = 0;  // offsets from the start of the wave's part; wave: doubles per wave
+    int gs = 0, mo = 0, F = 0;  // (hmc: between rs and the end of the wave's part)
 
     DrawLds() = default;
-    static constexpr bool has_erow(DrawKind kind) { return kind == DRAW_GRAD || kind == DRAW_HESS || kind == DRAW_SAMPLE; }
-    // (every kind but DRAW_DRAG, whose layout is drag() below: of() is the way in that knows all seven)
+    static constexpr bool has_erow(DrawKind kind) { return kind == DRAW_GRAD || kind == DRAW_HESS || kind == DRAW_SAMPLE || kind == DRAW_HMC; }
+    // (every kind but DRAW_DRAG, whose layout is drag() below: of() is the way in that knows all eight)
     __host__ __device__ constexpr DrawLds(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) {
 #ifndef __HIP_DEVICE_COMPILE__
         if (kind == DRAW_DRAG) abort();  // a constant expression that gets here does not compile; the kernels name their kind and never do
 #endif
-        const bool recipe = kind != DRAW_ROWS, adj = has_erow(kind), hess = kind == DRAW_HESS;
+        const bool recipe = kind != DRAW_ROWS, adj = has_erow(kind), hess = kind == DRAW_HESS, hmc = kind == DRAW_HMC, chain = kind == DRAW_CHAIN || hmc;
         const int ng1 = nG + 1, nnzp = (nnz + 1) & ~1, ndtp = (ndt + 1) & ~1, gpn = hess && !jeffreys ? P * nG * nG : 0;
         int o = J1 * J1;
         fp = o, o += recipe ? RECIPE_MAXTR * RECIPE_FPOW : 0;
@@ -3678,7 +3681,7 @@ struct DrawLds {
         erow = o, o += adj ? nnzp / 2 : 0;
         drow = o, o += hess ? ndtp / 2 : 0;
         dcol = o, o += hess ? ndtp / 2 : 0;
-        pr = o, o += kind == DRAW_CHAIN ? CHAIN_PRI : 0;
+        pr = o, o += chain ? CHAIN_PRI : 0;
         wg = o;
         o = 0;
         th = o, o += recipe ? 34 : 0;
@@ -3693,9 +3696,12 @@ struct DrawLds {
         Gp = o, o += gpn;
         Mp = o, o += gpn;
         bs = o, o += kind == DRAW_SAMPLE ? ADJ_KB * nG : 0;
-        tc = o, o += kind == DRAW_CHAIN ? RECIPE_MAXP : 0;
-        tp = o, o += kind == DRAW_CHAIN ? RECIPE_MAXP : 0;
-        rs = o, o += kind == DRAW_CHAIN ? 2 * MARG_OUT : 0;
+        tc = o, o += chain ? RECIPE_MAXP : 0;
+        tp = o, o += chain ? RECIPE_MAXP : 0;
+        rs = o, o += chain ? 2 * MARG_OUT : 0;
+        gs = o, o += hmc ? 2 * RECIPE_MAXP : 0;
+        mo = o, o += hmc ? RECIPE_MAXP : 0;
+        F = o, o += hmc ? P * P : 0;
         wave = o;
     }
     // DRAW_DRAG: the chain kind's layout with room for the end walker -- its W_c behind the start walker's (at W2(J1)), its powers of f
@@ -3707,6 +3713,7 @@ struct DrawLds {
         L.fp += J1 * J1;
         L.col += more, L.erow += more, L.drow += more, L.dcol += more, L.pr += more, L.wg += more;
         L.wave += 2 * MARG_OUT;
+        L.gs += 2 * MARG_OUT, L.mo += 2 * MARG_OUT, L.F += 2 * MARG_OUT;  // (empty, at the end of the wave's part)
         return L;
     }
     static __host__ __device__ constexpr DrawLds of(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) {
@@ -3723,16 +3730,18 @@ struct DrawLds {
     // region starts on an 8-byte boundary), whatever the arithmetic above becomes
     __host__ __device__ constexpr bool sound(DrawKind kind, int J1, int nG, int nnz, int ndt, int P, int jeffreys) const {
         const bool recipe = kind != DRAW_ROWS, adj = has_erow(kind), hess = kind == DRAW_HESS;
-        const bool drag = kind == DRAW_DRAG, chain = kind == DRAW_CHAIN || drag;
+        const bool drag = kind == DRAW_DRAG, hmc = kind == DRAW_HMC, chain = kind == DRAW_CHAIN || drag || hmc;
         const int ng1 = nG + 1, gpn = hess && !jeffreys ? P * nG * nG : 0;
-        const int at[] = {0, drag ? W2(J1) : fp, fp, drag ? fp2() : col, col, erow, drow, dcol, pr, wg}, atw[] = {th, val, H, G, K, dval, hv, u, w, Gp, Mp, bs, tc, tp, rs, wave};
+        const int at[] = {0, drag ? W2(J1) : fp, fp, drag ? fp2() : col, col, erow, drow, dcol, pr, wg},
+                  atw[] = {th, val, H, G, K, dval, hv, u, w, Gp, Mp, bs, tc, tp, rs, gs, mo, F, wave};
         const int len[] = {J1 * J1, drag ? J1 * J1 : 0, recipe ? RECIPE_MAXTR * RECIPE_FPOW : 0, drag ? RECIPE_MAXTR * RECIPE_FPOW : 0, recipe ? (nnz + 1) / 2 : 0,
                            adj ? (nnz + 1) / 2 : 0, hess ? (ndt + 1) / 2 : 0, hess ? (ndt + 1) / 2 : 0, chain ? CHAIN_PRI : 0};
         const int lenw[] = {recipe ? P + 1 : 0, recipe ? nnz : 0, ng1 * J1, ng1 * ng1, hess ? nG * nG : 0, hess ? ndt : 0, hess ? J1 : 0, hess ? P * nG : 0,
-                            hess ? P * nG : 0, gpn, gpn, kind == DRAW_SAMPLE ? ADJ_KB * nG : 0, chain ? P : 0, chain ? P : 0, drag ? 4 * MARG_OUT : chain ? 2 * MARG_OUT : 0};
+                            hess ? P * nG : 0, gpn, gpn, kind == DRAW_SAMPLE ? ADJ_KB * nG : 0, chain ? P : 0, chain ? P : 0, drag ? 4 * MARG_OUT : chain ? 2 * MARG_OUT : 0,
+                            hmc ? RECIPE_MAXP + P : 0, hmc ? P : 0, hmc ? P * P : 0};
         for (int i = 0; i < 9; ++i)
             if (at[i] + len[i] > at[i + 1]) return false;
-        for (int i = 0; i < 15; ++i)
+        for (int i = 0; i < 18; ++i)
             if (atw[i] + lenw[i] > atw[i + 1]) return false;
         return true;
     }
@@ -3753,8 +3762,13 @@ static_assert(draw_lds_pin(DRAW_SAMPLE, 1024) == 147816 + 16 * 1024 && draw_lds_
 static_assert(DrawLds::drag(82, 24, 1024, RECIPE_MAXP, 0).bytes(1) == 144808 && DrawLds::drag(82, 24, 1024, RECIPE_MAXP, 0).fit(160 * 1024) == 1 &&
                   DrawLds::drag(97, 24, 0, 1, 0).fit(160 * 1024) == 0,
               "DrawLds: drag at J + 1 = 82 and 97");
+// hmc, which adds erow, two gradients, the momentum and F [P][P] to the chain kind, at the largest shape that fits: four tracers
+// with NNLO (J + 1 = 109), nG = 24, 1024 recipe entries, P = 32, one wave; five tracers (J + 1 = 121) at that nG and recipe do not
+static_assert(DrawLds(DRAW_HMC, 109, 24, 1024, 0, RECIPE_MAXP, 0).bytes(1) == 149864 && DrawLds(DRAW_HMC, 109, 24, 1024, 0, RECIPE_MAXP, 0).fit(160 * 1024) == 1 &&
+                  DrawLds(DRAW_HMC, 121, 24, 1024, 0, 1, 0).fit(160 * 1024) == 0,
+              "DrawLds: hmc at J + 1 = 109 and 121");
 constexpr bool draw_lds_sound(int J1, int nG, int nnz, int ndt, int P) {
-    for (int kind = DRAW_ROWS; kind <= DRAW_DRAG; ++kind)
+    for (int kind = DRAW_ROWS; kind <= DRAW_HMC; ++kind)
         for (int jeffreys = 0; jeffreys < 2; ++jeffreys)
             if (!DrawLds::of((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys).sound((DrawKind)kind, J1, nG, nnz, ndt, P, jeffreys)) return false;
     return true;
@@ -4029,7 +4043,7 @@ __device__ __forceinline__ int recipe_col(int ent, int ntr) {
 // The forward pass of a params draw up to G (one wave; th, val, Hs and Gs are the wave's LDS, Ws, fp and col the workgroup's): theta,
 // val[n], H = R^ W_c and G = H R^^T as described at draws_logp_params_kernel.  G is ordered for the wave's reads on return.
 // WHO changes nothing in the function: the drag kernel instantiates its own copy (WHO = 1), because a sixth caller of the copy that the
-// five params kernels share moved their compiled code by a register or two.
+// five params kernels share moved their compiled code by a register or two; the HMC kernel likewise (WHO = 2).
 template <bool TWO, int WHO = 0>
 __device__ __forceinline__ void draws_recipe_forward(const RecipeTab& rt, const double* __restrict__ theta, long long d, int lane, int ng1, int J1,
                                                      const double* Ws, const double* fp, const int* col, double* th, double* val, double* Hs, double* Gs) {
@@ -4097,7 +4111,7 @@ __device__ __forceinline__ double* draws_stage(const DrawLds& L, double* sm, int
             dcol[t] = recipe_col(rt.ent[n], ntr);
         }
     }
-    if (KIND == DRAW_CHAIN)
+    if (KIND == DRAW_CHAIN || KIND == DRAW_HMC)
         for (int e = threadIdx.x; e < CHAIN_PRI; e += blockDim.x) sm[L.pr + e] = prior[e];
     recipe_fpow(f, c, ntr, threadIdx.x, sm + L.fp);
     __syncthreads();
@@ -4176,6 +4190,34 @@ struct RecipeGradTab {
     int lgP2;  // log2 of the smallest power of two >= max(P, 1): lane = share << lgP2 | p in the P sums
 };
 
+// The adjoint of one draw behind draws_solve<true> (S over G, ordered for the wave's reads): Rbar over val, then the P sums and their
+// butterfly -> sum_n Rbar[n] d val[n] / d theta_p in every lane whose low bits are p (-2 d ln P / d theta_p).  The gradient kernel and
+// the HMC kernel both call it, so a gradient has the same bits whichever call computed it.
+__device__ __forceinline__ double draws_grad_adjoint(const RecipeGradTab& gt, int lane, int ng1, int J1, int nnz, int P, const double* fp, const int* col,
+                                                     const int* erow, const double* th, double* val, const double* Hs, const double* Gs) {
+    const int pmask = (1 << gt.lgP2) - 1, gp = lane & pmask, share = lane >> gt.lgP2, nshare = 64 >> gt.lgP2;
+    // ---- Rbar at the non-zeros, over val
+    for (int n = lane; n < nnz; n += 64) {
+        const int g = erow[n];
+        const double* hc = Hs + col[n];
+        double acc = 0.0;
+        for (int h = 0; h < ng1; ++h) acc = fma(Gs[g * ng1 + h] + Gs[h * ng1 + g], hc[h * J1], acc);
+        val[n] = acc;
+    }
+    wave_lds_sync();
+    // ---- the P sums over the derivative table
+    double acc = 0.0;
+    if (gp < P) {
+        const int t1 = gt.pstart[gp + 1];
+        for (int t = gt.pstart[gp] + share; t < t1; t += nshare) {
+            const int q = gt.dpack[t];
+            acc = fma(gt.dcoef[t] * fp[q >> 18] * th[q & 63] * th[(q >> 6) & 63], val[gt.dent[t]], acc);
+        }
+    }
+    for (int m = 32; m > pmask; m >>= 1) acc += __shfl_xor(acc, m);
+    return acc;
+}
+
 // draws_logp_params_kernel with the gradient: the same outer shape and forward pass (draws_recipe_forward), then per draw
 //   solve          draws_solve<true>: the record, and S over G
 //   Rbar[n]        lanes over the entries n = (g, col): sum_h (S[g][h] + S[h][g]) H[h][col], written over val[n] (the computed F2^-1 is
@@ -4199,34 +4241,13 @@ __global__ __launch_bounds__(256) void draws_logp_grad_params_kernel(int ntr, in
     double* wave = draws_stage<DRAW_GRAD>(L, sm, wv, c, ntr, J1, rt, f, W, gt.erow);
     double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
     const int *col = reinterpret_cast<int*>(sm + L.col), *erow = reinterpret_cast<int*>(sm + L.erow);
-    const int pmask = (1 << gt.lgP2) - 1, gp = lane & pmask, share = lane >> gt.lgP2, nshare = 64 >> gt.lgP2;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
         draws_recipe_forward<TWO>(rt, theta, d, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
         const bool ok = draws_solve<true>(lane, nG, jeffreys, Gs, mu, sinv, out + (size_t)d * MARG_OUT);
         wave_lds_sync();
-        // ---- Rbar at the non-zeros, over val
-        for (int n = lane; n < nnz; n += 64) {
-            const int g = erow[n];
-            const double* hc = Hs + col[n];
-            double acc = 0.0;
-            for (int h = 0; h < ng1; ++h) acc = fma(Gs[g * ng1 + h] + Gs[h * ng1 + g], hc[h * J1], acc);
-            val[n] = acc;
-        }
-        wave_lds_sync();
-        // ---- the P sums over the derivative table
-        {
-            double acc = 0.0;
-            if (gp < P) {
-                const int t1 = gt.pstart[gp + 1];
-                for (int t = gt.pstart[gp] + share; t < t1; t += nshare) {
-                    const int q = gt.dpack[t];
-                    acc = fma(gt.dcoef[t] * fp[q >> 18] * th[q & 63] * th[(q >> 6) & 63], val[gt.dent[t]], acc);
-                }
-            }
-            for (int m = 32; m > pmask; m >>= 1) acc += __shfl_xor(acc, m);
-            if (lane < P) grad[(size_t)d * P + lane] = ok ? -0.5 * acc : nan;
-        }
+        const double acc = draws_grad_adjoint(gt, lane, ng1, J1, nnz, P, fp, col, erow, th, val, Hs, Gs);
+        if (lane < P) grad[(size_t)d * P + lane] = ok ? -0.5 * acc : nan;
         wave_lds_sync();  // (the next draw overwrites th, val, H and G)
     }
 }
@@ -4863,6 +4884,205 @@ __global__ __launch_bounds__(256) void draws_drag_params_kernel(int ntr, int nG,
         if (lane < P) theta[(size_t)d * P + lane] = tc[lane];
         if (lane < PAIR) fin[(size_t)d * PAIR + lane] = rs[cur * PAIR + lane];
         if (lane < 2) sums[(size_t)d * 2 + lane] = lane ? sb : sa;
+        if (lane == 0) nacc[d] = na;
+        wave_lds_sync();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Hamiltonian Monte Carlo over theta at fixed templates (eftb_draws_hmc_params): the chain kernel with leapfrog trajectories in the place of
+// its random-walk steps.  Target ln pi(theta) = ln P_marg(theta) + pri(theta) as there; the gradient g = grad ln P_marg + grad pri, the first
+// the bits of eftb_draws_logp_grad_params (draws_recipe_forward, draws_solve<true>, draws_grad_adjoint), the second
+// -((theta_p - loc_p) sinv_p) sinv_p.  Nothing random and nothing tuned happens here: the caller supplies the momenta mom [N][Tc][P]
+// (standard normals), lnu [N][Tc], the step size eps [N][Tc] of every trajectory, nleap and the lower-triangular F [N][P][P] with
+// M^-1 = F F^T (the momenta live in the whitened space: kinetic energy r.r / 2).
+// The chain kernel's outer shape and staging (with erow), then per chain
+//   start          record and gradient of the starting theta into slot 0, its pri; ln P not finite there, or an accept count of -1 from an
+//                  earlier launch: the chain has failed, NaN in its slots, theta and ratios, accept count -1
+//   trajectory i   r = mom[i], k = r.r / 2, h = eps / 2; r = r + h F^T g; then nleap times: theta' = theta' + eps F r, the box test, record
+//                  and gradient at theta' into the slot that is not the current one, r = r + (eps, the last time h) F^T g.  A position
+//                  outside the box, or ln P or a gradient component not finite, aborts the trajectory: it is rejected and the rest of its
+//                  trip runs without evaluations (wave-uniform flags from lane 0).  Otherwise
+//                      ratio = ((ln P' + pri') - k') - ((ln P + pri) - k),  accept iff lnu[i] < ratio
+//                  and the slot index flips on acceptance.  ratio (NaN where aborted) goes to ratio [N][Tc]
+//   store, end     as the chain kernel's, per trajectory
+// Lane p < P owns component p of theta', r and g.  F^T g, F r, the updates, k, grad pri and the ratio are evaluated with every operation
+// rounded on its own (no contraction), sums in ascending index order, so that NumPy reproduces them bit for bit.  Every loop's trip count is
+// fixed at launch.  LDS: DrawLds, DRAW_HMC.
+// ------------------------------------------------------------------------------------------------
+// r_p = r_p + c (F^T g)_p, (F^T g)_p = sum_{q >= p} F[q][p] g_q
+__device__ __forceinline__ void hmc_kick(int P, int lane, const double* F, const double* g, double* mo, double c) {
+#pragma clang fp contract(off)
+    if (lane < P) {
+        double acc = 0.0;
+        for (int q = 0; q < P; ++q)
+            if (q >= lane) acc = acc + F[q * P + lane] * g[q];
+        mo[lane] = mo[lane] + c * acc;
+    }
+}
+
+// theta_p = theta_p + eps (F r)_p, (F r)_p = sum_{q <= p} F[p][q] r_q
+__device__ __forceinline__ void hmc_drift(int P, int lane, const double* F, const double* mo, double* t, double eps) {
+#pragma clang fp contract(off)
+    if (lane < P) {
+        double acc = 0.0;
+        for (int q = 0; q < P; ++q)
+            if (q <= lane) acc = acc + F[lane * P + q] * mo[q];
+        t[lane] = t[lane] + eps * acc;
+    }
+}
+
+__device__ __forceinline__ double hmc_kinetic(int P, const double* mo) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int p = 0; p < P; ++p) acc = acc + mo[p] * mo[p];
+    return 0.5 * acc;
+}
+
+// g_p of the target from d ln P / d theta_p: the prior's term is added where the parameter has a prior (sinv_p != 0)
+__device__ __forceinline__ double hmc_grad(double gl, double t, double loc, double s) {
+#pragma clang fp contract(off)
+    if (s != 0.0) {
+        const double q = (t - loc) * s;
+        gl = gl + -(q * s);
+    }
+    return gl;
+}
+
+__device__ __forceinline__ double hmc_ratio(double lp1, double pri1, double k1, double lp0, double pri0, double k0) {
+#pragma clang fp contract(off)
+    return ((lp1 + pri1) - k1) - ((lp0 + pri0) - k0);
+}
+
+// record of the theta in t to o [MARG_OUT] and the target's gradient there to g [P] (one wave; both ordered for the wave's reads on return).
+// The forward pass is the copy WHO = 2 (see draws_recipe_forward)
+template <bool TWO>
+__device__ __forceinline__ void hmc_eval(const RecipeTab& rt, const RecipeGradTab& gt, int lane, int nG, int J1, int jeffreys, const double* Ws, const double* fp,
+                                         const int* col, const int* erow, const double* pr, const double* __restrict__ mu, const double* __restrict__ sinv,
+                                         const double* t, double* th, double* val, double* Hs, double* Gs, double* o, double* g) {
+    const int ng1 = nG + 1, P = rt.P;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    draws_recipe_forward<TWO, 2>(rt, t, 0, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+    const bool ok = draws_solve<true>(lane, nG, jeffreys, Gs, mu, sinv, o);
+    wave_lds_sync();
+    const double acc = draws_grad_adjoint(gt, lane, ng1, J1, rt.nnz, P, fp, col, erow, th, val, Hs, Gs);
+    if (lane < P) g[lane] = hmc_grad(ok ? -0.5 * acc : nan, t[lane], pr[2 * RECIPE_MAXP + lane], pr[3 * RECIPE_MAXP + lane]);
+    wave_lds_sync();
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(256) void draws_hmc_params_kernel(int ntr, int nG, int J1, int jeffreys, int Tc, int t0, int thin, int kc, int kstride, int nleap,
+                                                               RecipeTab rt, RecipeGradTab gt, const long long* __restrict__ offsets, double* __restrict__ theta,
+                                                               long long* __restrict__ nacc, const double* __restrict__ f, const double* __restrict__ W,
+                                                               const double* __restrict__ mu, const double* __restrict__ sinv,
+                                                               const double* __restrict__ prior, const double* __restrict__ mom,
+                                                               const double* __restrict__ lnu, const double* __restrict__ eps,
+                                                               const double* __restrict__ factor, double* __restrict__ chain, double* __restrict__ rec,
+                                                               double* __restrict__ ratio) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int P = rt.P;
+    const long long d0 = offsets[c], d1 = offsets[c + 1];
+    if (d0 + (long long)blockIdx.y * nw >= d1) return;  // (workgroup-uniform: no chain for this share)
+    const DrawLds L(DRAW_HMC, J1, nG, rt.nnz, 0, P, jeffreys);
+    double* wave = draws_stage<DRAW_HMC>(L, sm, wv, c, ntr, J1, rt, f, W, gt.erow, nullptr, 0, prior);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    double *tc = wave + L.tc, *tp = wave + L.tp, *rs = wave + L.rs, *gs = wave + L.gs, *mo = wave + L.mo, *Fs = wave + L.F;
+    const int *col = reinterpret_cast<int*>(sm + L.col), *erow = reinterpret_cast<int*>(sm + L.erow);
+    const double* pr = sm + L.pr;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (long long d = d0 + (long long)blockIdx.y * nw + wv; d < d1; d += (long long)gridDim.y * nw) {
+        long long na = nacc[d];
+        double* oc = chain + (size_t)d * kstride * P;
+        double* orec = rec + (size_t)d * kstride * MARG_OUT;
+        if (lane < P) tc[lane] = tp[lane] = theta[(size_t)d * P + lane];
+        for (int e = lane; e < P * P; e += 64) Fs[e] = factor[(size_t)d * P * P + e];
+        wave_lds_sync();
+        int cur = 0;
+        double lp0 = nan, pri0 = 0.0;
+        if (na >= 0) {  // (wave-uniform)
+            hmc_eval<TWO>(rt, gt, lane, nG, J1, jeffreys, Ws, fp, col, erow, pr, mu, sinv, tp, th, val, Hs, Gs, rs, gs);
+            lp0 = rs[0];
+            pri0 = chain_prior(P, tp, pr);
+        }
+        if (!__builtin_amdgcn_readfirstlane((int)__builtin_isfinite(lp0))) {  // a failed chain
+            for (int k = 0; k < kc; ++k) {
+                if (lane < P) oc[(size_t)k * P + lane] = nan;
+                if (lane < MARG_OUT) orec[(size_t)k * MARG_OUT + lane] = nan;
+            }
+            for (int i = lane; i < Tc; i += 64) ratio[(size_t)d * Tc + i] = nan;
+            if (lane < P) theta[(size_t)d * P + lane] = nan;
+            if (lane == 0) nacc[d] = -1;
+            wave_lds_sync();
+            continue;
+        }
+        int left = thin - t0 % thin, k = 0;
+        for (int i = 0; i < Tc; ++i) {
+            const double e = eps[(size_t)d * Tc + i], h = 0.5 * e;
+            if (lane < P) {
+                mo[lane] = mom[((size_t)d * Tc + i) * P + lane];
+                tp[lane] = tc[lane];
+            }
+            wave_lds_sync();
+            const double k0 = hmc_kinetic(P, mo);
+            wave_lds_sync();  // (every lane has read the momentum it was dealt)
+            hmc_kick(P, lane, Fs, gs + cur * RECIPE_MAXP, mo, h);
+            wave_lds_sync();
+            double* ot = rs + (cur ^ 1) * MARG_OUT;
+            double* gn = gs + (cur ^ 1) * RECIPE_MAXP;
+            int bad = 0;  // (wave-uniform: the trajectory is aborted)
+            for (int s = 0; s < nleap; ++s) {
+                if (bad) continue;
+                hmc_drift(P, lane, Fs, mo, tp, e);
+                wave_lds_sync();
+                bool in = true;
+                for (int p = 0; p < P; ++p) {
+                    const double v = tp[p];
+                    in = in && v >= pr[p] && v <= pr[RECIPE_MAXP + p];
+                }
+                if (!__builtin_amdgcn_readfirstlane((int)in)) {
+                    bad = 1;
+                    continue;
+                }
+                // (wave-uniform from here: the forward pass, the solve and the adjoint are wave-synchronous)
+                hmc_eval<TWO>(rt, gt, lane, nG, J1, jeffreys, Ws, fp, col, erow, pr, mu, sinv, tp, th, val, Hs, Gs, ot, gn);
+                bool fin = __builtin_isfinite(ot[0]);
+                for (int p = 0; p < P; ++p) fin = fin && __builtin_isfinite(gn[p]);
+                if (!__builtin_amdgcn_readfirstlane((int)fin)) {
+                    bad = 1;
+                    continue;
+                }
+                hmc_kick(P, lane, Fs, gn, mo, s == nleap - 1 ? h : e);
+                wave_lds_sync();
+            }
+            int acc = 0;
+            double lp1 = nan, pri1 = 0.0, lr = nan;
+            if (!bad) {
+                lp1 = ot[0];
+                pri1 = chain_prior(P, tp, pr);
+                lr = hmc_ratio(lp1, pri1, hmc_kinetic(P, mo), lp0, pri0, k0);
+                acc = __builtin_amdgcn_readfirstlane((int)(lnu[(size_t)d * Tc + i] < lr));
+            }
+            if (lane == 0) ratio[(size_t)d * Tc + i] = lr;
+            if (acc) {
+                cur ^= 1;
+                lp0 = lp1;
+                pri0 = pri1;
+                ++na;
+                if (lane < P) tc[lane] = tp[lane];
+            }
+            if (--left == 0) {
+                left = thin;
+                if (k < kc) {  // (always: the host counts the slots of the launch the same way)
+                    if (lane < P) oc[(size_t)k * P + lane] = tc[lane];
+                    if (lane < MARG_OUT) orec[(size_t)k * MARG_OUT + lane] = rs[cur * MARG_OUT + lane];
+                }
+                ++k;
+            }
+            wave_lds_sync();  // (the next trajectory overwrites the momentum, the trial theta, th, val, H, G and the other record and gradient)
+        }
+        if (lane < P) theta[(size_t)d * P + lane] = tc[lane];
         if (lane == 0) nacc[d] = na;
         wave_lds_sync();
     }

@@ -430,6 +430,12 @@ struct eftb_engine {
     std::vector<int> drg_host_pair;
     bool drg_lds = false;  // the LDS opt-in of its kernel is done
     std::vector<double> drg_host_fin;
+    // eftb_draws_hmc_params, which shares the chain call's buffers (chn_step holds a launch's momenta): one launch's slice of eps [N][Tc], the
+    // factors [N][P][P] and the launch's ratios [N][Tc] with their landing block; grown on demand
+    double *hmc_eps = nullptr, *hmc_fac = nullptr, *hmc_ratio = nullptr;
+    size_t hmc_eps_cap = 0, hmc_fac_cap = 0, hmc_ratio_cap = 0;
+    std::vector<double> hmc_host_fac, hmc_host_ratio;
+    bool hmc_lds = false;  // the LDS opt-in of its kernel is done
 };
 
 static void sub_stop_thread(eftb_engine* e);
@@ -4140,13 +4146,13 @@ constexpr int CHAIN_STEPS = 256;
 // what the chain calls refuse in their own arguments, after draws_params_check: no parameter, T, thin (at least thin_min), step, lnu, the prior
 // on theta and a theta0 outside the box; pri [CHAIN_PRI] = lower | upper | loc | sinv is the table their kernels read
 static int chain_args_check(const char* who, int P, long long N, int T, int thin, int thin_min, const double* theta0, const double* step, const double* lnu,
-                            const double* lower, const double* upper, const double* ploc, const double* pscale, double* pri) {
+                            const double* lower, const double* upper, const double* ploc, const double* pscale, double* pri, const char* step_name = "step") {
     if (P < 1) return fail("%s: the draw recipe has no parameters to move", who);
     if (T < 1) return fail("%s: T = %d steps, at least 1", who, T);
     if (thin < thin_min || thin > T) return fail("%s: thin = %d outside [%d, T = %d]", who, thin, thin_min, T);
     const long long TP = (long long)T * P;
     for (long long q = 0; q < N * TP; ++q)
-        if (!std::isfinite(step[q])) return fail("%s: step[%lld][%lld][%d] is not finite", who, q / TP, q / P % T, (int)(q % P));
+        if (!std::isfinite(step[q])) return fail("%s: %s[%lld][%lld][%d] is not finite", who, step_name, q / TP, q / P % T, (int)(q % P));
     for (long long q = 0; q < N * T; ++q)
         if (!(lnu[q] <= 0.0)) return fail("%s: lnu[%lld][%lld] = %g is not the logarithm of a uniform in [0, 1]", who, q / T, q % T, lnu[q]);
     for (int p = 0; p < P; ++p) {
@@ -4257,6 +4263,142 @@ int eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_t
     if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
     return draws_chain_params_impl(e, who, G, N, T, thin, offsets, theta0, e->grp_f.data(), step, lnu, lower, upper, prior_loc,
                                    prior_scale, chain, logp, fullchi2, best, last, naccept, &gr);
+}
+
+// ------------------------------------------------------------------------------------------------ Hamiltonian Monte Carlo over the draw parameters
+// eftb_draws_hmc_params and eftb_draws_hmc_params_datasets: the chain call's checks (chain_args_check on mom in the place of step), Gram
+// cache, prior table and buffers around draws_hmc_params_kernel.  A launch holds at most CHAIN_STEPS gradient evaluations per chain,
+// max(1, CHAIN_STEPS / nleap) trajectories; between the launches theta and the accept counts stay on the device and every launch recomputes
+// record and gradient of its start, so a chain's bits do not depend on the split
+static int draws_hmc_params_impl(eftb_engine* e, const char* who, int C, long long N, int T, int nleap, int thin, const int64_t* offsets, const double* theta0,
+                                 const double* f, const double* mom, const double* lnu, const double* eps, const double* factor, const double* lower,
+                                 const double* upper, const double* ploc, const double* pscale, double* chain, double* logp, double* fullchi2, double* best,
+                                 double* last, int64_t* naccept, double* log_ratio, const DrawGroups* gr = nullptr) {
+    long long maxcnt = 0;
+    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
+    const int ntr = e->ntr, nG = e->like_nG;
+    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
+    const eftb_engine::Recipe& rcp = e->recipe[0];
+    const int P = rcp.P;
+    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
+    if (int rc = chain_args_check(who, P, N, T, thin, 1, theta0, mom, lnu, lower, upper, ploc, pscale, pri, "mom")) return rc;
+    if (nleap < 1 || nleap > CHAIN_STEPS) return fail("%s: nleap = %d leapfrog steps outside [1, %d]", who, nleap, CHAIN_STEPS);
+    for (long long q = 0; q < N * T; ++q)
+        if (!(std::isfinite(eps[q]) && eps[q] > 0.0)) return fail("%s: eps[%lld][%lld] = %g is not a finite step size > 0", who, q / T, q % T, eps[q]);
+    if (factor)
+        for (long long n = 0; n < N; ++n)
+            for (int p = 0; p < P; ++p)
+                for (int q = 0; q <= p; ++q) {
+                    const double v = factor[((size_t)n * P + p) * P + q];
+                    if (!std::isfinite(v)) return fail("%s: factor[%lld][%d][%d] is not finite", who, n, p, q);
+                    if (q == p && !(v > 0.0)) return fail("%s: factor[%lld][%d][%d] = %g, the diagonal must be > 0", who, n, p, p, v);
+                }
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, DRAW_HMC, &rcp, &sh)) return rc;
+    if (!sh.nw)
+        return fail("%s: the trajectories of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS (%zu bytes per workgroup and %zu per wave "
+                    "of %d)", who, P, nG, sh.J1, sh.L.bytes_wg(), sh.L.bytes_wave(), 160 * 1024);
+    if (N == 0) return 0;
+    const int Tl = std::max(1, CHAIN_STEPS / nleap);  // trajectories per launch
+    const int K = T / thin, kstride = std::max(1, std::min(K, Tl / thin + 1)), Tmax = std::min(T, Tl);
+    DrawRun run;
+    if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
+    if (!e->hmc_lds) {  // the large dynamic LDS for this call's kernel, once per engine (as draws_lds_optin for the others)
+        for (const void* k : {reinterpret_cast<const void*>(&draws_hmc_params_kernel<false>), reinterpret_cast<const void*>(&draws_hmc_params_kernel<true>)})
+            HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        e->hmc_lds = true;
+    }
+    char shape[112];
+    snprintf(shape, sizeof shape, "N = %lld chains x T = %d trajectories with P = %d parameters", N, T, P);
+    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(e, pp, cap, n, elem, who, what, shape); };
+    if (int rc = grow(&e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, "the momenta")) return rc;
+    if (int rc = grow(&e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, "lnu")) return rc;
+    if (int rc = grow(&e->hmc_eps, &e->hmc_eps_cap, (size_t)N * Tmax, "eps")) return rc;
+    if (int rc = grow(&e->hmc_ratio, &e->hmc_ratio_cap, (size_t)N * Tmax, "the ratios")) return rc;
+    if (int rc = grow(&e->hmc_fac, &e->hmc_fac_cap, (size_t)N * P * P, "the factors")) return rc;
+    if (int rc = grow(&e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
+    if (int rc = grow(&e->chn_nacc, &e->chn_nacc_cap, (size_t)N, "the accept counts", sizeof(long long))) return rc;
+    if (int rc = grow(&e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, "the stored states")) return rc;
+    if (int rc = grow(&e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * MARG_OUT, "the stored records")) return rc;
+    RecipeGradTab gt{};
+    gt.dcoef = rcp.dcoef;
+    gt.pstart = rcp.dtab;
+    gt.dent = gt.pstart + P + 1;
+    gt.dpack = gt.dent + rcp.ndt;
+    gt.erow = gt.dpack + rcp.ndt;
+    while ((1 << gt.lgP2) < P) ++gt.lgP2;
+    hipStream_t st = e->stream;
+    // the lower triangles (NULL: the identity); what lies above the diagonal never reaches the device
+    e->hmc_host_fac.assign((size_t)N * P * P, 0.0);
+    for (long long n = 0; n < N; ++n)
+        for (int p = 0; p < P; ++p)
+            for (int q = 0; q <= p; ++q) e->hmc_host_fac[((size_t)n * P + p) * P + q] = factor ? factor[((size_t)n * P + p) * P + q] : (q == p ? 1.0 : 0.0);
+    HIPCHK(hipMemcpyAsync(e->hmc_fac, e->hmc_host_fac.data(), (size_t)N * P * P * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
+    e->chn_host_chain.resize((size_t)N * kstride * P);
+    e->chn_host_rec.resize((size_t)N * kstride * MARG_OUT);
+    e->hmc_host_ratio.resize((size_t)N * Tmax);
+    for (int t0 = 0; t0 < T; t0 += Tl) {
+        const int Tc = std::min(Tl, T - t0), k0 = t0 / thin, kc = (t0 + Tc) / thin - k0;
+        // this launch's trajectories of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
+        HIPCHK(hipMemcpy2DAsync(e->chn_step, (size_t)Tc * P * sizeof(double), mom + (size_t)t0 * P, (size_t)T * P * sizeof(double), (size_t)Tc * P * sizeof(double),
+                                (size_t)N, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
+                                hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpy2DAsync(e->hmc_eps, (size_t)Tc * sizeof(double), eps + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
+                                hipMemcpyHostToDevice, st));
+        launch_two(draws_hmc_params_kernel<false>, draws_hmc_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin, kc,
+                   kstride, nleap, run.rt, gt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu,
+                   e->hmc_eps, e->hmc_fac, e->chn_chain, e->chn_rec, e->hmc_ratio);
+        if (int rc = launched(who)) return rc;
+        if (!kc && !log_ratio) continue;
+        if (kc) {
+            HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, (size_t)N * kstride * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        if (log_ratio) HIPCHK(hipMemcpyAsync(e->hmc_host_ratio.data(), e->hmc_ratio, (size_t)N * Tc * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (long long n = 0; n < N; ++n) {
+            for (int k = 0; k < kc; ++k) {
+                const size_t to = (size_t)n * K + k0 + k, from = (size_t)n * kstride + k;
+                std::copy_n(e->chn_host_chain.data() + from * P, P, chain + to * P);
+                draws_unpack(e->chn_host_rec.data() + from * MARG_OUT, nG, to, logp, fullchi2, best);
+            }
+            if (log_ratio) std::copy_n(e->hmc_host_ratio.data() + (size_t)n * Tc, Tc, log_ratio + (size_t)n * T + t0);
+        }
+    }
+    e->chn_host_nacc.resize((size_t)N);
+    HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (long long n = 0; n < N; ++n) naccept[n] = e->chn_host_nacc[n];
+    return 0;
+}
+
+int eftb_draws_hmc_params(eftb_engine* e, int C, long long N, int T, int nleap, int thin, const int64_t* offsets, const double* theta0, const double* f,
+                          const double* mom, const double* lnu, const double* eps, const double* factor, const double* lower, const double* upper,
+                          const double* prior_loc, const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best, double* last,
+                          int64_t* naccept, double* log_ratio) {
+    static const char* who = "eftb_draws_hmc_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta0 || !mom || !lnu || !eps || !chain || !last || !naccept))) return fail("%s: null argument", who);
+    return draws_hmc_params_impl(e, who, C, N, T, nleap, thin, offsets, theta0, f, mom, lnu, eps, factor, lower, upper, prior_loc, prior_scale, chain, logp,
+                                 fullchi2, best, last, naccept, log_ratio);
+}
+
+int eftb_draws_hmc_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int T, int nleap, int thin,
+                                   const int64_t* offsets, const double* theta0, const double* f, const double* mom, const double* lnu, const double* eps,
+                                   const double* factor, const double* lower, const double* upper, const double* prior_loc, const double* prior_scale,
+                                   double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept, double* log_ratio) {
+    static const char* who = "eftb_draws_hmc_params_datasets";
+    if (e) sub_drain(e);
+    if (!e || !walker || !dataset || !offsets || !f || (N > 0 && (!theta0 || !mom || !lnu || !eps || !chain || !last || !naccept)))
+        return fail("%s: null argument", who);
+    DrawGroups gr{0, walker, dataset};
+    if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
+    return draws_hmc_params_impl(e, who, G, N, T, nleap, thin, offsets, theta0, e->grp_f.data(), mom, lnu, eps, factor, lower, upper, prior_loc, prior_scale,
+                                 chain, logp, fullchi2, best, last, naccept, log_ratio, &gr);
 }
 
 // ------------------------------------------------------------------------------------------------ dragging chains between two walkers

@@ -22,6 +22,8 @@ GaussianSamples = collections.namedtuple("GaussianSamples", "logp fullchi2 best 
 
 # what MarginalLikelihood.metropolis_draws_params returns; fullchi2 and best are None unless return_best is set
 DrawChains = collections.namedtuple("DrawChains", "theta logp naccept last fullchi2 best")
+# what MarginalLikelihood.hmc_draws_params returns: the fields of DrawChains, then log_ratio (None unless return_ratio is set)
+DrawTrajectories = collections.namedtuple("DrawTrajectories", "theta logp naccept last fullchi2 best log_ratio")
 DragChains = collections.namedtuple("DragChains", "theta logp_start logp_end last naccept last_logp_start last_logp_end sum_start sum_end log_ratio "
                                     "fullchi2_start fullchi2_end best_start best_end last_fullchi2_start last_fullchi2_end last_best_start last_best_end")
 
@@ -413,6 +415,84 @@ class MarginalLikelihood:
             L.check(self.eng.lib.eftb_draws_chain_params(self.eng._h, off.size - 1, N, T, thin, *tail))
         return DrawChains(theta, logp, nacc, last, full, best)
 
+    def hmc_draws_params(self, theta0, offsets, f, momentum, lnu, eps, nleap, factor=None, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None,
+                         groups=None, return_best=False, return_ratio=False):
+        """Hamiltonian Monte Carlo over theta at fixed templates, all T trajectories of nleap leapfrog steps of all N chains in one device call
+        (``eftb_draws_hmc_params``) instead of one gradient call per leapfrog step.  theta0, offsets, f, ``groups``, the box and the Gaussian
+        prior on theta are those of ``metropolis_draws_params``; the target is ln P_marg(theta) + ln prior(theta) and its gradient the bits of
+        ``logp_draws_params(..., grad=True)`` plus the prior's.  The caller supplies the randomness (``hmc_momenta``) and the tuning:
+        momentum [N, T, P] standard normals, lnu [N, T] logarithms of uniforms, eps the leapfrog step size (a scalar, [N] or [N, T]: jitter and
+        adapt it between calls), nleap the steps per trajectory and factor a lower-triangular F [P, P] or [N, P, P] with mass matrix
+        M^-1 = F F^T (``proposal_factor(H, scale=1.0)`` at a best fit; None: the identity).  A trajectory that leaves the box or meets a
+        ln P or gradient that is not finite is aborted and rejected (no reflection); otherwise it is accepted iff
+        lnu[n, t] < log_ratio[n, t], the change of ln pi - |r|^2 / 2 along it.
+        -> ``DrawTrajectories(theta [N, K, P], logp [N, K], naccept [N], last [N, P], fullchi2, best, log_ratio)`` with K = T // thin as
+        ``DrawChains``; with ``return_ratio`` log_ratio [N, T] (NaN where the trajectory was aborted), what a dual-averaging step-size
+        adaptation needs.  A T-trajectory call equals a T1 and a T2 call from ``last`` bit for bit.
+        Raises RuntimeError("det of F2ij <= 0") where a chain's starting point has no finite ln P."""
+        out = self._hmc_raw(theta0, offsets, f, momentum, lnu, eps, nleap, factor, thin, lower, upper, prior_loc, prior_scale, groups, return_best, return_ratio)
+        if np.any(out.naccept < 0):
+            raise RuntimeError("det of F2ij <= 0")
+        return out
+
+    def _hmc_raw(self, theta0, offsets, f, momentum, lnu, eps, nleap, factor=None, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None,
+                 groups=None, return_best=False, return_ratio=False):
+        """``hmc_draws_params`` without the RuntimeError: a chain that failed at its start has NaN states and ratios and naccept = -1"""
+        from .engine import _params_args
+
+        ntr, nG = self.eng.ntracers, self.nG
+        rec = getattr(self, "_recipe", None)
+        wk = ds = None
+        if groups is not None:
+            theta0, off, f, wk, ds = _groups_args(rec, theta0, offsets, f, ntr, groups)
+        else:
+            theta0, off, f = _params_args(rec, theta0, offsets, f, ntr)
+        N, P = theta0.shape
+        mom = np.ascontiguousarray(momentum, dtype=np.float64)
+        if mom.ndim != 3 or mom.shape[0] != N or mom.shape[2] != P or mom.shape[1] < 1:
+            raise ValueError(f"momentum must be [{N}, T, {P}] standard normals with T >= 1 trajectories")
+        T = mom.shape[1]
+        lnu = np.ascontiguousarray(lnu, dtype=np.float64)
+        if lnu.shape != (N, T):
+            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and trajectory")
+        eps = np.asarray(eps, dtype=np.float64)
+        if eps.shape not in ((), (N,), (N, T)):
+            raise ValueError(f"eps must be a scalar, [{N}] or [{N}, {T}]: the leapfrog step size")
+        eps = np.ascontiguousarray(np.broadcast_to(eps if eps.ndim != 1 else eps[:, None], (N, T)))
+        if isinstance(nleap, bool) or nleap != int(nleap) or int(nleap) < 1:
+            raise ValueError("nleap must be an integer >= 1: the leapfrog steps of a trajectory")
+        nleap = int(nleap)
+        if factor is not None:
+            factor = np.asarray(factor, dtype=np.float64)
+            if factor.shape not in ((P, P), (N, P, P)):
+                raise ValueError(f"factor must be [{P}, {P}] or [{N}, {P}, {P}]: a lower-triangular F with M^-1 = F F^T")
+            factor = np.ascontiguousarray(np.broadcast_to(factor, (N, P, P)))
+        if thin != int(thin) or not 1 <= thin <= T:
+            raise ValueError(f"thin must be an integer in [1, T = {T}]")
+        thin = int(thin)
+        pri = []
+        for name, a in (("lower", lower), ("upper", upper), ("prior_loc", prior_loc), ("prior_scale", prior_scale)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (P,):
+                    raise ValueError(f"{name} must be [{P}], one value per parameter")
+            pri.append(a)
+        K = T // thin
+        theta, logp, last, nacc = np.empty((N, K, P)), np.empty((N, K)), np.empty((N, P)), np.empty(N, dtype=np.int64)
+        full = np.empty((N, K)) if return_best else None
+        best = np.empty((N, K, nG)) if return_best else None
+        ratio = np.empty((N, T)) if return_ratio else None
+        i64p = C.POINTER(C.c_int64)
+        tail = (off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(mom), L.dptr(lnu), L.dptr(eps), L.dptr(factor)) + tuple(L.dptr(a) for a in pri) + (
+            L.dptr(theta), L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(last), nacc.ctypes.data_as(i64p), L.dptr(ratio))
+        if groups is not None:
+            i32p = C.POINTER(C.c_int32)
+            L.check(self.eng.lib.eftb_draws_hmc_params_datasets(self.eng._h, f.shape[0], wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p), N, T,
+                                                                nleap, thin, *tail))
+        else:
+            L.check(self.eng.lib.eftb_draws_hmc_params(self.eng._h, off.size - 1, N, T, nleap, thin, *tail))
+        return DrawTrajectories(theta, logp, nacc, last, full, best, ratio)
+
     def drag_draws_params(self, theta0, offsets, f, pairs, step, lnu, frac=None, thin=0, lower=None, upper=None, prior_loc=None, prior_scale=None,
                           return_best=False):
         """The fast steps of a dragging sampler (cobaya's ``drag: true``) between two slow points, all T steps of all N chains in one device
@@ -639,6 +719,18 @@ def metropolis_proposals(rng, N, T, factor):
     return np.ascontiguousarray(step), lnu
 
 
+def hmc_momenta(rng, N, T, P):
+    """The randomness of ``MarginalLikelihood.hmc_draws_params`` from a ``numpy.random.Generator``: -> (momentum [N, T, P], lnu [N, T]) with
+    momentum = rng.standard_normal((N, T, P)) and lnu = log(rng.random((N, T)))."""
+    for name, v in (("N", N), ("T", T), ("P", P)):
+        if v != int(v) or v < (0 if name == "N" else 1):
+            raise ValueError(f"{name} must be an integer >= {0 if name == 'N' else 1}")
+    mom = rng.standard_normal((int(N), int(T), int(P)))
+    with np.errstate(divide="ignore"):
+        lnu = np.log(rng.random((int(N), int(T))))
+    return mom, lnu
+
+
 def drag_fractions(T):
     """The schedule of a dragging step of T fast steps (cobaya's ``drag: true``; Neal 2005): the weight of the end point at fast step
     t = 1 ... T is t / (T + 1) -> frac [T].  The default of ``drag_draws_params``."""
@@ -658,4 +750,4 @@ def drag_accept(lnu_slow, result):
     return lnu_slow < result.log_ratio
 
 
-__all__ = ["MarginalLikelihood", "DrawChains", "DragChains", "drag_fractions", "drag_accept", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]
+__all__ = ["MarginalLikelihood", "DrawChains", "DrawTrajectories", "hmc_momenta", "DragChains", "drag_fractions", "drag_accept", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]

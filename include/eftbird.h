@@ -462,6 +462,39 @@ int  eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart,
                             double* fullchi2_start, double* fullchi2_end, double* best_start, double* best_end, double* last, int64_t* naccept,
                             double* sums);
 
+/* Hamiltonian Monte Carlo over the draw parameters in one device call: the chain call with leapfrog trajectories in the place of its
+ * random-walk steps.  Walkers, offsets, theta0, f, the target ln pi = ln P_marg + pri, the box and the prior on theta are the chain
+ * call's.  The caller supplies all randomness and all tuning: mom [N][T][P] (standard normals), lnu [N][T] (logarithms of uniforms, -inf
+ * allowed), eps [N][T] (the step size of every trajectory), nleap (leapfrog steps per trajectory, one value for the call) and factor
+ * [N][P][P] (or NULL: the identity), per chain a lower-triangular F with M^-1 = F F^T of which only the lower triangle is read.  The
+ * momenta live in the whitened space (kinetic energy r.r / 2).  With g = grad ln P_marg + grad pri, the first the bits of
+ * eftb_draws_logp_grad_params and (grad pri)_p = -((theta_p - loc_p) sinv_p) sinv_p (sinv_p = 0 skipped), trajectory t of chain n is
+ *     r = mom[n][t];  k = 1/2 sum_p r_p r_p;  h = 0.5 eps;  r = r + h u,  u_p = sum_{q >= p} F[q][p] g_q
+ *     nleap times:  theta_p = theta_p + eps v_p,  v_p = sum_{q <= p} F[p][q] r_q;  the box test, then record and g at theta;
+ *                   r = r + (eps, or h the last time) u
+ *     ratio = ((ln P' + pri') - k') - ((ln P + pri) - k);  accepted iff the trajectory was not aborted and lnu[n][t] < ratio
+ * all sums with the index ascending from 0 as acc = acc + x y, every operation rounded on its own: NumPy reproduces it bit for bit.  A
+ * trajectory is aborted, and so rejected, when a position lies outside the box (no reflection, no evaluation there) or its ln P or a
+ * component of g is not finite; that is no error.  After every thin-th trajectory the state is stored, as the chain call stores steps:
+ *     chain [N][K][P], logp [N][K], fullchi2 [N][K], best [N][K][nG], last [N][P], naccept [N]     K = T / thin, as the chain call
+ *     log_ratio [N][T] (or NULL)     ratio of every trajectory, NaN where it was aborted: what a step-size adaptation on the host needs
+ * The host splits T into launches of max(1, 256 / nleap) trajectories; only theta and the accept counts persist between them and every
+ * launch recomputes record and gradient of its start, so a T-trajectory call equals a T1 + T2 call from `last` bit for bit.  A chain whose
+ * theta0 has no finite ln P fails alone: NaN in its outputs (log_ratio included), naccept = -1.
+ * Refused before anything is copied, naming chain, trajectory and parameter where they apply: what eftb_draws_chain_params refuses (mom in
+ * the place of step), nleap < 1 or > 256, an eps that is not finite and positive, a factor entry of the lower triangle that is not finite,
+ * a diagonal entry <= 0, and a working set that does not fit the LDS (the chain call's plus the recipe's rows, 96 + P^2 doubles per wave;
+ * the message names P, nG and J + 1): four tracers with NNLO at nG = 24 and 1024 recipe entries fit with P = 32, five tracers there do not. */
+int  eftb_draws_hmc_params(eftb_engine* e, int C, long long N, int T, int nleap, int thin, const int64_t* offsets, const double* theta0, const double* f,
+                           const double* mom, const double* lnu, const double* eps, const double* factor, const double* lower, const double* upper,
+                           const double* prior_loc, const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best, double* last,
+                           int64_t* naccept, double* log_ratio);
+/* eftb_draws_hmc_params per group (walker[g], dataset[g]) of eftb_draws_logp_params_datasets: the same kernel on the groups' Gram matrices. */
+int  eftb_draws_hmc_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int T, int nleap, int thin,
+                                    const int64_t* offsets, const double* theta0, const double* f, const double* mom, const double* lnu, const double* eps,
+                                    const double* factor, const double* lower, const double* upper, const double* prior_loc, const double* prior_scale,
+                                    double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept, double* log_ratio);
+
 /* Pipelined sampler steps.  The per-step inputs (Pin, f, DA, H, bias rows, likelihood rows) and outputs (EFTB_B_PLK, EFTB_B_LOGP)
  * exist three times: one set is being evaluated, the next is already queued behind it, the third is being fetched from / refilled --
  *     eftb_stage_inputs(step i+1);  eftb_run_staged(step i+1);  eftb_fetch_previous(step i);   ...

@@ -65,6 +65,20 @@ On a tree without metropolis_draws_params (a) is skipped, so that the same file 
 same file times (b) on the parent commit.
 
     python tools/draws_probe.py --drag [--walkers G] [--steps T]
+
+--hmc [n,n,...]: Hamiltonian Monte Carlo over theta (MarginalLikelihood.hmc_draws_params) instead, for both shapes, --walkers
+walkers (default 128) x n chains each (default 1 and 8), --steps gradient evaluations per chain (default 256: one launch) as --steps / --leap
+trajectories of --leap leapfrog steps (default 8), medians of 9 cached calls with [min, max], on the same momenta, uniforms and step sizes:
+
+    (a) hmc      one hmc_draws_params call: all trajectories of all chains in the kernel
+    (b) loop     the host loop (tests/hmc_util.host_hmc): per leapfrog step one gradient call (eftb_draws_logp_grad_params), the integrator and the
+                 acceptance rule in NumPy
+    (c) ceiling  one logp_draws_params(grad=True) call on as many independent draws as (a) evaluates gradients
+
+(a) and (b) are asserted to return the same chains, accept counts and ratios.  On a tree without hmc_draws_params (a) is skipped, so that
+the same file (with tests/hmc_util.py beside it) times (b) and (c) on the parent commit.
+
+    python tools/draws_probe.py --hmc [--walkers C] [--steps E] [--leap L]
 """
 import argparse
 import json
@@ -453,6 +467,59 @@ def probe_drag(name, setup, G, n, T, repeats=9):
     return out
 
 
+def probe_hmc(name, setup, C, n, evals, nleap, eps, repeats=9):
+    """(a), (b), (c) of --hmc for one shape: C walkers x n chains x evals / nleap trajectories of nleap steps, medians with [min, max]"""
+    import hmc_util as HM
+
+    rng = np.random.default_rng(1)
+    N, T = C * n, max(1, evals // nleap)
+    eng, like, templ, _, ndata, nG, (rec, theta_build, fC), _ = setup(C, N, rng)
+    eng.put("TEMPL", templ)
+    theta0 = theta_build()
+    P = theta0.shape[1]
+    off = np.arange(C + 1) * n
+    like.set_draw_recipe(rec)
+    mom, lnu = rng.standard_normal((N, T, P)), np.log(rng.random((N, T)))
+    epsa = eps * rng.uniform(0.8, 1.2, (N, T))
+    stat = lambda ts: {"ms": 1e3 * float(np.median(ts)), "ms_spread": [1e3 * min(ts), 1e3 * max(ts)]}
+    out = {"shape": name, "walkers": C, "chains": N, "trajectories": T, "nleap": nleap, "eps": eps, "ndata": ndata, "nG": nG, "P": P}
+
+    import ctypes as ct
+
+    from eftpipe_amd import _lib as L
+
+    o64, fo = np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(fC, dtype=np.float64)
+    lp, gr = np.empty(N), np.empty((N, P))
+
+    def grad(theta):  # eftb_draws_logp_grad_params itself: logp_draws_params(grad=True) raises where a draw has det F2 <= 0, the library returns NaN there
+        L.check(eng.lib.eftb_draws_logp_grad_params(eng._h, C, N, o64.ctypes.data_as(ct.POINTER(ct.c_int64)), L.dptr(np.ascontiguousarray(theta)), L.dptr(fo),
+                                                    L.dptr(lp), L.dptr(gr), None, None))
+        return lp.copy(), gr.copy()
+
+    loop = lambda: HM.host_hmc(grad, theta0, mom, lnu, epsa, nleap)
+    want = loop()
+    out["accept_rate"] = float(np.mean(want["naccept"])) / T
+    out["aborted"] = int(np.sum(want["aborted"]))
+    out["loop"] = stat(times(loop, repeats))
+    many = np.ascontiguousarray(np.repeat(theta0, T * nleap, axis=0))
+    ceiling = lambda: like.logp_draws_params(many, off * T * nleap, fC, grad=True)
+    ceiling()
+    out["ceiling"] = stat(times(ceiling, repeats))
+    if hasattr(like, "hmc_draws_params"):
+        call = lambda: like.hmc_draws_params(theta0, off, fC, mom, lnu, epsa, nleap, return_ratio=True)
+        r = call()
+        assert np.array_equal(r.last, want["last"]) and np.array_equal(r.naccept, want["naccept"])  # the same chains as the loop
+        assert np.array_equal(r.theta, want["theta"]) and np.array_equal(r.log_ratio, want["log_ratio"], equal_nan=True)
+        out["hmc"] = stat(times(call, repeats))
+        out["loop_over_hmc"] = out["loop"]["ms"] / out["hmc"]["ms"]
+        out["hmc_over_ceiling"] = out["hmc"]["ms"] / out["ceiling"]["ms"]
+        out["evaluations_per_s"] = N * T * nleap / (1e-3 * out["hmc"]["ms"])
+        out["us_per_evaluation_per_wave"] = 1e3 * out["hmc"]["ms"] / (T * nleap + 1) if n == 1 else None  # (one chain per workgroup: its wave runs alone)
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--chains", nargs="?", const="1,8", default=None,
@@ -461,6 +528,10 @@ if __name__ == "__main__":
     ap.add_argument("--drag", nargs="?", const="1,8", default=None,
                     help="n[,n...] chains per pair of walkers (default 1,8): time drag_draws_params and the host loop of two logp_draws_params calls per step "
                          "on the same proposals")
+    ap.add_argument("--hmc", nargs="?", const="1,8", default=None,
+                    help="n[,n...] chains per walker (default 1,8): time hmc_draws_params, the host loop of logp_draws_params(grad=True) calls on the same "
+                         "inputs and one gradient call on as many independent draws")
+    ap.add_argument("--leap", type=int, default=8, help="leapfrog steps per trajectory of --hmc")
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--samples", nargs="?", const="1,8,64", default=None,
                     help="S[,S...] samples of the marginalised parameters per draw (default 1,8,64): time sample_gaussian_params with and without predict, the "
@@ -469,7 +540,11 @@ if __name__ == "__main__":
     ap.add_argument("--walkers", type=int, default=None)
     ap.add_argument("--datasets", type=int, default=0, help="M data vectors sharing the covariance: time the groups call, the per-vector loop and the plain call")
     a = ap.parse_args()
-    if a.drag:
+    if a.hmc:
+        for n in (int(x) for x in a.hmc.split(",")):
+            probe_hmc("marg", marg_setup, a.walkers or 128, n, a.steps, a.leap, 0.01)
+            probe_hmc("cfg3", cfg3_setup, a.walkers or 128, n, a.steps, a.leap, 0.01)
+    elif a.drag:
         for n in (int(x) for x in a.drag.split(",")):
             probe_drag("marg", marg_setup, a.walkers or 128, n, a.steps)
             probe_drag("cfg3", cfg3_setup, a.walkers or 128, n, a.steps)
