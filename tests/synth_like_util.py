@@ -109,6 +109,33 @@ def floor_of(case, kind, quantity):
     return SYNTH_FLOOR[case][kind][quantity]
 
 
+# The LOGP stage's product U = V C^-1 (launch_times_invcov, the one caller of gemm_narrow_kernel with blockIdx.y > 0) past one column group
+# of 128 data points: exactly one group, one column in a second group, three groups with one column in the last.  Two tracers on 3 x 50
+# blocks; the LOGP stage alone is asked (the draw calls may refuse such footprints).  WIDE_FLOOR: the Gram route against the data-space
+# yardstick, Jeffreys on and off, as test_draw_synthetic.py::test_wide_logp_floors prints it; the device's stage call is held to
+# hess_util.device_bar of each.
+WIDE = {n: dict(ntr=2, nnlo=False, nG=3, nl=3, nx=50, ndata=n, P=2) for n in (128, 129, 257)}
+WIDE_SEEDS = {128: 2128, 129: 2129, 257: 2257}
+WIDE_FLOOR = {
+    128: dict(logp=4.4e-15, fullchi2=4.6e-15, best=1.4e-13),
+    129: dict(logp=3.1e-15, fullchi2=3.1e-15, best=1.1e-13),
+    257: dict(logp=1.0e-14, fullchi2=1.0e-14, best=1.9e-13),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def wide_problem(ndata):
+    return problem(seed=WIDE_SEEDS[ndata], **WIDE[ndata])
+
+
+@functools.lru_cache(maxsize=None)
+def wide_reference(ndata, jeffreys=False):
+    """yardstick() of every draw of a WIDE likelihood (ln P, full chi2 and best are what the stage call is compared with)"""
+    pb = wide_problem(ndata)
+    z = normals(pb.theta.shape[0], 1, pb.nG)
+    return [yardstick(pb, d, z[d], jeffreys, hess=False) for d in range(pb.theta.shape[0])]
+
+
 def problem(ntr, nnlo, nG, nl, nx, ndata, P, seed, flat=False, counts=COUNTS, singular=None):
     """-> a namespace of templ [C ntr, nl, 24, nx], templn (or None), index [ndata], D, invcov, loc, scale, rec (a DrawRecipe), theta [N, P],
     f [C, ntr], counts, walker [N].  singular = g: every term of Gaussian row g carries a factor theta_0, so that a draw with theta_0 = 0

@@ -89,6 +89,33 @@ def test_gram_route_floors(case, kind):
         assert device_bar(rec) < 1e-6, (k, rec)  # a benign construction: the bars that follow stay meaningful
 
 
+@pytest.mark.parametrize("ndata", list(SY.WIDE))
+def test_wide_logp_floors(ndata):
+    """The likelihoods past one column group of the U = V C^-1 product (ndata = 128, 129, 257; the LOGP stage alone): ln P, full chi2 and
+    best of the Gram route against the data-space yardstick on every draw, Jeffreys off and on -- the worst values are those recorded in
+    WIDE_FLOOR (pinned as test_gram_route_floors pins SYNTH_FLOOR), and every draw is positive definite"""
+    pb = SY.wide_problem(ndata)
+    assert pb.ndata == ndata and pb.index.size == ndata and np.array_equal(pb.invcov, pb.invcov.T)
+    assert set(pb.index // (pb.nl * pb.nx)) == set(range(pb.ntr))
+    errs = []
+    for jeff in (False, True):
+        ref = SY.wide_reference(ndata, jeff)
+        for d, y in enumerate(ref):
+            assert np.isfinite(y["logp"]) and np.all(np.linalg.eigvalsh(y["F2"]) > 0)
+            ff, tw, tn = SY.of_walker(pb, pb.walker[d])
+            W = GU.gram_matrix(tw, pb.index, pb.D, pb.invcov, tn)
+            logp = SY.CU.gram_record(pb.rec, pb.theta[d], ff, W, pb.loc, pb.scale, jeff)
+            best, _, _, full = SU.gram_samples(pb.rec, pb.theta[d], ff, W, pb.loc, pb.scale, np.zeros((1, pb.nG)))
+            errs.append(SY.errors(pb, d, y, None, logp, full, best, None, None, None, None, None))
+    got = SY.worst(errs)
+    print("ndata %d floors:" % ndata, "dict(" + ", ".join("%s=%.1e" % kv for kv in got.items()) + ")")
+    for k in ("logp", "fullchi2", "best"):
+        rec = SY.WIDE_FLOOR[ndata][k]
+        assert got[k] <= 1.5 * rec, (k, got[k], rec)
+        assert rec <= max(10.0 * got[k], 1e-13), (k, got[k], rec)
+        assert device_bar(rec) < 1e-6, (k, rec)
+
+
 @pytest.mark.parametrize("case,kind", ALL)
 def test_input_conditions(case, kind):
     """every draw has a finite ln P and finite samples (F2 positive definite: the yardsticks' Cholesky factor exists), all theta are

@@ -195,6 +195,29 @@ def test_every_call_at_every_shape(case):
     eng.close()
 
 
+@pytest.mark.parametrize("ndata", list(SY.WIDE))
+def test_logp_stage_past_one_column_group(ndata):
+    """U = V C^-1 of the LOGP stage (launch_times_invcov: gemm_narrow_kernel over column groups of 128, the one launch with blockIdx.y > 0)
+    at ndata = 128 (exactly one group), 129 (one column in a second group) and 257 (three groups): 14 walkers x 4 rows = 56 rows, three
+    and a half 16-row workgroups, K = ndata.  The stage call alone, against the oracle.marginal yardstick as test_every_call_at_every_shape
+    compares its stage call; bars: hess_util.device_bar of synth_like_util.WIDE_FLOOR (measured on the host by test_draw_synthetic.py)."""
+    from eftpipe_amd.marginal import MarginalLikelihood
+
+    pb = SY.wide_problem(ndata)
+    N, nG, ntr = pb.theta.shape[0], pb.nG, pb.ntr
+    eng = _engine(pb, N * ntr)
+    rows = pb.rec.rows(pb.theta, pb.f[pb.walker])
+    _put(eng, pb, pb.walker)
+    for jeff in (False, True):
+        ref = SY.wide_reference(ndata, jeff)
+        like = MarginalLikelihood(eng, pb.index, pb.D, pb.invcov, pb.loc, pb.scale, jeffreys=jeff)
+        ls, fs, bs = like.logp(rows.reshape(N * ntr, nG + 1, 24), return_best=True)
+        assert ls.shape == (N,) and np.all(np.isfinite(ls)) and np.all(np.isfinite(bs))
+        _report("ndata %d%s" % (ndata, " jeffreys" if jeff else ""), "stage",
+                SY.worst([SY.errors(pb, d, ref[d], None, ls[d], fs[d], bs[d], None, None, None, None, None) for d in range(N)]), SY.WIDE_FLOOR[ndata])
+    eng.close()
+
+
 @pytest.mark.parametrize("case", ["Ef", "Gf", "I"])
 def test_failing_draw_between_regular_ones(case):
     """nG = 24 at four, two and one waves: one draw with an exactly zero row and column of F2 (test_draw_synthetic.py) in the middle of
