@@ -5088,4 +5088,192 @@ __global__ __launch_bounds__(256) void draws_hmc_params_kernel(int ntr, int nG, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Parallel tempering over theta at fixed templates (eftb_draws_temper_params): ladders of R chains ("rungs") at inverse temperatures
+// 1 >= beta_0 > ... > beta_{R-1} >= 0 that exchange states.  Chain n is rung n % R of ladder n / R; rung r targets
+//     ln pi_r(theta) = beta_r ln P_marg(theta) + pri(theta)
+// with ln P_marg tempered as a whole (the Gaussian priors of the marginalised parameters included) and pri, the chain kernel's prior on
+// theta, not tempered.  One workgroup of R waves (blockDim = 64 R, R <= TEMPER_MAXR) works one ladder at a time, wave r its rung r, and
+// loops over the ladders of its (walker, share): every wave of the workgroup has the same trip count.  Per rung the kernel is the chain
+// kernel's: draws_stage, draws_recipe_forward + draws_solve<false> (the bits of eftb_draws_logp_params), chain_prior, temper_accept in the
+// place of chain_accept (beta = 1: the product is exact and the bits are chain_accept's).
+//   start          the record of every rung's starting theta and its pri.  The rungs publish "ln P is finite and no earlier launch has
+//                  failed" through LDS and the whole workgroup decides before the step loop: one rung without, and the ladder has failed,
+//                  NaN in every slot, theta and sum of every rung, accept and swap counts -1
+//   step i         the chain kernel's step with beta_r ln P in the place of ln P
+//   swap event     after the steps whose global number g has (g + 1) % S == 0 (S = 0: never; s0 steps remain to the launch's first event,
+//                  whose global number j has the parity jpar): the pairs (r, r + 1), r = j mod 2, r + 1 < R.  Every rung publishes ln P,
+//                  pri and the index of its current record slot; barrier; the wave of the lower rung of a pair decides,
+//                      x = (beta_r - beta_{r+1}) (ln P_{r+1} - ln P_r),    accept iff lnus[ladder][event][r] < x          (temper_swap)
+//                  from lane 0, counts it and publishes the decision; barrier; both waves of an accepted pair read the other's theta,
+//                  current record, ln P and pri into registers; barrier; they write them over their own.  Temperature, accept count, swap
+//                  count and sum stay with the rung (the wave)
+//   after both     sum = sum + ln P of the rung's current state (untempered); the chain kernel's store after every thin-th step
+//   end            theta, nacc, sums [N] and nswap [ladders][max(R - 1, 1)] (pair r: wave r) hold the state after the launch
+// Barriers: two around the failed-ladder decision (the second keeps the next ladder's flags off waves that still read these) and the three
+// of a swap event are the only ones behind draws_stage, and every wave of the workgroup reaches each the same number of times --
+// the swap condition, the failed-ladder decision, the ladder loop and the early return for an empty share are workgroup-uniform, and a rung
+// whose proposal left the box skips its evaluation, which holds no barrier.  No wave spins on another; no atomics; every value goes to
+// memory by an ordinary vector store.  Every loop's trip count is fixed at launch.
+// LDS: DrawLds, DRAW_CHAIN, at R waves, then the exchange xch [TEMPER_XCH]: ln P | pri | record slot | decision | alive, TEMPER_MAXR each.
+// ------------------------------------------------------------------------------------------------
+constexpr int TEMPER_MAXR = 8, TEMPER_XCH = 5 * TEMPER_MAXR;
+
+__device__ __forceinline__ bool temper_accept(double lnu, double beta, double lp1, double pri1, double lp0, double pri0) {
+#pragma clang fp contract(off)
+    return __builtin_isfinite(lp1) && lnu < (beta * lp1 + pri1) - (beta * lp0 + pri0);
+}
+
+__device__ __forceinline__ bool temper_swap(double lnu, double beta_lo, double beta_hi, double lp_lo, double lp_hi) {
+#pragma clang fp contract(off)
+    return lnu < (beta_lo - beta_hi) * (lp_hi - lp_lo);
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(64 * TEMPER_MAXR) void draws_temper_params_kernel(
+    int ntr, int nG, int J1, int jeffreys, int R, int Tc, int t0, int thin, int kc, int kstride, int S, int s0, int jpar, int nswc, RecipeTab rt,
+    const long long* __restrict__ offsets, double* __restrict__ theta, long long* __restrict__ nacc, long long* __restrict__ nswap,
+    double* __restrict__ sums, const double* __restrict__ f, const double* __restrict__ W, const double* __restrict__ mu,
+    const double* __restrict__ sinv, const double* __restrict__ prior, const double* __restrict__ beta, const double* __restrict__ step,
+    const double* __restrict__ lnu, const double* __restrict__ lnus, double* __restrict__ chain, double* __restrict__ rec) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (the rung; blockDim = 64 R)
+    const int ng1 = nG + 1, P = rt.P, npair = R > 1 ? R - 1 : 1;
+    const long long d0 = offsets[c], nlad = (offsets[c + 1] - d0) / R;
+    if ((long long)blockIdx.y >= nlad) return;  // (workgroup-uniform: no ladder for this share)
+    const DrawLds L(DRAW_CHAIN, J1, nG, rt.nnz, 0, P, jeffreys);
+    double* wave = draws_stage<DRAW_CHAIN>(L, sm, wv, c, ntr, J1, rt, f, W, nullptr, nullptr, 0, prior);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    double *tc = wave + L.tc, *tp = wave + L.tp, *rs = wave + L.rs;
+    double* xch = sm + L.wg + R * L.wave;
+    double *xl = xch, *xp = xch + TEMPER_MAXR, *xc = xch + 2 * TEMPER_MAXR, *xd = xch + 3 * TEMPER_MAXR, *xf = xch + 4 * TEMPER_MAXR;
+    const int* col = reinterpret_cast<int*>(sm + L.col);
+    const double* pr = sm + L.pr;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double bt = beta[wv];
+    for (long long l = blockIdx.y; l < nlad; l += gridDim.y) {  // (workgroup-uniform)
+        const long long d = d0 + l * R + wv, lad = (d0 + l * R) / R;
+        long long na = nacc[d], ns = wv < npair ? nswap[lad * npair + wv] : 0;
+        double sl = sums[d];
+        double* oc = chain + (size_t)d * kstride * P;
+        double* orec = rec + (size_t)d * kstride * MARG_OUT;
+        if (lane < P) tc[lane] = tp[lane] = theta[(size_t)d * P + lane];
+        wave_lds_sync();
+        int cur = 0;
+        double lp0 = nan, pri0 = 0.0;
+        if (na >= 0) {  // (wave-uniform)
+            draws_recipe_forward<TWO>(rt, tp, 0, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+            draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, rs);
+            wave_lds_sync();
+            lp0 = rs[0];
+            pri0 = chain_prior(P, tp, pr);
+        }
+        if (lane == 0) xf[wv] = __builtin_isfinite(lp0) ? 1.0 : 0.0;
+        __syncthreads();
+        bool alive = true;
+        for (int r = 0; r < R; ++r) alive = alive && xf[r] != 0.0;
+        __syncthreads();  // (the next ladder's flags wait for every wave to have read these)
+        if (!__builtin_amdgcn_readfirstlane((int)alive)) {  // a failed ladder (workgroup-uniform)
+            for (int k = 0; k < kc; ++k) {
+                if (lane < P) oc[(size_t)k * P + lane] = nan;
+                if (lane < MARG_OUT) orec[(size_t)k * MARG_OUT + lane] = nan;
+            }
+            if (lane < P) theta[(size_t)d * P + lane] = nan;
+            if (lane == 0) {
+                nacc[d] = -1;
+                sums[d] = nan;
+                if (wv < npair) nswap[lad * npair + wv] = -1;
+            }
+            wave_lds_sync();
+            continue;
+        }
+        int left = thin - t0 % thin, k = 0, sleft = s0, ev = 0;
+        for (int i = 0; i < Tc; ++i) {
+            if (lane < P) tp[lane] = tc[lane] + step[((size_t)d * Tc + i) * P + lane];
+            wave_lds_sync();
+            bool in = true;
+            for (int p = 0; p < P; ++p) {
+                const double v = tp[p];
+                in = in && v >= pr[p] && v <= pr[RECIPE_MAXP + p];
+            }
+            int acc = 0;
+            double lp1 = nan, pri1 = 0.0;
+            if (__builtin_amdgcn_readfirstlane((int)in)) {  // (wave-uniform; no barrier inside)
+                double* ot = rs + (cur ^ 1) * MARG_OUT;
+                draws_recipe_forward<TWO>(rt, tp, 0, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+                draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, ot);
+                wave_lds_sync();
+                lp1 = ot[0];
+                pri1 = chain_prior(P, tp, pr);
+                acc = __builtin_amdgcn_readfirstlane((int)temper_accept(lnu[(size_t)d * Tc + i], bt, lp1, pri1, lp0, pri0));
+            }
+            if (acc) {
+                cur ^= 1;
+                lp0 = lp1;
+                pri0 = pri1;
+                ++na;
+                if (lane < P) tc[lane] = tp[lane];
+            }
+            if (S > 0 && --sleft == 0) {  // a swap event (workgroup-uniform)
+                sleft = S;
+                const int par = (jpar + ev) & 1;
+                const int low = ((wv - par) & 1) ? wv - 1 : wv;  // (the lower rung of this wave's pair; -1 or R - 1: none)
+                const bool paired = low >= 0 && low + 1 < R;
+                const int other = low == wv ? wv + 1 : low;
+                if (lane == 0) {
+                    xl[wv] = lp0;
+                    xp[wv] = pri0;
+                    xc[wv] = (double)cur;
+                }
+                __syncthreads();
+                if (paired && low == wv) {
+                    const double u = lnus[((size_t)lad * nswc + ev) * (R - 1) + low];
+                    const int sw = __builtin_amdgcn_readfirstlane((int)temper_swap(u, bt, beta[wv + 1], lp0, xl[wv + 1]));
+                    if (lane == 0) xd[low] = (double)sw;
+                    ns += sw;
+                }
+                __syncthreads();
+                int sw = 0;
+                if (paired) sw = __builtin_amdgcn_readfirstlane((int)(xd[low] != 0.0));
+                double tq = 0.0, rq = 0.0, lq = 0.0, pq = 0.0;
+                if (sw) {
+                    const double* ow = sm + L.wg + other * L.wave;
+                    const int oslot = __builtin_amdgcn_readfirstlane((int)xc[other]);
+                    if (lane < P) tq = ow[L.tc + lane];
+                    if (lane < MARG_OUT) rq = ow[L.rs + oslot * MARG_OUT + lane];
+                    lq = xl[other];
+                    pq = xp[other];
+                }
+                __syncthreads();
+                if (sw) {
+                    if (lane < P) tc[lane] = tq;
+                    if (lane < MARG_OUT) rs[cur * MARG_OUT + lane] = rq;
+                    lp0 = lq;
+                    pri0 = pq;
+                    wave_lds_sync();
+                }
+                ++ev;
+            }
+            sl = sl + lp0;
+            if (--left == 0) {
+                left = thin;
+                if (k < kc) {  // (always: the host counts the slots of the launch the same way)
+                    if (lane < P) oc[(size_t)k * P + lane] = tc[lane];
+                    if (lane < MARG_OUT) orec[(size_t)k * MARG_OUT + lane] = rs[cur * MARG_OUT + lane];
+                }
+                ++k;
+            }
+            wave_lds_sync();  // (the next step overwrites the trial theta, th, val, H, G and the other record)
+        }
+        if (lane < P) theta[(size_t)d * P + lane] = tc[lane];
+        if (lane == 0) {
+            nacc[d] = na;
+            sums[d] = sl;
+            if (wv < npair) nswap[lad * npair + wv] = ns;
+        }
+        wave_lds_sync();
+    }
+}
+
 }  // namespace eftb

@@ -240,6 +240,12 @@ struct eftb_engine {
     long long* chn_nacc = nullptr;
     std::vector<double> chn_host_chain, chn_host_rec;
     std::vector<long long> chn_host_nacc;
+    // eftb_draws_temper_params, which shares the chain call's buffers: beta [TEMPER_MAXR], one launch's slice of lnu_swap [ladders][events][R - 1],
+    // the swap counts [ladders][max(R - 1, 1)] and the sums of ln P [N], with the landing block of the counts; grown on demand
+    double *tmp_beta = nullptr, *tmp_lnus = nullptr, *tmp_sums = nullptr;
+    size_t tmp_beta_cap = 0, tmp_lnus_cap = 0, tmp_sums_cap = 0, tmp_nswap_cap = 0;
+    long long* tmp_nswap = nullptr;
+    std::vector<long long> tmp_host_nswap;
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -2551,12 +2557,18 @@ static int draws_logp_shape(eftb_engine* e, const char* who, DrawKind kind, cons
 // one wave, so this message is never seen.
 static int draws_no_fit(const char* who, int J1) { return fail("%s: the Gram matrix of %d columns does not fit the LDS", who, J1); }
 
+// draws_temper_params_kernel is named at the end of this file alone: a kernel is emitted where it is first named, and behind every other one
+// it leaves their compiled code, label numbers included, the parent's (isa_counts.json)
+using TemperKernel = decltype(&draws_temper_params_kernel<false>);
+static TemperKernel temper_kernel(bool two);
+
 // the large dynamic LDS for every logp draw kernel, once per engine
 static int draws_lds_optin(eftb_engine* e) {
     if (e->drw_lds) return 0;
 #define DRAW_PAIR(k) reinterpret_cast<const void*>(&k<false>), reinterpret_cast<const void*>(&k<true>)
     for (const void* k : {DRAW_PAIR(draws_logp_kernel), DRAW_PAIR(draws_logp_params_kernel), DRAW_PAIR(draws_logp_grad_params_kernel),
-                          DRAW_PAIR(draws_logp_hess_params_kernel), DRAW_PAIR(draws_sample_params_kernel), DRAW_PAIR(draws_chain_params_kernel)})
+                          DRAW_PAIR(draws_logp_hess_params_kernel), DRAW_PAIR(draws_sample_params_kernel), DRAW_PAIR(draws_chain_params_kernel),
+                          reinterpret_cast<const void*>(temper_kernel(false)), reinterpret_cast<const void*>(temper_kernel(true))})
         HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #undef DRAW_PAIR
     e->drw_lds = true;
@@ -4176,11 +4188,20 @@ static int chain_args_check(const char* who, int P, long long N, int T, int thin
 
 // eftb_draws_chain_params and eftb_draws_chain_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group): the checks, W_c
 // and uploads of draws_logp_params_impl, then draws_chain_params_kernel once per CHAIN_STEPS steps.  Between the launches theta and the accept
-// counts stay on the device; every launch's stored states and records come back behind it
+// counts stay on the device; every launch's stored states and records come back behind it.
+// tm (eftb_draws_temper_params and its _datasets): the same path around draws_temper_params_kernel, one workgroup of R waves per ladder; the
+// swap counts and the sums of ln P persist beside theta and the accept counts, and every launch takes its own events out of lnu_swap
+struct TemperArgs {
+    int R, S;
+    long long first_step;
+    const double *beta, *lnu_swap;
+    int64_t* nswap;
+    double* sum_logp;
+};
 static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0,
                                    const double* f, const double* step, const double* lnu, const double* lower, const double* upper, const double* ploc,
                                    const double* pscale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept,
-                                   const DrawGroups* gr = nullptr) {
+                                   const DrawGroups* gr = nullptr, const TemperArgs* tm = nullptr) {
     long long maxcnt = 0;
     if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
     const int ntr = e->ntr, nG = e->like_nG;
@@ -4189,8 +4210,48 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     const int P = rcp.P;
     double pri[CHAIN_PRI];  // lower | upper | loc | sinv
     if (int rc = chain_args_check(who, P, N, T, thin, 1, theta0, step, lnu, lower, upper, ploc, pscale, pri)) return rc;
+    const int R = tm ? tm->R : 1, S = tm ? tm->S : 0, npair = std::max(R - 1, 1);
+    const long long first = tm ? tm->first_step : 0;
+    long long nlad = 0, nsw = 0;  // the ladders of the call and the swap events in it
+    if (tm) {
+        if (R < 1 || R > TEMPER_MAXR) return fail("%s: R = %d rungs outside [1, %d]", who, R, TEMPER_MAXR);
+        for (int c = 0; c < C; ++c)
+            if ((offsets[c + 1] - offsets[c]) % R)
+                return fail("%s: %s %d owns %lld chains, not a multiple of R = %d rungs", who, gr ? "group" : "walker", c,
+                            (long long)(offsets[c + 1] - offsets[c]), R);
+        for (int r = 0; r < R; ++r) {
+            if (!(tm->beta[r] >= 0.0 && tm->beta[r] <= 1.0)) return fail("%s: beta[%d] = %g outside [0, 1]", who, r, tm->beta[r]);
+            if (r && !(tm->beta[r] < tm->beta[r - 1]))
+                return fail("%s: beta[%d] = %g is not below beta[%d] = %g: rung %d must be hotter than rung %d", who, r, tm->beta[r], r - 1, tm->beta[r - 1], r,
+                            r - 1);
+        }
+        if (S < 0) return fail("%s: S = %d steps between swap events, at least 0 (no swaps)", who, S);
+        if (first < 0) return fail("%s: first_step = %lld, at least 0", who, first);
+        nlad = N / R;
+        nsw = S ? (first + T) / S - first / S : 0;
+        if (nsw > 0 && R > 1 && N > 0) {
+            if (!tm->lnu_swap) return fail("%s: lnu_swap is NULL with %lld swap events in the call and R = %d rungs", who, nsw, R);
+            for (long long l = 0; l < nlad; ++l)
+                for (long long j = 0; j < nsw; ++j)
+                    for (int r = (int)((first / S + j) & 1); r < R - 1; r += 2) {  // (the pairs event j tries: the others are not read)
+                        const double v = tm->lnu_swap[(l * nsw + j) * (R - 1) + r];
+                        if (!(v <= 0.0))
+                            return fail("%s: lnu_swap[%lld][%lld][%d] = %g (ladder, event, rung) is not the logarithm of a uniform in [0, 1]", who, l, j, r, v);
+                    }
+        }
+    }
     DrawShape sh;
     if (int rc = draws_logp_shape(e, who, DRAW_CHAIN, &rcp, &sh)) return rc;
+    if (tm) {  // a workgroup of R waves and the exchange behind them, whatever the chain call would take
+        const size_t xch = TEMPER_XCH * sizeof(double);
+        int fit = 0;
+        while (fit < TEMPER_MAXR && sh.L.bytes(fit + 1) + xch <= 160 * 1024) ++fit;
+        if (R > fit)
+            return fail("%s: a ladder of R = %d rungs needs %d waves in one workgroup, but %d fit the LDS beside the Gram matrix of J + 1 = %d columns with "
+                        "nG = %d and P = %d parameters", who, R, R, fit, sh.J1, nG, P);
+        sh.nw = R;
+        sh.lds = sh.L.bytes(R) + xch;
+    }
     // Unreachable: the largest shape there is (J + 1 = 121, nG = 24, 1024 recipe entries) takes 161288 of the 163840 bytes at one wave.
     if (!sh.nw) return fail("%s: the chains of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS", who, P, nG, sh.J1);
     if (N == 0) return 0;
@@ -4207,6 +4268,18 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     if (int rc = grow(&e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, "the stored states")) return rc;
     if (int rc = grow(&e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * MARG_OUT, "the stored records")) return rc;
     hipStream_t st = e->stream;
+    auto events = [&](int t0, int Tc) { return S ? (int)((first + t0 + Tc) / S - (first + t0) / S) : 0; };  // the swap events of the launch at t0
+    if (tm) {
+        int most = 0;
+        for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) most = std::max(most, events(t0, std::min(CHAIN_STEPS, T - t0)));
+        if (int rc = grow(&e->tmp_beta, &e->tmp_beta_cap, TEMPER_MAXR, "beta")) return rc;
+        if (int rc = grow(&e->tmp_lnus, &e->tmp_lnus_cap, (size_t)nlad * most * (R - 1), "lnu_swap")) return rc;
+        if (int rc = grow(&e->tmp_sums, &e->tmp_sums_cap, (size_t)N, "the sums of ln P")) return rc;
+        if (int rc = grow(&e->tmp_nswap, &e->tmp_nswap_cap, (size_t)nlad * npair, "the swap counts", sizeof(long long))) return rc;
+        HIPCHK(hipMemcpyAsync(e->tmp_beta, tm->beta, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(e->tmp_sums, 0, (size_t)N * sizeof(double), st));
+        HIPCHK(hipMemsetAsync(e->tmp_nswap, 0, (size_t)nlad * npair * sizeof(long long), st));
+    }
     HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
     e->chn_host_chain.resize((size_t)N * kstride * P);
@@ -4218,9 +4291,23 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
                                 (size_t)N, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
                                 hipMemcpyHostToDevice, st));
-        launch_two(draws_chain_params_kernel<false>, draws_chain_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin, kc,
-                   kstride, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu, e->chn_chain,
-                   e->chn_rec);
+        if (tm) {
+            // this launch's events of every ladder: step first + t0 is the launch's first, s0 steps remain to its first event, whose global
+            // number is g0 / S
+            const long long g0 = first + t0;
+            const int nswc = events(t0, Tc), s0 = S ? (int)(S - g0 % S) : 0, jpar = S ? (int)((g0 / S) & 1) : 0;
+            if (nswc && R > 1) {
+                const size_t row = (size_t)nswc * (R - 1) * sizeof(double);
+                HIPCHK(hipMemcpy2DAsync(e->tmp_lnus, row, tm->lnu_swap + (size_t)(g0 / S - first / S) * (R - 1), (size_t)nsw * (R - 1) * sizeof(double), row,
+                                        (size_t)nlad, hipMemcpyHostToDevice, st));
+            }
+            launch_two(temper_kernel(false), temper_kernel(true), sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, R, Tc, t0,
+                       thin, kc, kstride, S, s0, jpar, nswc, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, e->tmp_nswap, e->tmp_sums, run.f, run.W, e->like_mu,
+                       e->like_sinv, e->chn_pri, e->tmp_beta, e->chn_step, e->chn_lnu, e->tmp_lnus, e->chn_chain, e->chn_rec);
+        } else
+            launch_two(draws_chain_params_kernel<false>, draws_chain_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin,
+                       kc, kstride, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu,
+                       e->chn_chain, e->chn_rec);
         if (int rc = launched(who)) return rc;
         if (!kc) continue;
         HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4236,8 +4323,15 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     e->chn_host_nacc.resize((size_t)N);
     HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (tm) {
+        e->tmp_host_nswap.resize((size_t)nlad * npair);
+        HIPCHK(hipMemcpyAsync(tm->sum_logp, e->tmp_sums, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(e->tmp_host_nswap.data(), e->tmp_nswap, (size_t)nlad * npair * sizeof(long long), hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     for (long long n = 0; n < N; ++n) naccept[n] = e->chn_host_nacc[n];
+    if (tm)
+        for (long long q = 0; q < nlad * npair; ++q) tm->nswap[q] = e->tmp_host_nswap[q];
     return 0;
 }
 
@@ -4263,6 +4357,38 @@ int eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_t
     if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
     return draws_chain_params_impl(e, who, G, N, T, thin, offsets, theta0, e->grp_f.data(), step, lnu, lower, upper, prior_loc,
                                    prior_scale, chain, logp, fullchi2, best, last, naccept, &gr);
+}
+
+// ------------------------------------------------------------------------------------------------ parallel tempering over the draw parameters
+// eftb_draws_temper_params and eftb_draws_temper_params_datasets: draws_chain_params_impl with the ladders' arguments
+int eftb_draws_temper_params(eftb_engine* e, int C, long long N, int R, int T, int S, long long first_step, int thin, const int64_t* offsets,
+                             const double* theta0, const double* f, const double* beta, const double* step, const double* lnu, const double* lnu_swap,
+                             const double* lower, const double* upper, const double* prior_loc, const double* prior_scale, double* chain, double* logp,
+                             double* fullchi2, double* best, double* last, int64_t* naccept, int64_t* nswap, double* sum_logp) {
+    static const char* who = "eftb_draws_temper_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || !beta || (N > 0 && (!theta0 || !step || !lnu || !chain || !last || !naccept || !nswap || !sum_logp)))
+        return fail("%s: null argument", who);
+    const TemperArgs tm{R, S, first_step, beta, lnu_swap, nswap, sum_logp};
+    return draws_chain_params_impl(e, who, C, N, T, thin, offsets, theta0, f, step, lnu, lower, upper, prior_loc, prior_scale, chain, logp, fullchi2, best,
+                                   last, naccept, nullptr, &tm);
+}
+
+int eftb_draws_temper_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int R, int T, int S,
+                                      long long first_step, int thin, const int64_t* offsets, const double* theta0, const double* f, const double* beta,
+                                      const double* step, const double* lnu, const double* lnu_swap, const double* lower, const double* upper,
+                                      const double* prior_loc, const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best,
+                                      double* last, int64_t* naccept, int64_t* nswap, double* sum_logp) {
+    static const char* who = "eftb_draws_temper_params_datasets";
+    if (e) sub_drain(e);
+    if (!e || !walker || !dataset || !offsets || !f || !beta ||
+        (N > 0 && (!theta0 || !step || !lnu || !chain || !last || !naccept || !nswap || !sum_logp)))
+        return fail("%s: null argument", who);
+    DrawGroups gr{0, walker, dataset};
+    if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
+    const TemperArgs tm{R, S, first_step, beta, lnu_swap, nswap, sum_logp};
+    return draws_chain_params_impl(e, who, G, N, T, thin, offsets, theta0, e->grp_f.data(), step, lnu, lower, upper, prior_loc, prior_scale, chain, logp,
+                                   fullchi2, best, last, naccept, &gr, &tm);
 }
 
 // ------------------------------------------------------------------------------------------------ Hamiltonian Monte Carlo over the draw parameters
@@ -4509,3 +4635,6 @@ int eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, 
     }
     return 0;
 }
+
+// (the one place that names draws_temper_params_kernel: see the declaration above draws_lds_optin)
+static TemperKernel temper_kernel(bool two) { return two ? &draws_temper_params_kernel<true> : &draws_temper_params_kernel<false>; }

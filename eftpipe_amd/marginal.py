@@ -24,6 +24,8 @@ GaussianSamples = collections.namedtuple("GaussianSamples", "logp fullchi2 best 
 DrawChains = collections.namedtuple("DrawChains", "theta logp naccept last fullchi2 best")
 # what MarginalLikelihood.hmc_draws_params returns: the fields of DrawChains, then log_ratio (None unless return_ratio is set)
 DrawTrajectories = collections.namedtuple("DrawTrajectories", "theta logp naccept last fullchi2 best log_ratio")
+# what MarginalLikelihood.temper_draws_params returns; fullchi2 and best are None unless return_best is set
+TemperedChains = collections.namedtuple("TemperedChains", "theta logp fullchi2 best last naccept nswap sum_logp beta")
 DragChains = collections.namedtuple("DragChains", "theta logp_start logp_end last naccept last_logp_start last_logp_end sum_start sum_end log_ratio "
                                     "fullchi2_start fullchi2_end best_start best_end last_fullchi2_start last_fullchi2_end last_best_start last_best_end")
 
@@ -373,9 +375,29 @@ class MarginalLikelihood:
 
     def _chains_raw(self, theta0, offsets, f, step, lnu, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None, groups=None, return_best=False):
         """``metropolis_draws_params`` without the RuntimeError: a chain that failed at its start has NaN states and naccept = -1"""
+        nG = self.nG
+        theta0, off, f, wk, ds, step, lnu, thin, pri = self._chain_args(theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, groups)
+        (N, T, P), K = step.shape, step.shape[1] // thin
+        theta, logp, last, nacc = np.empty((N, K, P)), np.empty((N, K)), np.empty((N, P)), np.empty(N, dtype=np.int64)
+        full = np.empty((N, K)) if return_best else None
+        best = np.empty((N, K, nG)) if return_best else None
+        i64p = C.POINTER(C.c_int64)
+        tail = (off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(step), L.dptr(lnu)) + tuple(L.dptr(a) for a in pri) + (
+            L.dptr(theta), L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(last), nacc.ctypes.data_as(i64p))
+        if groups is not None:
+            i32p = C.POINTER(C.c_int32)
+            L.check(self.eng.lib.eftb_draws_chain_params_datasets(self.eng._h, f.shape[0], wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p), N, T,
+                                                                  thin, *tail))
+        else:
+            L.check(self.eng.lib.eftb_draws_chain_params(self.eng._h, off.size - 1, N, T, thin, *tail))
+        return DrawChains(theta, logp, nacc, last, full, best)
+
+    def _chain_args(self, theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, groups):
+        """the arguments of ``metropolis_draws_params`` (and of ``temper_draws_params``, which shares them) as the library takes them, shape errors
+        raised here -> theta0, off, f, walker, dataset (None without groups), step, lnu, thin, [lower, upper, prior_loc, prior_scale]"""
         from .engine import _params_args
 
-        ntr, nG = self.eng.ntracers, self.nG
+        ntr = self.eng.ntracers
         rec = getattr(self, "_recipe", None)
         wk = ds = None
         if groups is not None:
@@ -400,20 +422,71 @@ class MarginalLikelihood:
                 if a.shape != (P,):
                     raise ValueError(f"{name} must be [{P}], one value per parameter")
             pri.append(a)
-        K = T // thin
+        return theta0, off, f, wk, ds, step, lnu, thin, pri
+
+    def temper_draws_params(self, theta0, offsets, f, beta, step, lnu, lnu_swap=None, swap_every=0, first_step=0, thin=1, lower=None, upper=None,
+                            prior_loc=None, prior_scale=None, groups=None, return_best=False):
+        """Parallel tempering over theta at fixed templates, all T steps and every swap of all ladders in one device call
+        (``eftb_draws_temper_params``) instead of one chain call per swap interval.  beta [R] (``temper_ladder``) are the inverse temperatures,
+        1 >= beta[0] > ... > beta[R - 1] >= 0, R <= 8; theta0 [N, P], offsets, f, ``groups``, the box and the Gaussian prior on theta are those of
+        ``metropolis_draws_params`` with N = nlad R: chain n is rung n % R of ladder n // R, and every walker (group) owns a multiple of R
+        chains.  Rung r targets beta[r] ln P_marg(theta) + ln prior(theta): ln P_marg is tempered as a whole, the Gaussian priors of the
+        marginalised parameters with it; the prior on theta is not.  The caller supplies the randomness (``temper_proposals``): step [N, T, P],
+        lnu [N, T] and lnu_swap [nlad, nsw, R - 1] with nsw = (first_step + T) // S - first_step // S, S = ``swap_every`` (0: no swaps).  Step i
+        is global step g = first_step + i: the Metropolis step of ``metropolis_draws_params`` against the rung's target, then, if
+        (g + 1) % S == 0, swap event j = (g + 1) // S - 1: the pairs (r, r + 1) with r = j mod 2 are exchanged iff
+        lnu_swap[ladder, j_local, r] < (beta[r] - beta[r + 1]) (ln P[r + 1] - ln P[r]).  States move, temperatures stay: chain n is always at
+        beta[n % R].
+        -> ``TemperedChains(theta [N, K, P], logp [N, K], fullchi2, best, last [N, P], naccept [N], nswap [nlad, max(R - 1, 1)], sum_logp [N],
+        beta [R])`` with K = T // thin: the states as ``DrawChains``, ln P untempered (the bits of ``logp_draws_params`` there), the accepted swaps
+        per adjacent pair, and the sum of ln P over the call's T steps per rung (sum_logp / T is <ln P> at beta[r], the integrand of
+        thermodynamic integration).  A call continues from ``last`` with first_step advanced by T, bit for bit.
+        Raises RuntimeError("det of F2ij <= 0") where a rung's starting point has no finite ln P (its whole ladder fails)."""
+        out = self._temper_raw(theta0, offsets, f, beta, step, lnu, lnu_swap, swap_every, first_step, thin, lower, upper, prior_loc, prior_scale, groups,
+                               return_best)
+        if np.any(out.naccept < 0):
+            raise RuntimeError("det of F2ij <= 0")
+        return out
+
+    def _temper_raw(self, theta0, offsets, f, beta, step, lnu, lnu_swap=None, swap_every=0, first_step=0, thin=1, lower=None, upper=None, prior_loc=None,
+                    prior_scale=None, groups=None, return_best=False):
+        """``temper_draws_params`` without the RuntimeError: a ladder that failed at its start has NaN states and naccept = nswap = -1"""
+        nG = self.nG
+        theta0, off, f, wk, ds, step, lnu, thin, pri = self._chain_args(theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, groups)
+        (N, T, P), K = step.shape, step.shape[1] // thin
+        beta = np.asarray(beta, dtype=np.float64)
+        if beta.ndim != 1 or beta.size < 1:
+            raise ValueError("beta must be [R]: the inverse temperatures of the rungs, R >= 1")
+        beta = np.ascontiguousarray(beta)
+        R = beta.size
+        if N % R:
+            raise ValueError(f"theta0 holds {N} chains, not a multiple of the R = {R} rungs of beta")
+        for name, v in (("swap_every", swap_every), ("first_step", first_step)):
+            if v != int(v) or v < 0:
+                raise ValueError(f"{name} must be an integer >= 0")
+        S, first = int(swap_every), int(first_step)
+        nlad, nsw = N // R, ((first + T) // S - first // S if S else 0)
+        if lnu_swap is not None:
+            lnu_swap = np.ascontiguousarray(lnu_swap, dtype=np.float64)
+            if lnu_swap.shape != (nlad, nsw, R - 1):
+                raise ValueError(f"lnu_swap must be [{nlad}, {nsw}, {R - 1}]: the logarithm of a uniform per ladder, swap event and adjacent pair")
+        elif nsw and R > 1 and nlad:
+            raise ValueError(f"lnu_swap must be [{nlad}, {nsw}, {R - 1}]: the call holds {nsw} swap events")
         theta, logp, last, nacc = np.empty((N, K, P)), np.empty((N, K)), np.empty((N, P)), np.empty(N, dtype=np.int64)
         full = np.empty((N, K)) if return_best else None
         best = np.empty((N, K, nG)) if return_best else None
+        nswap, sums = np.empty((nlad, max(R - 1, 1)), dtype=np.int64), np.empty(N)
         i64p = C.POINTER(C.c_int64)
-        tail = (off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(step), L.dptr(lnu)) + tuple(L.dptr(a) for a in pri) + (
-            L.dptr(theta), L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(last), nacc.ctypes.data_as(i64p))
+        head = (N, R, T, S, first, thin, off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(beta), L.dptr(step), L.dptr(lnu), L.dptr(lnu_swap))
+        tail = tuple(L.dptr(a) for a in pri) + (L.dptr(theta), L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(last), nacc.ctypes.data_as(i64p),
+                                                nswap.ctypes.data_as(i64p), L.dptr(sums))
         if groups is not None:
             i32p = C.POINTER(C.c_int32)
-            L.check(self.eng.lib.eftb_draws_chain_params_datasets(self.eng._h, f.shape[0], wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p), N, T,
-                                                                  thin, *tail))
+            L.check(self.eng.lib.eftb_draws_temper_params_datasets(self.eng._h, f.shape[0], wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p), *head,
+                                                                   *tail))
         else:
-            L.check(self.eng.lib.eftb_draws_chain_params(self.eng._h, off.size - 1, N, T, thin, *tail))
-        return DrawChains(theta, logp, nacc, last, full, best)
+            L.check(self.eng.lib.eftb_draws_temper_params(self.eng._h, off.size - 1, *head, *tail))
+        return TemperedChains(theta, logp, full, best, last, nacc, nswap, sums, beta)
 
     def hmc_draws_params(self, theta0, offsets, f, momentum, lnu, eps, nleap, factor=None, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None,
                          groups=None, return_best=False, return_ratio=False):
@@ -719,6 +792,49 @@ def metropolis_proposals(rng, N, T, factor):
     return np.ascontiguousarray(step), lnu
 
 
+def temper_ladder(R, beta_min):
+    """The inverse temperatures of ``MarginalLikelihood.temper_draws_params``: a geometric ladder beta [R] from 1 down to beta_min,
+    beta[r] = beta_min^(r / (R - 1)) (R = 1: [1]), with 0 < beta_min < 1 for R > 1."""
+    if R != int(R) or R < 1:
+        raise ValueError("R must be an integer >= 1")
+    R = int(R)
+    if R == 1:
+        return np.ones(1)
+    if not 0.0 < beta_min < 1.0:
+        raise ValueError("beta_min must lie in (0, 1): a geometric ladder does not reach 0")
+    beta = float(beta_min) ** (np.arange(R) / (R - 1))
+    beta[0], beta[-1] = 1.0, float(beta_min)
+    return beta
+
+
+def temper_proposals(rng, nlad, beta, T, factor, swap_every, first_step=0, widen=None):
+    """The randomness of ``MarginalLikelihood.temper_draws_params`` from a ``numpy.random.Generator``: -> (step [nlad R, T, P], lnu [nlad R, T],
+    lnu_swap [nlad, nsw, R - 1]) with nsw = (first_step + T) // swap_every - first_step // swap_every (swap_every = 0: nsw = 0).  step and lnu are
+    ``metropolis_proposals`` for the nlad R chains (factor [P, P] or [nlad R, P, P]), the increments of rung r multiplied by widen[r]; the
+    default 1 / sqrt(beta[r]) keeps the acceptance of a Gaussian target level along the ladder and needs every beta > 0 (ValueError otherwise)."""
+    beta = np.asarray(beta, dtype=np.float64)
+    if beta.ndim != 1 or beta.size < 1:
+        raise ValueError("beta must be [R]")
+    R = beta.size
+    for name, v, lo in (("nlad", nlad, 0), ("T", T, 1), ("swap_every", swap_every, 0), ("first_step", first_step, 0)):
+        if v != int(v) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}")
+    nlad, T, S, first = int(nlad), int(T), int(swap_every), int(first_step)
+    if widen is None:
+        if np.any(beta <= 0.0):
+            raise ValueError("a rung at beta = 0 has no default widening 1 / sqrt(beta): pass widen [R]")
+        widen = 1.0 / np.sqrt(beta)
+    widen = np.asarray(widen, dtype=np.float64)
+    if widen.shape != (R,):
+        raise ValueError(f"widen must be [{R}], one factor per rung")
+    step, lnu = metropolis_proposals(rng, nlad * R, T, factor)
+    step = step * np.tile(widen, nlad)[:, None, None]
+    nsw = (first + T) // S - first // S if S else 0
+    with np.errstate(divide="ignore"):
+        lnu_swap = np.log(rng.random((nlad, nsw, max(R - 1, 0))))
+    return np.ascontiguousarray(step), lnu, lnu_swap
+
+
 def hmc_momenta(rng, N, T, P):
     """The randomness of ``MarginalLikelihood.hmc_draws_params`` from a ``numpy.random.Generator``: -> (momentum [N, T, P], lnu [N, T]) with
     momentum = rng.standard_normal((N, T, P)) and lnu = log(rng.random((N, T)))."""
@@ -750,4 +866,4 @@ def drag_accept(lnu_slow, result):
     return lnu_slow < result.log_ratio
 
 
-__all__ = ["MarginalLikelihood", "DrawChains", "DrawTrajectories", "hmc_momenta", "DragChains", "drag_fractions", "drag_accept", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]
+__all__ = ["MarginalLikelihood", "DrawChains", "DrawTrajectories", "TemperedChains", "temper_ladder", "temper_proposals", "hmc_momenta", "DragChains", "drag_fractions", "drag_accept", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]

@@ -429,6 +429,53 @@ int  eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_
                                       const double* lower, const double* upper, const double* prior_loc, const double* prior_scale, double* chain,
                                       double* logp, double* fullchi2, double* best, double* last, int64_t* naccept);
 
+/* Parallel tempering over theta at fixed templates: nlad ladders of R chains ("rungs") at the inverse temperatures beta [R],
+ * 1 >= beta[0] > beta[1] > ... > beta[R - 1] >= 0, all T steps and every exchange between rungs in the kernel, one workgroup of R waves per
+ * ladder.  The N = nlad R chains are counted by offsets as in eftb_draws_chain_params; chain n is rung n % R of ladder n / R, and every
+ * walker's (group's) count is a multiple of R, so that no ladder straddles two walkers.  Rung r targets
+ *     ln pi_r(theta) = beta[r] ln P_marg(theta) + pri(theta)
+ * with ln P_marg the record of eftb_draws_logp_params, tempered as a whole -- it contains the Gaussian priors of the marginalised parameters,
+ * which are therefore tempered with it -- and pri the chain call's prior on theta (box and independent Gaussians, the same arithmetic),
+ * which is not.  Step i of the call is global step g = first_step + i:
+ *     within a rung   the chain call's step: theta' = theta + step[n][i]; outside the box: rejected without an evaluation; otherwise accepted
+ *                     iff ln P' is finite and lnu[n][i] < (beta[r] ln P' + pri') - (beta[r] ln P + pri), every operation rounded on its own.
+ *                     beta[r] = 1: the products are exact, and a rung that never swaps is eftb_draws_chain_params' chain bit for bit
+ *     swap event      after step i if (g + 1) % S == 0, event j = (g + 1) / S - 1 counted from the chain's beginning: the pairs (r, r + 1) with
+ *                     r = j mod 2 and r + 1 < R are tried.  x = (beta[r] - beta[r + 1]) (ln P_{r+1} - ln P_r), two differences and a product,
+ *                     each rounded; accepted iff lnu_swap[ladder][j_local][r] < x (-inf: always), where j_local counts the call's events from 0.
+ *                     lnu_swap is [nlad][nsw][R - 1] with nsw = (first_step + T) / S - first_step / S (integer divisions); the entries of
+ *                     the pairs an event does not try are not read.  On acceptance the two rungs exchange theta, the record (ln P, full
+ *                     chi2, best fit) and pri; temperatures, naccept and sum_logp stay with the rung.  S = 0: no swaps (lnu_swap may be NULL)
+ *     then            sum_logp[n] = sum_logp[n] + ln P of rung n's current state (untempered): a sequential sum of T terms, <ln P> at
+ *                     beta[r] times T, what thermodynamic integration asks for; and after every thin-th step of the call (thin does not
+ *                     look at first_step) the state is stored
+ * Outputs, with K = T / thin:
+ *     chain [N][K][P], logp [N][K], fullchi2 [N][K], best [N][K][nG] (the last three each or NULL), last [N][P], naccept [N]
+ *                           as eftb_draws_chain_params; the records are untempered, the bits of eftb_draws_logp_params at the stored theta
+ *     nswap [nlad][max(R - 1, 1)]   accepted swaps of every adjacent pair
+ *     sum_logp [N]
+ * A T-step call equals a T1-step call at first_step = s and a T2-step call at first_step = s + T1 from `last`, with step, lnu and lnu_swap
+ * split accordingly, bit for bit in chain, records and last, naccept and nswap summed; sum_logp starts anew in every call and is not
+ * claimed to combine.  The host splits T into launches of at most 256 steps; theta, naccept, nswap and sum_logp persist on the device
+ * between them and every launch recomputes the records of its starting states.  A ladder's bits depend neither on the other ladders of
+ * the call nor on their order.
+ * A ladder one of whose rungs starts without a finite ln P (det F2 <= 0) fails as a whole: NaN in chain, logp, fullchi2, best, last and
+ * sum_logp of every rung, naccept = nswap = -1; the other ladders are not touched.
+ * Refused before anything is copied, naming ladder, rung, step or parameter where they apply: what eftb_draws_chain_params refuses, R
+ * outside [1, 8], a walker whose chain count is no multiple of R, beta NaN, outside [0, 1] or not strictly decreasing, S < 0, first_step < 0,
+ * a read entry of lnu_swap NaN or > 0, lnu_swap NULL with nsw > 0 and R > 1, and an R that does not fit the LDS: the chain call's working
+ * set at R waves plus 40 doubles for the exchange, 320 bytes, within 160 KB (the message names R, the waves that fit, J + 1, nG and P). */
+int  eftb_draws_temper_params(eftb_engine* e, int C, long long N, int R, int T, int S, long long first_step, int thin, const int64_t* offsets,
+                              const double* theta0, const double* f, const double* beta, const double* step, const double* lnu, const double* lnu_swap,
+                              const double* lower, const double* upper, const double* prior_loc, const double* prior_scale, double* chain, double* logp,
+                              double* fullchi2, double* best, double* last, int64_t* naccept, int64_t* nswap, double* sum_logp);
+/* eftb_draws_temper_params per group (walker[g], dataset[g]) of eftb_draws_logp_params_datasets: the same kernel on the groups' Gram matrices. */
+int  eftb_draws_temper_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int R, int T, int S,
+                                       long long first_step, int thin, const int64_t* offsets, const double* theta0, const double* f, const double* beta,
+                                       const double* step, const double* lnu, const double* lnu_swap, const double* lower, const double* upper,
+                                       const double* prior_loc, const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best,
+                                       double* last, int64_t* naccept, int64_t* nswap, double* sum_logp);
+
 /* Dragging chains between two cosmologies in one device call (the fast steps of cobaya's `drag: true` behind one slow proposal): the
  * chain call against a target that slides from a start walker to an end walker.  C walkers are resident, each with its own templates and
  * f [C][ntr]; pair g = (a = wstart[g], b = wend[g]) of G pairs (walkers may repeat, a = b is allowed) owns the chains

@@ -79,6 +79,19 @@ trajectories of --leap leapfrog steps (default 8), medians of 9 cached calls wit
 the same file (with tests/hmc_util.py beside it) times (b) and (c) on the parent commit.
 
     python tools/draws_probe.py --hmc [--walkers C] [--steps E] [--leap L]
+
+--temper [n,n,...]: parallel tempering over theta (MarginalLikelihood.temper_draws_params) instead, for both shapes, --walkers
+walkers (default 128) x n ladders each (default 1 and 4) of R = 4 rungs on the geometric ladder from 1 to 0.1, --steps T steps (default 256)
+with a swap event every fourth, medians of 9 cached calls with [min, max], on the same proposals and uniforms:
+
+    (a) temper   one temper_draws_params call: all T steps of all rungs and every swap in the kernel
+    (b) loop     T / 4 metropolis_draws_params calls of four steps with the swaps in NumPy between them: the only route without (a)
+    (c) chains   one metropolis_draws_params call of the same N T steps, without swaps: (a) / (c) is the price of the barriers
+
+(a) and (b) are asserted to return the same ladders and swap counts.  On a tree without temper_draws_params (a) is skipped, so that the same
+file times (b) and (c) on the parent commit.
+
+    python tools/draws_probe.py --temper [--walkers C] [--steps T]
 """
 import argparse
 import json
@@ -520,8 +533,68 @@ def probe_hmc(name, setup, C, n, evals, nleap, eps, repeats=9):
     return out
 
 
+def probe_temper(name, setup, C, nlad, R=4, T=256, S=4, repeats=9):
+    """(a), (b), (c) of --temper for one shape: C walkers x nlad ladders of R rungs x T steps with a swap event every S, medians of `repeats`
+    cached calls with [min, max].  (b), the only route without the tempering call, runs on a tree that lacks it too"""
+    rng = np.random.default_rng(1)
+    N = C * nlad * R
+    eng, like, templ, _, ndata, nG, (rec, theta_build, fC), _ = setup(C, N, rng)
+    eng.put("TEMPL", templ)
+    theta0 = theta_build()
+    P = theta0.shape[1]
+    off = np.arange(C + 1) * nlad * R
+    like.set_draw_recipe(rec)
+    beta = 0.1 ** (np.arange(R) / max(R - 1, 1))  # (temper_ladder(R, 0.1), spelled out for the tree without it)
+    bt = np.tile(beta, N // R)
+    step = 0.3 * (theta_build() - np.median(theta0, axis=0))[:, None, :] * rng.standard_normal((N, T, 1)) + 0.01 * rng.standard_normal((N, T, P))
+    step = np.ascontiguousarray(step / np.sqrt(bt)[:, None, None])
+    lnu = np.log(rng.random((N, T)))
+    lnus = np.log(rng.random((N // R, T // S, R - 1)))
+    stat = lambda ts: {"ms": 1e3 * float(np.median(ts)), "ms_spread": [1e3 * min(ts), 1e3 * max(ts)]}
+    out = {"shape": name, "walkers": C, "ladders": N // R, "rungs": R, "steps": T, "swap_every": S, "ndata": ndata, "nG": nG, "P": P}
+    # (b) T / S chain calls of S steps, the swaps in NumPy between them.  The chain call has no temperature: without a Gaussian prior on theta,
+    # lnu / beta < ln P' - ln P is the tempered rule up to the rounding of one product
+    lnu_b = lnu / bt[:, None]
+    base = np.arange(N // R) * R
+
+    def loop():
+        cur, nswap = theta0, np.zeros((N // R, R - 1), dtype=np.int64)
+        for j in range(T // S):
+            r = like.metropolis_draws_params(cur, off, fC, np.ascontiguousarray(step[:, j * S : (j + 1) * S]), np.ascontiguousarray(lnu_b[:, j * S : (j + 1) * S]))
+            cur, lp = r.last, r.logp[:, -1]
+            for q in range(j % 2, R - 1, 2):
+                lo, hi = base + q, base + q + 1
+                sw = lnus[:, j, q] < (beta[q] - beta[q + 1]) * (lp[hi] - lp[lo])
+                a, b = lo[sw], hi[sw]
+                cur[a], cur[b] = cur[b].copy(), cur[a].copy()
+                nswap[:, q] += sw
+        return cur, nswap
+
+    last, nswap = loop()
+    out["swap_rate"] = (nswap.sum(0) / ((T // S + 1 - np.arange(R - 1) % 2) // 2 * (N // R))).tolist()
+    out["loop"] = stat(times(loop, repeats))
+    plain = lambda: like.metropolis_draws_params(theta0, off, fC, step, lnu)  # (c) the same N T steps without a swap or a barrier
+    plain()
+    out["chains"] = stat(times(plain, repeats))
+    if hasattr(like, "temper_draws_params"):
+        call = lambda: like.temper_draws_params(theta0, off, fC, beta, step, lnu, lnus, swap_every=S)
+        r = call()
+        assert np.array_equal(r.last, last) and np.array_equal(r.nswap, nswap)  # the same ladders as the loop
+        out["accept_rate"] = (r.naccept.reshape(-1, R).mean(0) / T).tolist()
+        out["temper"] = stat(times(call, repeats))
+        out["loop_over_temper"] = out["loop"]["ms"] / out["temper"]["ms"]
+        out["temper_over_chains"] = out["temper"]["ms"] / out["chains"]["ms"]
+        out["steps_per_s"] = N * T / (1e-3 * out["temper"]["ms"])
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--temper", nargs="?", const="1,4", default=None,
+                    help="n[,n...] ladders of four rungs per walker (default 1,4), a swap event every fourth step: time temper_draws_params, the loop of "
+                         "steps / 4 metropolis_draws_params calls with the swaps in NumPy on the same inputs, and one chain call of as many steps")
     ap.add_argument("--chains", nargs="?", const="1,8", default=None,
                     help="n[,n...] chains per walker (default 1,8): time metropolis_draws_params, the host loop of logp_draws_params calls on the same "
                          "proposals and one logp_draws_params call on as many independent draws")
@@ -540,7 +613,11 @@ if __name__ == "__main__":
     ap.add_argument("--walkers", type=int, default=None)
     ap.add_argument("--datasets", type=int, default=0, help="M data vectors sharing the covariance: time the groups call, the per-vector loop and the plain call")
     a = ap.parse_args()
-    if a.hmc:
+    if a.temper:
+        for n in (int(x) for x in a.temper.split(",")):
+            probe_temper("marg", marg_setup, a.walkers or 128, n, T=a.steps)
+            probe_temper("cfg3", cfg3_setup, a.walkers or 128, n, T=a.steps)
+    elif a.hmc:
         for n in (int(x) for x in a.hmc.split(",")):
             probe_hmc("marg", marg_setup, a.walkers or 128, n, a.steps, a.leap, 0.01)
             probe_hmc("cfg3", cfg3_setup, a.walkers or 128, n, a.steps, a.leap, 0.01)
