@@ -4186,153 +4186,146 @@ static int chain_args_check(const char* who, int P, long long N, int T, int thin
     return 0;
 }
 
-// eftb_draws_chain_params and eftb_draws_chain_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group): the checks, W_c
-// and uploads of draws_logp_params_impl, then draws_chain_params_kernel once per CHAIN_STEPS steps.  Between the launches theta and the accept
-// counts stay on the device; every launch's stored states and records come back behind it.
-// tm (eftb_draws_temper_params and its _datasets): the same path around draws_temper_params_kernel, one workgroup of R waves per ladder; the
-// swap counts and the sums of ln P persist beside theta and the accept counts, and every launch takes its own events out of lnu_swap
-struct TemperArgs {
-    int R, S;
-    long long first_step;
-    const double *beta, *lnu_swap;
-    int64_t* nswap;
-    double* sum_logp;
+// What the four sampler calls (chains, tempering, HMC, dragging) share on the host.  Each of them reads: chain_front, its own checks, its shape,
+// chain_buffers, its own buffers and one-time uploads, chain_run around its own launch, chain_fetch, its own outputs, chain_end
+struct ChainCall {
+    eftb_engine* e;
+    const char* who;
+    long long N, maxcnt;    // chains; the most of them one walker (group, pair) owns
+    int T, thin, P, nG;
+    int per_launch, width;  // steps (trajectories) of a launch; doubles of a stored record: MARG_OUT, or two of them for a pair of walkers
+    int K, kstride, Tmax;   // stored states of a chain in the call, at most in one launch, and the steps of the longest launch
+    char shape[112];        // the size of the call, for a refused allocation
+    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
 };
+struct ChainRecords {  // where a walker's records go, slot by slot through draws_unpack
+    double *logp, *fullchi2, *best;
+};
+using ChainLaunch = std::function<int(int t0, int Tc, int kc)>;       // this launch's own uploads, then launch_two with the sampler's kernel
+using ChainMore = std::function<int(int t0, int Tc, bool landed)>;  // more to bring back behind a launch: enqueue it, then (landed) hand it out
+
+// the refusals no sampler words itself, in the order of the draw calls: C owners (unit; the block must hold nwalk walkers) of the N chains,
+// f [Cf][ntr], then chain_args_check on the moves (step or mom) -> maxcnt, P, nG and pri
+static int chain_front(ChainCall* c, int C, const char* unit, int nwalk, int Cf, int thin_min, const int64_t* offsets, const double* theta0, const double* f,
+                       const double* moves, const double* lnu, const double* lower, const double* upper, const double* ploc, const double* pscale,
+                       const char* moves_name = "step") {
+    eftb_engine* e = c->e;
+    if (int rc = draws_logp_check(e, c->who, C, c->N, offsets, &c->maxcnt, unit, nwalk)) return rc;
+    c->nG = e->like_nG;
+    if (int rc = draws_params_check(e, c->who, 0, c->nG + 1, Cf, c->N, theta0, f)) return rc;
+    c->P = e->recipe[0].P;
+    return chain_args_check(c->who, c->P, c->N, c->T, c->thin, thin_min, theta0, moves, lnu, lower, upper, ploc, pscale, c->pri, moves_name);
+}
+
+static int chain_grow(const ChainCall& c, void* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) {
+    return grow_dev(c.e, pp, cap, n, elem, c.who, what, c.shape);
+}
+
+// the split into launches of per_launch steps and the buffers every sampler has, records of `width` doubles; `moves` and `unit` are the
+// caller's words for a refused allocation.  thin = 0 (dragging alone allows it) stores nothing
+static int chain_buffers(ChainCall& c, int per_launch, int width, const char* moves, const char* unit) {
+    eftb_engine* e = c.e;
+    c.per_launch = per_launch;
+    c.width = width;
+    c.K = c.thin ? c.T / c.thin : 0;
+    c.kstride = c.thin ? std::max(1, std::min(c.K, per_launch / c.thin + 1)) : 1;
+    c.Tmax = std::min(c.T, per_launch);
+    snprintf(c.shape, sizeof c.shape, "N = %lld chains x T = %d %s with P = %d parameters", c.N, c.T, unit, c.P);
+    const size_t N = (size_t)c.N;
+    if (int rc = chain_grow(c, &e->chn_step, &e->chn_step_cap, N * c.Tmax * c.P, moves)) return rc;
+    if (int rc = chain_grow(c, &e->chn_lnu, &e->chn_lnu_cap, N * c.Tmax, "lnu")) return rc;
+    if (int rc = chain_grow(c, &e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
+    if (int rc = chain_grow(c, &e->chn_nacc, &e->chn_nacc_cap, N, "the accept counts", sizeof(long long))) return rc;
+    if (int rc = chain_grow(c, &e->chn_chain, &e->chn_chain_cap, N * c.kstride * c.P, "the stored states")) return rc;
+    return chain_grow(c, &e->chn_rec, &e->chn_rec_cap, N * c.kstride * width, "the stored records");
+}
+
+// The prior table and the zeroed accept counts (behind the caller's own one-time uploads), then one launch per per_launch steps.  Between the
+// launches theta and the accept counts stay on the device; the states and records a launch stored come back behind it, into chain [N][K][P] and,
+// one ChainRecords per MARG_OUT of the width, into slot k of `slots` per chain.  A launch that stored nothing is not waited for, unless `more`
+// brings something back behind every launch
+static int chain_run(const ChainCall& c, const double* moves, const double* lnu, double* chain, const ChainRecords* rec, int slots, const ChainLaunch& launch,
+                     const ChainMore& more = nullptr) {
+    eftb_engine* e = c.e;
+    const size_t N = (size_t)c.N, P = (size_t)c.P, W = (size_t)c.width, T = (size_t)c.T, K = (size_t)c.K, kstride = (size_t)c.kstride;
+    const int nG = c.nG, thin = c.thin;
+    hipStream_t st = e->stream;
+    HIPCHK(hipMemcpyAsync(e->chn_pri, c.pri, sizeof(c.pri), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(e->chn_nacc, 0, N * sizeof(long long), st));
+    e->chn_host_chain.resize(N * kstride * P);
+    e->chn_host_rec.resize(N * kstride * W);
+    const double *hchain = e->chn_host_chain.data(), *hrec = e->chn_host_rec.data();
+    for (int t0 = 0; t0 < c.T; t0 += c.per_launch) {
+        const int Tc = std::min(c.per_launch, c.T - t0), k0 = thin ? t0 / thin : 0, kc = thin ? (t0 + Tc) / thin - k0 : 0;
+        // this launch's steps of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
+        HIPCHK(hipMemcpy2DAsync(e->chn_step, Tc * P * sizeof(double), moves + t0 * P, T * P * sizeof(double), Tc * P * sizeof(double), N,
+                                hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpy2DAsync(e->chn_lnu, Tc * sizeof(double), lnu + t0, T * sizeof(double), Tc * sizeof(double), N, hipMemcpyHostToDevice, st));
+        if (int rc = launch(t0, Tc, kc)) return rc;
+        if (int rc = launched(c.who)) return rc;
+        if (!kc && !more) continue;
+        if (kc) {
+            HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, N * kstride * W * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        if (more)
+            if (int rc = more(t0, Tc, false)) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t n = 0; n < N; ++n)
+            for (int k = 0; k < kc; ++k) {
+                const size_t from = n * kstride + k;
+                std::copy_n(hchain + from * P, P, chain + (n * K + k0 + k) * P);
+                for (size_t r = 0; r * MARG_OUT < W; ++r)
+                    draws_unpack(hrec + from * W + r * MARG_OUT, nG, n * slots + k0 + k, rec[r].logp, rec[r].fullchi2, rec[r].best);
+            }
+        if (more)
+            if (int rc = more(t0, Tc, true)) return rc;
+    }
+    return 0;
+}
+
+// the end of a call: `last` and the accept counts are enqueued, the caller enqueues its own outputs behind them, and chain_end waits for all
+// of it and widens the counts
+static int chain_fetch(const ChainCall& c, double* last) {
+    eftb_engine* e = c.e;
+    e->chn_host_nacc.resize((size_t)c.N);
+    HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)c.N * c.P * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)c.N * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+    return 0;
+}
+static int chain_end(const ChainCall& c, int64_t* naccept) {
+    HIPCHK(hipStreamSynchronize(c.e->stream));
+    for (long long n = 0; n < c.N; ++n) naccept[n] = c.e->chn_host_nacc[n];
+    return 0;
+}
+
+// eftb_draws_chain_params and eftb_draws_chain_params_datasets (gr; C counts the groups, offsets and f [C][ntr] are per group): the checks, W_c
+// and uploads of draws_logp_params_impl, then draws_chain_params_kernel once per CHAIN_STEPS steps
 static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0,
                                    const double* f, const double* step, const double* lnu, const double* lower, const double* upper, const double* ploc,
                                    const double* pscale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept,
-                                   const DrawGroups* gr = nullptr, const TemperArgs* tm = nullptr) {
-    long long maxcnt = 0;
-    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
-    const int ntr = e->ntr, nG = e->like_nG;
-    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
-    const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int P = rcp.P;
-    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
-    if (int rc = chain_args_check(who, P, N, T, thin, 1, theta0, step, lnu, lower, upper, ploc, pscale, pri)) return rc;
-    const int R = tm ? tm->R : 1, S = tm ? tm->S : 0, npair = std::max(R - 1, 1);
-    const long long first = tm ? tm->first_step : 0;
-    long long nlad = 0, nsw = 0;  // the ladders of the call and the swap events in it
-    if (tm) {
-        if (R < 1 || R > TEMPER_MAXR) return fail("%s: R = %d rungs outside [1, %d]", who, R, TEMPER_MAXR);
-        for (int c = 0; c < C; ++c)
-            if ((offsets[c + 1] - offsets[c]) % R)
-                return fail("%s: %s %d owns %lld chains, not a multiple of R = %d rungs", who, gr ? "group" : "walker", c,
-                            (long long)(offsets[c + 1] - offsets[c]), R);
-        for (int r = 0; r < R; ++r) {
-            if (!(tm->beta[r] >= 0.0 && tm->beta[r] <= 1.0)) return fail("%s: beta[%d] = %g outside [0, 1]", who, r, tm->beta[r]);
-            if (r && !(tm->beta[r] < tm->beta[r - 1]))
-                return fail("%s: beta[%d] = %g is not below beta[%d] = %g: rung %d must be hotter than rung %d", who, r, tm->beta[r], r - 1, tm->beta[r - 1], r,
-                            r - 1);
-        }
-        if (S < 0) return fail("%s: S = %d steps between swap events, at least 0 (no swaps)", who, S);
-        if (first < 0) return fail("%s: first_step = %lld, at least 0", who, first);
-        nlad = N / R;
-        nsw = S ? (first + T) / S - first / S : 0;
-        if (nsw > 0 && R > 1 && N > 0) {
-            if (!tm->lnu_swap) return fail("%s: lnu_swap is NULL with %lld swap events in the call and R = %d rungs", who, nsw, R);
-            for (long long l = 0; l < nlad; ++l)
-                for (long long j = 0; j < nsw; ++j)
-                    for (int r = (int)((first / S + j) & 1); r < R - 1; r += 2) {  // (the pairs event j tries: the others are not read)
-                        const double v = tm->lnu_swap[(l * nsw + j) * (R - 1) + r];
-                        if (!(v <= 0.0))
-                            return fail("%s: lnu_swap[%lld][%lld][%d] = %g (ladder, event, rung) is not the logarithm of a uniform in [0, 1]", who, l, j, r, v);
-                    }
-        }
-    }
+                                   const DrawGroups* gr = nullptr) {
+    ChainCall c{e, who, N, 0, T, thin};
+    if (int rc = chain_front(&c, C, gr ? "group" : "walker", gr ? gr->nwalk : -1, C, 1, offsets, theta0, f, step, lnu, lower, upper, ploc, pscale)) return rc;
+    const int ntr = e->ntr, nG = c.nG;
     DrawShape sh;
-    if (int rc = draws_logp_shape(e, who, DRAW_CHAIN, &rcp, &sh)) return rc;
-    if (tm) {  // a workgroup of R waves and the exchange behind them, whatever the chain call would take
-        const size_t xch = TEMPER_XCH * sizeof(double);
-        int fit = 0;
-        while (fit < TEMPER_MAXR && sh.L.bytes(fit + 1) + xch <= 160 * 1024) ++fit;
-        if (R > fit)
-            return fail("%s: a ladder of R = %d rungs needs %d waves in one workgroup, but %d fit the LDS beside the Gram matrix of J + 1 = %d columns with "
-                        "nG = %d and P = %d parameters", who, R, R, fit, sh.J1, nG, P);
-        sh.nw = R;
-        sh.lds = sh.L.bytes(R) + xch;
-    }
+    if (int rc = draws_logp_shape(e, who, DRAW_CHAIN, &e->recipe[0], &sh)) return rc;
     // Unreachable: the largest shape there is (J + 1 = 121, nG = 24, 1024 recipe entries) takes 161288 of the 163840 bytes at one wave.
-    if (!sh.nw) return fail("%s: the chains of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS", who, P, nG, sh.J1);
+    if (!sh.nw) return fail("%s: the chains of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS", who, c.P, nG, sh.J1);
     if (N == 0) return 0;
-    const int K = T / thin, kstride = std::max(1, std::min(K, CHAIN_STEPS / thin + 1)), Tmax = std::min(T, CHAIN_STEPS);
     DrawRun run;
-    if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
-    char shape[96];
-    snprintf(shape, sizeof shape, "N = %lld chains x T = %d steps with P = %d parameters", N, T, P);
-    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(e, pp, cap, n, elem, who, what, shape); };
-    if (int rc = grow(&e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, "the steps")) return rc;
-    if (int rc = grow(&e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, "lnu")) return rc;
-    if (int rc = grow(&e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
-    if (int rc = grow(&e->chn_nacc, &e->chn_nacc_cap, (size_t)N, "the accept counts", sizeof(long long))) return rc;
-    if (int rc = grow(&e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, "the stored states")) return rc;
-    if (int rc = grow(&e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * MARG_OUT, "the stored records")) return rc;
-    hipStream_t st = e->stream;
-    auto events = [&](int t0, int Tc) { return S ? (int)((first + t0 + Tc) / S - (first + t0) / S) : 0; };  // the swap events of the launch at t0
-    if (tm) {
-        int most = 0;
-        for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) most = std::max(most, events(t0, std::min(CHAIN_STEPS, T - t0)));
-        if (int rc = grow(&e->tmp_beta, &e->tmp_beta_cap, TEMPER_MAXR, "beta")) return rc;
-        if (int rc = grow(&e->tmp_lnus, &e->tmp_lnus_cap, (size_t)nlad * most * (R - 1), "lnu_swap")) return rc;
-        if (int rc = grow(&e->tmp_sums, &e->tmp_sums_cap, (size_t)N, "the sums of ln P")) return rc;
-        if (int rc = grow(&e->tmp_nswap, &e->tmp_nswap_cap, (size_t)nlad * npair, "the swap counts", sizeof(long long))) return rc;
-        HIPCHK(hipMemcpyAsync(e->tmp_beta, tm->beta, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(e->tmp_sums, 0, (size_t)N * sizeof(double), st));
-        HIPCHK(hipMemsetAsync(e->tmp_nswap, 0, (size_t)nlad * npair * sizeof(long long), st));
-    }
-    HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
-    e->chn_host_chain.resize((size_t)N * kstride * P);
-    e->chn_host_rec.resize((size_t)N * kstride * MARG_OUT);
-    for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) {
-        const int Tc = std::min(CHAIN_STEPS, T - t0), k0 = t0 / thin, kc = (t0 + Tc) / thin - k0;
-        // this launch's steps of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
-        HIPCHK(hipMemcpy2DAsync(e->chn_step, (size_t)Tc * P * sizeof(double), step + (size_t)t0 * P, (size_t)T * P * sizeof(double), (size_t)Tc * P * sizeof(double),
-                                (size_t)N, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
-                                hipMemcpyHostToDevice, st));
-        if (tm) {
-            // this launch's events of every ladder: step first + t0 is the launch's first, s0 steps remain to its first event, whose global
-            // number is g0 / S
-            const long long g0 = first + t0;
-            const int nswc = events(t0, Tc), s0 = S ? (int)(S - g0 % S) : 0, jpar = S ? (int)((g0 / S) & 1) : 0;
-            if (nswc && R > 1) {
-                const size_t row = (size_t)nswc * (R - 1) * sizeof(double);
-                HIPCHK(hipMemcpy2DAsync(e->tmp_lnus, row, tm->lnu_swap + (size_t)(g0 / S - first / S) * (R - 1), (size_t)nsw * (R - 1) * sizeof(double), row,
-                                        (size_t)nlad, hipMemcpyHostToDevice, st));
-            }
-            launch_two(temper_kernel(false), temper_kernel(true), sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, R, Tc, t0,
-                       thin, kc, kstride, S, s0, jpar, nswc, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, e->tmp_nswap, e->tmp_sums, run.f, run.W, e->like_mu,
-                       e->like_sinv, e->chn_pri, e->tmp_beta, e->chn_step, e->chn_lnu, e->tmp_lnus, e->chn_chain, e->chn_rec);
-        } else
-            launch_two(draws_chain_params_kernel<false>, draws_chain_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin,
-                       kc, kstride, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu,
-                       e->chn_chain, e->chn_rec);
-        if (int rc = launched(who)) return rc;
-        if (!kc) continue;
-        HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, (size_t)N * kstride * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (long long n = 0; n < N; ++n)
-            for (int k = 0; k < kc; ++k) {
-                const size_t to = (size_t)n * K + k0 + k, from = (size_t)n * kstride + k;
-                std::copy_n(e->chn_host_chain.data() + from * P, P, chain + to * P);
-                draws_unpack(e->chn_host_rec.data() + from * MARG_OUT, nG, to, logp, fullchi2, best);
-            }
-    }
-    e->chn_host_nacc.resize((size_t)N);
-    HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, st));
-    if (tm) {
-        e->tmp_host_nswap.resize((size_t)nlad * npair);
-        HIPCHK(hipMemcpyAsync(tm->sum_logp, e->tmp_sums, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(e->tmp_host_nswap.data(), e->tmp_nswap, (size_t)nlad * npair * sizeof(long long), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    for (long long n = 0; n < N; ++n) naccept[n] = e->chn_host_nacc[n];
-    if (tm)
-        for (long long q = 0; q < nlad * npair; ++q) tm->nswap[q] = e->tmp_host_nswap[q];
-    return 0;
+    if (int rc = draws_params_begin(e, who, C, N, c.maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
+    if (int rc = chain_buffers(c, CHAIN_STEPS, MARG_OUT, "the steps", "steps")) return rc;
+    const ChainRecords rec{logp, fullchi2, best};
+    auto launch = [&](int t0, int Tc, int kc) {
+        launch_two(draws_chain_params_kernel<false>, draws_chain_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, e->stream, ntr, nG, sh.J1, e->jeffreys, Tc,
+                   t0, thin, kc, c.kstride, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step,
+                   e->chn_lnu, e->chn_chain, e->chn_rec);
+        return 0;
+    };
+    if (int rc = chain_run(c, step, lnu, chain, &rec, c.K, launch)) return rc;
+    if (int rc = chain_fetch(c, last)) return rc;
+    return chain_end(c, naccept);
 }
 
 int eftb_draws_chain_params(eftb_engine* e, int C, long long N, int T, int thin, const int64_t* offsets, const double* theta0, const double* f,
@@ -4360,7 +4353,92 @@ int eftb_draws_chain_params_datasets(eftb_engine* e, int C, int G, const int32_t
 }
 
 // ------------------------------------------------------------------------------------------------ parallel tempering over the draw parameters
-// eftb_draws_temper_params and eftb_draws_temper_params_datasets: draws_chain_params_impl with the ladders' arguments
+// eftb_draws_temper_params and eftb_draws_temper_params_datasets: the chain call's checks, Gram cache and buffers around
+// draws_temper_params_kernel, one workgroup of R waves per ladder.  The swap counts and the sums of ln P persist beside theta and the accept
+// counts, and every launch takes its own events out of lnu_swap
+static int draws_temper_params_impl(eftb_engine* e, const char* who, int C, long long N, int R, int T, int S, long long first, int thin,
+                                    const int64_t* offsets, const double* theta0, const double* f, const double* beta, const double* step, const double* lnu,
+                                    const double* lnu_swap, const double* lower, const double* upper, const double* ploc, const double* pscale, double* chain,
+                                    double* logp, double* fullchi2, double* best, double* last, int64_t* naccept, int64_t* nswap, double* sum_logp,
+                                    const DrawGroups* gr = nullptr) {
+    ChainCall c{e, who, N, 0, T, thin};
+    if (int rc = chain_front(&c, C, gr ? "group" : "walker", gr ? gr->nwalk : -1, C, 1, offsets, theta0, f, step, lnu, lower, upper, ploc, pscale)) return rc;
+    const int ntr = e->ntr, nG = c.nG, P = c.P, npair = std::max(R - 1, 1);
+    if (R < 1 || R > TEMPER_MAXR) return fail("%s: R = %d rungs outside [1, %d]", who, R, TEMPER_MAXR);
+    for (int w = 0; w < C; ++w)
+        if ((offsets[w + 1] - offsets[w]) % R)
+            return fail("%s: %s %d owns %lld chains, not a multiple of R = %d rungs", who, gr ? "group" : "walker", w,
+                        (long long)(offsets[w + 1] - offsets[w]), R);
+    for (int r = 0; r < R; ++r) {
+        if (!(beta[r] >= 0.0 && beta[r] <= 1.0)) return fail("%s: beta[%d] = %g outside [0, 1]", who, r, beta[r]);
+        if (r && !(beta[r] < beta[r - 1]))
+            return fail("%s: beta[%d] = %g is not below beta[%d] = %g: rung %d must be hotter than rung %d", who, r, beta[r], r - 1, beta[r - 1], r, r - 1);
+    }
+    if (S < 0) return fail("%s: S = %d steps between swap events, at least 0 (no swaps)", who, S);
+    if (first < 0) return fail("%s: first_step = %lld, at least 0", who, first);
+    const long long nlad = N / R, nsw = S ? (first + T) / S - first / S : 0;  // the ladders of the call and the swap events in it
+    if (nsw > 0 && R > 1 && N > 0) {
+        if (!lnu_swap) return fail("%s: lnu_swap is NULL with %lld swap events in the call and R = %d rungs", who, nsw, R);
+        for (long long l = 0; l < nlad; ++l)
+            for (long long j = 0; j < nsw; ++j)
+                for (int r = (int)((first / S + j) & 1); r < R - 1; r += 2) {  // (the pairs event j tries: the others are not read)
+                    const double v = lnu_swap[(l * nsw + j) * (R - 1) + r];
+                    if (!(v <= 0.0))
+                        return fail("%s: lnu_swap[%lld][%lld][%d] = %g (ladder, event, rung) is not the logarithm of a uniform in [0, 1]", who, l, j, r, v);
+                }
+    }
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, DRAW_CHAIN, &e->recipe[0], &sh)) return rc;
+    // a workgroup of R waves and the exchange behind them, whatever the chain call would take
+    const size_t xch = TEMPER_XCH * sizeof(double);
+    int fit = 0;
+    while (fit < TEMPER_MAXR && sh.L.bytes(fit + 1) + xch <= 160 * 1024) ++fit;
+    if (R > fit)
+        return fail("%s: a ladder of R = %d rungs needs %d waves in one workgroup, but %d fit the LDS beside the Gram matrix of J + 1 = %d columns with "
+                    "nG = %d and P = %d parameters", who, R, R, fit, sh.J1, nG, P);
+    sh.nw = R;
+    sh.lds = sh.L.bytes(R) + xch;
+    if (N == 0) return 0;
+    DrawRun run;
+    if (int rc = draws_params_begin(e, who, C, N, c.maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
+    if (int rc = chain_buffers(c, CHAIN_STEPS, MARG_OUT, "the steps", "steps")) return rc;
+    hipStream_t st = e->stream;
+    auto events = [&](int t0, int Tc) { return S ? (int)((first + t0 + Tc) / S - (first + t0) / S) : 0; };  // the swap events of the launch at t0
+    int most = 0;
+    for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) most = std::max(most, events(t0, std::min(CHAIN_STEPS, T - t0)));
+    if (int rc = chain_grow(c, &e->tmp_beta, &e->tmp_beta_cap, TEMPER_MAXR, "beta")) return rc;
+    if (int rc = chain_grow(c, &e->tmp_lnus, &e->tmp_lnus_cap, (size_t)nlad * most * (R - 1), "lnu_swap")) return rc;
+    if (int rc = chain_grow(c, &e->tmp_sums, &e->tmp_sums_cap, (size_t)N, "the sums of ln P")) return rc;
+    if (int rc = chain_grow(c, &e->tmp_nswap, &e->tmp_nswap_cap, (size_t)nlad * npair, "the swap counts", sizeof(long long))) return rc;
+    HIPCHK(hipMemcpyAsync(e->tmp_beta, beta, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(e->tmp_sums, 0, (size_t)N * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(e->tmp_nswap, 0, (size_t)nlad * npair * sizeof(long long), st));
+    const ChainRecords rec{logp, fullchi2, best};
+    auto launch = [&](int t0, int Tc, int kc) {
+        // this launch's events of every ladder: step first + t0 is the launch's first, s0 steps remain to its first event, whose global
+        // number is g0 / S
+        const long long g0 = first + t0;
+        const int nswc = events(t0, Tc), s0 = S ? (int)(S - g0 % S) : 0, jpar = S ? (int)((g0 / S) & 1) : 0;
+        if (nswc && R > 1) {
+            const size_t row = (size_t)nswc * (R - 1) * sizeof(double);
+            HIPCHK(hipMemcpy2DAsync(e->tmp_lnus, row, lnu_swap + (size_t)(g0 / S - first / S) * (R - 1), (size_t)nsw * (R - 1) * sizeof(double), row,
+                                    (size_t)nlad, hipMemcpyHostToDevice, st));
+        }
+        launch_two(temper_kernel(false), temper_kernel(true), sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, R, Tc, t0, thin, kc,
+                   c.kstride, S, s0, jpar, nswc, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, e->tmp_nswap, e->tmp_sums, run.f, run.W, e->like_mu,
+                   e->like_sinv, e->chn_pri, e->tmp_beta, e->chn_step, e->chn_lnu, e->tmp_lnus, e->chn_chain, e->chn_rec);
+        return 0;
+    };
+    if (int rc = chain_run(c, step, lnu, chain, &rec, c.K, launch)) return rc;
+    e->tmp_host_nswap.resize((size_t)nlad * npair);
+    if (int rc = chain_fetch(c, last)) return rc;
+    HIPCHK(hipMemcpyAsync(sum_logp, e->tmp_sums, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(e->tmp_host_nswap.data(), e->tmp_nswap, (size_t)nlad * npair * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (int rc = chain_end(c, naccept)) return rc;
+    for (long long q = 0; q < nlad * npair; ++q) nswap[q] = e->tmp_host_nswap[q];
+    return 0;
+}
+
 int eftb_draws_temper_params(eftb_engine* e, int C, long long N, int R, int T, int S, long long first_step, int thin, const int64_t* offsets,
                              const double* theta0, const double* f, const double* beta, const double* step, const double* lnu, const double* lnu_swap,
                              const double* lower, const double* upper, const double* prior_loc, const double* prior_scale, double* chain, double* logp,
@@ -4369,9 +4447,8 @@ int eftb_draws_temper_params(eftb_engine* e, int C, long long N, int R, int T, i
     if (e) sub_drain(e);
     if (!e || !offsets || !f || !beta || (N > 0 && (!theta0 || !step || !lnu || !chain || !last || !naccept || !nswap || !sum_logp)))
         return fail("%s: null argument", who);
-    const TemperArgs tm{R, S, first_step, beta, lnu_swap, nswap, sum_logp};
-    return draws_chain_params_impl(e, who, C, N, T, thin, offsets, theta0, f, step, lnu, lower, upper, prior_loc, prior_scale, chain, logp, fullchi2, best,
-                                   last, naccept, nullptr, &tm);
+    return draws_temper_params_impl(e, who, C, N, R, T, S, first_step, thin, offsets, theta0, f, beta, step, lnu, lnu_swap, lower, upper, prior_loc,
+                                    prior_scale, chain, logp, fullchi2, best, last, naccept, nswap, sum_logp);
 }
 
 int eftb_draws_temper_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int R, int T, int S,
@@ -4386,9 +4463,8 @@ int eftb_draws_temper_params_datasets(eftb_engine* e, int C, int G, const int32_
         return fail("%s: null argument", who);
     DrawGroups gr{0, walker, dataset};
     if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
-    const TemperArgs tm{R, S, first_step, beta, lnu_swap, nswap, sum_logp};
-    return draws_chain_params_impl(e, who, G, N, T, thin, offsets, theta0, e->grp_f.data(), step, lnu, lower, upper, prior_loc, prior_scale, chain, logp,
-                                   fullchi2, best, last, naccept, &gr, &tm);
+    return draws_temper_params_impl(e, who, G, N, R, T, S, first_step, thin, offsets, theta0, e->grp_f.data(), beta, step, lnu, lnu_swap, lower, upper,
+                                    prior_loc, prior_scale, chain, logp, fullchi2, best, last, naccept, nswap, sum_logp, &gr);
 }
 
 // ------------------------------------------------------------------------------------------------ Hamiltonian Monte Carlo over the draw parameters
@@ -4400,14 +4476,11 @@ static int draws_hmc_params_impl(eftb_engine* e, const char* who, int C, long lo
                                  const double* f, const double* mom, const double* lnu, const double* eps, const double* factor, const double* lower,
                                  const double* upper, const double* ploc, const double* pscale, double* chain, double* logp, double* fullchi2, double* best,
                                  double* last, int64_t* naccept, double* log_ratio, const DrawGroups* gr = nullptr) {
-    long long maxcnt = 0;
-    if (int rc = draws_logp_check(e, who, C, N, offsets, &maxcnt, gr ? "group" : "walker", gr ? gr->nwalk : -1)) return rc;
-    const int ntr = e->ntr, nG = e->like_nG;
-    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
+    ChainCall c{e, who, N, 0, T, thin};
+    if (int rc = chain_front(&c, C, gr ? "group" : "walker", gr ? gr->nwalk : -1, C, 1, offsets, theta0, f, mom, lnu, lower, upper, ploc, pscale, "mom"))
+        return rc;
+    const int ntr = e->ntr, nG = c.nG, P = c.P;
     const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int P = rcp.P;
-    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
-    if (int rc = chain_args_check(who, P, N, T, thin, 1, theta0, mom, lnu, lower, upper, ploc, pscale, pri, "mom")) return rc;
     if (nleap < 1 || nleap > CHAIN_STEPS) return fail("%s: nleap = %d leapfrog steps outside [1, %d]", who, nleap, CHAIN_STEPS);
     for (long long q = 0; q < N * T; ++q)
         if (!(std::isfinite(eps[q]) && eps[q] > 0.0)) return fail("%s: eps[%lld][%lld] = %g is not a finite step size > 0", who, q / T, q % T, eps[q]);
@@ -4425,27 +4498,17 @@ static int draws_hmc_params_impl(eftb_engine* e, const char* who, int C, long lo
         return fail("%s: the trajectories of P = %d parameters with nG = %d and J + 1 = %d columns do not fit the LDS (%zu bytes per workgroup and %zu per wave "
                     "of %d)", who, P, nG, sh.J1, sh.L.bytes_wg(), sh.L.bytes_wave(), 160 * 1024);
     if (N == 0) return 0;
-    const int Tl = std::max(1, CHAIN_STEPS / nleap);  // trajectories per launch
-    const int K = T / thin, kstride = std::max(1, std::min(K, Tl / thin + 1)), Tmax = std::min(T, Tl);
     DrawRun run;
-    if (int rc = draws_params_begin(e, who, C, N, maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
+    if (int rc = draws_params_begin(e, who, C, N, c.maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
     if (!e->hmc_lds) {  // the large dynamic LDS for this call's kernel, once per engine (as draws_lds_optin for the others)
         for (const void* k : {reinterpret_cast<const void*>(&draws_hmc_params_kernel<false>), reinterpret_cast<const void*>(&draws_hmc_params_kernel<true>)})
             HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         e->hmc_lds = true;
     }
-    char shape[112];
-    snprintf(shape, sizeof shape, "N = %lld chains x T = %d trajectories with P = %d parameters", N, T, P);
-    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(e, pp, cap, n, elem, who, what, shape); };
-    if (int rc = grow(&e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, "the momenta")) return rc;
-    if (int rc = grow(&e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, "lnu")) return rc;
-    if (int rc = grow(&e->hmc_eps, &e->hmc_eps_cap, (size_t)N * Tmax, "eps")) return rc;
-    if (int rc = grow(&e->hmc_ratio, &e->hmc_ratio_cap, (size_t)N * Tmax, "the ratios")) return rc;
-    if (int rc = grow(&e->hmc_fac, &e->hmc_fac_cap, (size_t)N * P * P, "the factors")) return rc;
-    if (int rc = grow(&e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
-    if (int rc = grow(&e->chn_nacc, &e->chn_nacc_cap, (size_t)N, "the accept counts", sizeof(long long))) return rc;
-    if (int rc = grow(&e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, "the stored states")) return rc;
-    if (int rc = grow(&e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * MARG_OUT, "the stored records")) return rc;
+    if (int rc = chain_buffers(c, std::max(1, CHAIN_STEPS / nleap), MARG_OUT, "the momenta", "trajectories")) return rc;
+    if (int rc = chain_grow(c, &e->hmc_eps, &e->hmc_eps_cap, (size_t)N * c.Tmax, "eps")) return rc;
+    if (int rc = chain_grow(c, &e->hmc_ratio, &e->hmc_ratio_cap, (size_t)N * c.Tmax, "the ratios")) return rc;
+    if (int rc = chain_grow(c, &e->hmc_fac, &e->hmc_fac_cap, (size_t)N * P * P, "the factors")) return rc;
     RecipeGradTab gt{};
     gt.dcoef = rcp.dcoef;
     gt.pstart = rcp.dtab;
@@ -4460,46 +4523,29 @@ static int draws_hmc_params_impl(eftb_engine* e, const char* who, int C, long lo
         for (int p = 0; p < P; ++p)
             for (int q = 0; q <= p; ++q) e->hmc_host_fac[((size_t)n * P + p) * P + q] = factor ? factor[((size_t)n * P + p) * P + q] : (q == p ? 1.0 : 0.0);
     HIPCHK(hipMemcpyAsync(e->hmc_fac, e->hmc_host_fac.data(), (size_t)N * P * P * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
-    e->chn_host_chain.resize((size_t)N * kstride * P);
-    e->chn_host_rec.resize((size_t)N * kstride * MARG_OUT);
-    e->hmc_host_ratio.resize((size_t)N * Tmax);
-    for (int t0 = 0; t0 < T; t0 += Tl) {
-        const int Tc = std::min(Tl, T - t0), k0 = t0 / thin, kc = (t0 + Tc) / thin - k0;
-        // this launch's trajectories of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
-        HIPCHK(hipMemcpy2DAsync(e->chn_step, (size_t)Tc * P * sizeof(double), mom + (size_t)t0 * P, (size_t)T * P * sizeof(double), (size_t)Tc * P * sizeof(double),
-                                (size_t)N, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
-                                hipMemcpyHostToDevice, st));
+    e->hmc_host_ratio.resize((size_t)N * c.Tmax);
+    const ChainRecords rec{logp, fullchi2, best};
+    auto launch = [&](int t0, int Tc, int kc) {
         HIPCHK(hipMemcpy2DAsync(e->hmc_eps, (size_t)Tc * sizeof(double), eps + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
                                 hipMemcpyHostToDevice, st));
         launch_two(draws_hmc_params_kernel<false>, draws_hmc_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin, kc,
-                   kstride, nleap, run.rt, gt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu,
+                   c.kstride, nleap, run.rt, gt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->chn_lnu,
                    e->hmc_eps, e->hmc_fac, e->chn_chain, e->chn_rec, e->hmc_ratio);
-        if (int rc = launched(who)) return rc;
-        if (!kc && !log_ratio) continue;
-        if (kc) {
-            HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, (size_t)N * kstride * MARG_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        if (log_ratio) HIPCHK(hipMemcpyAsync(e->hmc_host_ratio.data(), e->hmc_ratio, (size_t)N * Tc * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (long long n = 0; n < N; ++n) {
-            for (int k = 0; k < kc; ++k) {
-                const size_t to = (size_t)n * K + k0 + k, from = (size_t)n * kstride + k;
-                std::copy_n(e->chn_host_chain.data() + from * P, P, chain + to * P);
-                draws_unpack(e->chn_host_rec.data() + from * MARG_OUT, nG, to, logp, fullchi2, best);
+        return 0;
+    };
+    ChainMore ratios;  // with log_ratio every launch is waited for: the ratios of one that stores no state come back too
+    if (log_ratio)
+        ratios = [&](int t0, int Tc, bool landed) {
+            if (!landed) {
+                HIPCHK(hipMemcpyAsync(e->hmc_host_ratio.data(), e->hmc_ratio, (size_t)N * Tc * sizeof(double), hipMemcpyDeviceToHost, st));
+                return 0;
             }
-            if (log_ratio) std::copy_n(e->hmc_host_ratio.data() + (size_t)n * Tc, Tc, log_ratio + (size_t)n * T + t0);
-        }
-    }
-    e->chn_host_nacc.resize((size_t)N);
-    HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (long long n = 0; n < N; ++n) naccept[n] = e->chn_host_nacc[n];
-    return 0;
+            for (long long n = 0; n < N; ++n) std::copy_n(e->hmc_host_ratio.data() + (size_t)n * Tc, Tc, log_ratio + (size_t)n * T + t0);
+            return 0;
+        };
+    if (int rc = chain_run(c, mom, lnu, chain, &rec, c.K, launch, ratios)) return rc;
+    if (int rc = chain_fetch(c, last)) return rc;
+    return chain_end(c, naccept);
 }
 
 int eftb_draws_hmc_params(eftb_engine* e, int C, long long N, int T, int nleap, int thin, const int64_t* offsets, const double* theta0, const double* f,
@@ -4542,14 +4588,9 @@ int eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, 
     if (!e || !wstart || !wend || !offsets || !f || !frac || (N > 0 && (!theta0 || !step || !lnu || !last || !naccept || !sums)))
         return fail("%s: null argument", who);
     if (C < 1) return fail("%s: %d walkers", who, C);
-    long long maxcnt = 0;
-    if (int rc = draws_logp_check(e, who, G, N, offsets, &maxcnt, "pair", C)) return rc;
-    const int ntr = e->ntr, nG = e->like_nG;
-    if (int rc = draws_params_check(e, who, 0, nG + 1, C, N, theta0, f)) return rc;
-    const eftb_engine::Recipe& rcp = e->recipe[0];
-    const int P = rcp.P;
-    double pri[CHAIN_PRI];  // lower | upper | loc | sinv
-    if (int rc = chain_args_check(who, P, N, T, thin, 0, theta0, step, lnu, lower, upper, prior_loc, prior_scale, pri)) return rc;
+    ChainCall c{e, who, N, 0, T, thin};
+    if (int rc = chain_front(&c, G, "pair", C, C, 0, offsets, theta0, f, step, lnu, lower, upper, prior_loc, prior_scale)) return rc;
+    const int ntr = e->ntr, nG = c.nG, P = c.P;
     if (thin > 0 && N > 0 && !chain) return fail("%s: null argument (chain, with thin = %d)", who, thin);
     for (int g = 0; g < G; ++g) {
         if (wstart[g] < 0 || wstart[g] >= C) return fail("%s: wstart[%d] = %d outside [0, %d): the start walker of pair %d", who, g, wstart[g], C, g);
@@ -4558,12 +4599,11 @@ int eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, 
     for (int t = 0; t < T; ++t)
         if (!(frac[t] >= 0.0 && frac[t] <= 1.0)) return fail("%s: frac[%d] = %g outside [0, 1]", who, t, frac[t]);
     DrawShape sh;
-    if (int rc = draws_logp_shape(e, who, DRAW_DRAG, &rcp, &sh)) return rc;
+    if (int rc = draws_logp_shape(e, who, DRAW_DRAG, &e->recipe[0], &sh)) return rc;
     if (!sh.nw)
         return fail("%s: the call stages two Gram matrices of J + 1 = %d columns per workgroup; with nG = %d they do not fit the LDS beside one wave (%zu bytes per "
                     "workgroup and %zu per wave of %d)", who, sh.J1, nG, sh.L.bytes_wg(), sh.L.bytes_wave(), 160 * 1024);
     if (N == 0) return 0;
-    const int K = thin ? T / thin : 0, kstride = thin ? std::max(1, std::min(K, CHAIN_STEPS / thin + 1)) : 1, Tmax = std::min(T, CHAIN_STEPS);
     constexpr int PAIR = 2 * MARG_OUT;
     if (int rc = draws_logp_begin(e, who, G, N, sh.J1, offsets, C)) return rc;
     if (!e->drg_lds) {  // the large dynamic LDS for this call's kernel, once per engine (as draws_lds_optin for the others)
@@ -4573,66 +4613,34 @@ int eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, 
     }
     const double *dtheta = nullptr, *df = nullptr;
     if (int rc = draws_params_upload(e, P, C, N, theta0, f, &dtheta, &df)) return rc;
-    const dim3 grid(G, draw_shares(maxcnt, sh.nw, G)), block(64 * sh.nw);
-    const RecipeTab rt = recipe_tab(rcp);
-    char shape[96];
-    snprintf(shape, sizeof shape, "N = %lld chains x T = %d steps with P = %d parameters", N, T, P);
-    auto grow = [&](auto* pp, size_t* cap, size_t n, const char* what, size_t elem = sizeof(double)) { return grow_dev(e, pp, cap, n, elem, who, what, shape); };
-    if (int rc = grow(&e->chn_step, &e->chn_step_cap, (size_t)N * Tmax * P, "the steps")) return rc;
-    if (int rc = grow(&e->chn_lnu, &e->chn_lnu_cap, (size_t)N * Tmax, "lnu")) return rc;
-    if (int rc = grow(&e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
-    if (int rc = grow(&e->chn_nacc, &e->chn_nacc_cap, (size_t)N, "the accept counts", sizeof(long long))) return rc;
-    if (int rc = grow(&e->chn_chain, &e->chn_chain_cap, (size_t)N * kstride * P, "the stored states")) return rc;
-    if (int rc = grow(&e->chn_rec, &e->chn_rec_cap, (size_t)N * kstride * PAIR, "the stored records")) return rc;
-    if (int rc = grow(&e->drg_pair, &e->drg_pair_cap, 2 * (size_t)G, "the pairs", sizeof(int))) return rc;
-    if (int rc = grow(&e->drg_frac, &e->drg_frac_cap, (size_t)T, "frac")) return rc;
-    if (int rc = grow(&e->drg_sums, &e->drg_sums_cap, 2 * (size_t)N, "the sums")) return rc;
-    if (int rc = grow(&e->drg_fin, &e->drg_fin_cap, (size_t)N * PAIR, "the final records")) return rc;
+    const dim3 grid(G, draw_shares(c.maxcnt, sh.nw, G)), block(64 * sh.nw);
+    const RecipeTab rt = recipe_tab(e->recipe[0]);
+    if (int rc = chain_buffers(c, CHAIN_STEPS, PAIR, "the steps", "steps")) return rc;
+    if (int rc = chain_grow(c, &e->drg_pair, &e->drg_pair_cap, 2 * (size_t)G, "the pairs", sizeof(int))) return rc;
+    if (int rc = chain_grow(c, &e->drg_frac, &e->drg_frac_cap, (size_t)T, "frac")) return rc;
+    if (int rc = chain_grow(c, &e->drg_sums, &e->drg_sums_cap, 2 * (size_t)N, "the sums")) return rc;
+    if (int rc = chain_grow(c, &e->drg_fin, &e->drg_fin_cap, (size_t)N * PAIR, "the final records")) return rc;
     hipStream_t st = e->stream;
     e->drg_host_pair.assign(wstart, wstart + G);
     e->drg_host_pair.insert(e->drg_host_pair.end(), wend, wend + G);
     HIPCHK(hipMemcpyAsync(e->drg_pair, e->drg_host_pair.data(), 2 * (size_t)G * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(e->drg_frac, frac, (size_t)T * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->chn_pri, pri, sizeof(pri), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(e->chn_nacc, 0, (size_t)N * sizeof(long long), st));
-    e->chn_host_chain.resize((size_t)N * kstride * P);
-    e->chn_host_rec.resize((size_t)N * kstride * PAIR);
-    for (int t0 = 0; t0 < T; t0 += CHAIN_STEPS) {
-        const int Tc = std::min(CHAIN_STEPS, T - t0), k0 = thin ? t0 / thin : 0, kc = thin ? (t0 + Tc) / thin - k0 : 0;
-        // this launch's steps of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
-        HIPCHK(hipMemcpy2DAsync(e->chn_step, (size_t)Tc * P * sizeof(double), step + (size_t)t0 * P, (size_t)T * P * sizeof(double), (size_t)Tc * P * sizeof(double),
-                                (size_t)N, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpy2DAsync(e->chn_lnu, (size_t)Tc * sizeof(double), lnu + t0, (size_t)T * sizeof(double), (size_t)Tc * sizeof(double), (size_t)N,
-                                hipMemcpyHostToDevice, st));
-        launch_two(draws_drag_params_kernel<false>, draws_drag_params_kernel<true>, sh.J1, grid, block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin, kc, kstride, rt,
-                   e->drw_off, e->drg_pair, e->drg_pair + G, e->drw_theta, e->chn_nacc, e->drg_sums, df, e->drw_W, e->like_mu, e->like_sinv, e->chn_pri, e->drg_frac,
-                   e->chn_step, e->chn_lnu, e->chn_chain, e->chn_rec, e->drg_fin);
-        if (int rc = launched(who)) return rc;
-        if (!kc) continue;
-        HIPCHK(hipMemcpyAsync(e->chn_host_chain.data(), e->chn_chain, (size_t)N * kstride * P * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(e->chn_host_rec.data(), e->chn_rec, (size_t)N * kstride * PAIR * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (long long n = 0; n < N; ++n)
-            for (int k = 0; k < kc; ++k) {
-                const size_t to = (size_t)n * (K + 1) + k0 + k, from = (size_t)n * kstride + k;
-                std::copy_n(e->chn_host_chain.data() + from * P, P, chain + ((size_t)n * K + k0 + k) * P);
-                draws_unpack(e->chn_host_rec.data() + from * PAIR, nG, to, logp_start, fullchi2_start, best_start);
-                draws_unpack(e->chn_host_rec.data() + from * PAIR + MARG_OUT, nG, to, logp_end, fullchi2_end, best_end);
-            }
-    }
-    e->chn_host_nacc.resize((size_t)N);
+    const ChainRecords rec[2] = {{logp_start, fullchi2_start, best_start}, {logp_end, fullchi2_end, best_end}};
+    auto launch = [&](int t0, int Tc, int kc) {
+        launch_two(draws_drag_params_kernel<false>, draws_drag_params_kernel<true>, sh.J1, grid, block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, Tc, t0, thin, kc,
+                   c.kstride, rt, e->drw_off, e->drg_pair, e->drg_pair + G, e->drw_theta, e->chn_nacc, e->drg_sums, df, e->drw_W, e->like_mu, e->like_sinv, e->chn_pri,
+                   e->drg_frac, e->chn_step, e->chn_lnu, e->chn_chain, e->chn_rec, e->drg_fin);
+        return 0;
+    };
+    if (int rc = chain_run(c, step, lnu, chain, rec, c.K + 1, launch)) return rc;
     e->drg_host_fin.resize((size_t)N * PAIR);
-    HIPCHK(hipMemcpyAsync(last, e->drw_theta, (size_t)N * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = chain_fetch(c, last)) return rc;
     HIPCHK(hipMemcpyAsync(sums, e->drg_sums, 2 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(e->chn_host_nacc.data(), e->chn_nacc, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(e->drg_host_fin.data(), e->drg_fin, (size_t)N * PAIR * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (long long n = 0; n < N; ++n) {
-        naccept[n] = e->chn_host_nacc[n];
-        const size_t to = (size_t)n * (K + 1) + K;
-        draws_unpack(e->drg_host_fin.data() + (size_t)n * PAIR, nG, to, logp_start, fullchi2_start, best_start);
-        draws_unpack(e->drg_host_fin.data() + (size_t)n * PAIR + MARG_OUT, nG, to, logp_end, fullchi2_end, best_end);
-    }
+    if (int rc = chain_end(c, naccept)) return rc;
+    for (long long n = 0; n < N; ++n)  // the records of the state after step T: the last slot
+        for (int r = 0; r < 2; ++r)
+            draws_unpack(e->drg_host_fin.data() + (size_t)n * PAIR + r * MARG_OUT, nG, (size_t)n * (c.K + 1) + c.K, rec[r].logp, rec[r].fullchi2, rec[r].best);
     return 0;
 }
 

@@ -375,12 +375,9 @@ class MarginalLikelihood:
 
     def _chains_raw(self, theta0, offsets, f, step, lnu, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None, groups=None, return_best=False):
         """``metropolis_draws_params`` without the RuntimeError: a chain that failed at its start has NaN states and naccept = -1"""
-        nG = self.nG
         theta0, off, f, wk, ds, step, lnu, thin, pri = self._chain_args(theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, groups)
-        (N, T, P), K = step.shape, step.shape[1] // thin
-        theta, logp, last, nacc = np.empty((N, K, P)), np.empty((N, K)), np.empty((N, P)), np.empty(N, dtype=np.int64)
-        full = np.empty((N, K)) if return_best else None
-        best = np.empty((N, K, nG)) if return_best else None
+        N, T, P = step.shape
+        theta, logp, last, nacc, full, best = self._chain_out(N, T // thin, P, return_best)
         i64p = C.POINTER(C.c_int64)
         tail = (off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(step), L.dptr(lnu)) + tuple(L.dptr(a) for a in pri) + (
             L.dptr(theta), L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(last), nacc.ctypes.data_as(i64p))
@@ -392,37 +389,48 @@ class MarginalLikelihood:
             L.check(self.eng.lib.eftb_draws_chain_params(self.eng._h, off.size - 1, N, T, thin, *tail))
         return DrawChains(theta, logp, nacc, last, full, best)
 
-    def _chain_args(self, theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, groups):
-        """the arguments of ``metropolis_draws_params`` (and of ``temper_draws_params``, which shares them) as the library takes them, shape errors
-        raised here -> theta0, off, f, walker, dataset (None without groups), step, lnu, thin, [lower, upper, prior_loc, prior_scale]"""
+    def _chain_args(self, theta0, offsets, f, moves, lnu, thin, lower, upper, prior_loc, prior_scale, groups, name="step", kind="proposal increments",
+                    unit="steps", per="step", thin_min=1, pair_words=()):
+        """the arguments the four sampler calls share as the library takes them, shape errors raised here -> theta0, off, f, walker, dataset (None
+        without groups), moves, lnu, thin, [lower, upper, prior_loc, prior_scale].  The caller words its moves [N, T, P] (``name``, what ``kind`` of
+        numbers they are, the ``unit`` T counts and the one lnu holds a uniform ``per``), says how small thin may be and, with ``pair_words``, that
+        ``groups`` are the pairs of ``drag_draws_params`` in the wording of ``_groups_args``"""
         from .engine import _params_args
 
         ntr = self.eng.ntracers
         rec = getattr(self, "_recipe", None)
         wk = ds = None
-        if groups is not None:
-            theta0, off, f, wk, ds = _groups_args(rec, theta0, offsets, f, ntr, groups)
+        if groups is not None or pair_words:
+            theta0, off, f, wk, ds = _groups_args(rec, theta0, offsets, f, ntr, groups, *pair_words)
         else:
             theta0, off, f = _params_args(rec, theta0, offsets, f, ntr)
         N, P = theta0.shape
-        step = np.ascontiguousarray(step, dtype=np.float64)
-        if step.ndim != 3 or step.shape[0] != N or step.shape[2] != P or step.shape[1] < 1:
-            raise ValueError(f"step must be [{N}, T, {P}] proposal increments with T >= 1 steps")
-        T = step.shape[1]
+        moves = np.ascontiguousarray(moves, dtype=np.float64)
+        if moves.ndim != 3 or moves.shape[0] != N or moves.shape[2] != P or moves.shape[1] < 1:
+            raise ValueError(f"{name} must be [{N}, T, {P}] {kind} with T >= 1 {unit}")
+        T = moves.shape[1]
         lnu = np.ascontiguousarray(lnu, dtype=np.float64)
         if lnu.shape != (N, T):
-            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and step")
-        if thin != int(thin) or not 1 <= thin <= T:
-            raise ValueError(f"thin must be an integer in [1, T = {T}]")
+            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and {per}")
+        if thin != int(thin) or not thin_min <= thin <= T:
+            raise ValueError(f"thin must be an integer in [{thin_min}, T = {T}]")
         thin = int(thin)
         pri = []
-        for name, a in (("lower", lower), ("upper", upper), ("prior_loc", prior_loc), ("prior_scale", prior_scale)):
+        for key, a in (("lower", lower), ("upper", upper), ("prior_loc", prior_loc), ("prior_scale", prior_scale)):
             if a is not None:
                 a = np.ascontiguousarray(a, dtype=np.float64)
                 if a.shape != (P,):
-                    raise ValueError(f"{name} must be [{P}], one value per parameter")
+                    raise ValueError(f"{key} must be [{P}], one value per parameter")
             pri.append(a)
-        return theta0, off, f, wk, ds, step, lnu, thin, pri
+        return theta0, off, f, wk, ds, moves, lnu, thin, pri
+
+    def _chain_out(self, N, K, P, return_best, slots=None):
+        """the arrays a sampler call fills -> theta [N, K, P], logp [N, slots], last [N, P], naccept [N], and with ``return_best`` fullchi2
+        [N, slots] and best [N, slots, nG], else None; slots = K unless the call keeps more records than states"""
+        slots = K if slots is None else slots
+        full = np.empty((N, slots)) if return_best else None
+        best = np.empty((N, slots, self.nG)) if return_best else None
+        return np.empty((N, K, P)), np.empty((N, slots)), np.empty((N, P)), np.empty(N, dtype=np.int64), full, best
 
     def temper_draws_params(self, theta0, offsets, f, beta, step, lnu, lnu_swap=None, swap_every=0, first_step=0, thin=1, lower=None, upper=None,
                             prior_loc=None, prior_scale=None, groups=None, return_best=False):
@@ -451,9 +459,8 @@ class MarginalLikelihood:
     def _temper_raw(self, theta0, offsets, f, beta, step, lnu, lnu_swap=None, swap_every=0, first_step=0, thin=1, lower=None, upper=None, prior_loc=None,
                     prior_scale=None, groups=None, return_best=False):
         """``temper_draws_params`` without the RuntimeError: a ladder that failed at its start has NaN states and naccept = nswap = -1"""
-        nG = self.nG
         theta0, off, f, wk, ds, step, lnu, thin, pri = self._chain_args(theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, groups)
-        (N, T, P), K = step.shape, step.shape[1] // thin
+        N, T, P = step.shape
         beta = np.asarray(beta, dtype=np.float64)
         if beta.ndim != 1 or beta.size < 1:
             raise ValueError("beta must be [R]: the inverse temperatures of the rungs, R >= 1")
@@ -472,9 +479,7 @@ class MarginalLikelihood:
                 raise ValueError(f"lnu_swap must be [{nlad}, {nsw}, {R - 1}]: the logarithm of a uniform per ladder, swap event and adjacent pair")
         elif nsw and R > 1 and nlad:
             raise ValueError(f"lnu_swap must be [{nlad}, {nsw}, {R - 1}]: the call holds {nsw} swap events")
-        theta, logp, last, nacc = np.empty((N, K, P)), np.empty((N, K)), np.empty((N, P)), np.empty(N, dtype=np.int64)
-        full = np.empty((N, K)) if return_best else None
-        best = np.empty((N, K, nG)) if return_best else None
+        theta, logp, last, nacc, full, best = self._chain_out(N, T // thin, P, return_best)
         nswap, sums = np.empty((nlad, max(R - 1, 1)), dtype=np.int64), np.empty(N)
         i64p = C.POINTER(C.c_int64)
         head = (N, R, T, S, first, thin, off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(beta), L.dptr(step), L.dptr(lnu), L.dptr(lnu_swap))
@@ -511,23 +516,9 @@ class MarginalLikelihood:
     def _hmc_raw(self, theta0, offsets, f, momentum, lnu, eps, nleap, factor=None, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None,
                  groups=None, return_best=False, return_ratio=False):
         """``hmc_draws_params`` without the RuntimeError: a chain that failed at its start has NaN states and ratios and naccept = -1"""
-        from .engine import _params_args
-
-        ntr, nG = self.eng.ntracers, self.nG
-        rec = getattr(self, "_recipe", None)
-        wk = ds = None
-        if groups is not None:
-            theta0, off, f, wk, ds = _groups_args(rec, theta0, offsets, f, ntr, groups)
-        else:
-            theta0, off, f = _params_args(rec, theta0, offsets, f, ntr)
-        N, P = theta0.shape
-        mom = np.ascontiguousarray(momentum, dtype=np.float64)
-        if mom.ndim != 3 or mom.shape[0] != N or mom.shape[2] != P or mom.shape[1] < 1:
-            raise ValueError(f"momentum must be [{N}, T, {P}] standard normals with T >= 1 trajectories")
-        T = mom.shape[1]
-        lnu = np.ascontiguousarray(lnu, dtype=np.float64)
-        if lnu.shape != (N, T):
-            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and trajectory")
+        theta0, off, f, wk, ds, mom, lnu, thin, pri = self._chain_args(theta0, offsets, f, momentum, lnu, thin, lower, upper, prior_loc, prior_scale, groups,
+                                                                       "momentum", "standard normals", "trajectories", "trajectory")
+        N, T, P = mom.shape
         eps = np.asarray(eps, dtype=np.float64)
         if eps.shape not in ((), (N,), (N, T)):
             raise ValueError(f"eps must be a scalar, [{N}] or [{N}, {T}]: the leapfrog step size")
@@ -540,20 +531,7 @@ class MarginalLikelihood:
             if factor.shape not in ((P, P), (N, P, P)):
                 raise ValueError(f"factor must be [{P}, {P}] or [{N}, {P}, {P}]: a lower-triangular F with M^-1 = F F^T")
             factor = np.ascontiguousarray(np.broadcast_to(factor, (N, P, P)))
-        if thin != int(thin) or not 1 <= thin <= T:
-            raise ValueError(f"thin must be an integer in [1, T = {T}]")
-        thin = int(thin)
-        pri = []
-        for name, a in (("lower", lower), ("upper", upper), ("prior_loc", prior_loc), ("prior_scale", prior_scale)):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (P,):
-                    raise ValueError(f"{name} must be [{P}], one value per parameter")
-            pri.append(a)
-        K = T // thin
-        theta, logp, last, nacc = np.empty((N, K, P)), np.empty((N, K)), np.empty((N, P)), np.empty(N, dtype=np.int64)
-        full = np.empty((N, K)) if return_best else None
-        best = np.empty((N, K, nG)) if return_best else None
+        theta, logp, last, nacc, full, best = self._chain_out(N, T // thin, P, return_best)
         ratio = np.empty((N, T)) if return_ratio else None
         i64p = C.POINTER(C.c_int64)
         tail = (off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(mom), L.dptr(lnu), L.dptr(eps), L.dptr(factor)) + tuple(L.dptr(a) for a in pri) + (
@@ -590,34 +568,16 @@ class MarginalLikelihood:
 
     def _drag_raw(self, theta0, offsets, f, pairs, step, lnu, frac=None, thin=0, lower=None, upper=None, prior_loc=None, prior_scale=None, return_best=False):
         """``drag_draws_params`` without the RuntimeError: a chain that failed at its start has NaN states, records and sums and naccept = -1"""
-        ntr, nG = self.eng.ntracers, self.nG
-        theta0, off, f, wa, wb = _groups_args(getattr(self, "_recipe", None), theta0, offsets, f, ntr, pairs, "pairs must be (start [G], end [G])", "pair")
-        N, P = theta0.shape
-        step = np.ascontiguousarray(step, dtype=np.float64)
-        if step.ndim != 3 or step.shape[0] != N or step.shape[2] != P or step.shape[1] < 1:
-            raise ValueError(f"step must be [{N}, T, {P}] proposal increments with T >= 1 steps")
-        T = step.shape[1]
-        lnu = np.ascontiguousarray(lnu, dtype=np.float64)
-        if lnu.shape != (N, T):
-            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and step")
+        theta0, off, f, wa, wb, step, lnu, thin, pri = self._chain_args(theta0, offsets, f, step, lnu, thin, lower, upper, prior_loc, prior_scale, pairs,
+                                                                        thin_min=0, pair_words=("pairs must be (start [G], end [G])", "pair"))
+        N, T, P = step.shape
         frac = drag_fractions(T) if frac is None else np.ascontiguousarray(frac, dtype=np.float64)
         if frac.shape != (T,):
             raise ValueError(f"frac must be [{T}]: the weight of the end point at every step")
-        if thin != int(thin) or not 0 <= thin <= T:
-            raise ValueError(f"thin must be an integer in [0, T = {T}]")
-        thin = int(thin)
-        pri = []
-        for name, a in (("lower", lower), ("upper", upper), ("prior_loc", prior_loc), ("prior_scale", prior_scale)):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (P,):
-                    raise ValueError(f"{name} must be [{P}], one value per parameter")
-            pri.append(a)
         K = T // thin if thin else 0
-        theta, last, nacc, sums = np.empty((N, K, P)), np.empty((N, P)), np.empty(N, dtype=np.int64), np.empty((N, 2))
-        la, lb = np.empty((N, K + 1)), np.empty((N, K + 1))
-        fa, fb = (np.empty((N, K + 1)), np.empty((N, K + 1))) if return_best else (None, None)
-        ba, bb = (np.empty((N, K + 1, nG)), np.empty((N, K + 1, nG))) if return_best else (None, None)
+        theta, la, last, nacc, fa, ba = self._chain_out(N, K, P, return_best, slots=K + 1)  # (the record of the state after step T in the last slot)
+        lb, fb, bb = (None if a is None else np.empty_like(a) for a in (la, fa, ba))
+        sums = np.empty((N, 2))
         i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
         L.check(self.eng.lib.eftb_draws_drag_params(self.eng._h, f.shape[0], wa.size, wa.ctypes.data_as(i32p), wb.ctypes.data_as(i32p), N, T, thin,
                                                     off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(frac), L.dptr(step), L.dptr(lnu),

@@ -143,6 +143,17 @@ def test_long_chain_crosses_the_launch_boundary(golden):
     eng.close()
 
 
+def test_a_launch_that_stores_nothing_before_one_that_does(golden):
+    """T = 300, thin = 299: the launch of steps 1 ... 256 stores no state and brings nothing back, the second stores the one state there is.
+    The state, its record, `last` and the accept counts are the host loop's."""
+    case, inp = long_inputs()
+    eng = _engine(golden, "auto", case)
+    like = _like(eng, case, 0)
+    got, _ = _compare(like, _offsets([3, 0, 0, 0]), case["f"], inp, 299)
+    assert got.theta.shape == (3, 1, inp["theta0"].shape[1]) and np.all(got.naccept > 0)
+    eng.close()
+
+
 def test_split_batches_and_theta_priors(golden):
     case = chain_case("auto")
     eng = _engine(golden, "auto", case)

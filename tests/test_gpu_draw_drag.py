@@ -224,6 +224,20 @@ def test_long_drag_crosses_the_launch_boundary(golden):
     eng.close()
 
 
+def test_a_launch_that_stores_nothing_before_one_that_does(golden):
+    """T = 300, thin = 299: the launch of steps 1 ... 256 stores no state and brings nothing back, the second stores the one state there is.
+    The record arrays have K + 1 = 2 slots: the stored one and, from the copy at the end of the call, the one after step T.  All of it,
+    `last`, the accept counts and the sums are the host loop's."""
+    _, inp = long_inputs()  # the first 3 chains of auto, walker 0
+    case = DU.drag_case("auto")
+    C = len(case["Ws"])
+    eng = _engine(golden, "auto", case)
+    like = _like(eng, case, 0)
+    got, _ = _compare(like, case["f"], ([0, 0], [C // 2, 0]), [2, 1], inp, 299)
+    assert got.theta.shape[:2] == (3, 1) and got.logp_end.shape == (3, 1) and got.last_logp_end.shape == (3,) and np.all(got.naccept > 0)
+    eng.close()
+
+
 def test_chains_do_not_depend_on_the_batch(golden):
     """the batch split over two calls with other offsets and the pairs in another order: the same bits per chain"""
     case = DU.drag_case("full")

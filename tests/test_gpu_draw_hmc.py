@@ -150,6 +150,30 @@ def test_launch_boundaries(golden):
     eng.close()
 
 
+def test_launches_that_store_nothing_before_one_that_does(golden):
+    """nleap = 128, T = 5, thin = 5: two trajectories per launch, so three launches, of which the first two store no state.  With
+    return_ratio they still bring their ratios back, all five of every chain; without it they bring nothing back.  The chain is the host
+    loop's and the same in both runs.  The step sizes are those of the nleap = 4 runs over 32: trajectories of the same length."""
+    hc = hmc_case("auto", 70, 6)
+    case = hc["case"]
+    eng = _engine(golden, "auto", case)
+    like = _like(eng, case, 0)
+    sel = slice(0, 3)
+    inp, off, f = _inputs(hc, sel), _offsets([3, 0, 0, 0]), case["f"]
+    inp = dict(inp, mom=np.ascontiguousarray(inp["mom"][:, :5]), lnu=np.ascontiguousarray(inp["lnu"][:, :5]))
+    name, F, eps = hc["variants"][1]
+    F, eps = F[sel], eps[sel, :5] / 32.0
+    got, want = _compare(like, off, f, inp, eps, 128, F, 5)
+    print("nleap = 128: naccept", got.naccept, "aborted", want["aborted"], "log_ratio", got.log_ratio)
+    assert got.theta.shape[1] == 1 and got.log_ratio.shape == (3, 5) and np.any(got.naccept > 0) and np.any(np.isfinite(got.log_ratio[:, :4]))
+    opt = {k: inp[k] for k in ("lower", "upper", "prior_loc", "prior_scale")}
+    lean = like.hmc_draws_params(inp["theta0"], off, f, inp["mom"], inp["lnu"], eps, 128, factor=F, thin=5, return_best=True, **opt)
+    assert lean.log_ratio is None
+    for name in FIELDS[:-1]:
+        assert np.array_equal(getattr(lean, name), getattr(got, name)), name
+    eng.close()
+
+
 def test_split_batches(golden):
     """a batch split over two calls with other offsets: the same bits per chain; no chains at all; eps as a scalar and per chain"""
     hc = hmc_case("auto")

@@ -137,6 +137,17 @@ def test_long_ladder_crosses_the_launch_boundary(golden):
     eng.close()
 
 
+def test_a_launch_that_stores_nothing_before_one_that_does(golden):
+    """T = 300, thin = 299, S = 4, R = 4: the launch of steps 1 ... 256 stores no state and brings nothing back, the second stores the one
+    state there is.  The state, its record, `last`, the accept and swap counts and the sums of ln P are the host loop's."""
+    case, lin = TU.long_ladder()
+    eng = _engine(golden, "auto", case)
+    like = _like(eng, case, 0)
+    got, _ = _compare(like, _offsets(lin["counts"]), case["f"], lin, 299, S=4)
+    assert lin["beta"].size == 4 and got.theta.shape[:2] == (lin["theta0"].shape[0], 1) and np.all(got.naccept > 0) and np.all(got.nswap > 0)
+    eng.close()
+
+
 def test_order_and_split_of_the_ladders(golden):
     """the same ladders in another order, and split over two calls with other offsets, give the same bits per ladder"""
     case, lin = TU.ladder_case("auto")
