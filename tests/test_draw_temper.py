@@ -1,11 +1,14 @@
 """Parallel tempering over the draw parameters on the host (no GPU): temper_util.host_ladder, the NumPy restatement of
 eftb_draws_temper_params, against a bimodal target with known tempered distributions and on its edge cases; the helpers temper_ladder and
 temper_proposals; the inputs of the GPU tests (test_gpu_draw_temper.py), checked here to move, to swap and to be refused on every rung, pair
-and ladder; and the argument errors MarginalLikelihood.temper_draws_params raises before it touches the library."""
+and ladder; the rungs that fit the LDS at the synthetic likelihoods and the ladders the GPU tests run there, checked to mix in sum; and the
+argument errors MarginalLikelihood.temper_draws_params raises before it touches the library."""
 import numpy as np
 import pytest
 
 import chain_util as CU
+import grad_util as GU
+import synth_like_util as SY
 import temper_util as TU
 from test_draw_chains import _like, _walk, chain_case
 
@@ -270,6 +273,103 @@ def test_long_ladder_swaps_on_both_sides_of_the_launch_boundary():
         print("naccept", r["naccept"], "nswap", r["nswap"].tolist(), "of", r["tried"][0])
         assert np.all(r["naccept"] > 0 if r is head else r["naccept"].reshape(2, 4).sum(1) > 0) and np.all(r["nswap"].sum(0) > 0)
     assert np.all(head["nswap"] + tail["nswap"] < head["tried"] + tail["tried"]) and np.all(head["nswap"] + tail["nswap"] > 0)
+
+
+# ----------------------------------------------------------------------------- the ladders on the synthetic likelihoods
+def test_rung_table():
+    """TEMPER_RUNGS is lds_waves on each case's own recipe and TEMPER_RUNGS_PADDED at 1024 entries, the shapes taken as test_draw_hmc.hmc_shape
+    takes them; the ladders of the GPU tests fit, and stand at the limit wherever the LDS sets one below eight"""
+    from test_draw_hmc import hmc_shape
+    from test_gpu_draw_synthetic import _padded_recipe
+
+    assert set(TU.TEMPER_RUNGS) == set(TU.TEMPER_RUNGS_PADDED) == set(SY.CASES)
+    for case in SY.CASES:
+        J1, nG, nnz = TU.case_shape(case)
+        assert (J1, nG, nnz) == hmc_shape(case)[:3]
+        assert TU.lds_waves(J1, nG, nnz) == TU.TEMPER_RUNGS[case] and TU.lds_waves(J1, nG, TU.PADDED) == TU.TEMPER_RUNGS_PADDED[case], case
+    for case, R in TU.SYNTH_R.items():
+        assert R <= TU.TEMPER_RUNGS[case] and (R == TU.TEMPER_RUNGS[case] or TU.TEMPER_RUNGS[case] == 8), case
+    # the padded recipe the device meets holds its 1024 entries; no recipe of one tracer can (25 rows x 27 columns)
+    assert TU.case_shape("F", _padded_recipe(SY.case_problem("F").rec, TU.PADDED))[2] == TU.PADDED
+    assert all(TU.lds_waves(28, 24, n) == 8 for n in range(107, 25 * 27 + 1))
+
+
+def _synthetic_target(name, lin, jeff):
+    from test_gpu_draw_synthetic import _padded_recipe
+
+    pb = SY.case_problem(name.split("/")[0])
+    rec = _padded_recipe(pb.rec, TU.PADDED) if name.endswith("/1024") else None
+    return pb, TU.SyntheticTarget(pb, lin["walker"], jeff, rec=rec, Ds=lin.get("Ds"), dataset=lin.get("dataset"))
+
+
+def _mixes(name, lin, S, thin):
+    T = lin["step"].shape[1]
+    for jeff in (False, True):
+        pb, target = _synthetic_target(name, lin, jeff)
+        assert np.all(lin["theta0"] >= lin["lower"]) and np.all(lin["theta0"] <= lin["upper"])
+        r = TU.host_ladder(target.records, lin["theta0"], lin["beta"], lin["step"], lin["lnu"], lin["lnu_swap"], S, 0, thin, lin["lower"], lin["upper"],
+                           np.full(pb.P, TU.PRIOR_LOC), np.full(pb.P, TU.PRIOR_SCALE))
+        print(name, "R", lin["beta"].size, "jeffreys", jeff, {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(r, T).items()})
+        assert TU.mixed_in_sum(r, T) and np.all(np.isfinite(r["logp"])) and len(r["extras"]) == 2 and r["extras"][1].shape == r["theta"].shape[:2] + (pb.nG,)
+
+
+@pytest.mark.parametrize("name", list(TU.SYNTH_TUNING))
+def test_synthetic_inputs_mix(name):
+    """the ladders the GPU tests run on the synthetic likelihoods meet the mixing condition (temper_util.mixed_in_sum) on the host target, without
+    and with Jeffreys, under the Gaussian theta priors: every case at its rungs, case F under the padded recipe at four, Gf at three, and the
+    T = 260 ladders of case G"""
+    if name == "G/long":
+        case, lin = TU.synthetic_inputs(name, TU.LONG_LADDERS, S=TU.LONG_S)
+        assert lin["step"].shape[:2] == (6, 260) and lin["lnu_swap"].shape == (2, 86, 2)
+        return _mixes(name, lin, TU.LONG_S, TU.LONG_THIN)
+    case, lin = TU.synthetic_inputs(name)
+    R = lin["beta"].size
+    assert lin["step"].shape[1] <= 96 and lin["counts"] == [2 * R, 0, R]
+    _mixes(name, lin, TU.SYNTH_S, TU.SYNTH_THIN)
+
+
+@pytest.mark.parametrize("n0, kw", [(60, dict()), (300, dict(kind="flat", singular=SY.CASES["Gf"]["nG"] // 2 + 1))], ids=["gauss", "flat-singular"])
+def test_three_wave_inputs_mix(n0, kw):
+    """the three-wave GPU tests run case Gf at T = 4, S = 2 (each pair tried once per ladder) with 690 and 1372 ladders on walker 0, under the
+    Gaussian prior and under the flat prior with the singular recipe.  The ladders come from one generator, so fewer of them are other
+    ladders, not a subset: here 60 (Gaussian prior) and 300 (flat prior, singular recipe) on walker 0 and one on walker 2, the same recipe of
+    inputs at sizes the host evaluates in seconds, already meet the condition in sum; the device tests assert it on their own ladders.  Under
+    the flat prior the hottest pair keeps its states in one event of 27 (51 of 1373 at the device's size, 0 of 61), hence the 300"""
+    pb = SY.case_problem("Gf", **kw)
+    _, lin = TU.synthetic_inputs("Gf", [n0, 0, 1], T=4, S=2, **kw)
+    assert lin["beta"].size == 3 and lin["step"].shape[:2] == (3 * n0 + 3, 4)
+    r = TU.host_ladder(TU.SyntheticTarget(pb, lin["walker"]).records, lin["theta0"], lin["beta"], lin["step"], lin["lnu"], lin["lnu_swap"], 2, 0, 2, lin["lower"],
+                       lin["upper"], np.full(pb.P, TU.PRIOR_LOC), np.full(pb.P, TU.PRIOR_SCALE))
+    print("Gf T = 4", kw, {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(r, 4).items()})
+    assert TU.mixed_in_sum(r, 4) and np.all(np.isfinite(r["logp"]))
+
+
+def test_groups_inputs_mix():
+    """the ladders of the groups test (case C, two data sets): the whole call mixes on the host, every chain against its group's data vector"""
+    from test_draw_datasets import datasets
+
+    pb = SY.case_problem("C")
+    whole, counts, plain, own = TU.groups_inputs("C")
+    assert counts == [4, 8, 4, 4] and own.tolist() == list(range(4, 12)) + list(range(16, 20))
+    for k in ("theta0", "step", "lnu"):
+        assert np.array_equal(whole[k][own], plain[k])
+    assert np.array_equal(whole["lnu_swap"][own[::4] // 4], plain["lnu_swap"])
+    _mixes("C", dict(whole, Ds=datasets(pb.D, pb.invcov, 2)), TU.SYNTH_S, TU.SYNTH_THIN)
+
+
+def test_synthetic_target_is_the_gram_route():
+    """SyntheticTarget returns chain_util.gram_record's ln P and sample_util.gram_samples' full chi2 and best fit bit for bit: the same statements"""
+    import sample_util as SU
+
+    for case, jeff in (("C", False), ("E", True)):
+        pb = SY.case_problem(case)
+        lp, full, best = TU.SyntheticTarget(pb, pb.walker, jeff).records(pb.theta)
+        for d in (0, 3, 11):
+            ff, tw, tn = SY.of_walker(pb, pb.walker[d])
+            W = GU.gram_matrix(tw, pb.index, pb.D, pb.invcov, tn)
+            assert lp[d] == CU.gram_record(pb.rec, pb.theta[d], ff, W, pb.loc, pb.scale, jeff)
+            b, _, _, f0 = SU.gram_samples(pb.rec, pb.theta[d], ff, W, pb.loc, pb.scale, np.zeros((1, pb.nG)))
+            assert np.array_equal(best[d], b) and full[d] == f0
 
 
 # ----------------------------------------------------------------------------- argument errors raised before the library is touched

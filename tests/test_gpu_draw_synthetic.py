@@ -16,6 +16,9 @@ those of the launcher's formula when the table was written, for the reader):
     Gf   4   no   24  97  3 x 5   31    5   G with ndata >= nG: a proper flat prior at nw = 2 (the failing-draw tests)
     Ef   1   yes  24  28  3 x 10  27    4   E with ndata >= nG: the same at nw = 4
 
+(The tempering call chooses its own wave count, one per rung: the rungs that fit at each case are temper_util.TEMPER_RUNGS, and its ladders
+on these likelihoods are in test_gpu_draw_temper.py.)
+
 Three walkers own 9, 0 and 5 draws: one has none, one more than twice the widest workgroup's waves.  Yardsticks: the data-space ones of
 grad_util, hess_util and sample_util around oracle.marginal, pinned on the host by test_draw_synthetic.py; bars: hess_util.device_bar of
 synth_like_util.SYNTH_FLOOR.  What the calls promise to share they are asked to share bit for bit, and a draw's bits must not depend on

@@ -2,12 +2,15 @@
 Yardstick: the project's own synchronous route -- temper_util.host_ladder (pinned to the mathematics by test_draw_temper.py) around the records
 of eftb_draws_logp_params, as test_gpu_draw_chains._records asks for them.  Everything is compared bit for bit: the states, ln P, full chi2,
 the best fits, the last state, the accept counts, the swap counts and the sums of ln P.  The inputs are those test_draw_temper.py has checked
-to move, to swap and to be refused on every rung and pair; the replayed ladders are asked again."""
+to move, to swap and to be refused on every rung and pair; the replayed ladders are asked again.  The fixtures reach nG = 14, P = 6, three
+tracers and eight rungs; the tests of the last section run the ladders on synth_like_util's likelihoods, up to nG = 24, P = 8, five tracers
+and the rung counts the LDS limits (temper_util.TEMPER_RUNGS)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import synth_like_util as SY
 import temper_util as TU
 from test_draw_datasets import datasets
 from test_gpu_draw_chains import _engine, _like, _records, _stored_records_are_the_draw_call
@@ -335,4 +338,217 @@ def test_ladder_that_does_not_fit_the_lds():
             with pytest.raises(L.EftbError, match="R = %d rungs needs %d waves in one workgroup, but %d fit the LDS .* J \\+ 1 = %d columns with nG = %d and P = %d" %
                                (R, R, fit, J1, pb.nG, pb.P)):
                 like.temper_draws_params(theta0, off, pb.f, beta, step, lnu, swaps, swap_every=2)
+    eng.close()
+
+
+# ----------------------------------------------------------------------------- the synthetic likelihoods (synth_like_util.CASES)
+def _synthetic(name, kind="gauss", singular=None):
+    """the engine of a synthetic case with its templates put: name as the entries of temper_util.SYNTH_TUNING ("F/1024": case F under the
+    recipe padded to 1024 entries) -> pb, rec (None: the case's own), eng, like(jeffreys).  A likelihood sets the engine's Jeffreys switch,
+    recipe and data sets when it is built, so like(...) is called where the likelihood is used, one at a time."""
+    from test_gpu_draw_synthetic import _engine as s_engine, _like as s_like, _padded_recipe, _put
+
+    pb = SY.case_problem(name.split("/")[0], kind, singular)
+    rec = _padded_recipe(pb.rec, TU.PADDED) if name.endswith("/1024") else None
+    eng = s_engine(pb, len(pb.counts) * pb.ntr)
+    _put(eng, pb)
+    return pb, rec, eng, lambda jeffreys=False: s_like(eng, pb, jeffreys, rec=rec)
+
+
+def _fields_equal(a, b, note):
+    for name in FIELDS:
+        assert np.array_equal(getattr(a, name), getattr(b, name), equal_nan=True), (note, name)
+
+
+def _join(first, second, whole, note):
+    """two calls, the second continued from the first's `last`, are the one call"""
+    for name in ("theta", "logp", "fullchi2", "best"):
+        assert np.array_equal(np.concatenate([getattr(first, name), getattr(second, name)], axis=1), getattr(whole, name)), (note, name)
+    assert np.array_equal(second.last, whole.last) and np.array_equal(first.naccept + second.naccept, whole.naccept), note
+    assert np.array_equal(first.nswap + second.nswap, whole.nswap), note
+
+
+@pytest.mark.parametrize("case", list(TU.SYNTH_R))
+def test_synthetic_shapes(case):
+    """Ladders at every shape the fixtures do not reach (temper_util.SYNTH_R: eight rungs at the smallest shape and at nG = 24, where all 26
+    record slots are live in every exchange; nl = 1; two tracers with ndata < 16; NNLO columns of two and of four tracers; the most rungs
+    that fit at three, four and five tracers, five of them at TWO with nG odd; P = 8; one rung, with swap uniforms supplied, behind the
+    largest footprint).  S = 3, thin = 5, a box and Gaussian theta priors, without and with Jeffreys, two ladders on walker 0, none on 1,
+    one on 2: the host loop around the device's own records, bit for bit.  The inputs meet temper_util.mixed_in_sum on the device's ln P as
+    they do on the host (test_draw_temper.py); the draw call returns the same bits before and after."""
+    pb, _, eng, make = _synthetic(case)
+    _, lin = TU.synthetic_inputs(case)
+    R, (N, T, P) = lin["beta"].size, lin["step"].shape
+    assert R == TU.SYNTH_R[case] and lin["counts"] == [2 * R, 0, R]
+    off, prior, K = SY.offsets(lin["counts"]), TU.theta_prior(P), T // TU.SYNTH_THIN
+    plain = None
+    for jeff in (False, True):
+        like = make(jeff)
+        before = like.logp_draws_params(lin["theta0"], off, pb.f, return_best=True)
+        if jeff:  # the second pass is another target: ln P without ln det F2, the same best fits
+            assert np.all(before[0] != plain[0]) and np.array_equal(before[2], plain[2])
+        plain = before
+        got, want = _compare(like, off, pb.f, lin, TU.SYNTH_THIN, S=TU.SYNTH_S, **prior)
+        print(case, "R", R, {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(want, T).items()})
+        assert TU.mixed_in_sum(want, T)
+        assert got.theta.shape == (N, K, P) and got.best.shape == (N, K, pb.nG) and got.nswap.shape == (3, max(R - 1, 1)) and got.sum_logp.shape == (N,)
+        assert all(np.all(np.isfinite(a)) for a in (got.theta, got.logp, got.fullchi2, got.best, got.last, got.sum_logp)) and np.all(got.nswap >= 0)
+        _stored_records_are_the_draw_call(like, off, pb.f, got)
+        for a, b in zip(before, like.logp_draws_params(lin["theta0"], off, pb.f, return_best=True)):  # the Gram cache and the buffers are not disturbed
+            assert np.array_equal(a, b)
+        if R == 1:  # one rung with S = 3 and swap uniforms supplied (there is no pair to read them) is the chain call
+            assert lin["lnu_swap"].shape == (3, T // TU.SYNTH_S, 0) and np.all(got.nswap == 0)
+            ch = like.metropolis_draws_params(lin["theta0"], off, pb.f, lin["step"], lin["lnu"], thin=TU.SYNTH_THIN, lower=lin["lower"], upper=lin["upper"], **prior)
+            for name in ("theta", "logp", "last", "naccept"):
+                assert np.array_equal(getattr(got, name), getattr(ch, name)), name
+    eng.close()
+
+
+@pytest.mark.parametrize("name", ["F", "H", "J", "F/1024"])
+def test_rungs_at_the_lds_limit(name):
+    """The most rungs that fit (temper_util.TEMPER_RUNGS: five at case F, three at H and J; four at F under the recipe padded to 1024 entries,
+    whose own five no longer fit) run and are the host loop; one rung more is refused by a message that names R, the rungs that fit, J + 1,
+    nG and P; after the refusal the chain call and the call at the limit return their earlier bits.  (Case E has no such limit: a recipe of
+    one tracer holds at most 675 entries, and eight rungs fit beside every one of them.)"""
+    from eftpipe_amd import _lib as L
+
+    pb, rec, eng, make = _synthetic(name)
+    like = make()
+    case = name.split("/")[0]
+    J1, nG, nnz = TU.case_shape(case, rec)
+    fit = (TU.TEMPER_RUNGS_PADDED if rec is not None else TU.TEMPER_RUNGS)[case]
+    assert TU.lds_waves(J1, nG, nnz) == fit < 8 and nnz == (TU.PADDED if rec is not None else nnz)
+    _, lin = TU.synthetic_inputs(name)
+    T, P = lin["step"].shape[1], pb.P
+    assert lin["beta"].size == fit
+    off, prior = SY.offsets(lin["counts"]), TU.theta_prior(P)
+    chain = lambda: like.metropolis_draws_params(lin["theta0"], off, pb.f, lin["step"], lin["lnu"], thin=TU.SYNTH_THIN, lower=lin["lower"], upper=lin["upper"],
+                                                 return_best=True, **prior)
+    ch = chain()
+    got, want = _compare(like, off, pb.f, lin, TU.SYNTH_THIN, S=TU.SYNTH_S, **prior)
+    print(name, "R", fit, {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(want, T).items()})
+    assert TU.mixed_in_sum(want, T) and np.all(np.isfinite(got.logp))
+    _stored_records_are_the_draw_call(like, off, pb.f, got)
+    _, more = TU.synthetic_inputs(name, T=6, R=fit + 1)
+    with pytest.raises(L.EftbError, match="R = %d rungs needs %d waves in one workgroup, but %d fit the LDS .* J \\+ 1 = %d columns with nG = %d and P = %d" %
+                       (fit + 1, fit + 1, fit, J1, nG, P)):
+        like.temper_draws_params(more["theta0"], SY.offsets(more["counts"]), pb.f, more["beta"], more["step"], more["lnu"], more["lnu_swap"], swap_every=TU.SYNTH_S,
+                                 lower=more["lower"], upper=more["upper"], **prior)
+    for a, b in zip(ch, chain()):
+        assert np.array_equal(a, b)
+    again, _ = _compare(like, off, pb.f, lin, TU.SYNTH_THIN, S=TU.SYNTH_S, **prior)
+    _fields_equal(again, got, "after the refusal")
+    eng.close()
+
+
+def test_odd_ladder_across_the_launch_boundary():
+    """Case G at its three rungs, T = 260 > 256, S = 3, thin = 7, one ladder on each of two walkers.  The first launch holds the 85 events
+    0 ... 84, the last on step 254 (counted from 0), and ends on step 255 between two events: the second launch starts one step into an
+    interval (two steps to its first event) and on the odd pair (1, 2), which the first launch started on (0, 1); at R = 3 one rung idles in
+    every event.  The call is the host loop, and equals the continuations from `last` after 100 steps (one step past event 32), after 98
+    (two steps before it) and after 99 (on it) with first_step set."""
+    pb, _, eng, make = _synthetic("G")
+    like = make()
+    _, lin = TU.synthetic_inputs("G/long", TU.LONG_LADDERS, S=TU.LONG_S)
+    S, T, prior = TU.LONG_S, 260, TU.theta_prior(pb.P)
+    assert lin["beta"].size == 3 and lin["step"].shape[:2] == (6, T) and (256 // S) % 2 == 1 and 256 % S == 1
+    off = SY.offsets(lin["counts"])
+    got, _ = _compare(like, off, pb.f, lin, TU.LONG_THIN, S=S, **prior)
+    one, want = _compare(like, off, pb.f, lin, 1, S=S, **prior)
+    print("G/long", {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(want, T).items()})
+    assert TU.mixed_in_sum(want, T)
+    assert np.array_equal(got.theta, one.theta[:, 6::7]) and np.array_equal(got.best, one.best[:, 6::7]) and np.array_equal(got.last, one.last)
+    assert np.array_equal(got.nswap, one.nswap) and np.array_equal(got.naccept, one.naccept) and np.array_equal(got.sum_logp, one.sum_logp)
+    for T1 in (100, 98, 99):
+        cut = lambda a, b: dict(lin, step=np.ascontiguousarray(lin["step"][:, a:b]), lnu=np.ascontiguousarray(lin["lnu"][:, a:b]),
+                                lnu_swap=np.ascontiguousarray(lin["lnu_swap"][:, a // S : b // S]))
+        first, _ = _compare(like, off, pb.f, cut(0, T1), 1, S=S, **prior)
+        second, _ = _compare(like, off, pb.f, dict(cut(T1, T), theta0=first.last), 1, S=S, first_step=T1, **prior)
+        _join(first, second, one, T1)
+    eng.close()
+
+
+def _many_ladders(n0, **kw):
+    """case Gf at its three rungs with n0 ladders on walker 0 and one on walker 2, T = 4, S = 2: events 0 and 1 try each pair once"""
+    _, lin = TU.synthetic_inputs("Gf", [n0, 0, 1], T=4, S=2, **kw)
+    assert lin["beta"].size == 3
+    return lin
+
+
+def test_every_workgroup_loops_at_three_waves():
+    """nG = 24 at three waves (case Gf): the launcher spreads a walker's ladders over up to 2048 / C workgroups (draw_shares), 682 with the C = 3
+    walkers of the case, so with 690 ladders on walker 0 the first eight workgroups take a second ladder in the same LDS.  The host loop, bit
+    for bit"""
+    pb, _, eng, make = _synthetic("Gf")
+    like = make()
+    n0 = 2048 // len(pb.counts) + 8  # (2048 / C workgroups per walker, C walkers: not the rung count, which is 3 as well)
+    lin = _many_ladders(n0)
+    got, want = _compare(like, SY.offsets(lin["counts"]), pb.f, lin, 2, S=2, **TU.theta_prior(pb.P))
+    print("Gf", n0 + 1, "ladders", {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(want, 4).items()})
+    assert got.nswap.shape == (n0 + 1, 2) and TU.mixed_in_sum(want, 4) and np.all(np.isfinite(got.logp))
+    eng.close()
+
+
+def test_failed_ladder_at_three_waves():
+    """Case Gf under its flat prior with the singular recipe of test_failing_draw_between_regular_ones (theta_0 = 0: an exactly zero row and
+    column of F2).  A walker's ladders go to 2048 / C = 682 workgroups (C = 3 walkers); walker 0 owns 2 x 682 + 8 ladders, so workgroup 3
+    works the ladders 3, 685 and 1367; rung 1 of ladder 685 starts on the singular plane.  That ladder is NaN in every field with naccept = nswap = -1, and every other ladder, those before and after it in
+    the same workgroup's LDS included, has the bits of the call without it."""
+    nG = SY.CASES["Gf"]["nG"]
+    kw = dict(kind="flat", singular=nG // 2 + 1)
+    pb, _, eng, make = _synthetic("Gf", **kw)
+    like = make()
+    wgs, R = 2048 // len(pb.counts), 3  # the workgroups of a walker (2048 / C at C = 3 walkers) and the rungs
+    assert wgs == 682
+    n0, bad = 2 * wgs + 8, wgs + 3
+    lin = _many_ladders(n0, **kw)
+    lin["theta0"][bad * R + 1, 0] = 0.0
+    lin["lower"][0] = -0.1  # (the box holds the singular start)
+    off, prior = SY.offsets(lin["counts"]), TU.theta_prior(pb.P)
+    with pytest.raises(RuntimeError, match="det of F2ij"):
+        like.temper_draws_params(lin["theta0"], off, pb.f, lin["beta"], lin["step"], lin["lnu"], lin["lnu_swap"], swap_every=2, lower=lin["lower"], upper=lin["upper"],
+                                 **prior)
+    raw, want = _compare(like, off, pb.f, lin, 2, S=2, raw=True, **prior)
+    print("Gf flat, singular", n0 + 1, "ladders", {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(want, 4).items()})
+    chains = np.arange(bad * R, bad * R + R)
+    keep = np.setdiff1d(np.arange(lin["theta0"].shape[0]), chains)
+    assert np.all(raw.naccept[chains] == -1) and np.all(raw.nswap[bad] == -1) and np.all(np.isnan(raw.sum_logp[chains]))
+    assert all(np.all(np.isnan(a[chains])) for a in (raw.theta, raw.logp, raw.fullchi2, raw.best, raw.last))
+    assert all(np.all(np.isfinite(a[keep])) for a in (raw.theta, raw.logp, raw.fullchi2, raw.best, raw.last, raw.sum_logp))
+    assert np.all(raw.naccept[keep] >= 0) and np.all(np.delete(raw.nswap, bad, axis=0) >= 0) and TU.mixed_in_sum(want, 4)
+    rest = dict(_pick(lin, keep), counts=[(n0 - 1) * R, 0, R])
+    alone, _ = _compare(like, SY.offsets(rest["counts"]), pb.f, rest, 2, S=2, **prior)
+    for name in FIELDS:
+        a, b = getattr(alone, name), getattr(raw, name)
+        assert np.array_equal(a, np.delete(b, bad, axis=0) if name == "nswap" else b[keep]), name
+    eng.close()
+
+
+def test_groups_at_two_tracers():
+    """groups= at two tracers (case C, ndata < 16) with two data vectors and groups that repeat a walker, four rungs: the call is the host
+    loop around logp_draws_params(groups=) on every group's own data, and the groups on data set 0 return the bits of the call without groups"""
+    pb, _, eng, make = _synthetic("C")
+    whole, counts, plain, own = TU.groups_inputs("C")
+    wk, ds = np.array([g[0] for g in TU.GROUPS]), np.array([g[1] for g in TU.GROUPS])
+    off, prior, T, R = SY.offsets(counts), TU.theta_prior(pb.P), whole["step"].shape[1], whole["beta"].size
+    Ds = datasets(pb.D, pb.invcov, 2)
+    assert np.array_equal(Ds[0], pb.D) and R == 4
+    first = None
+    for jeff in (False, True):
+        like = make(jeff)
+        like.set_datasets(Ds)
+        start = _records(like, off, pb.f, (wk, ds))(whole["theta0"])[0]
+        assert first is None or np.all(start != first)  # (the second pass is another target: ln P without ln det F2)
+        first = start
+        got, want = _compare(like, off, pb.f, whole, TU.SYNTH_THIN, S=TU.SYNTH_S, groups=(wk, ds), **prior)
+        print("C groups", {k: np.asarray(v).tolist() for k, v in TU.mixing_counts(want, T).items()})
+        assert TU.mixed_in_sum(want, T) and np.all(np.isfinite(got.logp))
+        _stored_records_are_the_draw_call(like, off, pb.f, got, groups=(wk, ds))
+        base, _ = _compare(like, SY.offsets(plain["counts"]), pb.f, plain, TU.SYNTH_THIN, S=TU.SYNTH_S, **prior)
+        for name in FIELDS:
+            a, b = getattr(base, name), getattr(got, name)
+            assert np.array_equal(a, b[own[::R] // R] if name == "nswap" else b[own]), name
+        # the groups on data set 1 are fitted to another vector: other bits than the same ladders would have on data set 0
+        lp1, lp0 = _records(like, off, pb.f, (wk, ds))(whole["theta0"])[0][:R], _records(like, SY.offsets([0, 0, R]), pb.f)(whole["theta0"][:R])[0]
+        assert np.all(lp1 != lp0)
     eng.close()
