@@ -43,7 +43,7 @@ RECIPE_LOGP, RECIPE_REDUCE = 0, 1
 
 EXPORTS = ("eftb_create eftb_set_table eftb_finalize eftb_set_option eftb_dominant_time eftb_kernel_time eftb_kernel_time_ex eftb_set_likelihood eftb_destroy eftb_add_operator eftb_apply_operator "
            "eftb_set_operator_stochastic eftb_set_tracers eftb_set_pipeline_operator_tracer eftb_set_pipeline_operator eftb_set_template_dims eftb_put eftb_get eftb_buffer_size eftb_run "
-           "eftb_sync eftb_run_timed eftb_stage_inputs eftb_run_staged eftb_fetch_previous eftb_fetch_back eftb_fetch_view eftb_step eftb_flush eftb_set_step_output eftb_step_trace eftb_submit_stats eftb_eval_batch eftb_eval_logp_batch eftb_draws_logp eftb_draws_reduce eftb_set_draw_recipe eftb_draws_logp_params eftb_draws_reduce_params eftb_draws_logp_grad_params eftb_draws_logp_hess_params eftb_set_likelihood_datasets eftb_draws_logp_params_datasets eftb_draws_sample_params eftb_draws_sample_params_datasets eftb_draws_chain_params eftb_draws_chain_params_datasets eftb_draws_temper_params eftb_draws_temper_params_datasets eftb_draws_drag_params eftb_draws_hmc_params eftb_draws_hmc_params_datasets eftb_host_alloc eftb_host_free eftb_comm_unique_id eftb_comm_init eftb_gather_plk eftb_fetch_gathered eftb_gathered_view "
+           "eftb_sync eftb_run_timed eftb_stage_inputs eftb_run_staged eftb_fetch_previous eftb_fetch_back eftb_fetch_view eftb_step eftb_flush eftb_set_step_output eftb_step_trace eftb_submit_stats eftb_eval_batch eftb_eval_logp_batch eftb_draws_logp eftb_draws_reduce eftb_set_draw_recipe eftb_draws_logp_params eftb_draws_reduce_params eftb_draws_logp_grad_params eftb_draws_logp_hess_params eftb_set_likelihood_datasets eftb_draws_logp_params_datasets eftb_draws_sample_params eftb_draws_sample_params_datasets eftb_draws_chain_params eftb_draws_chain_params_datasets eftb_draws_temper_params eftb_draws_temper_params_datasets eftb_draws_ensemble_params eftb_draws_ensemble_params_datasets eftb_draws_drag_params eftb_draws_hmc_params eftb_draws_hmc_params_datasets eftb_host_alloc eftb_host_free eftb_comm_unique_id eftb_comm_init eftb_gather_plk eftb_fetch_gathered eftb_gathered_view "
            "eftb_window_precompute eftb_mfma_f64_peak eftb_stream_read_probe eftb_last_error eftb_version eftb_source_hash").split()
 
 _lib = None
@@ -100,6 +100,8 @@ def load():
     lib.eftb_draws_chain_params_datasets.argtypes, lib.eftb_draws_chain_params_datasets.restype = [vp, i32, i32, i32p, i32p, ll, i32, i32, i64p] + [dp] * 13 + [i64p], i32
     lib.eftb_draws_temper_params.argtypes, lib.eftb_draws_temper_params.restype = [vp, i32, ll, i32, i32, i32, ll, i32, i64p] + [dp] * 15 + [i64p, i64p, dp], i32
     lib.eftb_draws_temper_params_datasets.argtypes, lib.eftb_draws_temper_params_datasets.restype = [vp, i32, i32, i32p, i32p, ll, i32, i32, i32, ll, i32, i64p] + [dp] * 15 + [i64p, i64p, dp], i32
+    lib.eftb_draws_ensemble_params.argtypes, lib.eftb_draws_ensemble_params.restype = [vp, i32, ll, i32, i32, i32, i64p, dp, dp, dp, i32p, dp] + [dp] * 9 + [i64p], i32
+    lib.eftb_draws_ensemble_params_datasets.argtypes, lib.eftb_draws_ensemble_params_datasets.restype = [vp, i32, i32, i32p, i32p, ll, i32, i32, i32, i64p, dp, dp, dp, i32p, dp] + [dp] * 9 + [i64p], i32
     lib.eftb_draws_drag_params.argtypes, lib.eftb_draws_drag_params.restype = [vp, i32, i32, i32p, i32p, ll, i32, i32, i64p] + [dp] * 17 + [i64p, dp], i32
     lib.eftb_draws_hmc_params.argtypes, lib.eftb_draws_hmc_params.restype = [vp, i32, ll, i32, i32, i32, i64p] + [dp] * 15 + [i64p, dp], i32
     lib.eftb_draws_hmc_params_datasets.argtypes, lib.eftb_draws_hmc_params_datasets.restype = [vp, i32, i32, i32p, i32p, ll, i32, i32, i32, i64p] + [dp] * 15 + [i64p, dp], i32

@@ -3645,6 +3645,9 @@ __device__ __forceinline__ bool draws_solve(int lane, int nG, int jeffreys, doub
 
 constexpr int RECIPE_MAXP = 32, RECIPE_MAXTERMS = 1024, RECIPE_FPOW = 7, RECIPE_MAXTR = 8;  // (draw recipes: see RecipeTab)
 constexpr int CHAIN_PRI = 4 * RECIPE_MAXP;                                                 // the prior table of the chain kernel
+// the ensemble kernel: members of an ensemble and waves of its workgroup at most, and a member's slot in the ensemble area of the LDS,
+// theta [RECIPE_MAXP] | record [MARG_OUT] | ln P | pri | accept count
+constexpr int ENS_MAXK = 64, ENS_MAXW = 8, ENS_REC = RECIPE_MAXP, ENS_LP = ENS_REC + MARG_OUT, ENS_PRI = ENS_LP + 1, ENS_NA = ENS_PRI + 1, ENS_SLOT = ENS_NA + 1;
 
 // The dynamic LDS of a draw kernel, in doubles: what the host sizes the launch from and what the kernel takes its pointers from.
 //   per workgroup  W_c [J1][J1] at 0, then (all but rows) fp [RECIPE_MAXTR][RECIPE_FPOW] and the int tables, two ints to a double:
@@ -3657,6 +3660,7 @@ constexpr int CHAIN_PRI = 4 * RECIPE_MAXP;                                      
 //                  drag    tc | tp as chain | rs [2][2][MARG_OUT] (two pairs of records, start | end walker in each)
 //                  hmc     tc | tp | rs as chain | gs [2][RECIPE_MAXP] (the gradients of the two records) | mo [RECIPE_MAXP] (the momentum)
 //                          | F [P][P] (the chain's factor); erow is staged as for the gradient
+//   ensemble       (the ensemble kernel alone, behind the parts of its nw waves of the chain kind, at ens(nw)) K slots of ENS_SLOT doubles
 // nnzp and ndtp: the entries of the recipe and its derivative records, rounded up to even.  A region a kind does not have is empty.
 enum DrawKind { DRAW_ROWS, DRAW_PARAMS, DRAW_GRAD, DRAW_HESS, DRAW_SAMPLE, DRAW_CHAIN, DRAW_DRAG, DRAW_HMC };
 
@@ -3724,6 +3728,15 @@ struct DrawLds {
     __host__ __device__ constexpr size_t bytes_wg() const { return (size_t)wg * sizeof(double); }
     __host__ __device__ constexpr size_t bytes_wave() const { return (size_t)wave * sizeof(double); }
     __host__ __device__ constexpr size_t bytes(int nw) const { return bytes_wg() + nw * bytes_wave(); }
+    // the ensemble area of the ensemble kernel (chain kind): where it starts behind nw waves, the bytes of a launch with K members, and the
+    // waves of a workgroup, min(ENS_MAXW, K / 2, as many as fit beside W_c and the area); 0 if one does not
+    __host__ __device__ constexpr int ens(int nw) const { return wg + nw * wave; }
+    __host__ __device__ constexpr size_t bytes_ens(int nw, int K) const { return bytes(nw) + (size_t)K * ENS_SLOT * sizeof(double); }
+    __host__ __device__ constexpr int fit_ens(int K, size_t limit) const {
+        int nw = 0;
+        while (nw < ENS_MAXW && 2 * (nw + 1) <= K && bytes_ens(nw + 1, K) <= limit) ++nw;
+        return nw;
+    }
     // the waves of a workgroup: 4, 2 or 1, as many as fit beside W_c (drag: beside both); 0 if one does not
     __host__ __device__ constexpr int fit(size_t limit) const { return bytes(4) <= limit ? 4 : bytes(2) <= limit ? 2 : bytes(1) <= limit ? 1 : 0; }
     // every region holds what its kernel keeps there and ends where the next begins or before (the int tables in whole doubles, so every
@@ -3767,6 +3780,12 @@ static_assert(DrawLds::drag(82, 24, 1024, RECIPE_MAXP, 0).bytes(1) == 144808 && 
 static_assert(DrawLds(DRAW_HMC, 109, 24, 1024, 0, RECIPE_MAXP, 0).bytes(1) == 149864 && DrawLds(DRAW_HMC, 109, 24, 1024, 0, RECIPE_MAXP, 0).fit(160 * 1024) == 1 &&
                   DrawLds(DRAW_HMC, 121, 24, 1024, 0, 1, 0).fit(160 * 1024) == 0,
               "DrawLds: hmc at J + 1 = 109 and 121");
+// the ensemble area: 61 doubles per member; at the largest shape four members beside one wave, at the fixtures' (J + 1 = 25, nG = 3) eight
+// waves beside ENS_MAXK members
+static_assert(ENS_SLOT == 61 && DrawLds(DRAW_CHAIN, 121, 24, 1024, 0, RECIPE_MAXP, 0).fit_ens(4, 160 * 1024) == 1 &&
+                  DrawLds(DRAW_CHAIN, 121, 24, 1024, 0, RECIPE_MAXP, 0).fit_ens(6, 160 * 1024) == 0 &&
+                  DrawLds(DRAW_CHAIN, 25, 3, 37, 0, 5, 0).fit_ens(ENS_MAXK, 160 * 1024) == 8 && DrawLds(DRAW_CHAIN, 25, 3, 37, 0, 5, 0).fit_ens(6, 160 * 1024) == 3,
+              "DrawLds: the ensemble area");
 constexpr bool draw_lds_sound(int J1, int nG, int nnz, int ndt, int P) {
     for (int kind = DRAW_ROWS; kind <= DRAW_HMC; ++kind)
         for (int jeffreys = 0; jeffreys < 2; ++jeffreys)
@@ -5273,6 +5292,185 @@ __global__ __launch_bounds__(64 * TEMPER_MAXR) void draws_temper_params_kernel(
             if (wv < npair) nswap[lad * npair + wv] = ns;
         }
         wave_lds_sync();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Affine-invariant ensembles over theta at fixed templates (eftb_draws_ensemble_params): the stretch move of Goodman & Weare.  Chain n is
+// member n % K of ensemble n / K; members 0 ... K/2 - 1 are half 0, the rest half 1; the target is the chain kernel's ln P_marg + pri.
+// One workgroup of nw waves (nw <= K/2, ENS_MAXW at most) works one ensemble at a time and loops over the ensembles of its (walker,
+// share).  The members' states live in the ensemble area of the LDS behind the waves' parts (DrawLds::ens), ENS_SLOT doubles each:
+// theta [RECIPE_MAXP] | record [MARG_OUT] | ln P | pri | accept count.  Member q of a half belongs to wave q % nw, which alone writes its
+// slot; a wave keeps the trial theta (tp) and the trial record (rs) in its own part.  Per evaluation the kernel is the chain kernel's:
+// draws_stage, draws_recipe_forward + draws_solve<false> (the bits of eftb_draws_logp_params), chain_prior, chain_accept.
+//   start          the owning waves compute record and pri of every member's starting theta, pass by pass, into its slot (ln P = NaN for
+//                  an accept count of -1 from an earlier launch); barrier; every wave reads all K ln P: one not finite and the ensemble
+//                  has failed, NaN in every slot and theta of every member, accept counts -1; barrier
+//   sweep i        half 0 against half 1, barrier, half 1 against half 0, barrier.  In a half-sweep wave w takes the members
+//                  q = w, w + nw, ... of the active half, ceil((K/2) / nw) passes.  Member k with partner j = member pick[n][i] of the
+//                  other half:  theta' = theta_j + z[n][i] (theta_k - theta_j)  (ens_stretch); outside the box: rejected without an
+//                  evaluation; otherwise accepted iff ln P' is finite and lnq[n][i] < (ln P' + pri') - (ln P + pri); on acceptance trial
+//                  theta and record go over the member's slot
+//   store          after every thin-th sweep each wave stores its members' theta and record, from slots that it alone writes
+//   end            theta and nacc hold the state after the launch
+// Barriers: the two around the failed-ensemble decision and one behind each half-sweep are the only ones behind draws_stage, and every
+// wave of the workgroup reaches each the same number of times -- the decision, the ensemble loop and the early return for an empty share are
+// workgroup-uniform, every wave has the same number of passes, and a wave without a member in the last pass, or a member whose proposal left
+// the box, skips its evaluation under a wave-uniform branch that holds no barrier.  Within a half-sweep writes touch only the active
+// half, each slot by the wave that owns it, and reads of other waves' slots touch only the passive half: every write is across a barrier
+// from every read of the same slot by another wave.  No wave spins on another; no atomics; every value goes to memory by an ordinary
+// vector store.  Every loop's trip count is fixed at launch.
+// LDS: DrawLds, DRAW_CHAIN, at nw waves (tc and the second record of a wave are not used), then the ensemble area [K][ENS_SLOT].
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double ens_stretch(double z, double tk, double tj) {
+#pragma clang fp contract(off)
+    const double d = tk - tj;
+    return tj + z * d;
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(64 * ENS_MAXW) void draws_ensemble_params_kernel(int ntr, int nG, int J1, int jeffreys, int K, int Tc, int t0, int thin, int kc,
+                                                                               int kstride, RecipeTab rt, const long long* __restrict__ offsets,
+                                                                               double* __restrict__ theta, long long* __restrict__ nacc,
+                                                                               const double* __restrict__ f, const double* __restrict__ W,
+                                                                               const double* __restrict__ mu, const double* __restrict__ sinv,
+                                                                               const double* __restrict__ prior, const double* __restrict__ z,
+                                                                               const int* __restrict__ pick, const double* __restrict__ lnq,
+                                                                               double* __restrict__ chain, double* __restrict__ rec) {
+    extern __shared__ double sm[];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ng1 = nG + 1, P = rt.P, half = K >> 1, npass = (half + nw - 1) / nw;
+    const long long d0 = offsets[c], nens = (offsets[c + 1] - d0) / K;
+    if ((long long)blockIdx.y >= nens) return;  // (workgroup-uniform: no ensemble for this share)
+    const DrawLds L(DRAW_CHAIN, J1, nG, rt.nnz, 0, P, jeffreys);
+    double* wave = draws_stage<DRAW_CHAIN>(L, sm, wv, c, ntr, J1, rt, f, W, nullptr, nullptr, 0, prior);
+    double *Ws = sm, *fp = sm + L.fp, *th = wave + L.th, *val = wave + L.val, *Hs = wave + L.H, *Gs = wave + L.G;
+    double *tp = wave + L.tp, *rs = wave + L.rs;
+    double* ens = sm + L.ens(nw);
+    const int* col = reinterpret_cast<int*>(sm + L.col);
+    const double* pr = sm + L.pr;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (long long l = blockIdx.y; l < nens; l += gridDim.y) {  // (workgroup-uniform)
+        const long long db = d0 + l * K;
+        // ---- start: the records of this wave's members
+        for (int h = 0; h < 2; ++h)
+            for (int ps = 0; ps < npass; ++ps) {
+                const int q = wv + ps * nw;
+                if (q < half) {  // (wave-uniform; no barrier inside)
+                    const int k = h * half + q;
+                    const long long d = db + k;
+                    double* me = ens + k * ENS_SLOT;
+                    const long long na = nacc[d];
+                    if (lane < P) tp[lane] = me[lane] = theta[(size_t)d * P + lane];
+                    wave_lds_sync();
+                    double lp0 = nan, pri0 = 0.0;
+                    if (na >= 0) {  // (wave-uniform)
+                        draws_recipe_forward<TWO>(rt, tp, 0, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+                        draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, rs);
+                        wave_lds_sync();
+                        lp0 = rs[0];
+                        pri0 = chain_prior(P, tp, pr);
+                        if (lane < MARG_OUT) me[ENS_REC + lane] = rs[lane];
+                    }
+                    if (lane == 0) {
+                        me[ENS_LP] = lp0;
+                        me[ENS_PRI] = pri0;
+                        me[ENS_NA] = (double)na;
+                    }
+                    wave_lds_sync();  // (the next member overwrites tp, th, val, H, G and rs)
+                }
+            }
+        __syncthreads();
+        bool alive = true;
+        for (int k = 0; k < K; ++k) alive = alive && __builtin_isfinite(ens[k * ENS_SLOT + ENS_LP]);
+        __syncthreads();  // (the first half-sweep, and a failed ensemble's successor, write slots that every wave must have read)
+        if (!__builtin_amdgcn_readfirstlane((int)alive)) {  // a failed ensemble (workgroup-uniform)
+            for (int h = 0; h < 2; ++h)
+                for (int ps = 0; ps < npass; ++ps) {
+                    const int q = wv + ps * nw;
+                    if (q < half) {
+                        const long long d = db + h * half + q;
+                        double* oc = chain + (size_t)d * kstride * P;
+                        double* orec = rec + (size_t)d * kstride * MARG_OUT;
+                        for (int k = 0; k < kc; ++k) {
+                            if (lane < P) oc[(size_t)k * P + lane] = nan;
+                            if (lane < MARG_OUT) orec[(size_t)k * MARG_OUT + lane] = nan;
+                        }
+                        if (lane < P) theta[(size_t)d * P + lane] = nan;
+                        if (lane == 0) nacc[d] = -1;
+                    }
+                }
+            continue;
+        }
+        int left = thin - t0 % thin, ks = 0;
+        for (int i = 0; i < Tc; ++i) {
+            for (int h = 0; h < 2; ++h) {
+                for (int ps = 0; ps < npass; ++ps) {
+                    const int q = wv + ps * nw;
+                    if (q < half) {  // (wave-uniform; no barrier inside)
+                        const int k = h * half + q;
+                        const size_t at = (size_t)(db + k) * Tc + i;
+                        double* me = ens + k * ENS_SLOT;
+                        const double* you = ens + ((1 - h) * half + pick[at]) * ENS_SLOT;
+                        if (lane < P) tp[lane] = ens_stretch(z[at], me[lane], you[lane]);
+                        wave_lds_sync();
+                        bool in = true;
+                        for (int p = 0; p < P; ++p) {
+                            const double v = tp[p];
+                            in = in && v >= pr[p] && v <= pr[RECIPE_MAXP + p];
+                        }
+                        if (__builtin_amdgcn_readfirstlane((int)in)) {  // (wave-uniform: the forward pass and the solve are wave-synchronous)
+                            draws_recipe_forward<TWO>(rt, tp, 0, lane, ng1, J1, Ws, fp, col, th, val, Hs, Gs);
+                            draws_solve<false>(lane, nG, jeffreys, Gs, mu, sinv, rs);
+                            wave_lds_sync();
+                            const double lp1 = rs[0], pri1 = chain_prior(P, tp, pr);
+                            if (__builtin_amdgcn_readfirstlane((int)chain_accept(lnq[at], lp1, pri1, me[ENS_LP], me[ENS_PRI]))) {
+                                const double na = me[ENS_NA] + 1.0;
+                                wave_lds_sync();  // (every lane has read ln P, pri and the count of the slot)
+                                if (lane < P) me[lane] = tp[lane];
+                                if (lane < MARG_OUT) me[ENS_REC + lane] = rs[lane];
+                                if (lane == 0) {
+                                    me[ENS_LP] = lp1;
+                                    me[ENS_PRI] = pri1;
+                                    me[ENS_NA] = na;
+                                }
+                            }
+                        }
+                        wave_lds_sync();  // (the next member overwrites the trial theta, th, val, H, G and the trial record)
+                    }
+                }
+                __syncthreads();  // (the half that moved is the other half's partner next)
+            }
+            if (--left == 0) {
+                left = thin;
+                if (ks < kc)  // (always: the host counts the slots of the launch the same way)
+                    for (int h = 0; h < 2; ++h)
+                        for (int ps = 0; ps < npass; ++ps) {
+                            const int q = wv + ps * nw;
+                            if (q < half) {
+                                const int k = h * half + q;
+                                const long long d = db + k;
+                                const double* me = ens + k * ENS_SLOT;
+                                if (lane < P) chain[((size_t)d * kstride + ks) * P + lane] = me[lane];
+                                if (lane < MARG_OUT) rec[((size_t)d * kstride + ks) * MARG_OUT + lane] = me[ENS_REC + lane];
+                            }
+                        }
+                ++ks;
+            }
+        }
+        for (int h = 0; h < 2; ++h)
+            for (int ps = 0; ps < npass; ++ps) {
+                const int q = wv + ps * nw;
+                if (q < half) {
+                    const int k = h * half + q;
+                    const long long d = db + k;
+                    const double* me = ens + k * ENS_SLOT;
+                    if (lane < P) theta[(size_t)d * P + lane] = me[lane];
+                    if (lane == 0) nacc[d] = (long long)me[ENS_NA];
+                }
+            }
+        // (no barrier: the next ensemble's starts go to slots that their own waves alone have touched since the last half-sweep's barrier)
     }
 }
 

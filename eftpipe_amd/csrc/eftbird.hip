@@ -246,6 +246,10 @@ struct eftb_engine {
     size_t tmp_beta_cap = 0, tmp_lnus_cap = 0, tmp_sums_cap = 0, tmp_nswap_cap = 0;
     long long* tmp_nswap = nullptr;
     std::vector<long long> tmp_host_nswap;
+    // eftb_draws_ensemble_params, which shares the chain call's buffers (z goes where step goes, lnq where lnu goes): one launch's slice of
+    // pick [N][Tc]; grown on demand
+    int* ens_pick = nullptr;
+    size_t ens_pick_cap = 0;
     // EFTB_O_GRAPH / EFTB_GRAPH=1: whole-pipeline runs (masks that start at PREP) are captured once into a HIP graph per launch
     // state and replayed -- one host call per step instead of ~30, for hosts whose cores are busy or throttled.  Off by default: on
     // ROCm 7.2 the replay is 2-3 % slower than the plain launches when the host keeps up (0.566 vs 0.553 ms per 128, 0.169 vs 0.144 ms at B = 1)
@@ -2561,6 +2565,9 @@ static int draws_no_fit(const char* who, int J1) { return fail("%s: the Gram mat
 // it leaves their compiled code, label numbers included, the parent's (isa_counts.json)
 using TemperKernel = decltype(&draws_temper_params_kernel<false>);
 static TemperKernel temper_kernel(bool two);
+// (and draws_ensemble_params_kernel behind it, for the same reason)
+using EnsembleKernel = decltype(&draws_ensemble_params_kernel<false>);
+static EnsembleKernel ensemble_kernel(bool two);
 
 // the large dynamic LDS for every logp draw kernel, once per engine
 static int draws_lds_optin(eftb_engine* e) {
@@ -2568,7 +2575,8 @@ static int draws_lds_optin(eftb_engine* e) {
 #define DRAW_PAIR(k) reinterpret_cast<const void*>(&k<false>), reinterpret_cast<const void*>(&k<true>)
     for (const void* k : {DRAW_PAIR(draws_logp_kernel), DRAW_PAIR(draws_logp_params_kernel), DRAW_PAIR(draws_logp_grad_params_kernel),
                           DRAW_PAIR(draws_logp_hess_params_kernel), DRAW_PAIR(draws_sample_params_kernel), DRAW_PAIR(draws_chain_params_kernel),
-                          reinterpret_cast<const void*>(temper_kernel(false)), reinterpret_cast<const void*>(temper_kernel(true))})
+                          reinterpret_cast<const void*>(temper_kernel(false)), reinterpret_cast<const void*>(temper_kernel(true)),
+                          reinterpret_cast<const void*>(ensemble_kernel(false)), reinterpret_cast<const void*>(ensemble_kernel(true))})
         HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #undef DRAW_PAIR
     e->drw_lds = true;
@@ -4156,16 +4164,17 @@ int eftb_draws_sample_params_datasets(eftb_engine* e, int C, int G, const int32_
 constexpr int CHAIN_STEPS = 256;
 
 // what the chain calls refuse in their own arguments, after draws_params_check: no parameter, T, thin (at least thin_min), step, lnu, the prior
-// on theta and a theta0 outside the box; pri [CHAIN_PRI] = lower | upper | loc | sinv is the table their kernels read
+// on theta and a theta0 outside the box; pri [CHAIN_PRI] = lower | upper | loc | sinv is the table their kernels read.  step and lnu NULL
+// (the ensemble call): the caller checks its own moves behind this
 static int chain_args_check(const char* who, int P, long long N, int T, int thin, int thin_min, const double* theta0, const double* step, const double* lnu,
                             const double* lower, const double* upper, const double* ploc, const double* pscale, double* pri, const char* step_name = "step") {
     if (P < 1) return fail("%s: the draw recipe has no parameters to move", who);
     if (T < 1) return fail("%s: T = %d steps, at least 1", who, T);
     if (thin < thin_min || thin > T) return fail("%s: thin = %d outside [%d, T = %d]", who, thin, thin_min, T);
     const long long TP = (long long)T * P;
-    for (long long q = 0; q < N * TP; ++q)
+    for (long long q = 0; step && q < N * TP; ++q)
         if (!std::isfinite(step[q])) return fail("%s: %s[%lld][%lld][%d] is not finite", who, step_name, q / TP, q / P % T, (int)(q % P));
-    for (long long q = 0; q < N * T; ++q)
+    for (long long q = 0; lnu && q < N * T; ++q)
         if (!(lnu[q] <= 0.0)) return fail("%s: lnu[%lld][%lld] = %g is not the logarithm of a uniform in [0, 1]", who, q / T, q % T, lnu[q]);
     for (int p = 0; p < P; ++p) {
         const double lo = lower ? lower[p] : -INFINITY, hi = upper ? upper[p] : INFINITY, sc = pscale ? pscale[p] : INFINITY;
@@ -4194,6 +4203,7 @@ struct ChainCall {
     long long N, maxcnt;    // chains; the most of them one walker (group, pair) owns
     int T, thin, P, nG;
     int per_launch, width;  // steps (trajectories) of a launch; doubles of a stored record: MARG_OUT, or two of them for a pair of walkers
+    int mw;                 // doubles of a chain's moves per step: P, or 1 for the stretch factors of the ensemble call
     int K, kstride, Tmax;   // stored states of a chain in the call, at most in one launch, and the steps of the longest launch
     char shape[112];        // the size of the call, for a refused allocation
     double pri[CHAIN_PRI];  // lower | upper | loc | sinv
@@ -4221,18 +4231,19 @@ static int chain_grow(const ChainCall& c, void* pp, size_t* cap, size_t n, const
     return grow_dev(c.e, pp, cap, n, elem, c.who, what, c.shape);
 }
 
-// the split into launches of per_launch steps and the buffers every sampler has, records of `width` doubles; `moves` and `unit` are the
-// caller's words for a refused allocation.  thin = 0 (dragging alone allows it) stores nothing
-static int chain_buffers(ChainCall& c, int per_launch, int width, const char* moves, const char* unit) {
+// the split into launches of per_launch steps and the buffers every sampler has, records of `width` doubles, moves of `mw` doubles per chain and step (every caller says which: P, or 1 for
+// the ensemble call's stretch factors); `moves` and `unit` are the caller's words for a refused allocation.  thin = 0 (dragging alone allows it) stores nothing
+static int chain_buffers(ChainCall& c, int per_launch, int width, int mw, const char* moves, const char* unit) {
     eftb_engine* e = c.e;
     c.per_launch = per_launch;
     c.width = width;
+    c.mw = mw;
     c.K = c.thin ? c.T / c.thin : 0;
     c.kstride = c.thin ? std::max(1, std::min(c.K, per_launch / c.thin + 1)) : 1;
     c.Tmax = std::min(c.T, per_launch);
     snprintf(c.shape, sizeof c.shape, "N = %lld chains x T = %d %s with P = %d parameters", c.N, c.T, unit, c.P);
     const size_t N = (size_t)c.N;
-    if (int rc = chain_grow(c, &e->chn_step, &e->chn_step_cap, N * c.Tmax * c.P, moves)) return rc;
+    if (int rc = chain_grow(c, &e->chn_step, &e->chn_step_cap, N * c.Tmax * c.mw, moves)) return rc;
     if (int rc = chain_grow(c, &e->chn_lnu, &e->chn_lnu_cap, N * c.Tmax, "lnu")) return rc;
     if (int rc = chain_grow(c, &e->chn_pri, &e->chn_pri_cap, CHAIN_PRI, "the prior table")) return rc;
     if (int rc = chain_grow(c, &e->chn_nacc, &e->chn_nacc_cap, N, "the accept counts", sizeof(long long))) return rc;
@@ -4240,14 +4251,15 @@ static int chain_buffers(ChainCall& c, int per_launch, int width, const char* mo
     return chain_grow(c, &e->chn_rec, &e->chn_rec_cap, N * c.kstride * width, "the stored records");
 }
 
-// The prior table and the zeroed accept counts (behind the caller's own one-time uploads), then one launch per per_launch steps.  Between the
+// The prior table and the zeroed accept counts (behind the caller's own one-time uploads), then one launch per per_launch steps.  (The moves
+// are c.mw doubles per step: P for the four calls that add increments or momenta, which enqueue what they always did.)  Between the
 // launches theta and the accept counts stay on the device; the states and records a launch stored come back behind it, into chain [N][K][P] and,
 // one ChainRecords per MARG_OUT of the width, into slot k of `slots` per chain.  A launch that stored nothing is not waited for, unless `more`
 // brings something back behind every launch
 static int chain_run(const ChainCall& c, const double* moves, const double* lnu, double* chain, const ChainRecords* rec, int slots, const ChainLaunch& launch,
                      const ChainMore& more = nullptr) {
     eftb_engine* e = c.e;
-    const size_t N = (size_t)c.N, P = (size_t)c.P, W = (size_t)c.width, T = (size_t)c.T, K = (size_t)c.K, kstride = (size_t)c.kstride;
+    const size_t N = (size_t)c.N, P = (size_t)c.P, W = (size_t)c.width, T = (size_t)c.T, K = (size_t)c.K, kstride = (size_t)c.kstride, M = (size_t)c.mw;
     const int nG = c.nG, thin = c.thin;
     hipStream_t st = e->stream;
     HIPCHK(hipMemcpyAsync(e->chn_pri, c.pri, sizeof(c.pri), hipMemcpyHostToDevice, st));
@@ -4257,8 +4269,8 @@ static int chain_run(const ChainCall& c, const double* moves, const double* lnu,
     const double *hchain = e->chn_host_chain.data(), *hrec = e->chn_host_rec.data();
     for (int t0 = 0; t0 < c.T; t0 += c.per_launch) {
         const int Tc = std::min(c.per_launch, c.T - t0), k0 = thin ? t0 / thin : 0, kc = thin ? (t0 + Tc) / thin - k0 : 0;
-        // this launch's steps of every chain: rows of Tc P (Tc) doubles out of the caller's rows of T P (T)
-        HIPCHK(hipMemcpy2DAsync(e->chn_step, Tc * P * sizeof(double), moves + t0 * P, T * P * sizeof(double), Tc * P * sizeof(double), N,
+        // this launch's steps of every chain: rows of Tc M (Tc) doubles out of the caller's rows of T M (T), M = P but for the ensemble call
+        HIPCHK(hipMemcpy2DAsync(e->chn_step, Tc * M * sizeof(double), moves + t0 * M, T * M * sizeof(double), Tc * M * sizeof(double), N,
                                 hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpy2DAsync(e->chn_lnu, Tc * sizeof(double), lnu + t0, T * sizeof(double), Tc * sizeof(double), N, hipMemcpyHostToDevice, st));
         if (int rc = launch(t0, Tc, kc)) return rc;
@@ -4315,7 +4327,7 @@ static int draws_chain_params_impl(eftb_engine* e, const char* who, int C, long 
     if (N == 0) return 0;
     DrawRun run;
     if (int rc = draws_params_begin(e, who, C, N, c.maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
-    if (int rc = chain_buffers(c, CHAIN_STEPS, MARG_OUT, "the steps", "steps")) return rc;
+    if (int rc = chain_buffers(c, CHAIN_STEPS, MARG_OUT, c.P, "the steps", "steps")) return rc;
     const ChainRecords rec{logp, fullchi2, best};
     auto launch = [&](int t0, int Tc, int kc) {
         launch_two(draws_chain_params_kernel<false>, draws_chain_params_kernel<true>, sh.J1, run.grid, run.block, sh.lds, e->stream, ntr, nG, sh.J1, e->jeffreys, Tc,
@@ -4401,7 +4413,7 @@ static int draws_temper_params_impl(eftb_engine* e, const char* who, int C, long
     if (N == 0) return 0;
     DrawRun run;
     if (int rc = draws_params_begin(e, who, C, N, c.maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
-    if (int rc = chain_buffers(c, CHAIN_STEPS, MARG_OUT, "the steps", "steps")) return rc;
+    if (int rc = chain_buffers(c, CHAIN_STEPS, MARG_OUT, c.P, "the steps", "steps")) return rc;
     hipStream_t st = e->stream;
     auto events = [&](int t0, int Tc) { return S ? (int)((first + t0 + Tc) / S - (first + t0) / S) : 0; };  // the swap events of the launch at t0
     int most = 0;
@@ -4467,6 +4479,87 @@ int eftb_draws_temper_params_datasets(eftb_engine* e, int C, int G, const int32_
                                     prior_loc, prior_scale, chain, logp, fullchi2, best, last, naccept, nswap, sum_logp, &gr);
 }
 
+// ------------------------------------------------------------------------------------------------ affine-invariant ensembles over the draw parameters
+// eftb_draws_ensemble_params and eftb_draws_ensemble_params_datasets: the chain call's checks (but for its rules on step and lnu), Gram cache
+// and buffers around draws_ensemble_params_kernel, one workgroup per ensemble.  z travels where the chain call's step does (one double per
+// sweep), lnq where lnu does, and every launch takes its own sweeps out of pick
+static int draws_ensemble_params_impl(eftb_engine* e, const char* who, int C, long long N, int K, int T, int thin, const int64_t* offsets,
+                                      const double* theta0, const double* f, const double* z, const int32_t* pick, const double* lnq, const double* lower,
+                                      const double* upper, const double* ploc, const double* pscale, double* chain, double* logp, double* fullchi2,
+                                      double* best, double* last, int64_t* naccept, const DrawGroups* gr = nullptr) {
+    ChainCall c{e, who, N, 0, T, thin};
+    if (int rc = chain_front(&c, C, gr ? "group" : "walker", gr ? gr->nwalk : -1, C, 1, offsets, theta0, f, nullptr, nullptr, lower, upper, ploc, pscale))
+        return rc;
+    const int ntr = e->ntr, nG = c.nG, P = c.P;
+    if (K < 2 || K > ENS_MAXK || (K & 1)) return fail("%s: K = %d members, not an even number in [2, %d]", who, K, ENS_MAXK);
+    for (int w = 0; w < C; ++w)
+        if ((offsets[w + 1] - offsets[w]) % K)
+            return fail("%s: %s %d owns %lld chains, not a multiple of K = %d members", who, gr ? "group" : "walker", w,
+                        (long long)(offsets[w + 1] - offsets[w]), K);
+    for (long long q = 0; q < N * T; ++q) {
+        const long long n = q / T, t = q % T;
+        if (!(z[q] > 0.0) || !std::isfinite(z[q]))
+            return fail("%s: z[%lld][%lld] = %g (ensemble %lld, member %lld, sweep %lld) is not a finite stretch factor > 0", who, n, t, z[q], n / K, n % K, t);
+        if (pick[q] < 0 || pick[q] >= K / 2)
+            return fail("%s: pick[%lld][%lld] = %d (ensemble %lld, member %lld, sweep %lld) outside [0, K / 2 = %d)", who, n, t, (int)pick[q], n / K, n % K, t,
+                        K / 2);
+        if (!(lnq[q] < INFINITY))
+            return fail("%s: lnq[%lld][%lld] = %g (ensemble %lld, member %lld, sweep %lld) is NaN or +inf", who, n, t, lnq[q], n / K, n % K, t);
+    }
+    DrawShape sh;
+    if (int rc = draws_logp_shape(e, who, DRAW_CHAIN, &e->recipe[0], &sh)) return rc;
+    // a workgroup of min(ENS_MAXW, K / 2) waves or as many as fit beside the ensemble area, whatever the chain call would take
+    sh.nw = sh.L.fit_ens(K, 160 * 1024);
+    if (!sh.nw)
+        return fail("%s: an ensemble of K = %d members needs %zu bytes of LDS for its states, which leave no room for one wave beside the Gram matrix "
+                    "of J + 1 = %d columns with nG = %d and P = %d parameters (%zu bytes per workgroup and %zu per wave, within %d)", who, K,
+                    (size_t)K * ENS_SLOT * sizeof(double), sh.J1, nG, P, sh.L.bytes_wg(), sh.L.bytes_wave(), 160 * 1024);
+    sh.lds = sh.L.bytes_ens(sh.nw, K);
+    if (N == 0) return 0;
+    DrawRun run;
+    if (int rc = draws_params_begin(e, who, C, N, c.maxcnt, sh, offsets, theta0, f, gr, &run)) return rc;
+    run.grid = dim3(C, draw_shares(c.maxcnt, K, C));  // (a workgroup takes one ensemble at a time)
+    if (int rc = chain_buffers(c, CHAIN_STEPS, MARG_OUT, 1, "the stretch factors", "sweeps")) return rc;
+    if (int rc = chain_grow(c, &e->ens_pick, &e->ens_pick_cap, (size_t)N * c.Tmax, "pick", sizeof(int))) return rc;
+    hipStream_t st = e->stream;
+    const ChainRecords rec{logp, fullchi2, best};
+    auto launch = [&](int t0, int Tc, int kc) {
+        HIPCHK(hipMemcpy2DAsync(e->ens_pick, (size_t)Tc * sizeof(int), pick + t0, (size_t)T * sizeof(int), (size_t)Tc * sizeof(int), (size_t)N,
+                                hipMemcpyHostToDevice, st));
+        launch_two(ensemble_kernel(false), ensemble_kernel(true), sh.J1, run.grid, run.block, sh.lds, st, ntr, nG, sh.J1, e->jeffreys, K, Tc, t0, thin, kc,
+                   c.kstride, run.rt, e->drw_off, e->drw_theta, e->chn_nacc, run.f, run.W, e->like_mu, e->like_sinv, e->chn_pri, e->chn_step, e->ens_pick,
+                   e->chn_lnu, e->chn_chain, e->chn_rec);
+        return 0;
+    };
+    if (int rc = chain_run(c, z, lnq, chain, &rec, c.K, launch)) return rc;
+    if (int rc = chain_fetch(c, last)) return rc;
+    return chain_end(c, naccept);
+}
+
+int eftb_draws_ensemble_params(eftb_engine* e, int C, long long N, int K, int T, int thin, const int64_t* offsets, const double* theta0, const double* f,
+                               const double* z, const int32_t* pick, const double* lnq, const double* lower, const double* upper, const double* prior_loc,
+                               const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept) {
+    static const char* who = "eftb_draws_ensemble_params";
+    if (e) sub_drain(e);
+    if (!e || !offsets || !f || (N > 0 && (!theta0 || !z || !pick || !lnq || !chain || !last || !naccept))) return fail("%s: null argument", who);
+    return draws_ensemble_params_impl(e, who, C, N, K, T, thin, offsets, theta0, f, z, pick, lnq, lower, upper, prior_loc, prior_scale, chain, logp, fullchi2,
+                                      best, last, naccept);
+}
+
+int eftb_draws_ensemble_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int K, int T, int thin,
+                                        const int64_t* offsets, const double* theta0, const double* f, const double* z, const int32_t* pick,
+                                        const double* lnq, const double* lower, const double* upper, const double* prior_loc, const double* prior_scale,
+                                        double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept) {
+    static const char* who = "eftb_draws_ensemble_params_datasets";
+    if (e) sub_drain(e);
+    if (!e || !walker || !dataset || !offsets || !f || (N > 0 && (!theta0 || !z || !pick || !lnq || !chain || !last || !naccept)))
+        return fail("%s: null argument", who);
+    DrawGroups gr{0, walker, dataset};
+    if (int rc = draws_groups_check(e, who, C, G, f, &gr)) return rc;
+    return draws_ensemble_params_impl(e, who, G, N, K, T, thin, offsets, theta0, e->grp_f.data(), z, pick, lnq, lower, upper, prior_loc, prior_scale, chain,
+                                      logp, fullchi2, best, last, naccept, &gr);
+}
+
 // ------------------------------------------------------------------------------------------------ Hamiltonian Monte Carlo over the draw parameters
 // eftb_draws_hmc_params and eftb_draws_hmc_params_datasets: the chain call's checks (chain_args_check on mom in the place of step), Gram
 // cache, prior table and buffers around draws_hmc_params_kernel.  A launch holds at most CHAIN_STEPS gradient evaluations per chain,
@@ -4505,7 +4598,7 @@ static int draws_hmc_params_impl(eftb_engine* e, const char* who, int C, long lo
             HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         e->hmc_lds = true;
     }
-    if (int rc = chain_buffers(c, std::max(1, CHAIN_STEPS / nleap), MARG_OUT, "the momenta", "trajectories")) return rc;
+    if (int rc = chain_buffers(c, std::max(1, CHAIN_STEPS / nleap), MARG_OUT, c.P, "the momenta", "trajectories")) return rc;
     if (int rc = chain_grow(c, &e->hmc_eps, &e->hmc_eps_cap, (size_t)N * c.Tmax, "eps")) return rc;
     if (int rc = chain_grow(c, &e->hmc_ratio, &e->hmc_ratio_cap, (size_t)N * c.Tmax, "the ratios")) return rc;
     if (int rc = chain_grow(c, &e->hmc_fac, &e->hmc_fac_cap, (size_t)N * P * P, "the factors")) return rc;
@@ -4615,7 +4708,7 @@ int eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, 
     if (int rc = draws_params_upload(e, P, C, N, theta0, f, &dtheta, &df)) return rc;
     const dim3 grid(G, draw_shares(c.maxcnt, sh.nw, G)), block(64 * sh.nw);
     const RecipeTab rt = recipe_tab(e->recipe[0]);
-    if (int rc = chain_buffers(c, CHAIN_STEPS, PAIR, "the steps", "steps")) return rc;
+    if (int rc = chain_buffers(c, CHAIN_STEPS, PAIR, c.P, "the steps", "steps")) return rc;
     if (int rc = chain_grow(c, &e->drg_pair, &e->drg_pair_cap, 2 * (size_t)G, "the pairs", sizeof(int))) return rc;
     if (int rc = chain_grow(c, &e->drg_frac, &e->drg_frac_cap, (size_t)T, "frac")) return rc;
     if (int rc = chain_grow(c, &e->drg_sums, &e->drg_sums_cap, 2 * (size_t)N, "the sums")) return rc;
@@ -4646,3 +4739,5 @@ int eftb_draws_drag_params(eftb_engine* e, int C, int G, const int32_t* wstart, 
 
 // (the one place that names draws_temper_params_kernel: see the declaration above draws_lds_optin)
 static TemperKernel temper_kernel(bool two) { return two ? &draws_temper_params_kernel<true> : &draws_temper_params_kernel<false>; }
+// (and the one place that names draws_ensemble_params_kernel)
+static EnsembleKernel ensemble_kernel(bool two) { return two ? &draws_ensemble_params_kernel<true> : &draws_ensemble_params_kernel<false>; }

@@ -390,11 +390,12 @@ class MarginalLikelihood:
         return DrawChains(theta, logp, nacc, last, full, best)
 
     def _chain_args(self, theta0, offsets, f, moves, lnu, thin, lower, upper, prior_loc, prior_scale, groups, name="step", kind="proposal increments",
-                    unit="steps", per="step", thin_min=1, pair_words=()):
+                    unit="steps", per="step", thin_min=1, pair_words=(), flat=False):
         """the arguments the four sampler calls share as the library takes them, shape errors raised here -> theta0, off, f, walker, dataset (None
         without groups), moves, lnu, thin, [lower, upper, prior_loc, prior_scale].  The caller words its moves [N, T, P] (``name``, what ``kind`` of
         numbers they are, the ``unit`` T counts and the one lnu holds a uniform ``per``), says how small thin may be and, with ``pair_words``, that
-        ``groups`` are the pairs of ``drag_draws_params`` in the wording of ``_groups_args``"""
+        ``groups`` are the pairs of ``drag_draws_params`` in the wording of ``_groups_args``; ``flat``: the moves are one number per chain and
+        step, [N, T] (the stretch factors of ``ensemble_draws_params``, whose lnu may be of either sign)"""
         from .engine import _params_args
 
         ntr = self.eng.ntracers
@@ -406,12 +407,15 @@ class MarginalLikelihood:
             theta0, off, f = _params_args(rec, theta0, offsets, f, ntr)
         N, P = theta0.shape
         moves = np.ascontiguousarray(moves, dtype=np.float64)
-        if moves.ndim != 3 or moves.shape[0] != N or moves.shape[2] != P or moves.shape[1] < 1:
+        if flat:
+            if moves.ndim != 2 or moves.shape[0] != N or moves.shape[1] < 1:
+                raise ValueError(f"{name} must be [{N}, T] {kind} with T >= 1 {unit}")
+        elif moves.ndim != 3 or moves.shape[0] != N or moves.shape[2] != P or moves.shape[1] < 1:
             raise ValueError(f"{name} must be [{N}, T, {P}] {kind} with T >= 1 {unit}")
         T = moves.shape[1]
         lnu = np.ascontiguousarray(lnu, dtype=np.float64)
         if lnu.shape != (N, T):
-            raise ValueError(f"lnu must be [{N}, {T}]: the logarithm of a uniform per chain and {per}")
+            raise ValueError(f"{'lnq' if flat else 'lnu'} must be [{N}, {T}]: the logarithm of a uniform per chain and {per}")
         if thin != int(thin) or not thin_min <= thin <= T:
             raise ValueError(f"thin must be an integer in [{thin_min}, T = {T}]")
         thin = int(thin)
@@ -492,6 +496,52 @@ class MarginalLikelihood:
         else:
             L.check(self.eng.lib.eftb_draws_temper_params(self.eng._h, off.size - 1, *head, *tail))
         return TemperedChains(theta, logp, full, best, last, nacc, nswap, sums, beta)
+
+    def ensemble_draws_params(self, starts, offsets, f, K, z, pick, lnq, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None, groups=None,
+                              return_best=False):
+        """Affine-invariant ensembles over theta at fixed templates (the stretch move of Goodman & Weare, as in emcee), all T sweeps of all
+        ensembles in one device call (``eftb_draws_ensemble_params``) instead of 2 T ``logp_draws_params`` calls with the rule in NumPy
+        between them.  An ensemble takes the scale and orientation of its proposals from its own members: the call needs no proposal matrix.
+        starts [N, P], offsets, f, ``groups``, the box and the Gaussian prior on theta are those of ``metropolis_draws_params`` with
+        N = nens K: chain n is member n % K of ensemble n // K, K even with 2 <= K <= 64, and every walker (group) owns a multiple of K
+        chains.  Members 0 ... K/2 - 1 are half 0, the rest half 1.  The caller supplies the randomness (``stretch_proposals``): z [N, T] > 0,
+        pick [N, T] in [0, K/2) and lnq [N, T].  Sweep t moves half 0 against the current half 1, then half 1 against the new half 0: member
+        k proposes theta_j + z[n, t] (theta_k - theta_j) with j = member pick[n, t] of the other half, rejects it without an evaluation
+        outside the box, and accepts iff ln P' is finite and lnq[n, t] < (ln P' + pri') - (ln P + pri).  lnq = ln u - (P - 1) ln z carries the
+        Jacobian of the stretch, so it may be positive.
+        -> ``DrawChains(theta [N, Kt, P], logp [N, Kt], naccept [N], last [N, P], fullchi2, best)`` with Kt = T // thin, as
+        ``metropolis_draws_params``; a T-sweep call equals a T1-sweep call and a T2-sweep call from ``last`` bit for bit.
+        Raises RuntimeError("det of F2ij <= 0") where a member's starting point has no finite ln P (its whole ensemble fails)."""
+        out = self._ensemble_raw(starts, offsets, f, K, z, pick, lnq, thin, lower, upper, prior_loc, prior_scale, groups, return_best)
+        if np.any(out.naccept < 0):
+            raise RuntimeError("det of F2ij <= 0")
+        return out
+
+    def _ensemble_raw(self, starts, offsets, f, K, z, pick, lnq, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None, groups=None,
+                      return_best=False):
+        """``ensemble_draws_params`` without the RuntimeError: an ensemble that failed at its start has NaN states and naccept = -1"""
+        theta0, off, f, wk, ds, z, lnq, thin, pri = self._chain_args(starts, offsets, f, z, lnq, thin, lower, upper, prior_loc, prior_scale, groups,
+                                                                     name="z", kind="stretch factors", unit="sweeps", per="sweep", flat=True)
+        (N, T), P = z.shape, theta0.shape[1]
+        if K != int(K):
+            raise ValueError("K must be an integer: the members of an ensemble")
+        K = int(K)
+        if K < 1 or N % K:
+            raise ValueError(f"starts holds {N} chains, not a multiple of the K = {K} members of an ensemble")
+        pick = np.asarray(pick)
+        if pick.shape != (N, T) or pick.dtype.kind not in "iu":
+            raise ValueError(f"pick must be [{N}, {T}] integers: the partner of every member in every sweep")
+        pick = np.ascontiguousarray(pick, dtype=np.int32)
+        theta, logp, last, nacc, full, best = self._chain_out(N, T // thin, P, return_best)
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        tail = (N, K, T, thin, off.ctypes.data_as(i64p), L.dptr(theta0), L.dptr(f), L.dptr(z), pick.ctypes.data_as(i32p), L.dptr(lnq)) + tuple(
+            L.dptr(a) for a in pri) + (L.dptr(theta), L.dptr(logp), L.dptr(full), L.dptr(best), L.dptr(last), nacc.ctypes.data_as(i64p))
+        if groups is not None:
+            L.check(self.eng.lib.eftb_draws_ensemble_params_datasets(self.eng._h, f.shape[0], wk.size, wk.ctypes.data_as(i32p), ds.ctypes.data_as(i32p),
+                                                                     *tail))
+        else:
+            L.check(self.eng.lib.eftb_draws_ensemble_params(self.eng._h, off.size - 1, *tail))
+        return DrawChains(theta, logp, nacc, last, full, best)
 
     def hmc_draws_params(self, theta0, offsets, f, momentum, lnu, eps, nleap, factor=None, thin=1, lower=None, upper=None, prior_loc=None, prior_scale=None,
                          groups=None, return_best=False, return_ratio=False):
@@ -795,6 +845,27 @@ def temper_proposals(rng, nlad, beta, T, factor, swap_every, first_step=0, widen
     return np.ascontiguousarray(step), lnu, lnu_swap
 
 
+def stretch_proposals(rng, nens, K, T, P, a=2.0):
+    """The randomness of ``MarginalLikelihood.ensemble_draws_params`` from a ``numpy.random.Generator``: -> (z [nens K, T], pick [nens K, T]
+    (int32), lnq [nens K, T]).  z = ((a - 1) u + 1)^2 / a with u uniform has the density g(z) ~ 1 / sqrt(z) on [1 / a, a] of Goodman &
+    Weare's stretch move, pick = rng.integers(K / 2) is the partner in the other half, and lnq = ln u' - (P - 1) ln z carries the move's
+    Jacobian z^(P - 1) to the uniform's side.  a > 1 (ValueError otherwise); 2 is emcee's default."""
+    for name, v, lo in (("nens", nens, 0), ("K", K, 2), ("T", T, 1), ("P", P, 1)):
+        if v != int(v) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}")
+    nens, K, T, P = int(nens), int(K), int(T), int(P)
+    if K % 2:
+        raise ValueError("K must be even: an ensemble moves half against half")
+    if not a > 1.0:
+        raise ValueError("a must be > 1: the stretch factors lie in [1 / a, a]")
+    N = nens * K
+    z = ((a - 1.0) * rng.random((N, T)) + 1.0) ** 2 / a
+    pick = rng.integers(K // 2, size=(N, T)).astype(np.int32)
+    with np.errstate(divide="ignore"):
+        lnq = np.log(rng.random((N, T))) - (P - 1) * np.log(z)
+    return z, pick, lnq
+
+
 def hmc_momenta(rng, N, T, P):
     """The randomness of ``MarginalLikelihood.hmc_draws_params`` from a ``numpy.random.Generator``: -> (momentum [N, T, P], lnu [N, T]) with
     momentum = rng.standard_normal((N, T, P)) and lnu = log(rng.random((N, T)))."""
@@ -826,4 +897,4 @@ def drag_accept(lnu_slow, result):
     return lnu_slow < result.log_ratio
 
 
-__all__ = ["MarginalLikelihood", "DrawChains", "DrawTrajectories", "TemperedChains", "temper_ladder", "temper_proposals", "hmc_momenta", "DragChains", "drag_fractions", "drag_accept", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]
+__all__ = ["MarginalLikelihood", "DrawChains", "DrawTrajectories", "TemperedChains", "temper_ladder", "temper_proposals", "stretch_proposals", "hmc_momenta", "DragChains", "drag_fractions", "drag_accept", "metropolis_proposals", "proposal_factor", "data_index", "newton_maximize", "gaussian_params", "gaussian_rows", "gaussian_rows_many", "joint_draw_recipe", "joint_gaussian_rows", "joint_gaussian_rows_many"]

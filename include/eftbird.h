@@ -476,6 +476,40 @@ int  eftb_draws_temper_params_datasets(eftb_engine* e, int C, int G, const int32
                                        const double* prior_loc, const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best,
                                        double* last, int64_t* naccept, int64_t* nswap, double* sum_logp);
 
+/* Affine-invariant ensembles over theta at fixed templates (the stretch move of Goodman & Weare 2010, as in emcee): nens ensembles of K
+ * members each, all T sweeps in the kernel, one workgroup per ensemble.  An ensemble takes the scale and orientation of its proposals from
+ * its own members, so the call needs no proposal matrix.  The N = nens K chains are counted by offsets as in eftb_draws_chain_params; chain
+ * n is member n % K of ensemble n / K, and every walker's (group's) count is a multiple of K, so that no ensemble straddles two walkers.
+ * K is even, 2 <= K <= 64; members 0 ... K/2 - 1 are half 0, the rest half 1.  The target is the chain call's,
+ *     ln pi(theta) = ln P_marg(theta) + pri(theta),
+ * pri its prior on theta (box and independent Gaussians, the same arithmetic).  Sweep t = 0 ... T - 1 moves half 0 against the current
+ * positions of half 1, then half 1 against the new positions of half 0.  Member k (chain n) moves as
+ *     partner      j = member pick[n][t] of the other half, 0 <= pick < K/2       (pick [N][T], int32)
+ *     proposal     per parameter d = theta_k - theta_j, theta' = theta_j + z[n][t] d, each operation rounded on its own     (z [N][T] > 0)
+ *     box          outside the box: rejected without an evaluation
+ *     acceptance   otherwise accepted iff ln P' is finite and lnq[n][t] < (ln P' + pri') - (ln P + pri), the chain call's expression
+ * The caller folds the Jacobian of the stretch into its uniform, lnq = ln u - (P - 1) ln z: the device takes no logarithm.  lnq may
+ * therefore be positive; -inf accepts every finite proposal.  After every thin-th sweep every member's state and record are stored.
+ * Outputs, with Kt = T / thin: chain [N][Kt][P], logp [N][Kt], fullchi2 [N][Kt], best [N][Kt][nG] (the last three each or NULL), last [N][P]
+ * and naccept [N] as eftb_draws_chain_params; every record is the bits of eftb_draws_logp_params at the stored theta.
+ * A T-sweep call equals a T1-sweep call and a T2-sweep call from `last`, with z, pick and lnq split accordingly, bit for bit, naccept
+ * summed.  The host splits T into launches of at most 256 sweeps; theta and naccept persist on the device between them and every launch
+ * recomputes the records of its starting states.  An ensemble's bits depend neither on the other ensembles of the call nor on their order.
+ * An ensemble one of whose members starts without a finite ln P (det F2 <= 0) fails as a whole: NaN in chain, logp, fullchi2, best and
+ * last of every member, naccept = -1; the other ensembles are not touched.
+ * Refused before anything is copied, naming ensemble, member, sweep or parameter where they apply: what eftb_draws_chain_params refuses but
+ * for its rules on step and lnu, K odd or outside [2, 64], a walker whose chain count is no multiple of K, z NaN, infinite or <= 0, pick
+ * outside [0, K/2), lnq NaN or +inf, and a K whose states leave no room for one wave: the chain call's working set at W waves plus 61
+ * doubles per member within 160 KB, W = min(8, K/2, the waves that fit) (the message names K, J + 1, nG and P). */
+int  eftb_draws_ensemble_params(eftb_engine* e, int C, long long N, int K, int T, int thin, const int64_t* offsets, const double* theta0, const double* f,
+                                const double* z, const int32_t* pick, const double* lnq, const double* lower, const double* upper, const double* prior_loc,
+                                const double* prior_scale, double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept);
+/* eftb_draws_ensemble_params per group (walker[g], dataset[g]) of eftb_draws_logp_params_datasets: the same kernel on the groups' Gram matrices. */
+int  eftb_draws_ensemble_params_datasets(eftb_engine* e, int C, int G, const int32_t* walker, const int32_t* dataset, long long N, int K, int T, int thin,
+                                         const int64_t* offsets, const double* theta0, const double* f, const double* z, const int32_t* pick,
+                                         const double* lnq, const double* lower, const double* upper, const double* prior_loc, const double* prior_scale,
+                                         double* chain, double* logp, double* fullchi2, double* best, double* last, int64_t* naccept);
+
 /* Dragging chains between two cosmologies in one device call (the fast steps of cobaya's `drag: true` behind one slow proposal): the
  * chain call against a target that slides from a start walker to an end walker.  C walkers are resident, each with its own templates and
  * f [C][ntr]; pair g = (a = wstart[g], b = wend[g]) of G pairs (walkers may repeat, a = b is allowed) owns the chains

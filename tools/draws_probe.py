@@ -92,6 +92,19 @@ with a swap event every fourth, medians of 9 cached calls with [min, max], on th
 file times (b) and (c) on the parent commit.
 
     python tools/draws_probe.py --temper [--walkers C] [--steps T]
+
+--ensemble [n,n,...]: affine-invariant ensembles over theta (MarginalLikelihood.ensemble_draws_params) instead, for both shapes,
+--walkers walkers (default 128) x n ensembles each (default 1 and 4) of K = 8 members, --steps T sweeps (default 256), medians of 9 cached
+calls with [min, max], on the same stretch factors, partners and uniforms:
+
+    (a) ensemble  one ensemble_draws_params call: all T sweeps of all ensembles in the kernel
+    (b) loop      2 T logp_draws_params calls, one per half-sweep on the half that moves, with the rule in NumPy: the only route without (a)
+    (c) chains    one metropolis_draws_params call of the same N T evaluations: (a) / (c) is the price of the two barriers per sweep
+
+(a) and (b) are asserted to return the same ensembles.  On a tree without ensemble_draws_params (a) is skipped, so that the same file times (b)
+and (c) on the parent commit.
+
+    python tools/draws_probe.py --ensemble [--walkers C] [--steps T]
 """
 import argparse
 import json
@@ -590,8 +603,76 @@ def probe_temper(name, setup, C, nlad, R=4, T=256, S=4, repeats=9):
     return out
 
 
+def probe_ensemble(name, setup, C, nens, K=8, T=256, a=2.0, repeats=9):
+    """(a), (b), (c) of --ensemble for one shape: C walkers x nens ensembles of K members x T sweeps, medians of `repeats` cached calls with
+    [min, max].  (b), the only route without the ensemble call, runs on a tree that lacks it too"""
+    rng = np.random.default_rng(1)
+    N, half = C * nens * K, K // 2
+    eng, like, templ, _, ndata, nG, (rec, theta_build, fC), _ = setup(C, N, rng)
+    eng.put("TEMPL", templ)
+    theta0 = theta_build()
+    P = theta0.shape[1]
+    off = np.arange(C + 1) * nens * K
+    like.set_draw_recipe(rec)
+    # (stretch_proposals(rng, C nens, K, T, P, a), spelled out for the tree without it)
+    z = ((a - 1.0) * rng.random((N, T)) + 1.0) ** 2 / a
+    pick = rng.integers(half, size=(N, T)).astype(np.int32)
+    lnq = np.log(rng.random((N, T))) - (P - 1) * np.log(z)
+    stat = lambda ts: {"ms": 1e3 * float(np.median(ts)), "ms_spread": [1e3 * min(ts), 1e3 * max(ts)]}
+    out = {"shape": name, "walkers": C, "ensembles": N // K, "members": K, "sweeps": T, "ndata": ndata, "nG": nG, "P": P}
+    n = np.arange(N)
+    halves = [n[n % K // half == h] for h in (0, 1)]  # the chains of each half, in chain order: half the chains of every walker
+    base = n // K * K
+
+    def loop():
+        cur = theta0.copy()
+        lp = like.logp_draws_params(cur, off, fC)
+        nacc = np.zeros(N, dtype=np.int64)
+        for t in range(T):
+            for h in (0, 1):
+                act = halves[h]
+                tj = cur[base[act] + (1 - h) * half + pick[act, t]]
+                d = cur[act] - tj
+                trial = tj + z[act, t, None] * d
+                try:
+                    lp1 = like.logp_draws_params(trial, off // 2, fC)
+                except RuntimeError:  # det F2 <= 0 at a proposal: the public call has no NaN to give, the half-sweep is lost for all chains
+                    lp1, out["loop_hit_nan"] = np.full(act.size, np.nan), True
+                acc = np.isfinite(lp1) & (lnq[act, t] < lp1 - lp[act])
+                cur[act[acc]], lp[act[acc]] = trial[acc], lp1[acc]
+                nacc[act] += acc
+        return cur, nacc
+
+    last, nacc = loop()
+    out["accept_rate"] = float(np.mean(nacc)) / T
+    out["loop"] = stat(times(loop, repeats))
+    step = 0.01 * rng.standard_normal((N, T, P))
+    lnu = np.log(rng.random((N, T)))
+    plain = lambda: like.metropolis_draws_params(theta0, off, fC, step, lnu)  # (c) the same N T evaluations without a barrier
+    plain()
+    out["chains"] = stat(times(plain, repeats))
+    if hasattr(like, "ensemble_draws_params"):
+        call = lambda: like.ensemble_draws_params(theta0, off, fC, K, z, pick, lnq)
+        r = call()
+        # the same ensembles as the loop -- unless the loop lost a half-sweep to a NaN proposal, which the result then says
+        out["same_as_loop"] = None if "loop_hit_nan" in out else bool(np.array_equal(r.last, last) and np.array_equal(r.naccept, nacc))
+        assert out["same_as_loop"] is not False
+        if out["same_as_loop"] is None:
+            print("draws_probe: the loop met det F2 <= 0 at a proposal; (a) was NOT compared with (b) at this shape", flush=True)
+        out["ensemble"] = stat(times(call, repeats))
+        out["loop_over_ensemble"] = out["loop"]["ms"] / out["ensemble"]["ms"]
+        out["ensemble_over_chains"] = out["ensemble"]["ms"] / out["chains"]["ms"]
+        out["evaluations_per_s"] = N * T / (1e-3 * out["ensemble"]["ms"])
+    eng.close()
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ensemble", nargs="?", const="1,4", default=None,
+                    help="n[,n...] ensembles of eight members per walker (default 1,4): time ensemble_draws_params, the loop of 2 x steps "
+                         "logp_draws_params calls with the rule in NumPy on the same inputs, and one chain call of as many evaluations")
     ap.add_argument("--temper", nargs="?", const="1,4", default=None,
                     help="n[,n...] ladders of four rungs per walker (default 1,4), a swap event every fourth step: time temper_draws_params, the loop of "
                          "steps / 4 metropolis_draws_params calls with the swaps in NumPy on the same inputs, and one chain call of as many steps")
@@ -613,7 +694,11 @@ if __name__ == "__main__":
     ap.add_argument("--walkers", type=int, default=None)
     ap.add_argument("--datasets", type=int, default=0, help="M data vectors sharing the covariance: time the groups call, the per-vector loop and the plain call")
     a = ap.parse_args()
-    if a.temper:
+    if a.ensemble:
+        for n in (int(x) for x in a.ensemble.split(",")):
+            probe_ensemble("marg", marg_setup, a.walkers or 128, n, T=a.steps)
+            probe_ensemble("cfg3", cfg3_setup, a.walkers or 128, n, T=a.steps)
+    elif a.temper:
         for n in (int(x) for x in a.temper.split(",")):
             probe_temper("marg", marg_setup, a.walkers or 128, n, T=a.steps)
             probe_temper("cfg3", cfg3_setup, a.walkers or 128, n, T=a.steps)
